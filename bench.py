@@ -29,7 +29,15 @@ tasks (labelled synthetic stand-ins), resolve, finalize — and reports prove-ph
 rank 0 joins them: the job's only collective);
 `--native-agent` = the one-process multi-GPU design.
 
-The JSON line also carries
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline needs: it sets up, warms up, times the K steps with no
+per-kernel events, and prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step = wall ms of one timed step, config,
+host, per_rank, backend).  `--dump-outputs DIR` then also writes the last timed step's receipts (seal and commit roots of each of its
+segments) as DIR/seal_<segment>.npy and DIR/roots_<segment>.npy in float64; the inputs are fixed by the arguments, so two builds
+can be compared file by file.  `--full` adds every other measurement below (the --no-* switches select among them).
+
+Every line carries
+  per_rank, backend one row per rank (rank, device, proofs, seconds) and the backend's world size: whether RCCL saw N ranks, and balance;
+and with `--full` also
   single_proof_ms   wall clock of a lone proof (the reference's agent proves one segment at a time per process), no HIP events around it;
                     .spin_wait = the same with the host thread busy-waiting on its stream (the one-proof-at-a-time latency mode);
                     .plain_hal = the same segment proved from OUTSIDE the library through the plain Hal-trait entry points of SURVEY 8(b2)
@@ -38,7 +46,6 @@ The JSON line also carries
                     the ~9 GB of buffers allocated inside every proof as upstream does (`alloc_per_proof`: through the library's bx_alloc pool,
                     and on raw hipMalloc / hipFree);
   pcie_inclusive    untimed extra at N=1: the same workload with 80 MB per segment over PCIe, two deep (`value` stays inputs-resident);
-  per_rank, backend one row per rank (rank, device, proofs, seconds) and the backend's world size: whether RCCL saw N ranks, and balance;
   roofline      the NTT/LDE entry point named by BASELINE's metric (`roofline.dominant` = the job's dominant kernel, hash_rows, against
                 the VALU issue peak; `roofline.traffic_over_algorithmic` = PMC bytes / algorithmic bytes of the LDE): algorithmic bytes / HIP-event time on the HAL
                 stream over the timed region, against the 8 TB/s HBM peak (DESIGN.md §4 explains why this path is
@@ -620,6 +627,33 @@ def _prove_ids(k):
 
 _prove_ids.cache = {}
 
+DUMP_OUTPUTS_BYTES = 64 << 20  # --dump-outputs: cap over all ranks
+
+
+def dump_outputs(dirname, receipts, per_step, world):
+    """--dump-outputs: what the timed path handed its caller in its last step — the receipts of this rank's last `per_step`
+    segments (seal words and the four commit roots) — as float64 .npy named by segment index, so that two builds run with the same
+    arguments can be compared file by file.  Every u32 word is exact in float64.  Segments are written in index order until this
+    rank's share of the 64 MB cap would be exceeded.  Returns the names written."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_OUTPUTS_BYTES // max(world, 1)
+    names = []
+    for i in sorted(receipts)[-per_step:]:
+        r = receipts[i]
+        arrays = {f"seal_{i}": r.seal}
+        if r.roots is not None:
+            arrays[f"roots_{i}"] = r.roots
+        nbytes = sum(8 * a.size for a in arrays.values())
+        if nbytes > budget:
+            break
+        budget -= nbytes
+        for name, a in arrays.items():
+            np.save(os.path.join(dirname, name + ".npy"), np.asarray(a, dtype=np.float64))
+            names.append(name)
+    return names
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -662,7 +696,14 @@ def main():
     ap.add_argument("--no-pcie-extra", action="store_true", help="skip the untimed PCIe-inclusive leg (80 MB segments) of the default N=1 run")
     ap.add_argument("--rendezvous-only", action="store_true", help="test hook: rendezvous + one all-reduce counting the ranks, print {n_gpus, ranks_counted} and exit (no GPU needed with --dist-backend gloo)")
     ap.add_argument("--dump", type=str, default=None, help="directory: every rank writes rank{r}.npz with the segment indices it claimed in the timed region and their seals (parity tests of the N>1 path)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR", help="after the timed steps, write what the last step handed its "
+                    "caller — every segment's seal and commit roots — as DIR/seal_<segment>.npy and DIR/roots_<segment>.npy (float64; at most 64 MB)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline line does not need: per-kernel HIP events on one lane, "
+                    "the isolated probe and roofline, lone-proof latency and the plain-Hal driver, the PCIe-inclusive leg, cpu_baseline, "
+                    "agent_mode and (N > 1) the native-agent child; the --no-* switches above select among these")
     args = ap.parse_args()
+    if args.dump_outputs and (args.job or args.native_agent or args.rendezvous_only):
+        ap.error("--dump-outputs applies to the segment-proof path, not to --job, --native-agent or --rendezvous-only")
     widths = tuple(int(x) for x in args.widths.split(","))
     if args.wait:
         os.environ["BX_WAIT"] = args.wait
@@ -735,7 +776,8 @@ def main():
         lock = threading.Lock()
         done = [0]
         last = [None]
-        claimed = {}
+        claimed = {}  # segment index -> receipt, for --dump / --dump-outputs
+        keep = tag == "timed" and bool(args.dump or args.dump_outputs)
         by_server = {id(sv): 0 for sv in servers}
 
         def claim(sv):
@@ -761,12 +803,13 @@ def main():
                     return
                 seg = Segment.synthetic(index=idx, po2=args.po2)
                 if buf is None:
-                    last[0] = sv.prove_segment(seg)
+                    r = sv.prove_segment(seg)
                 else:
                     buf[:28] = seg.to_bytes()[:28]
-                    last[0] = sv.prove_segment_buffer(buf, index=idx)
-                if args.dump and tag == "timed":
-                    claimed[idx] = last[0].seal
+                    r = sv.prove_segment_buffer(buf, index=idx)
+                last[0] = r
+                if keep:
+                    claimed[idx] = r
 
         def worker_two_deep(sv, buf):
             # segment k+1 is staged and uploaded while segment k is proved — the feeder thread makes the pinned copy and
@@ -793,10 +836,11 @@ def main():
                 idx = handed.get()
                 if idx is None:
                     break
-                last[0] = sv.prove_submitted(index=idx)
+                r = sv.prove_submitted(index=idx)
+                last[0] = r
                 free.release()
-                if args.dump and tag == "timed":
-                    claimed[idx] = last[0].seal
+                if keep:
+                    claimed[idx] = r
             ft.join()
 
         if len(servers) == 1:
@@ -811,8 +855,9 @@ def main():
             os.makedirs(args.dump, exist_ok=True)
             order = sorted(claimed)
             np.savez(os.path.join(args.dump, f"rank{rank}.npz"), indices=np.array(order, dtype=np.int64),
-                     **{f"seal_{i}": claimed[i] for i in order})
+                     **{f"seal_{i}": claimed[i].seal for i in order})
         run.by_server = by_server
+        run.claimed = claimed
         return done[0], last[0]
 
     per_rank = args.steps * len(servers)
@@ -825,7 +870,8 @@ def main():
     # Live per-entry-point HIP events (the durations behind `roofline_in_region` and `kernels`) on ONE lane per rank: an event
     # record is a barrier packet between two kernels, and bracketing every entry point of every lane costs 0.9 % of the rate at any
     # lane count (profiles/r03_ab_live_profile.jsonl).  The profiled lane's segments are what the per-segment figures divide by.
-    live = [] if args.no_live_profile else servers[:1]
+    # Per-kernel figures are part of --full only: a plain run times the steps with no events at all.
+    live = servers[:1] if args.full and not args.no_live_profile else []
     for sv in servers:
         sv.hal.profile_reset()
         sv.hal.profile_enable(any(sv is x for x in live))
@@ -851,11 +897,12 @@ def main():
     # who did what: one row per rank, so that a SCALE run says by itself whether the backend saw N ranks and whether they were balanced
     per_rank_rows = [{"rank": int(r[0]), "device": int(r[1]), "proofs": int(r[2]), "seconds": round(r[3], 4)}
                      for r in gather_over_ranks([rank, local_rank, proved, elapsed_own], dist)]
+    dumped = dump_outputs(args.dump_outputs, run.claimed, len(servers), world) if args.dump_outputs else None
 
     # One proof alone (untimed, rank 0): the reference's agent proves one segment at a time per process.  No HIP events around the
     # entry points here (an event record is a barrier packet), wall clock around bx_prove_segment_bytes.
     single_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         sv = servers[0]
         ts = []
         for k in range(4):
@@ -883,7 +930,7 @@ def main():
     # include time-slicing with the other stream, so one extra segment is proved alone to get each entry point's own
     # duration (this is what a rocprofv3 --kernel-trace of `--inflight 1` reports).
     iso = {}
-    if rank == 0 and len(servers) > 1:
+    if rank == 0 and args.full and len(servers) > 1:
         sv = servers[0]
         sv.hal.profile_reset()
         sv.hal.profile_enable(True)
@@ -899,7 +946,7 @@ def main():
         single_ms["plain_hal"] = plain_hal_probe(args, servers[0], single_ms["min"])
     barrier()
 
-    if rank == 0:
+    if rank == 0 and args.full:
         kernels = {}
         for name, r in prof.items():
             ms = r["ms"] / max(r["calls"], 1)
@@ -1057,14 +1104,17 @@ def main():
         circ_ops = ("witgen_fill", "scatter", "witgen_derive", "accum_gather", "accum_build", "prefix_products", "accum_store", "eval_check")
         circ_ms = sum(src_c[k]["ms_per_segment"] for k in circ_ops if k in src_c)
         all_ms = sum(v["ms_per_segment"] for v in src_c.values())
+
+    if rank == 0:
         circuit_view = {"kind": "synthetic AIR (include/bx_prover.h), not rv32im: public words bound to the trace, seeded ZK noise rows (last 1994), but no image id / claim; lift is not included",
                         "included": ["witness generation (synthetic) with ZK noise rows", "accumulate (prefix_products)", "eval_check (synthetic constraints / vanishing polynomial)",
                                      "3 trace commits + check commit", "DEEP", "FRI", "50 queries"],
                         "excluded": ["rv32im preflight/witgen/eval_check (generated code, not in the reference tree)", "lift (recursion circuit)",
                                      "CPU verification of the seal (reported in agent_mode)"],
-                        "terms": int(receipt.seal[4]), "degree": int(receipt.seal[5]),
-                        "stages_ms_per_segment": {k: src_c[k]["ms_per_segment"] for k in circ_ops if k in src_c},
-                        "share_of_gpu_time": round(circ_ms / all_ms, 3) if all_ms else None}
+                        "terms": int(receipt.seal[4]), "degree": int(receipt.seal[5])}
+        if args.full:
+            circuit_view.update({"stages_ms_per_segment": {k: src_c[k]["ms_per_segment"] for k in circ_ops if k in src_c},
+                                 "share_of_gpu_time": round(circ_ms / all_ms, 3) if all_ms else None})
         out = {
             "metric": "segment-proofs/sec @ 2^20 cycles",
             "value": proved_total / elapsed,
@@ -1093,6 +1143,14 @@ def main():
                      "cpus_allowed": len(os.sched_getaffinity(0)),
                      "note": "getrusage(RUSAGE_SELF) user+system over the timed region of rank 0 (all lane threads) / proofs; "
                              "the GPU boxes give a container 16 CPUs for 8 GPUs, i.e. 2 per GPU (profiles/r03_host_budget.json)"},
+            "per_rank": per_rank_rows,
+            "backend": (None if dist is None else {"name": dist.get_backend(), "world_size": dist.get_world_size()}),
+            "full": bool(args.full),
+        }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+    if rank == 0 and args.full:
+        out.update({
             "roofline": {**roofline, "dominant": {"kernel": dominant.get("kernel"), "bound": "valu",
                                                   "frac_issue": dominant.get("frac_of_mul_class_peak"), "frac_algorithmic": dominant.get("frac_algorithmic"),
                                                   "valu_insts_per_permutation": dominant.get("valu_insts_per_permutation"),
@@ -1101,8 +1159,6 @@ def main():
                                                           "against 1024 SIMDs x 2.4 GHz / 4 (multiply class), frac_algorithmic counts only the 1356 x 3 "
                                                           "multiply instructions a permutation needs (SURVEY 8d)"}},
             "single_proof_ms": single_ms,
-            "per_rank": per_rank_rows,
-            "backend": (None if dist is None else {"name": dist.get_backend(), "world_size": dist.get_world_size()}),
             "roofline_in_region": roofline_in_region,
             "roofline_dominant": dominant,
             "roofline_job": job_valu_view(proved_total / elapsed / max(world, 1)),
@@ -1113,7 +1169,7 @@ def main():
                                      "profiles/r03_ab_live_profile.jsonl); `kernels` and `roofline_in_region` are that lane's WALL times while the "
                                      "other lanes share the GPU (not kernel durations); `kernels_isolated` / `roofline` are one segment alone"},
             "replayed_profiles": replayed_profiles(),
-        }
+        })
         if world == 1 and not args.no_pcie_extra and not args.segment_bytes and args.po2 >= 18:
             # Untimed extra (never `value`): the same workload with every segment carrying the ~80 MB the reference's 2^20-cycle
             # segment serializes to (executor.rs:45): pinned copy + upload on the copy stream per proof, two deep.
@@ -1144,7 +1200,7 @@ def main():
                 out["cpu_baseline"] = {"error": str(e)}
     for sv in servers:
         sv.close()
-    if world > 1 and not args.no_native_agent_extra:
+    if args.full and world > 1 and not args.no_native_agent_extra:
         # Untimed extra at N > 1: the other multi-GPU design measured by the same command.  Every rank has released its
         # provers; rank 0 runs `bench.py --native-agent` over all N devices in a CHILD process under a timeout (a failure or a
         # hang there cannot take the primary line with it), the other ranks wait at the barrier.
@@ -1188,7 +1244,7 @@ def main():
             if rank == 0:
                 out["native_agent"] = {"error": f"{type(e).__name__}: {e}"}
     if rank == 0:
-        if world == 1 and not args.no_agent_mode:
+        if args.full and world == 1 and not args.no_agent_mode:
             # Untimed extra (never `value`): the same workload claimed through the native feed loop (bx_agent_poll_work:
             # hot-store GET -> prove -> CPU verify -> SETEX -> UNLINK -> update_task_done) with the same number of lanes.
             try:

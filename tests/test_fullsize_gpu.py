@@ -155,7 +155,7 @@ def _run_bench_two_ranks_on_one_gpu(extra, dump, timeout=900):
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--device", "0",
-           "--no-cpu-baseline", "--no-agent-mode", "--dump", dump] + extra
+           "--full", "--no-cpu-baseline", "--no-agent-mode", "--dump", dump] + extra
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -221,7 +221,7 @@ def _run_bench_ranks(ranks, extra, timeout=900):
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(ranks), "--dist-backend", "gloo", "--device", "0",
-           "--no-cpu-baseline", "--no-agent-mode"] + extra
+           "--full", "--no-cpu-baseline", "--no-agent-mode"] + extra
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     t0 = time.time()
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=root)
@@ -270,7 +270,7 @@ def test_rccl_rendezvous_barrier_and_all_reduce_of_the_multi_rank_path(tmp_path)
     po2 = 12
     for extra, want_indices in ((["--steps", "2"], [0, 1, 2, 3]), (["--steps", "1", "--steal", "--batch", "5"], [0, 1, 2, 3, 4])):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
-               "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--no-cpu-baseline",
+               "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--full", "--no-cpu-baseline",
                "--no-agent-mode", "--po2", str(po2), "--widths", "4,12,4", "--warmup", "1", "--inflight", "2", "--dump", str(tmp_path)] + extra
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
@@ -282,3 +282,43 @@ def test_rccl_rendezvous_barrier_and_all_reduce_of_the_multi_rank_path(tmp_path)
         for i in want_indices:
             want, _ = ol.prove_segment(po2, 4, 12, 4, Segment.synthetic(i, po2=po2).seed)
             assert np.array_equal(d[f"seal_{i}"], want)
+
+
+def test_plain_bench_line_and_dumped_outputs_of_the_last_step(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times K steps and prints the headline line without the --full extras;
+    --dump-outputs writes the last step's receipts (seal and commit roots of each of its segments, float64), which equal the
+    oracle's and come out the same in a second run with the same arguments."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from boundless_amd.prover import Segment
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    po2, steps, lanes = 12, 3, 2
+    outs, dirs = [], [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--po2", str(po2),
+               "--widths", "4,12,4", "--inflight", str(lanes), "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        outs.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+    out = outs[0]
+    assert out["steps"] == steps and out["config"]["segments_proved"] == steps * lanes and out["full"] is False
+    assert abs(out["value"] - steps * lanes / (out["ms_per_step"] * steps / 1e3)) / out["value"] < 1e-6
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert out[k] is not None
+    for k in ("single_proof_ms", "kernels", "kernels_isolated", "roofline", "replayed_profiles", "pcie_inclusive", "cpu_baseline", "agent_mode"):
+        assert k not in out, k
+    last = range((steps - 1) * lanes, steps * lanes)
+    names = sorted(f"{n}_{i}" for i in last for n in ("seal", "roots"))
+    assert sorted(out["dumped_outputs"]) == names
+    assert sorted(os.listdir(dirs[0])) == sorted(os.listdir(dirs[1])) == [n + ".npy" for n in names]
+    for i in last:
+        seal, roots = (np.load(dirs[0] / f"{n}_{i}.npy") for n in ("seal", "roots"))
+        assert seal.dtype == roots.dtype == np.float64
+        want_seal, want_roots = ol.prove_segment(po2, 4, 12, 4, Segment.synthetic(i, po2=po2).seed)
+        assert np.array_equal(seal, want_seal.astype(np.float64)) and np.array_equal(roots, want_roots.astype(np.float64)), i
+        for n in ("seal", "roots"):
+            assert np.array_equal(np.load(dirs[1] / f"{n}_{i}.npy"), np.load(dirs[0] / f"{n}_{i}.npy"))

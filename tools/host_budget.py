@@ -18,7 +18,7 @@ from boundless_amd.build import csrc_hash, device_code_hash  # noqa: E402
 
 
 def run(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", STEPS, "--warmup", "3", "--no-cpu-baseline"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", STEPS, "--warmup", "3", "--no-cpu-baseline"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     if not lines:
@@ -36,7 +36,7 @@ def run(extra):
 
 if __name__ == "__main__":
     STEPS = sys.argv[sys.argv.index("--steps") + 1] if "--steps" in sys.argv else "10"
-    res = {"device_code_sha": device_code_hash(), "csrc_sha": csrc_hash(), "what": __doc__.split("\n\n")[0], "command": f"bench.py --steps {STEPS} --warmup 3 --no-cpu-baseline [--cpus 2] --wait block|spin",
+    res = {"device_code_sha": device_code_hash(), "csrc_sha": csrc_hash(), "what": __doc__.split("\n\n")[0], "command": f"bench.py --full --steps {STEPS} --warmup 3 --no-cpu-baseline [--cpus 2] --wait block|spin",
            "cpus_allowed": len(os.sched_getaffinity(0)), "runs": {}}
     for cpus in (0, 2, 1):
         for wait in ("block", "poll", "spin"):

@@ -1,6 +1,6 @@
 """rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES counter CSV of a bench.py run -> wave-level VALU instructions per segment, per kernel.
 
-    rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES --output-format csv -d out -o pmc -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-agent-mode
+    rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES --output-format csv -d out -o pmc -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-agent-mode
     python tools/job_valu.py out/.../pmc_counter_collection.csv <segments proved in that run> profiles/r02_job_valu_insts.json
 """
 import collections

@@ -12,7 +12,7 @@ for g in 0 8 16 32 64; do
 done
 cat $O/opbench.txt
 for g in 0 8 32; do
-  BX_TUNABLES=ntt_group_cols=$g python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-agent-mode > $O/bench_g$g.json 2>/dev/null
+  BX_TUNABLES=ntt_group_cols=$g python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-agent-mode > $O/bench_g$g.json 2>/dev/null
   python - <<PY
 import json
 j=json.loads(open("$O/bench_g$g.json").read().strip().splitlines()[-1])

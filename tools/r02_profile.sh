@@ -3,7 +3,7 @@
 set -u
 O=gpurun_out/r2p; mkdir -p $O
 export TMPDIR=/tmp
-B="python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-agent-mode"
+B="python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-agent-mode"
 # 1. per-kernel time: the default command (3 segments in flight) and one segment in flight
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt3 -o kt -- $B > $O/bench_kt3.json 2>/dev/null
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt1 -o kt -- $B --inflight 1 > $O/bench_kt1.json 2>/dev/null
@@ -17,7 +17,7 @@ done
 python tools/pmc_traffic.py "$(find $O/pmc_FETCH_SIZE -name '*counter_collection.csv' | head -1)" "$(find $O/pmc_WRITE_SIZE -name '*counter_collection.csv' | head -1)" $O/r02_bench_pmc_traffic.json
 rm -rf $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE
 # 3. VALU instructions of the whole job, per segment: steps 2 x 3 lanes + warm-up 3 + 1 isolated probe = 10 segments
-rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES --output-format csv -d $O/pmc_valu -o pmc -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-agent-mode > /dev/null 2>&1
+rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES --output-format csv -d $O/pmc_valu -o pmc -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-agent-mode > /dev/null 2>&1
 python tools/job_valu.py "$(find $O/pmc_valu -name '*counter_collection.csv' | head -1)" 10 $O/r02_job_valu_insts.json
 rm -rf $O/pmc_valu
 head -12 $O/r02_bench_kernel_stats_default_cmd.csv

@@ -5,7 +5,7 @@ set -u
 O=gpurun_out/r2t; mkdir -p $O
 export TMPDIR=/tmp
 BX_TRACE=2 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d $O/mt -o mt -- \
-  python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-agent-mode --inflight 1 > $O/bench_mt.json 2> $O/bench_mt.err
+  python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-agent-mode --inflight 1 > $O/bench_mt.json 2> $O/bench_mt.err
 find $O/mt -name "*.csv" | sed 's/^/  /'
 for f in $(find $O/mt -name "*stats.csv"); do cp $f $O/r02_stage_trace_$(basename $f | sed 's/^mt_//'); done
 M=$(find $O/mt -name "*marker_api_trace.csv" | head -1)

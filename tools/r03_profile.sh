@@ -3,11 +3,11 @@
 set -u
 O=gpurun_out/r3p; mkdir -p $O
 export TMPDIR=/tmp
-B="python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-agent-mode"
+B="python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-agent-mode"
 # 0. the bench line of the driver's command, and the rate at 1..4 segments in flight under both wait policies
-python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/r03_bench_steps20_warmup5.json
+python bench.py --full --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/r03_bench_steps20_warmup5.json
 for w in poll spin; do for l in 1 2 3 4; do
-  python bench.py --steps 8 --warmup 2 --inflight $l --wait $w --no-cpu-baseline --no-agent-mode 2>/dev/null | tail -1 | python -c "import json,sys; j=json.loads(sys.stdin.read()); print(json.dumps({'wait':'$w','inflight':$l,'segment_proofs_per_s':round(j['value'],3),'ms_per_proof_per_lane':round(1e3*$l/j['value'],2),'host_cpu_s_per_proof':j['host_cpu_s_per_proof']}))"
+  python bench.py --full --steps 8 --warmup 2 --inflight $l --wait $w --no-cpu-baseline --no-agent-mode 2>/dev/null | tail -1 | python -c "import json,sys; j=json.loads(sys.stdin.read()); print(json.dumps({'wait':'$w','inflight':$l,'segment_proofs_per_s':round(j['value'],3),'ms_per_proof_per_lane':round(1e3*$l/j['value'],2),'host_cpu_s_per_proof':j['host_cpu_s_per_proof']}))"
 done; done > $O/r03_inflight_sweep.jsonl
 # 1. per-kernel time: the default command (3 segments in flight) and one segment in flight (the tracer times the kernels: no HIP events
 #    of our own around the entry points, they are barrier packets and show up as 10-20 us gaps)
@@ -24,7 +24,7 @@ done
 python tools/pmc_traffic.py "$(find $O/pmc_FETCH_SIZE -name '*counter_collection.csv' | head -1)" "$(find $O/pmc_WRITE_SIZE -name '*counter_collection.csv' | head -1)" $O/r03_bench_pmc_traffic.json
 rm -rf $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE
 # 3. VALU instructions of the whole job, per segment: steps 2 x 3 lanes + warm-up 3 + 1 isolated probe = 10 segments
-rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES --output-format csv -d $O/pmc_valu -o pmc -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-agent-mode > /dev/null 2>&1
+rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES --output-format csv -d $O/pmc_valu -o pmc -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-agent-mode > /dev/null 2>&1
 python tools/job_valu.py "$(find $O/pmc_valu -name '*counter_collection.csv' | head -1)" 10 $O/r03_job_valu_insts.json
 rm -rf $O/pmc_valu
 # 4. the helper entry points alone

@@ -31,7 +31,7 @@ done
 python tools/pmc_stalls.py $O/${TAG}_lde_stalls.json "ntt_passA_fwd12_multi_kernel,ntt_r16_kernel<false, false" $(find $O/pmc1 $O/pmc2 $O/pmc3 $O/pmc4 -name '*counter_collection.csv' 2>/dev/null)
 rm -rf $O/pmc1 $O/pmc2 $O/pmc3 $O/pmc4
 # 5. the headline, short
-python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-agent-mode --no-pcie-extra 2>/dev/null | tail -1 > $O/${TAG}_bench_short.json
+python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-agent-mode --no-pcie-extra 2>/dev/null | tail -1 > $O/${TAG}_bench_short.json
 python - <<PY
 import json
 j=json.load(open("$O/${TAG}_bench_short.json"))

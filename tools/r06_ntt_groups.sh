@@ -17,7 +17,7 @@ cat $O/ldebench.jsonl
 # inside the job: one and three segments in flight
 : > $O/bench.jsonl
 for l in 1 3; do for g in 0 4 8 12; do
-  BX_TUNABLES=ntt_group_cols=$g python bench.py --steps 8 --warmup 3 --inflight $l --no-cpu-baseline --no-agent-mode --no-pcie-extra --no-plain-hal 2>/dev/null | tail -1 > $O/b.json
+  BX_TUNABLES=ntt_group_cols=$g python bench.py --full --steps 8 --warmup 3 --inflight $l --no-cpu-baseline --no-agent-mode --no-pcie-extra --no-plain-hal 2>/dev/null | tail -1 > $O/b.json
   python - <<PY >> $O/bench.jsonl
 import json
 j=json.load(open("$O/b.json"))
