@@ -76,8 +76,8 @@ void parallel_ranges(size_t n, F&& body) {  // body(begin, end)
     for (auto& x : th) x.join();
 }
 
-// Merkle root of the committed code group of the synthetic circuit for (po2, w_code)
-const char* host_control_id(uint32_t po2, uint32_t wc, uint32_t out[8]) {
+// Merkle root of the committed code group of the synthetic circuit for (po2, w_code) under a hash suite
+const char* host_control_id(uint32_t po2, uint32_t wc, int suite, uint32_t out[8]) {
     if (po2 < 9 || po2 > 24 || wc < 1 || wc >= 65536) return "bx_synthetic_control_id_host: shape out of range";
     const size_t n = (size_t)1 << po2, dom = 4 * n;
     if ((double)wc * (double)dom * 4.0 > 6.0e9) return "bx_synthetic_control_id_host: the code group is too large for the host computation (build a verifier context from bx_prover_control_id instead)";
@@ -104,8 +104,9 @@ const char* host_control_id(uint32_t po2, uint32_t wc, uint32_t out[8]) {
             });
         for (auto& x : th) x.join();
     }
-    HostPoseidon2 h;
-    h.load(POSEIDON2_RC, POSEIDON2_DIAG);
+    HostPoseidon2 h2;
+    h2.load(POSEIDON2_RC, POSEIDON2_DIAG);
+    const HostSuite h{suite, &h2};
     std::vector<uint32_t> layer(8 * dom);
     parallel_ranges(dom, [&](size_t b, size_t e) {
         std::vector<uint32_t> row(wc);
@@ -119,7 +120,7 @@ const char* host_control_id(uint32_t po2, uint32_t wc, uint32_t out[8]) {
     for (size_t sz = dom; sz > 1; sz >>= 1) {
         std::vector<uint32_t> next(8 * (sz / 2));
         parallel_ranges(sz / 2, [&](size_t b, size_t e) {
-            for (size_t i = b; i < e; ++i) h.hash_elems(&next[8 * i], &layer[16 * i], 16);  // hash_pair == sponge of 16 words
+            for (size_t i = b; i < e; ++i) h.hash_pair(&next[8 * i], &layer[16 * i], &layer[16 * i + 8]);
         });
         layer.swap(next);
     }
@@ -143,10 +144,10 @@ const size_t N_TABLE = 0;
 #endif
 
 std::mutex cache_mu;
-std::map<std::pair<uint32_t, uint32_t>, Digest> cache;  // (po2, w_code) -> host-computed control ID
+std::map<std::array<uint32_t, 3>, Digest> cache;  // (po2, w_code, suite) -> host-computed control ID
 
-const char* synth_control_id(uint32_t po2, uint32_t wc, uint32_t out[8], bool use_table) {
-    if (use_table && wc == 16)
+const char* synth_control_id(uint32_t po2, uint32_t wc, int suite, uint32_t out[8], bool use_table) {
+    if (use_table && wc == 16 && suite == SUITE_POSEIDON2)  // the generated table holds Poseidon2 IDs
         for (size_t i = 0; i < N_TABLE; ++i)
             if (SYNTH_CONTROL_IDS_W16[i].po2 == po2) {
                 memcpy(out, SYNTH_CONTROL_IDS_W16[i].id, 32);
@@ -154,41 +155,50 @@ const char* synth_control_id(uint32_t po2, uint32_t wc, uint32_t out[8], bool us
             }
     {
         std::lock_guard<std::mutex> g(cache_mu);
-        auto it = cache.find({po2, wc});
+        auto it = cache.find({po2, wc, (uint32_t)suite});
         if (it != cache.end()) {
             memcpy(out, it->second.data(), 32);
             return nullptr;
         }
     }
     Digest d;
-    if (const char* e = host_control_id(po2, wc, d.data())) return e;
+    if (const char* e = host_control_id(po2, wc, suite, d.data())) return e;
     std::lock_guard<std::mutex> g(cache_mu);
-    cache[{po2, wc}] = d;
+    cache[{po2, wc, (uint32_t)suite}] = d;
     memcpy(out, d.data(), 32);
     return nullptr;
 }
 }  // namespace
 
 namespace bx {
-const char* synth_check_code(void*, const bx_segment_params* s, const uint32_t root[8]) {
+const char* synth_check_code_suite(const bx_segment_params* s, const uint32_t root[8], int suite) {
     if (!s || !root) return "check_code: null argument";
     uint32_t id[8];
-    if (const char* e = synth_control_id(s->po2, s->w_code, id, true)) return e;
+    if (const char* e = synth_control_id(s->po2, s->w_code, suite, id, true)) return e;
     return memcmp(id, root, 32) == 0 ? nullptr : "the code group's root is not this circuit's control ID for the shape (the seal was made with another code group)";
+}
+const char* synth_check_code(void*, const bx_segment_params* s, const uint32_t root[8]) {
+    return synth_check_code_suite(s, root, SUITE_POSEIDON2);
 }
 }  // namespace bx
 
 struct bx_verifier_ctx {
-    std::vector<std::pair<uint32_t, Digest>> ids;
+    std::vector<std::pair<uint32_t, Digest>> ids;    // Poseidon2 control IDs
+    std::vector<std::pair<uint32_t, Digest>> sha;    // SHA-256 control IDs (any 32-bit words)
 };
 
 extern "C" {
 
 const char* bx_synthetic_control_id_host(uint32_t po2, uint32_t w_code, uint32_t id_out[8]) {
+    return bx_synthetic_control_id_host_hashfn(po2, w_code, "poseidon2", id_out);
+}
+const char* bx_synthetic_control_id_host_hashfn(uint32_t po2, uint32_t w_code, const char* hashfn, uint32_t id_out[8]) {
     static thread_local char err[256];
+    const int suite = parse_hash_suite(hashfn);
+    if (suite < 0) return "bx_synthetic_control_id_host: unknown hashfn (\"poseidon2\" or \"sha-256\")";
     if (!id_out) return "bx_synthetic_control_id_host: null output";
     try {
-        if (const char* e = synth_control_id(po2, w_code, id_out, false)) {
+        if (const char* e = synth_control_id(po2, w_code, suite, id_out, false)) {
             snprintf(err, sizeof err, "%s", e);
             return err;
         }
@@ -221,11 +231,30 @@ const char* bx_verifier_ctx_add_control_id(bx_verifier_ctx* v, uint32_t po2, con
         return "bx_verifier_ctx_add_control_id: out of memory";
     }
 }
-size_t bx_verifier_ctx_size(const bx_verifier_ctx* v) { return v ? v->ids.size() : 0; }
+const char* bx_verifier_ctx_add_control_id_hashfn(bx_verifier_ctx* v, uint32_t po2, const uint32_t id[8], const char* hashfn) {
+    const int suite = parse_hash_suite(hashfn);
+    if (suite < 0) return "bx_verifier_ctx_add_control_id: unknown hashfn (\"poseidon2\" or \"sha-256\")";
+    if (suite == SUITE_POSEIDON2) return bx_verifier_ctx_add_control_id(v, po2, id);
+    if (!v || !id) return "bx_verifier_ctx_add_control_id: null argument";
+    if (po2 < 9 || po2 > 24) return "bx_verifier_ctx_add_control_id: po2 must be in [9, 24]";
+    try {
+        Digest d;
+        memcpy(d.data(), id, 32);
+        for (auto& e : v->sha)
+            if (e.first == po2 && e.second == d) return nullptr;
+        v->sha.emplace_back(po2, d);
+        return nullptr;
+    } catch (const std::exception&) {
+        return "bx_verifier_ctx_add_control_id: out of memory";
+    }
+}
+size_t bx_verifier_ctx_size(const bx_verifier_ctx* v) { return v ? v->ids.size() + v->sha.size() : 0; }
 size_t bx_verifier_ctx_count(const bx_verifier_ctx* v, uint32_t po2) {
     size_t n = 0;
-    if (v)
+    if (v) {
         for (auto& e : v->ids) n += e.first == po2;
+        for (auto& e : v->sha) n += e.first == po2;
+    }
     return n;
 }
 
@@ -233,9 +262,12 @@ size_t bx_verifier_ctx_count(const bx_verifier_ctx* v, uint32_t po2) {
 
 namespace bx {
 // what verify.cpp asks a context: is `root` one of the IDs registered for po2?
-bool verifier_ctx_contains(const bx_verifier_ctx* v, uint32_t po2, const uint32_t root[8]) {
-    for (auto& e : v->ids)
+bool verifier_ctx_contains_suite(const bx_verifier_ctx* v, int suite, uint32_t po2, const uint32_t root[8]) {
+    for (auto& e : suite == SUITE_SHA256 ? v->sha : v->ids)
         if (e.first == po2 && memcmp(e.second.data(), root, 32) == 0) return true;
     return false;
+}
+bool verifier_ctx_contains(const bx_verifier_ctx* v, uint32_t po2, const uint32_t root[8]) {
+    return verifier_ctx_contains_suite(v, SUITE_POSEIDON2, po2, root);
 }
 }  // namespace bx

@@ -61,6 +61,7 @@ struct bx_ctx {
     uint32_t h_diag[24];
     uint32_t* d_p2 = nullptr;
     int live_provers = 0;  // bx_prover objects created on this ctx and not yet destroyed
+    int hash_suite = 0;    // bx::HashSuite of the Merkle entry points and of provers created on this ctx (bx_set_hash_suite)
 
     // deferred device-side errors (e.g. a scatter offset out of range): h_flag is pinned, host-coherent memory the kernels
     // write straight into (one word per kind of error, so plain stores suffice); the blocking entry points (bx_d2h, bx_sync)
@@ -278,6 +279,11 @@ const char* prefix_products_lookback(bx_ctx* c, uint32_t* io, size_t n, size_t c
 const char* ntt_init_tables(bx_ctx* c);
 void ntt_free_tables(bx_ctx* c);
 const char* poseidon2_upload_params(bx_ctx* c);
+// the `sha-256` suite's Merkle work (sha256.hip), dispatched to by the hash entry points of poseidon2.hip on a sha-256 ctx
+const char* sha256_hash_rows(bx_ctx* c, uint32_t* out, const uint32_t* matrix, size_t rows, size_t cols);
+const char* sha256_hash_fold(bx_ctx* c, uint32_t* io, size_t input_size, size_t output_size);
+const char* sha256_fold_layers(bx_ctx* c, uint32_t* nodes, size_t rows);
+const char* hash_rows_suite(bx_ctx* c, bx_buf out, bx_buf matrix, int suite);  // bx_hash_rows under an explicit suite (poseidon2.hip)
 
 // the synthetic circuit's device stages (circuit.hip), driven by prover.hip
 struct Circuit;

@@ -350,8 +350,8 @@ extern "C" const char* bx_device_name(bx_ctx* c, char* out, size_t cap) try {
     return nullptr;
 } BX_ABI_CATCH(c, "bx_device_name")
 
-// Hal::get_hash_suite / Hal::has_unified_memory: the one suite this HAL implements is the reference's default `poseidon2`
-// (ProverOpts::default(), bento/crates/workflow/src/lib.rs:246-249); MI355X HBM is not host-coherent unified memory.
+// The default suite, the reference's `poseidon2` (ProverOpts::default(), bento/crates/workflow/src/lib.rs:246-249); a ctx's own
+// suite is bx_ctx_hash_suite (sha256.hip).  Hal::has_unified_memory: MI355X HBM is not host-coherent unified memory.
 extern "C" const char* bx_hash_suite_name(void) { return "poseidon2"; }
 extern "C" int bx_has_unified_memory(bx_ctx*) { return 0; }
 

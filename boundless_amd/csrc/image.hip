@@ -18,6 +18,7 @@
 
 #include "ctx.hpp"
 #include "image.hpp"
+#include "sha256_suite.hpp"
 
 namespace bx {
 
@@ -157,7 +158,8 @@ static const char* image_node(bx_ctx* c, const bx_image* im, uint32_t top, uint3
             if ((m = bx_h2d(c, bx_buf{(uint32_t*)dpool.dptr + 8 * (size_t)given_base, 8 * n_given}, g.data(), g.size()))) break;
         }
         if ((m = bx_image_page_cells(c, mat, raw, n1))) break;
-        if ((m = bx_hash_rows(c, bx_buf{dpool.dptr, 8 * n1}, mat))) break;
+        // Poseidon2 whatever the ctx's suite: upstream's image ID does not depend on hashfn (bx_hash_fold_indexed is Poseidon2 only)
+        if ((m = hash_rows_suite(c, bx_buf{dpool.dptr, 8 * n1}, mat, SUITE_POSEIDON2))) break;
         for (int d = 0; d < top_level && !m; ++d)
             m = bx_hash_fold_indexed(c, bx_buf{(uint32_t*)dpool.dptr + 8 * level_out[d], 8 * level_cnt[d]}, dpool,
                                      bx_buf{(uint32_t*)dsel.dptr + level_off[d], 2 * level_cnt[d]}, level_cnt[d]);

@@ -10,6 +10,7 @@
 #include <new>
 
 #include "image.hpp"
+#include "sha256_suite.hpp"
 
 namespace {
 
@@ -69,57 +70,7 @@ static const char* load_elf(bx_image* im, const uint8_t* e, size_t len, uint32_t
     return nullptr;
 }
 
-// ---- SHA-256 (FIPS 180-4) for the SystemState digest: 70 bytes per image, host only ----
-static const uint32_t K256[64] = {
-    0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be,
-    0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa,
-    0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967, 0x27b70a85,
-    0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85, 0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3,
-    0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f,
-    0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
-struct Sha256 {
-    uint32_t h[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
-    uint8_t buf[64];
-    size_t fill = 0;
-    uint64_t total = 0;
-    static uint32_t rr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
-    void block(const uint8_t* p) {
-        uint32_t w[64];
-        for (int i = 0; i < 16; ++i) w[i] = (uint32_t)p[4 * i] << 24 | (uint32_t)p[4 * i + 1] << 16 | (uint32_t)p[4 * i + 2] << 8 | p[4 * i + 3];
-        for (int i = 16; i < 64; ++i)
-            w[i] = w[i - 16] + (rr(w[i - 15], 7) ^ rr(w[i - 15], 18) ^ (w[i - 15] >> 3)) + w[i - 7] + (rr(w[i - 2], 17) ^ rr(w[i - 2], 19) ^ (w[i - 2] >> 10));
-        uint32_t v[8];
-        memcpy(v, h, sizeof v);
-        for (int i = 0; i < 64; ++i) {
-            uint32_t t1 = v[7] + (rr(v[4], 6) ^ rr(v[4], 11) ^ rr(v[4], 25)) + ((v[4] & v[5]) ^ (~v[4] & v[6])) + K256[i] + w[i];
-            uint32_t t2 = (rr(v[0], 2) ^ rr(v[0], 13) ^ rr(v[0], 22)) + ((v[0] & v[1]) ^ (v[0] & v[2]) ^ (v[1] & v[2]));
-            for (int k = 7; k > 0; --k) v[k] = v[k - 1];
-            v[4] += t1;
-            v[0] = t1 + t2;
-        }
-        for (int k = 0; k < 8; ++k) h[k] += v[k];
-    }
-    void update(const uint8_t* p, size_t n) {
-        total += n;
-        while (n) {
-            size_t take = 64 - fill < n ? 64 - fill : n;
-            memcpy(buf + fill, p, take);
-            fill += take, p += take, n -= take;
-            if (fill == 64) block(buf), fill = 0;
-        }
-    }
-    void finish(uint8_t out[32]) {
-        const uint64_t bits = total * 8;
-        const uint8_t one = 0x80, zero = 0;
-        update(&one, 1);
-        while (fill != 56) update(&zero, 1);
-        uint8_t lenb[8];
-        for (int k = 0; k < 8; ++k) lenb[k] = (uint8_t)(bits >> (8 * (7 - k)));
-        update(lenb, 8);
-        for (int k = 0; k < 8; ++k) out[4 * k] = h[k] >> 24, out[4 * k + 1] = h[k] >> 16, out[4 * k + 2] = h[k] >> 8, out[4 * k + 3] = h[k];
-    }
-};
-
+// SHA-256 (FIPS 180-4) for the SystemState digest, 70 bytes per image: bx::Sha256 of sha256_suite.hpp
 
 }  // namespace
 
@@ -218,14 +169,14 @@ extern "C" void bx_system_state_digest(const uint32_t root[8], uint32_t pc, uint
     // tagged_struct("risc0.SystemState", down = [merkle_root], data = [pc]): SHA-256(tag digest | down | data LE | u16 LE count)
     static const char tag[] = "risc0.SystemState";
     uint8_t t[32], body[32 + 4 + 2];
-    Sha256 a;
+    bx::Sha256 a;
     a.update((const uint8_t*)tag, sizeof tag - 1);
     a.finish(t);
     for (int k = 0; k < 8; ++k)
         for (int j = 0; j < 4; ++j) body[4 * k + j] = (uint8_t)(root[k] >> (8 * j));
     for (int j = 0; j < 4; ++j) body[32 + j] = (uint8_t)(pc >> (8 * j));
     body[36] = 1, body[37] = 0;
-    Sha256 b;
+    bx::Sha256 b;
     b.update(t, 32);
     b.update(body, sizeof body);
     b.finish(out);

@@ -11,6 +11,7 @@
 // across the 64 lanes of a wave (lane r reads matrix[c*rows + r]).
 #include "ctx.hpp"
 #include "poseidon2_arith.hpp"
+#include "sha256_suite.hpp"
 #include "../../include/bx_image.h"
 
 namespace bx {
@@ -527,8 +528,8 @@ extern "C" const char* bx_poseidon2_get_params(bx_ctx* c, uint32_t* rc213, uint3
     return nullptr;
 } BX_ABI_CATCH(c, "bx_poseidon2_get_params")
 
-extern "C" const char* bx_hash_rows(bx_ctx* c, bx_buf out, bx_buf matrix) try {
-    if (!c) return "bx_hash_rows: null ctx";
+// Hal::hash_rows under a given suite (the image ID's leaves are Poseidon2 on every ctx: image.hip)
+const char* bx::hash_rows_suite(bx_ctx* c, bx_buf out, bx_buf matrix, int suite) {
     BX_REQUIRE(c, out.len % 8 == 0, "hash_rows: digest buffer length not a multiple of 8 words");
     size_t rows = out.len / 8;
     BX_REQUIRE(c, rows > 0 && matrix.len % rows == 0, "hash_rows: matrix.len not a multiple of rows");
@@ -536,7 +537,12 @@ extern "C" const char* bx_hash_rows(bx_ctx* c, bx_buf out, bx_buf matrix) try {
     size_t cols = matrix.len / rows;
     BX_ENTER(c);
     OpScope op(c, "hash_rows", 4.0 * (double)matrix.len + 32.0 * (double)rows);
+    if (suite == SUITE_SHA256) return sha256_hash_rows(c, (uint32_t*)out.dptr, (const uint32_t*)matrix.dptr, rows, cols);
     return launch_hash_rows(c, (uint32_t*)out.dptr, (const uint32_t*)matrix.dptr, rows, cols);
+}
+extern "C" const char* bx_hash_rows(bx_ctx* c, bx_buf out, bx_buf matrix) try {
+    if (!c) return "bx_hash_rows: null ctx";
+    return hash_rows_suite(c, out, matrix, c->hash_suite);
 } BX_ABI_CATCH(c, "bx_hash_rows")
 
 extern "C" const char* bx_hash_fold(bx_ctx* c, bx_buf io, size_t input_size, size_t output_size) try {
@@ -544,6 +550,7 @@ extern "C" const char* bx_hash_fold(bx_ctx* c, bx_buf io, size_t input_size, siz
     BX_REQUIRE(c, output_size <= io.len / 32 && input_size == 2 * output_size, "hash_fold: input_size must be 2*output_size, and the buffer hold 2*input_size digests");
     BX_ENTER(c);
     OpScope op(c, "hash_fold", 96.0 * (double)output_size);
+    if (c->hash_suite == SUITE_SHA256) return sha256_hash_fold(c, (uint32_t*)io.dptr, input_size, output_size);
     return launch_hash_fold(c, (uint32_t*)io.dptr, input_size, output_size);
 } BX_ABI_CATCH(c, "bx_hash_fold")
 
@@ -606,9 +613,11 @@ extern "C" const char* bx_merkle_build(bx_ctx* c, bx_buf nodes, bx_buf matrix, s
     uint32_t* n = (uint32_t*)nodes.dptr;
     {
         OpScope op(c, "hash_rows", 4.0 * (double)matrix.len + 32.0 * (double)rows);
-        BX_TRY(launch_hash_rows(c, n + 8 * rows, (const uint32_t*)matrix.dptr, rows, matrix.len / rows));
+        if (c->hash_suite == SUITE_SHA256) BX_TRY(sha256_hash_rows(c, n + 8 * rows, (const uint32_t*)matrix.dptr, rows, matrix.len / rows));
+        else BX_TRY(launch_hash_rows(c, n + 8 * rows, (const uint32_t*)matrix.dptr, rows, matrix.len / rows));
     }
     OpScope op(c, "hash_fold", 96.0 * (double)(rows - 1));
+    if (c->hash_suite == SUITE_SHA256) return sha256_fold_layers(c, n, rows);
     return merkle_fold_layers(c, n, rows);
 } BX_ABI_CATCH(c, "bx_merkle_build")
 // Extension: the fold half of bx_merkle_build alone — the leaves are already in nodes[rows .. 2 rows).
@@ -617,11 +626,13 @@ extern "C" const char* bx_merkle_fold(bx_ctx* c, bx_buf nodes, size_t rows) try 
     BX_REQUIRE(c, is_pow2(rows) && rows <= nodes.len / 16 && nodes.len == 16 * rows, "merkle_fold: nodes must hold 2*rows digests, rows a power of two");
     BX_ENTER(c);
     OpScope op(c, "hash_fold", 96.0 * (double)(rows - 1));
+    if (c->hash_suite == SUITE_SHA256) return sha256_fold_layers(c, (uint32_t*)nodes.dptr, rows);
     return merkle_fold_layers(c, (uint32_t*)nodes.dptr, rows);
 } BX_ABI_CATCH(c, "bx_merkle_fold")
 
 extern "C" const char* bx_transcript_step(bx_ctx* c, bx_buf state, bx_buf digests, size_t n_commit, bx_buf out_ext, size_t n_ext) try {
     if (!c) return "bx_transcript_step: null ctx";
+    BX_REQUIRE(c, c->hash_suite == SUITE_POSEIDON2, "transcript_step: the device transcript is Poseidon2's (a sha-256 ctx draws on the host)");
     BX_REQUIRE(c, state.dptr != nullptr && state.len >= 25, "transcript_step: the state is 24 cells and the pool counter");
     BX_REQUIRE(c, n_commit <= 64 && n_ext <= 64, "transcript_step: at most 64 commits and 64 challenges per step");
     BX_REQUIRE(c, digests.len >= 8 * n_commit && out_ext.len >= 4 * n_ext, "transcript_step: digests / out too small");

@@ -115,6 +115,7 @@ struct bx_prover {
     size_t N = 0;
     bool coeffs_bitrev = false;  // trace coefficients stay in bit-reversed order (N >= 2^15), see commit_group
     HostPoseidon2 h2;
+    HostSuite hs;  // the ctx's hash suite at create time (bx_set_hash_suite is refused while the prover lives): h2 or SHA-256
     Group groups[4];  // code, data, accum, check
     DevBuf combos, final_poly, which, xs, evals, rems, positions, qout;
     DevBuf code_w;  // the code group's WITNESS (what witgen reads); groups[0].coeffs is interpolated in place by the commit, which is
@@ -281,6 +282,7 @@ extern "C" const char* bx_prover_create_with_circuit(bx_ctx* c, const bx_segment
     p->coeffs_bitrev = shape->po2 >= 15 && c->deep_bitrev;
     p->err[0] = 0;
     p->h2.load(c->h_rc, c->h_diag);
+    p->hs = HostSuite{c->hash_suite, &p->h2};
     const size_t N = p->N, D = 4 * N;
     const uint32_t widths[4] = {shape->w_code, shape->w_data, shape->w_accum, BX_CHECK_SIZE};
     size_t total_taps = 0, max_w = 0;
@@ -558,7 +560,7 @@ static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t
     if (hipSetDevice(c->device) != hipSuccess) return perr(p, "bx_prove_segment: hipSetDevice failed");
     const size_t N = p->N, D = 4 * N;
     const uint32_t po2 = p->shape.po2;
-    Transcript T(&p->h2);
+    Transcript T(&p->h2, p->hs.suite);
     T.seal.reserve(p->seal_bound);
     TraceRange whole(c, "bx:prove_segment");
 
@@ -568,7 +570,7 @@ static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t
         uint32_t enc[BX_SEAL_HEADER_WORDS], dg[8];
         for (int i = 0; i < BX_SEAL_HEADER_WORDS; ++i) enc[i] = fp_encode(hdr[i]);
         T.write(hdr, BX_SEAL_HEADER_WORDS);
-        p->h2.hash_elems(dg, enc, BX_SEAL_HEADER_WORDS);
+        p->hs.hash_elems(dg, enc, BX_SEAL_HEADER_WORDS);
         T.commit(dg);
     }
     // ---- witness generation (code + data), then the commits in transcript order; the accumulate step needs the
@@ -587,7 +589,7 @@ static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t
         for (uint32_t i = 0; i < p->n_globals; ++i)
             if (globals[i] >= P) return perr(p, "bx_prove_segment: the circuit produced a non-canonical public word");
         T.write(globals, p->n_globals);
-        p->h2.hash_elems(dg, globals, p->n_globals);
+        p->hs.hash_elems(dg, globals, p->n_globals);
         T.commit(dg);
     }
     {   // code and data: neither commit needs anything from the transcript, so both are enqueued and ONE round trip brings back both
@@ -720,7 +722,7 @@ static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t
     {
         uint32_t dg[8];
         T.write(coeff_u.data(), coeff_u.size());
-        p->h2.hash_elems(dg, coeff_u.data(), coeff_u.size());
+        p->hs.hash_elems(dg, coeff_u.data(), coeff_u.size());
         T.commit(dg);
     }
     // ---- DEEP: mix every column into its combo, subtract the mixed u polynomials, divide by every tap point ----
@@ -785,7 +787,8 @@ static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t
     stage.next("bx:fri_prove");
     {
         bx_buf coeffs = p->final_poly.b;
-        const bool dev = c->dev_draws != 0 && !p->rounds.empty();
+        // (Poseidon2 only: there is no device-side SHA-256 RNG, so a sha-256 prover draws on the host whatever dev_draws says)
+        const bool dev = c->dev_draws != 0 && !p->rounds.empty() && p->hs.suite == SUITE_POSEIDON2;
         if (dev) {
             // A round's challenge depends on nothing but the round's root, so the device half of the transcript draws it
             // (bx_transcript_step: 1-2 permutations on one quad, ~20 us) and the fold reads it from device memory: no host round trip
@@ -834,7 +837,7 @@ static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t
             PV(bx_d2h(c, fc.data(), p->final_coeffs.b, fc.size()));
         }
         T.write(fc.data(), fc.size());
-        p->h2.hash_elems(dg, fc.data(), fc.size());
+        p->hs.hash_elems(dg, fc.data(), fc.size());
         T.commit(dg);
     }
     // ---- queries: positions come only from the RNG (writes do not feed it), so draw all 50 first, gather each tree

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "fp.hpp"
+#include "sha256_suite.hpp"
 
 #if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__) && !defined(BX_NO_HOST_AVX2)
 #define BX_HOST_AVX2 1
@@ -187,20 +188,43 @@ struct HostPoseidon2 {
     }
 };
 
-// WriteIOP: the seal is the concatenation of everything written; `commit` feeds the Poseidon2 RNG.
+// The host half of a hash suite (bx_set_hash_suite): the element hash of Merkle leaves and of what the transcript absorbs, and
+// the pair hash of Merkle interior nodes.  Poseidon2's pair hash is its 16-word sponge; SHA-256's is one compression
+// (sha256_suite.hpp, convention 3).
+struct HostSuite {
+    int suite = SUITE_POSEIDON2;
+    const HostPoseidon2* p2 = nullptr;  // the Poseidon2 table (used under SUITE_POSEIDON2 only)
+    void hash_elems(uint32_t out[8], const uint32_t* elems, size_t n) const {
+        if (suite == SUITE_SHA256) sha256_hash_elems(out, elems, n);
+        else p2->hash_elems(out, elems, n);
+    }
+    void hash_pair(uint32_t out[8], const uint32_t* a, const uint32_t* b) const {
+        if (suite == SUITE_SHA256) return sha256_hash_pair(out, a, b);
+        uint32_t pair[16];
+        memcpy(pair, a, 32);
+        memcpy(pair + 8, b, 32);
+        p2->hash_elems(out, pair, 16);
+    }
+};
+
+// WriteIOP: the seal is the concatenation of everything written; `commit` feeds the suite's RNG (Poseidon2Rng, or Sha256Rng).
 struct Transcript {
     const HostPoseidon2* h;
+    int suite;
     std::vector<uint32_t> seal;
     uint32_t cells[24];
     unsigned pool_used;
-    explicit Transcript(const HostPoseidon2* hp) : h(hp) { reset(); }
+    Sha256Rng sha;
+    explicit Transcript(const HostPoseidon2* hp, int s = SUITE_POSEIDON2) : h(hp), suite(s) { reset(); }
     void reset() {
         seal.clear();
         memset(cells, 0, sizeof cells);
         pool_used = 0;
+        sha.reset();
     }
     void write(const uint32_t* w, size_t n) { seal.insert(seal.end(), w, w + n); }
     void commit(const uint32_t digest[8]) {
+        if (suite == SUITE_SHA256) return sha.mix(digest);
         if (pool_used != 0) {
             h->mix(cells);
             pool_used = 0;
@@ -209,6 +233,7 @@ struct Transcript {
         h->mix(cells);
     }
     uint32_t random_elem() {
+        if (suite == SUITE_SHA256) return sha.random_elem();
         if (pool_used == 16) {
             h->mix(cells);
             pool_used = 0;
@@ -221,6 +246,7 @@ struct Transcript {
         return r;
     }
     uint32_t random_bits(unsigned bits) {
+        if (suite == SUITE_SHA256) return sha.random_bits(bits);
         uint32_t val = fp_decode(random_elem());
         for (int i = 0; i < 3; ++i) {
             uint32_t nv = fp_decode(random_elem());

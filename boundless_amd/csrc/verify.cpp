@@ -72,6 +72,9 @@ bool eq(const Fp4& a, const Fp4& b) { return a.c[0] == b.c[0] && a.c[1] == b.c[1
 Fp4 from_base(uint32_t v) { return Fp4{{v, 0, 0, 0}}; }
 uint32_t rou(unsigned k) { return fp_pow(fp_encode(137u), (uint64_t)1 << (27 - k)); }  // w_{2^k}
 
+// digest words: field elements under Poseidon2 (canonical only), any 32-bit value under SHA-256 (sha256_suite.hpp, convention 2)
+const uint32_t* digest_words(Reader& rd, const HostSuite& h, size_t k) { return h.suite == SUITE_SHA256 ? rd.take(k) : rd.take_elems(k); }
+
 // MerkleTreeVerifier: top layer read from the seal, root recomputed and committed
 struct TreeV {
     size_t rows, cols;
@@ -79,41 +82,36 @@ struct TreeV {
     std::vector<uint32_t> top;  // nodes [top_size, 2*top_size) as in the prover, indexable by node id - top_size
     uint32_t root[8];           // recomputed from the top layer
     size_t top_size() const { return (size_t)1 << top_layer; }
-    void read_and_commit(Reader& rd, Transcript& T, const HostPoseidon2& h, size_t rows_, size_t cols_) {
+    void read_and_commit(Reader& rd, Transcript& T, const HostSuite& h, size_t rows_, size_t cols_) {
         rows = rows_;
         cols = cols_;
         layers = ilog2u(rows);
         top_layer = top_layer_of(layers);
         size_t ts = top_size();
-        const uint32_t* t = rd.take_elems(8 * ts);
+        const uint32_t* t = digest_words(rd, h, 8 * ts);
         top.assign(t, t + 8 * ts);
         // fold the top layer to the root
         std::vector<uint32_t> layer(top);
         for (size_t sz = ts; sz > 1; sz >>= 1) {
             std::vector<uint32_t> next(8 * (sz / 2));
-            for (size_t i = 0; i < sz / 2; ++i) h.hash_elems(&next[8 * i], &layer[16 * i], 16);  // hash_pair == sponge of 16 words
+            for (size_t i = 0; i < sz / 2; ++i) h.hash_pair(&next[8 * i], &layer[16 * i], &layer[16 * i + 8]);
             layer.swap(next);
         }
         memcpy(root, layer.data(), 32);
         T.commit(root);
     }
     // reads `cols` values + the path from the seal, checks them against the top layer; returns the column values
-    const uint32_t* verify_open(Reader& rd, const HostPoseidon2& h, size_t idx) const {
+    const uint32_t* verify_open(Reader& rd, const HostSuite& h, size_t idx) const {
         const uint32_t* vals = rd.take_elems(cols);
         uint32_t cur[8];
         h.hash_elems(cur, vals, cols);
         size_t node = idx + rows;
         while (node >= 2 * top_size()) {
-            const uint32_t* sib = rd.take_elems(8);
-            uint32_t pair[16];
-            if (node & 1) {
-                memcpy(pair, sib, 32);
-                memcpy(pair + 8, cur, 32);
-            } else {
-                memcpy(pair, cur, 32);
-                memcpy(pair + 8, sib, 32);
-            }
-            h.hash_elems(cur, pair, 16);
+            const uint32_t* sib = digest_words(rd, h, 8);
+            uint32_t prev[8];
+            memcpy(prev, cur, 32);
+            if (node & 1) h.hash_pair(cur, sib, prev);
+            else h.hash_pair(cur, prev, sib);
             node >>= 1;
         }
         VCHECK(memcmp(cur, &top[8 * (node - top_size())], 32) == 0, "Merkle opening does not match the committed top layer");
@@ -123,7 +121,8 @@ struct TreeV {
 
 }  // namespace
 namespace bx {
-bool verifier_ctx_contains(const bx_verifier_ctx* v, uint32_t po2, const uint32_t root[8]);  // control_id.cpp
+bool verifier_ctx_contains_suite(const bx_verifier_ctx* v, int suite, uint32_t po2, const uint32_t root[8]);  // control_id.cpp
+const char* synth_check_code_suite(const bx_segment_params* s, const uint32_t root[8], int suite);
 }
 namespace {
 
@@ -142,10 +141,11 @@ int verify_threads() {
     return hw >= 4 ? 4 : hw >= 1 ? (int)hw : 1;
 }
 
-void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, const bx_verifier_ctx* vctx) {
-    HostPoseidon2 h;
-    h.load(POSEIDON2_RC, POSEIDON2_DIAG);
-    Transcript T(&h);
+void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, const bx_verifier_ctx* vctx, int suite) {
+    HostPoseidon2 h2;
+    h2.load(POSEIDON2_RC, POSEIDON2_DIAG);
+    const HostSuite h{suite, &h2};
+    Transcript T(&h2, suite);
     Reader rd{seal, words};
 
     // ---- header ----
@@ -188,7 +188,9 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
     // ---- the code group is the circuit's, not the prover's: its root must be a control ID (upstream: check_code(po2, root)).
     //      An explicit context is a lookup and is asked at once; the circuit's own check may have to compute the ID (seconds for
     //      a shape outside its table), so it runs last: only a seal that is otherwise a valid proof can make the verifier pay ----
-    if (vctx) VCHECK(verifier_ctx_contains(vctx, po2, trees[0].root), "the code group's root is not one of the verifier context's control IDs for this po2");
+    if (vctx) VCHECK(verifier_ctx_contains_suite(vctx, suite, po2, trees[0].root), "the code group's root is not one of the verifier context's control IDs for this po2");
+    else if (suite == SUITE_SHA256)  // a table's check_code knows one suite (it has no suite parameter): only the built-in circuit's IDs follow it
+        VCHECK(circ == bx_synthetic_circuit(), "no control IDs to check the code root against (sha-256: a plug-in circuit needs a verifier context)");
     else VCHECK(circ->check_code != nullptr, "no control IDs to check the code root against (the circuit table has no check_code: pass a verifier context)");
     trees[1].read_and_commit(rd, T, h, D, widths[1]);
     const Fp4 beta = T.random_ext();  // the accumulators' mix
@@ -454,7 +456,7 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
     if (rd.pos > rd.n) throw Fail{"seal truncated"};
     VCHECK(rd.pos == rd.n, "trailing words after the last query");
     if (!vctx) {
-        const char* ce = circ->check_code(circ->user, &shape, trees[0].root);
+        const char* ce = suite == SUITE_SHA256 ? synth_check_code_suite(&shape, trees[0].root, suite) : circ->check_code(circ->user, &shape, trees[0].root);
         VCHECK(ce == nullptr, std::string("control ID: ") + (ce ? ce : ""));
     }
 }
@@ -548,12 +550,21 @@ extern "C" const char* bx_verify_segment_with_circuit(const uint32_t* seal, size
 }
 extern "C" const char* bx_verify_segment_with_context(const uint32_t* seal, size_t seal_words, const bx_circuit_ops* circuit,
                                                       const bx_verifier_ctx* vctx) {
+    return bx_verify_segment_with_context_hashfn(seal, seal_words, "poseidon2", circuit, vctx);
+}
+extern "C" const char* bx_verify_segment_hashfn(const uint32_t* seal, size_t seal_words, const char* hashfn) {
+    return bx_verify_segment_with_context_hashfn(seal, seal_words, hashfn, nullptr, nullptr);
+}
+extern "C" const char* bx_verify_segment_with_context_hashfn(const uint32_t* seal, size_t seal_words, const char* hashfn,
+                                                             const bx_circuit_ops* circuit, const bx_verifier_ctx* vctx) {
     static thread_local char err[384];
+    const int suite = parse_hash_suite(hashfn);
+    if (suite < 0) return "bx_verify_segment: unknown hashfn (\"poseidon2\" or \"sha-256\")";
     if (!seal) return "bx_verify_segment: null seal";
     if (!circuit) circuit = bx_synthetic_circuit();
     if (!circuit->taps || !circuit->constraints_at) return "bx_verify_segment: circuit table incomplete";
     try {
-        verify(seal, seal_words, circuit, vctx);
+        verify(seal, seal_words, circuit, vctx, suite);
     } catch (const Fail& f) {
         snprintf(err, sizeof err, "bx_verify_segment: %s", f.msg.c_str());
         return err;

@@ -107,6 +107,8 @@ def load_library():
         "bx_profile_reset": [ctx],
         "bx_profile_report": [ctx, C.c_char_p, sz],
         "bx_set_tunable": [ctx, C.c_char_p, C.c_long],
+        "bx_set_hash_suite": [ctx, C.c_char_p],
+        "bx_ctx_hash_suite": [ctx],
     }
     for name, args in sigs.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export a declared symbol
@@ -182,7 +184,8 @@ class Buffer:
 class HipHal:
     """`impl Hal for HipHal` — one instance per GPU (one per agent process in the reference, compose.yml:113)."""
 
-    def __init__(self, device=0):
+    def __init__(self, device=0, hashfn="poseidon2"):
+        """hashfn: the ctx's hash suite (`ProverOpts::hashfn`): "poseidon2" (default) or "sha-256" (bx_set_hash_suite)."""
         self.lib = load_library()
         ctx = C.c_void_p()
         msg = self.lib.bx_init(device, C.byref(ctx))
@@ -194,6 +197,12 @@ class HipHal:
         for item in filter(None, os.environ.get("BX_TUNABLES", "").split(",")):
             name, _, value = item.partition("=")
             self._check(self.lib.bx_set_tunable(self.ctx, name.strip().encode(), int(value)))
+        if hashfn != "poseidon2":
+            try:
+                self.set_hash_suite(hashfn)
+            except HalError:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -381,8 +390,12 @@ class HipHal:
         return rc, d
 
     def get_hash_suite(self):
-        self.lib.bx_hash_suite_name.restype = C.c_char_p
-        return self.lib.bx_hash_suite_name().decode()
+        """Hal::get_hash_suite: the ctx's suite name, "poseidon2" or "sha-256"."""
+        return self.lib.bx_ctx_hash_suite(self.ctx).decode()
+
+    def set_hash_suite(self, hashfn):
+        """bx_set_hash_suite: refused for unknown names and while a prover exists on this ctx."""
+        self._check(self.lib.bx_set_hash_suite(self.ctx, str(hashfn).encode()))
 
     def has_unified_memory(self):
         self.lib.bx_has_unified_memory.argtypes, self.lib.bx_has_unified_memory.restype = [C.c_void_p], C.c_int

@@ -73,8 +73,9 @@ class SegmentReceipt:
     def verify_integrity(self, ctx=None):
         """`SegmentReceipt::verify_integrity_with_context` (bento/crates/workflow/src/tasks/prove.rs:53-55): CPU check of the
         whole seal (transcript, check identity, Merkle openings, DEEP quotients, FRI chain, code root == control ID).  `ctx` = a
-        VerifierContext; None = the built-in circuit's own control IDs.  Raises on rejection."""
-        verify_seal(self.seal, ctx=ctx)
+        VerifierContext; None = the built-in circuit's own control IDs.  The seal is checked under `hashfn`, the suite it was
+        made with (upstream carries it next to the seal the same way).  Raises on rejection."""
+        verify_seal(self.seal, ctx=ctx, hashfn=self.hashfn)
 
 
 class VerifierContext:
@@ -90,11 +91,15 @@ class VerifierContext:
             raise HalError(msg.decode())
         self.handle = h
 
-    def add_control_id(self, po2, digest_words):
+    def add_control_id(self, po2, digest_words, hashfn="poseidon2"):
+        """hashfn: the suite of the seals this ID is for (the context keeps each suite's IDs apart)."""
         d = np.ascontiguousarray(digest_words, dtype=np.uint32)
         if d.size != 8:
             raise HalError("a control ID is 8 digest words")
-        msg = self.lib.bx_verifier_ctx_add_control_id(self.handle, po2, d.ctypes.data)
+        if hashfn == "poseidon2":
+            msg = self.lib.bx_verifier_ctx_add_control_id(self.handle, po2, d.ctypes.data)
+        else:
+            msg = self.lib.bx_verifier_ctx_add_control_id_hashfn(self.handle, po2, d.ctypes.data, str(hashfn).encode())
         if msg:
             raise HalError(msg.decode())
         return self
@@ -162,18 +167,30 @@ def _declare(lib):
     lib.bx_prover_set_noise_seed.restype = C.c_char_p
     lib.bx_prover_last_upload.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(sz)]
     lib.bx_prover_last_upload.restype = C.c_char_p
+    lib.bx_verify_segment_hashfn.argtypes = [C.c_void_p, sz, C.c_char_p]
+    lib.bx_verify_segment_hashfn.restype = C.c_char_p
+    lib.bx_verify_segment_with_context_hashfn.argtypes = [C.c_void_p, sz, C.c_char_p, C.c_void_p, C.c_void_p]
+    lib.bx_verify_segment_with_context_hashfn.restype = C.c_char_p
+    lib.bx_verifier_ctx_add_control_id_hashfn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p]
+    lib.bx_verifier_ctx_add_control_id_hashfn.restype = C.c_char_p
+    lib.bx_synthetic_control_id_host_hashfn.argtypes = [C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]
+    lib.bx_synthetic_control_id_host_hashfn.restype = C.c_char_p
     lib._bx_prover_declared = True
 
 
-def verify_seal(seal_words, circuit=None, ctx=None):
+def verify_seal(seal_words, circuit=None, ctx=None, hashfn="poseidon2"):
     """Host-side verifier (include/bx_prover.h: bx_verify_segment); needs no GPU.  `circuit` = a bx_circuit_ops table
     (boundless_amd.circuit.CircuitOps) when the seal was made for another circuit than the built-in synthetic one; `ctx` = a
-    VerifierContext holding the control IDs the code root may be (None = the circuit's own check_code)."""
+    VerifierContext holding the control IDs the code root may be (None = the circuit's own check_code); `hashfn` = the suite the
+    seal was made under ("poseidon2" or "sha-256")."""
     lib = load_library()
     _declare(lib)
     a = np.ascontiguousarray(seal_words, dtype=np.uint32)
-    msg = lib.bx_verify_segment_with_context(a.ctypes.data, a.size, C.addressof(circuit) if circuit is not None else None,
-                                             ctx.handle if ctx is not None else None)
+    circ, vctx = C.addressof(circuit) if circuit is not None else None, ctx.handle if ctx is not None else None
+    if hashfn == "poseidon2":
+        msg = lib.bx_verify_segment_with_context(a.ctypes.data, a.size, circ, vctx)
+    else:
+        msg = lib.bx_verify_segment_with_context_hashfn(a.ctypes.data, a.size, str(hashfn).encode(), circ, vctx)
     if msg:
         raise HalError(msg.decode())
 
@@ -190,12 +207,15 @@ def set_verify_threads(threads):
         raise HalError(msg.decode())
 
 
-def synthetic_control_id_host(po2, w_code):
-    """The built-in circuit's control ID for (po2, w_code) computed on the host (include/bx_circuit.h); no GPU."""
+def synthetic_control_id_host(po2, w_code, hashfn="poseidon2"):
+    """The built-in circuit's control ID for (po2, w_code) under a hash suite, computed on the host (include/bx_circuit.h); no GPU."""
     lib = load_library()
     _declare(lib)
     out = np.zeros(8, np.uint32)
-    msg = lib.bx_synthetic_control_id_host(po2, w_code, out.ctypes.data)
+    if hashfn == "poseidon2":
+        msg = lib.bx_synthetic_control_id_host(po2, w_code, out.ctypes.data)
+    else:
+        msg = lib.bx_synthetic_control_id_host_hashfn(po2, w_code, str(hashfn).encode(), out.ctypes.data)
     if msg:
         raise HalError(msg.decode())
     return out
@@ -206,11 +226,16 @@ class HipProverServer:
 
     DEFAULT_WIDTHS = (16, 256, 64)  # SURVEY.md §8d synthetic segment
 
-    def __init__(self, device=0, po2=20, widths=DEFAULT_WIDTHS, hal=None, terms=0, degree=0, circuit=None):
+    def __init__(self, device=0, po2=20, widths=DEFAULT_WIDTHS, hal=None, terms=0, degree=0, circuit=None, hashfn=None):
         """terms / degree: the circuit's knobs (synthetic circuit: product terms per constraint, factors per term); 0 = defaults.
-        circuit: a bx_circuit_ops table (boundless_amd.circuit.CircuitOps) to prove another circuit than the built-in one."""
+        circuit: a bx_circuit_ops table (boundless_amd.circuit.CircuitOps) to prove another circuit than the built-in one.
+        hashfn: `ProverOpts::hashfn`, "poseidon2" or "sha-256"; None = the suite of `hal` (a context created here: "poseidon2").
+        A `hal` of another suite is switched (refused while another prover lives on it)."""
         self._own_hal = hal is None  # a context created here is released by close(); a caller's is the caller's
-        self.hal = hal or HipHal(device)
+        self.hal = hal or HipHal(device, hashfn=hashfn or "poseidon2")
+        if hashfn is not None and self.hal.get_hash_suite() != hashfn:
+            self.hal.set_hash_suite(hashfn)
+        self.hashfn = self.hal.get_hash_suite()
         self.lib = load_library()
         _declare(self.lib)
         self.po2 = po2
@@ -238,7 +263,8 @@ class HipProverServer:
             raise HalError(msg.decode())
         roots = np.zeros(32, np.uint32)
         self.lib.bx_prover_last_roots(self.handle, roots.ctypes.data)
-        return SegmentReceipt(seal=self._seal[: n.value].copy(), index=segment.index, po2=segment.po2, roots=roots.reshape(4, 8))
+        return SegmentReceipt(seal=self._seal[: n.value].copy(), index=segment.index, po2=segment.po2, hashfn=self.hashfn,
+                              roots=roots.reshape(4, 8))
 
     def prove_segment_bytes(self, blob, index=0):
         """The same from the serialized segment (`bincode::deserialize` + prove_segment in one call, prove.rs:36-49)."""
@@ -249,7 +275,7 @@ class HipProverServer:
             raise HalError(msg.decode())
         roots = np.zeros(32, np.uint32)
         self.lib.bx_prover_last_roots(self.handle, roots.ctypes.data)
-        return SegmentReceipt(seal=self._seal[: n.value].copy(), index=index, po2=self.po2, roots=roots.reshape(4, 8))
+        return SegmentReceipt(seal=self._seal[: n.value].copy(), index=index, po2=self.po2, hashfn=self.hashfn, roots=roots.reshape(4, 8))
 
     def prove_segment_buffer(self, buf, index=0):
         """prove_segment_bytes from a writable buffer (bytearray / numpy uint8) without the copy `bytes()` would make: what a
@@ -260,7 +286,7 @@ class HipProverServer:
         msg = self.lib.bx_prove_segment_bytes(self.handle, arr, mv.nbytes, self._seal.ctypes.data, self._seal.size, C.byref(n))
         if msg:
             raise HalError(msg.decode())
-        return SegmentReceipt(seal=self._seal[: n.value].copy(), index=index, po2=self.po2)
+        return SegmentReceipt(seal=self._seal[: n.value].copy(), index=index, po2=self.po2, hashfn=self.hashfn)
 
     def submit_segment_buffer(self, buf):
         mv = memoryview(buf)
@@ -283,7 +309,7 @@ class HipProverServer:
             raise HalError(msg.decode())
         roots = np.zeros(32, np.uint32)
         self.lib.bx_prover_last_roots(self.handle, roots.ctypes.data)
-        return SegmentReceipt(seal=self._seal[: n.value].copy(), index=index, po2=self.po2, roots=roots.reshape(4, 8))
+        return SegmentReceipt(seal=self._seal[: n.value].copy(), index=index, po2=self.po2, hashfn=self.hashfn, roots=roots.reshape(4, 8))
 
     def last_upload(self):
         """(milliseconds on the copy stream, bytes) of the upload of the segment proved last."""
@@ -301,7 +327,7 @@ class HipProverServer:
 
     def verifier_context(self):
         """A VerifierContext holding this prover's control ID (what an agent builds at start-up, lib.rs:241)."""
-        return VerifierContext().add_control_id(self.po2, self.control_id())
+        return VerifierContext().add_control_id(self.po2, self.control_id(), hashfn=self.hashfn)
 
     def close(self):
         if getattr(self, "handle", None):
@@ -318,6 +344,9 @@ class HipProverServer:
             pass
 
 
-def get_prover_server(device=0, po2=20, widths=HipProverServer.DEFAULT_WIDTHS):
-    """Counterpart of `risc0_zkvm::get_prover_server(&ProverOpts::default())` (bento/crates/workflow/src/lib.rs:247)."""
-    return HipProverServer(device=device, po2=po2, widths=widths)
+def get_prover_server(device=0, po2=20, widths=HipProverServer.DEFAULT_WIDTHS, hashfn="poseidon2"):
+    """Counterpart of `risc0_zkvm::get_prover_server(&ProverOpts { hashfn, .. })` (bento/crates/workflow/src/lib.rs:247 passes
+    ProverOpts::default(), i.e. "poseidon2"); "sha-256" is the other suite, anything else is refused."""
+    if hashfn not in ("poseidon2", "sha-256"):
+        raise HalError(f"unsupported hashfn {hashfn!r} (\"poseidon2\" or \"sha-256\")")
+    return HipProverServer(device=device, po2=po2, widths=widths, hashfn=hashfn)

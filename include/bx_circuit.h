@@ -104,7 +104,8 @@ const char* bx_prover_create_with_circuit(bx_ctx* ctx, const bx_segment_params* 
 /* bx_verify_segment against an explicit circuit (NULL = the synthetic one); the code root is checked by circuit->check_code. */
 const char* bx_verify_segment_with_circuit(const uint32_t* seal, size_t seal_words, const bx_circuit_ops* circuit);
 
-/* The circuit's control ID for the prover's shape: the Poseidon2 Merkle root of the committed code group, computed on the
+/* The circuit's control ID for the prover's shape: the Merkle root of the committed code group under the ctx's hash suite
+ * (bx_set_hash_suite: Poseidon2 by default, else SHA-256), computed on the
  * device with the kernels of a proof (code_group -> interpolate/zk_shift -> 4x LDE -> hash_rows -> tree).  Deterministic per
  * (circuit, shape).  Upstream ships these as a generated table (risc0-circuit-rv32im `control_id.rs`); an agent builds its
  * verifier context from this call at start-up (bento/crates/workflow/src/lib.rs:241 `verifier_ctx`).  Blocks; must not run
@@ -129,6 +130,17 @@ const char* bx_verify_segment_with_context(const uint32_t* seal, size_t seal_wor
  * evaluation on the coset 3<w_4N> -> Poseidon2 rows -> tree) behind bx_synthetic_circuit()->check_code for shapes outside its
  * built-in table (w_code = 16, po2 9..24).  Seconds at po2 >= 18; results are cached per (po2, w_code). */
 const char* bx_synthetic_control_id_host(uint32_t po2, uint32_t w_code, uint32_t id_out[8]);
+/* The same under a named hash suite ("poseidon2" or "sha-256"; anything else is refused).  SHA-256 IDs are computed and cached
+ * per (po2, w_code) like Poseidon2 IDs outside the table. */
+const char* bx_synthetic_control_id_host_hashfn(uint32_t po2, uint32_t w_code, const char* hashfn, uint32_t id_out[8]);
+/* bx_verifier_ctx_add_control_id for seals of a named hash suite.  A "sha-256" ID may hold any 32-bit words; the context keeps
+ * the IDs of each suite apart and a seal is only compared with those of the suite it is verified under. */
+const char* bx_verifier_ctx_add_control_id_hashfn(bx_verifier_ctx* v, uint32_t po2, const uint32_t id[8], const char* hashfn);
+/* bx_verify_segment_with_context for a seal made under the hash suite `hashfn` ("poseidon2" or "sha-256"; upstream carries it
+ * next to the seal in SegmentReceipt).  Under "sha-256" with vctx NULL only the synthetic circuit is accepted (its control IDs
+ * follow the suite; a plug-in circuit's check_code knows Poseidon2 IDs only): a plug-in circuit needs an explicit vctx. */
+const char* bx_verify_segment_with_context_hashfn(const uint32_t* seal, size_t seal_words, const char* hashfn, const bx_circuit_ops* circuit,
+                                                  const bx_verifier_ctx* vctx);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

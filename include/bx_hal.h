@@ -99,8 +99,18 @@ const char* bx_d2d(bx_ctx* ctx, bx_buf dst, bx_buf src, size_t words);
 const char* bx_eltwise_copy_elem_slice(bx_ctx* ctx, bx_buf into, const uint32_t* from, size_t from_len, size_t from_rows, size_t from_cols,
                                        size_t from_offset, size_t from_stride, size_t into_offset, size_t into_stride);
 const char* bx_sync(bx_ctx* ctx);
-/* Hal::get_hash_suite (its name: "poseidon2", the reference's default hashfn) and Hal::has_unified_memory (0). */
+/* The name of the default suite ("poseidon2", the reference's default hashfn) and Hal::has_unified_memory (0). */
 const char* bx_hash_suite_name(void);
+/* The ctx's hash suite (ProverOpts::hashfn): "poseidon2" (every ctx starts with it) or "sha-256".  Under "sha-256" bx_hash_rows,
+ * bx_hash_fold, bx_merkle_build, bx_merkle_fold, bx_prover_create and bx_prover_control_id follow FIPS 180-4 SHA-256 with the
+ * conventions of csrc/sha256_suite.hpp (rows: padded SHA-256 of the canonical values as little-endian bytes; interior nodes: one
+ * compression over the 64-byte pair; digests: the 32 output bytes as 8 little-endian words, not field elements).
+ * bx_hash_fold_indexed and the bx_image_* entry points stay Poseidon2 on every ctx (an image ID does not depend on hashfn), and
+ * bx_transcript_step is refused (there is no device-side SHA-256 RNG: a prover on a "sha-256" ctx draws on the host).
+ * Unknown names are refused, and so is a switch while a bx_prover exists on the ctx. */
+const char* bx_set_hash_suite(bx_ctx* ctx, const char* hashfn);
+/* Hal::get_hash_suite: the ctx's suite name (static storage) */
+const char* bx_ctx_hash_suite(bx_ctx* ctx);
 int bx_has_unified_memory(bx_ctx* ctx);
 
 /* ---- Hal NTT family ---- */
@@ -129,7 +139,8 @@ const char* bx_poseidon2_get_params(bx_ctx* ctx, uint32_t* rc213, uint32_t* diag
 /* The library's compiled-in default table, same layout; host only (no ctx, no GPU).  Its SHA-256 is pinned in
  * tests/golden/MANIFEST.json. */
 const char* bx_poseidon2_default_params(uint32_t* rc213, uint32_t* diag24);
-/* Hal::hash_rows(output, matrix): out_digests.len/8 rows; cols = matrix.len/rows. */
+/* Hal::hash_rows(output, matrix): out_digests.len/8 rows; cols = matrix.len/rows.  (This and the next three follow the ctx's
+ * hash suite: Poseidon2, or SHA-256 after bx_set_hash_suite(ctx, "sha-256").) */
 const char* bx_hash_rows(bx_ctx* ctx, bx_buf out_digests, bx_buf matrix);
 /* Hal::hash_fold(io, input_size, output_size): io[out+i] = H(io[in+2i] || io[in+2i+1]), digest indices. */
 const char* bx_hash_fold(bx_ctx* ctx, bx_buf io_digests, size_t input_size, size_t output_size);

@@ -1,0 +1,242 @@
+"""GPU: the `sha-256` hash suite (bx_set_hash_suite) — the HIP row / fold kernels and Merkle layers against tests/sha256_ref.py,
+suite switching, and whole proofs under it: accepted by the verifier, replayed cleanly by the independent Python transcript,
+deterministic, and refused where they must be."""
+import hashlib
+import os
+import sys
+import threading
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import sha256_ref as ref  # noqa: E402
+
+from boundless_amd.hal import HalError, HipHal  # noqa: E402
+from boundless_amd.prover import (HipProverServer, Segment, VerifierContext, get_prover_server,  # noqa: E402
+                                  synthetic_control_id_host, verify_seal)
+from oracle import oracle_lib as ol  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference")
+
+
+@pytest.fixture(scope="module")
+def shal():
+    h = HipHal(0, hashfn="sha-256")
+    yield h
+    h.close()
+
+
+def random_words(rng, n):
+    x = rng.integers(0, ref.P, n, dtype=np.uint64).astype(np.uint32)
+    x[: min(n, 3)] = [0, ref.P - 1, 1][: min(n, 3)]
+    return x
+
+
+@pytest.mark.parametrize("rows,cols_list", [(1, (0, 1, 13, 14, 15, 16, 17, 31, 32, 256, 352)),
+                                            (3, (0, 1, 13, 14, 15, 16, 17, 31, 32, 256, 352)),
+                                            (257, (0, 1, 13, 14, 15, 16, 17, 31, 32, 256)),
+                                            ((1 << 16) + 1, (1, 14, 17))])
+def test_hash_rows_matches_python(shal, rows, cols_list):
+    rng = np.random.default_rng(rows)
+    assert shal.get_hash_suite() == "sha-256"
+    for cols in cols_list:
+        for off in ((0,) if cols == 0 else (0, 3)):  # a slice at an unaligned word offset
+            m = random_words(rng, rows * cols + off)
+            buf = shal.copy_from(m) if m.size else shal.alloc(1)
+            src = buf.slice(off, rows * cols)
+            out = shal.alloc_digest(rows)
+            shal.hash_rows(out, src)
+            got = out.view().reshape(rows, 8)
+            want = ref.rows_hash(m[off:].reshape(cols, rows)) if cols else np.tile(ref.words_of(hashlib.sha256(b"").digest()), (rows, 1))
+            assert np.array_equal(got, want), (rows, cols, off)
+
+
+@pytest.mark.parametrize("log_rows", [1, 2, 6, 10, 14, 17, 18, 20])
+def test_merkle_fold_and_hash_fold_match_python(shal, log_rows):
+    rows = 1 << log_rows
+    rng = np.random.default_rng(log_rows)
+    leaves = rng.integers(0, 2**32, (rows, 8), dtype=np.uint64).astype(np.uint32)  # digest words: any 32-bit value
+    want = ref.merkle_nodes(leaves)
+    host = np.zeros((2 * rows, 8), np.uint32)
+    host[rows:] = leaves
+    nodes = shal.copy_from(host.reshape(-1))
+    shal._check(shal.lib.bx_merkle_fold(shal.ctx, nodes.raw, rows))
+    assert np.array_equal(nodes.view().reshape(2 * rows, 8)[1:], want[1:])
+    # one layer through bx_hash_fold
+    io = shal.copy_from(host.reshape(-1))
+    shal.hash_fold(io, rows, rows // 2)
+    assert np.array_equal(io.view().reshape(2 * rows, 8)[rows // 2:rows], want[rows // 2:rows])
+
+
+@pytest.mark.parametrize("log_rows,cols", [(1, 3), (12, 16), (20, 16)])
+def test_merkle_build_matches_python(shal, log_rows, cols):
+    rows = 1 << log_rows
+    rng = np.random.default_rng(cols + log_rows)
+    m = random_words(rng, rows * cols)
+    nodes = shal.alloc_digest(2 * rows)
+    shal.merkle_build(nodes, shal.copy_from(m), rows)
+    want = ref.merkle_nodes(ref.rows_hash(m.reshape(cols, rows)))
+    assert np.array_equal(nodes.view().reshape(2 * rows, 8)[1:], want[1:])
+
+
+def test_suite_switching_rules(shal):
+    h = HipHal(0)
+    try:
+        assert h.get_hash_suite() == "poseidon2"
+        for bad in ("sha256", "poseidon254", "", "SHA-256"):
+            with pytest.raises(HalError, match="unknown hashfn"):
+                h.set_hash_suite(bad)
+        with pytest.raises(HalError, match="unknown hashfn"):
+            HipHal(0, hashfn="blake2b")
+        # a default ctx in the same process still computes Poseidon2 words
+        rows, cols = 64, 20
+        m = random_words(np.random.default_rng(1), rows * cols)
+        out = h.alloc_digest(rows)
+        h.hash_rows(out, h.copy_from(m))
+        want = np.zeros(8 * rows, np.uint32)
+        ol.lib().bxo_hash_rows(want, m, rows, cols)
+        assert np.array_equal(out.view(), want)
+        h.set_hash_suite("sha-256")
+        assert h.get_hash_suite() == "sha-256"
+        srv = HipProverServer(0, po2=9, widths=(2, 4, 4), hal=h)
+        assert srv.hashfn == "sha-256"
+        with pytest.raises(HalError, match="destroy the provers"):
+            h.set_hash_suite("poseidon2")
+        srv.close()
+        h.set_hash_suite("poseidon2")
+        assert h.get_hash_suite() == "poseidon2"
+    finally:
+        h.close()
+
+
+def test_image_id_and_transcript_step_on_a_sha256_ctx(shal):
+    from boundless_amd import image
+
+    blob = open(os.path.join(REF, "boundless-povw-log-updater.bin"), "rb").read()
+    iid = open(os.path.join(REF, "boundless-povw-log-updater.iid"), "rb").read()
+    assert image.compute_image_id(blob, shal) == iid  # the image ID does not depend on hashfn
+    state = shal.alloc_zeroed(25)
+    dig = shal.alloc_zeroed(8)
+    out = shal.alloc_zeroed(4)
+    with pytest.raises(HalError, match="transcript_step"):
+        shal.transcript_step(state, dig, 1, out, 1)
+
+
+def prove(po2, widths, seed, hal=None, noise_seed=None, srv=None):
+    own = srv is None
+    srv = srv or HipProverServer(0, po2=po2, widths=widths, hal=hal, hashfn="sha-256")
+    try:
+        r = srv.prove_segment(Segment(index=0, po2=po2, seed=seed, noise_seed=noise_seed))
+        return r, srv.control_id()
+    finally:
+        if own:
+            srv.close()
+
+
+def test_sha256_proofs_at_random_shapes_verify_and_replay(shal):
+    rng = np.random.default_rng(2024)
+    for k in range(6):
+        po2 = int(rng.integers(9, 17))
+        widths = (int(rng.integers(1, 20)), int(rng.integers(1, 40)), int(rng.integers(1, 20)))
+        r, cid = prove(po2, widths, 1000 + k, hal=shal)
+        assert r.hashfn == "sha-256"
+        verify_seal(r.seal, hashfn="sha-256")
+        r.verify_integrity()
+        ref.replay_seal(r.seal)
+        assert np.array_equal(cid, r.roots[0])
+        assert np.array_equal(cid, synthetic_control_id_host(po2, widths[0], hashfn="sha-256")), (po2, widths)
+        with pytest.raises(HalError):
+            verify_seal(r.seal)  # not a Poseidon2 seal
+
+
+@pytest.mark.parametrize("po2", [20, 21])
+def test_sha256_proof_at_full_size(po2):
+    srv = get_prover_server(0, po2=po2, hashfn="sha-256")
+    try:
+        r = srv.prove_segment(Segment(index=0, po2=po2, seed=77))
+        verify_seal(r.seal, hashfn="sha-256")
+        ref.replay_seal(r.seal)
+        vctx = srv.verifier_context()
+        r.verify_integrity(ctx=vctx)
+        assert np.array_equal(srv.prove_segment(Segment(index=0, po2=po2, seed=77)).seal, r.seal)
+    finally:
+        srv.close()
+
+
+def test_sha256_seals_are_deterministic_across_lanes_and_tunables():
+    po2, widths = 12, (4, 16, 8)
+    base, _ = prove(po2, widths, 5, noise_seed=9)
+    again, _ = prove(po2, widths, 5, noise_seed=9)
+    assert np.array_equal(base.seal, again.seal)
+    # three provers in flight on three contexts
+    out = [None] * 3
+    def lane(i):
+        out[i] = prove(po2, widths, 5, noise_seed=9)[0].seal
+    th = [threading.Thread(target=lane, args=(i,)) for i in range(3)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    for s in out:
+        assert np.array_equal(s, base.seal)
+    for name in ("dev_draws", "gather_defer"):
+        h = HipHal(0, hashfn="sha-256")
+        try:
+            h._check(h.lib.bx_set_tunable(h.ctx, name.encode(), 1 if name == "dev_draws" else 0))
+            s, _ = prove(po2, widths, 5, hal=h, noise_seed=9)
+            assert np.array_equal(s.seal, base.seal), name
+        finally:
+            h.close()
+
+
+def test_sha256_seal_rejections(shal):
+    po2, widths = 10, (4, 8, 4)
+    r, cid = prove(po2, widths, 31, hal=shal)
+    seal = r.seal
+    verify_seal(seal, hashfn="sha-256")
+    p2_seal, _ = ol.prove_segment(po2, *widths, 31)
+    with pytest.raises(HalError):
+        verify_seal(p2_seal, hashfn="sha-256")
+    with pytest.raises(HalError):
+        verify_seal(seal)
+    # one flipped word: the code group's top layer, a sibling digest / opened value in the first query, the final coefficients
+    n_globals = 2
+    code_top = 6 + n_globals
+    ref.replay_seal(seal)
+    for where in ("top", "value", "final", "sibling"):
+        bad = seal.copy()
+        if where == "top":
+            i = code_top + 3
+        elif where == "value":
+            i = _queries_start(seal, po2, widths)
+        elif where == "sibling":
+            i = _queries_start(seal, po2, widths) + widths[0] + 2
+        else:
+            i = _queries_start(seal, po2, widths) - 5
+        bad[i] ^= 1
+        with pytest.raises(HalError):
+            verify_seal(bad, hashfn="sha-256")
+        with pytest.raises(ref.ReplayError):  # a flipped top node or final coefficient moves the query positions
+            ref.replay_seal(bad)
+    # a code root that is the Poseidon2 control ID is not a SHA-256 control ID
+    vctx = VerifierContext().add_control_id(po2, ol.control_id(po2, widths[0]), hashfn="sha-256")
+    with pytest.raises(HalError, match="control ID"):
+        verify_seal(seal, ctx=vctx, hashfn="sha-256")
+    verify_seal(seal, ctx=VerifierContext().add_control_id(po2, cid, hashfn="sha-256"), hashfn="sha-256")
+    with pytest.raises(HalError, match="control ID"):
+        verify_seal(seal, ctx=VerifierContext().add_control_id(po2, ol.control_id(po2, widths[0])), hashfn="sha-256")
+
+
+def _queries_start(seal, po2, widths):
+    """Offset of the first query's words: everything after it has a length fixed by the shape."""
+    N, D = 1 << po2, 4 << po2
+    shapes = [(D, w) for w in (*widths, ref.CHECK_SIZE)]
+    size = N
+    while size > ref.FRI_MIN_DEGREE:
+        shapes.append((4 * size // ref.FRI_FOLD, 4 * ref.FRI_FOLD))
+        size //= ref.FRI_FOLD
+    per_query = sum(c + 8 * ((r.bit_length() - 1) - ref._top_layer(r.bit_length() - 1)) for r, c in shapes)
+    return seal.size - ref.QUERIES * per_query
+
