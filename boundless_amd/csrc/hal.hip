@@ -18,6 +18,7 @@
 #include <unistd.h>
 
 #include "ctx.hpp"
+#include "groth16.hpp"
 #include "poseidon2_params.hpp"
 
 namespace bx {
@@ -322,6 +323,7 @@ extern "C" const char* bx_free(bx_ctx* c) try {
     if (!c) return nullptr;
     (void)hipSetDevice(c->device);
     (void)stream_wait(c);
+    groth16_release_keys(c);  // Groth16 keys still loaded on this ctx (bx_groth16.h)
     drain_profile(c);
     ntt_free_tables(c);
     if (c->d_p2) (void)hipFree(c->d_p2);
