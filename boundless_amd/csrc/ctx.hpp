@@ -149,6 +149,8 @@ struct bx_ctx {
     hipEvent_t wait_ev = nullptr;
     long eval_x4 = 1;                // batch_evaluate_any: 16-byte loads for whole 2^15-coefficient segments (0 = the dword kernel)
     long deep_bitrev = 1;            // segment prover: keep trace coefficients bit-reversed through the DEEP phase (read at bx_prover_create)
+    long code_commit_once = 1;       // segment prover, built-in circuit: commit the code group with a prover's first proof and keep it
+                                     // (0 = commit it again with every proof; read at bx_prover_create)
 
     // timing
     hipEvent_t t0 = nullptr, t1 = nullptr;

@@ -120,6 +120,12 @@ struct bx_prover {
     DevBuf combos, final_poly, which, xs, evals, rems, positions, qout;
     DevBuf code_w;  // the code group's WITNESS (what witgen reads); groups[0].coeffs is interpolated in place by the commit, which is
                     // enqueued before the segment's bytes have arrived (prove_prologue)
+    // The code group is a function of the shape alone (bx_circuit.h), so its commitment is made once per prover: the first proof (or
+    // bx_prover_control_id) runs prove_prologue and keeps what tree_fetch brought back for groups[0].tree; while code_committed holds,
+    // later proofs leave groups[0] and code_w alone (a proof only reads them after the prologue) and absorb code_top instead.
+    bool code_once = false;          // built-in circuit and the ctx tunable code_commit_once (read at create)
+    bool code_committed = false;     // groups[0].{coeffs,evaluated,tree.nodes}, code_w and code_top are this shape's; dropped by any error
+    std::vector<uint32_t> code_top;  // root + top layer of groups[0].tree as fetched: 8 * (2 * top_size - 1) words
     DevBuf tap_ptrs, tap_flags;  // per tap evaluation: the device address of its coefficient column and its storage order (N >= 2^15)
     std::vector<std::vector<uint32_t>> combo_backs;  // trace combos in order of first appearance; the check combo comes after them
     std::vector<uint32_t> tap_which;                 // polynomial index of every tap evaluation (fixed per shape)
@@ -280,6 +286,9 @@ extern "C" const char* bx_prover_create_with_circuit(bx_ctx* c, const bx_segment
         if (const char* e = circuit->normalize(circuit->user, &p->shape)) return set_msg(c, e);
     p->N = (size_t)1 << shape->po2;
     p->coeffs_bitrev = shape->po2 >= 15 && c->deep_bitrev;
+    // only the built-in circuit is known to the library to be shape-only (synth_code_cell with a constant seed); a plug-in's code_group
+    // is opaque and is called for every proof
+    p->code_once = circuit == bx_synthetic_circuit() && c->code_commit_once;
     p->err[0] = 0;
     p->h2.load(c->h_rc, c->h_diag);
     p->hs = HostSuite{c->hash_suite, &p->h2};
@@ -417,10 +426,12 @@ extern "C" const char* bx_prover_last_roots(const bx_prover* p, uint32_t roots_o
 
 static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t* seal_out, size_t seal_cap, size_t* seal_words);
 
-// What a proof can start before its segment has arrived: the code group (a function of the shape) and its whole commitment —
-// 2.2 ms of device work at 2^20 that the upload of the segment's bytes hides behind.  The witness of the code group is kept in
-// code_w for witgen (the commit interpolates groups[0].coeffs in place).  Enqueues only.
+// What a proof can start before its segment has arrived: the code group (a function of the shape) and its whole commitment.  The
+// witness of the code group is kept in code_w for witgen (the commit interpolates groups[0].coeffs in place).  Enqueues only.
+// With code_once this is the work of a prover's FIRST proof (or control ID) alone: once the commitment is kept (code_committed) there
+// is nothing to enqueue, and witgen waits for the segment's upload at once (what a lone proof pays for that: DESIGN.md section 5).
 static const char* prove_prologue(bx_prover* p) {
+    if (p->code_committed) return nullptr;
     bx_ctx* c = p->c;
     const bx_circuit_ops* circ = p->circ;
     TraceRange tr(c, "bx:commit_code");
@@ -477,18 +488,22 @@ extern "C" const char* bx_prove_submitted(bx_prover* p, uint32_t* seal_out, size
     SegSlot* sl = nullptr;
     {
         std::lock_guard<std::mutex> g(p->seg_mu);
-        if (p->seg_count == 0) return perr(p, "bx_prove_submitted: no segment was submitted");
+        if (p->seg_count == 0) {
+            p->code_committed = false;
+            return perr(p, "bx_prove_submitted: no segment was submitted");
+        }
         sl = &p->seg[p->seg_head];
     }
     const char* r = nullptr;
-    // the code group's commitment is enqueued first (bx_prove_segment_bytes did that before it even staged the bytes); everything from
-    // witgen on waits for the upload's event — on the stream, not on the host
+    // a code group's commitment the prover does not hold yet is enqueued first (bx_prove_segment_bytes did that before it even staged
+    // the bytes); everything from witgen on waits for the upload's event — on the stream, not on the host
     if (hipSetDevice(p->c->device) != hipSuccess) r = perr(p, "bx_prove_segment: hipSetDevice failed");
     else if (p->c->gq_n && (r = gather_flush(p->c)) != nullptr) {
     } else if (!p->prologue_done && (r = prove_prologue(p)) != nullptr) {
     } else if (hipStreamWaitEvent(p->c->stream, sl->up, 0) != hipSuccess) r = perr(p, "bx_prove_segment: could not order the proof behind the segment's upload");
     else r = prove_segment_impl(p, *sl, seal_out, seal_cap, seal_words);
     p->prologue_done = false;
+    if (r) p->code_committed = false;  // conservatively: the next proof commits the code group again
     // a proof ends with a blocking read-back of the whole stream, so the upload is over: its duration is on the two events
     if (!r && hipEventElapsedTime(&p->last_upload_ms, sl->up0, sl->up) == hipSuccess) p->last_upload_bytes = sl->len;
     if (r) (void)hipEventSynchronize(sl->up);  // failed before the stream got there: the slot must be idle before it is reused
@@ -498,21 +513,27 @@ extern "C" const char* bx_prove_submitted(bx_prover* p, uint32_t* seal_out, size
     return r;
 } BX_ABI_CATCH((p ? p->c : nullptr), "bx_prove_submitted")
 
-extern "C" const char* bx_prove_segment_bytes(bx_prover* p, const uint8_t* segment, size_t len, uint32_t* seal_out, size_t seal_cap, size_t* seal_words) try {
-    if (!p) return "bx_prove_segment_bytes: null prover";
+static const char* prove_segment_bytes_impl(bx_prover* p, const uint8_t* segment, size_t len, uint32_t* seal_out, size_t seal_cap, size_t* seal_words) {
     {
         std::lock_guard<std::mutex> g(p->seg_mu);
         if (p->seg_count != 0) return perr(p, "bx_prove_segment_bytes: segments submitted earlier are still outstanding (use bx_prove_submitted)");
     }
-    // start what does not need the bytes, then stage and upload them while the device works on it
+    // start what does not need the bytes (the code group's commitment, when the prover does not hold it yet), then stage and upload
+    // them while the device works on it
     if (hipSetDevice(p->c->device) != hipSuccess) return perr(p, "bx_prove_segment: hipSetDevice failed");
     if (const char* e = prove_prologue(p)) return e;
     p->prologue_done = true;
     if (const char* e = bx_prover_submit_segment(p, segment, len)) {
-        p->prologue_done = false;  // the code commitment just enqueued is simply redone by the next proof
+        p->prologue_done = false;  // a code commitment just enqueued is simply redone by the next proof
         return e;
     }
     return bx_prove_submitted(p, seal_out, seal_cap, seal_words);
+}
+extern "C" const char* bx_prove_segment_bytes(bx_prover* p, const uint8_t* segment, size_t len, uint32_t* seal_out, size_t seal_cap, size_t* seal_words) try {
+    if (!p) return "bx_prove_segment_bytes: null prover";
+    const char* r = prove_segment_bytes_impl(p, segment, len, seal_out, seal_cap, seal_words);
+    if (r) p->code_committed = false;  // any error: the next proof commits the code group again
+    return r;
 } BX_ABI_CATCH((p ? p->c : nullptr), "bx_prove_segment_bytes")
 
 extern "C" const char* bx_prover_last_upload(const bx_prover* p, double* ms, size_t* bytes) {
@@ -539,12 +560,15 @@ extern "C" const char* bx_prove_segment_zk(bx_prover* p, uint64_t seed, uint64_t
     return bx_prove_segment(p, seed, seal_out, seal_cap, seal_words);
 } BX_ABI_CATCH((p ? p->c : nullptr), "bx_prove_segment_zk")
 
-// The circuit's control ID for this shape: the code group through the same commit as in a proof, root read back.
-extern "C" const char* bx_prover_control_id(bx_prover* p, uint32_t id_out[8]) try {
-    if (!p) return "bx_prover_control_id: null prover";
-    if (!id_out) return perr(p, "bx_prover_control_id: null output");
+// The circuit's control ID for this shape: the code group through the same commit as in a proof, root read back.  It fills and is
+// served from the prover's kept code commitment: after the first call (or the first proof) nothing is launched.
+static const char* control_id_impl(bx_prover* p, uint32_t id_out[8]) {
     bx_ctx* c = p->c;
     if (hipSetDevice(c->device) != hipSuccess) return perr(p, "bx_prover_control_id: hipSetDevice failed");
+    if (p->code_committed) {
+        memcpy(id_out, p->code_top.data(), 32);
+        return nullptr;
+    }
     Group& G = p->groups[0];
     PV(prove_prologue(p));
     size_t used = 0;
@@ -552,7 +576,18 @@ extern "C" const char* bx_prover_control_id(bx_prover* p, uint32_t id_out[8]) tr
     PV(tree_fetch(p, G.tree, &used, &host));
     PV(d2h_batch_wait(c));
     memcpy(id_out, host, 32);
+    if (p->code_once) {
+        p->code_top.assign(host, host + 8 * (2 * G.tree.top_size() - 1));
+        p->code_committed = true;
+    }
     return nullptr;
+}
+extern "C" const char* bx_prover_control_id(bx_prover* p, uint32_t id_out[8]) try {
+    if (!p) return "bx_prover_control_id: null prover";
+    if (!id_out) return perr(p, "bx_prover_control_id: null output");
+    const char* r = control_id_impl(p, id_out);
+    if (r) p->code_committed = false;
+    return r;
 } BX_ABI_CATCH((p ? p->c : nullptr), "bx_prover_control_id")
 
 static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t* seal_out, size_t seal_cap, size_t* seal_words) {
@@ -580,7 +615,7 @@ static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t
     uint32_t globals[BX_MAX_GLOBALS];
     memset(globals, 0, sizeof globals);
     {
-        TraceRange tr(c, "bx:witgen");  // the code group and its commitment are already enqueued (prove_prologue)
+        TraceRange tr(c, "bx:witgen");  // the code group and its commitment are kept from an earlier proof or already enqueued (prove_prologue)
         PV(circ->witgen(circ->user, p->circ_state, c, p->code_w.b, p->groups[1].coeffs.b, seg.host, seg.len,
                         bx_buf{seg.dev, (seg.len + 3) / 4}, globals));
     }
@@ -598,9 +633,15 @@ static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t
         const uint32_t* host[2] = {nullptr, nullptr};
         TraceRange tr(c, "bx:commit_data");
         PV(commit_group_work(p, p->groups[1]));
-        PV(tree_fetch(p, p->groups[0].tree, &used, &host[0]));
+        if (!p->code_committed) PV(tree_fetch(p, p->groups[0].tree, &used, &host[0]));
         PV(tree_fetch(p, p->groups[1].tree, &used, &host[1]));
         PV(d2h_batch_wait(c));
+        if (p->code_committed) {
+            host[0] = p->code_top.data();  // the code tree's root and top layer as the first proof fetched them
+        } else if (p->code_once) {
+            p->code_top.assign(host[0], host[0] + 8 * (2 * p->groups[0].tree.top_size() - 1));
+            p->code_committed = true;
+        }
         for (int g = 0; g < 2; ++g) {
             tree_absorb(p->groups[g].tree, host[g], T);
             memcpy(p->last_roots + 8 * g, p->groups[g].tree.root, 32);

@@ -62,7 +62,10 @@ typedef struct bx_circuit_ops {
      * ALONE — never of the segment — because its Merkle root is the circuit's CONTROL ID for that shape: what upstream's
      * verifier compares the seal's code root with (`check_code`, risc0-zkp 3.0.3 verify; the table one level up is
      * contracts/src/blake3-groth16/ControlID.sol:13).  bx_prove_segment calls it before witgen; bx_prover_control_id runs it
-     * through the same commit to produce the ID. */
+     * through the same commit to produce the ID.  A plug-in's code_group is opaque to the library and is called, and its group
+     * committed, for every proof.  The built-in circuit's is known to be shape-only, so a prover commits it the first time (first
+     * proof or bx_prover_control_id) and keeps the commitment for its lifetime (ctx tunable code_commit_once, default 1); an
+     * opt-in for plug-ins needs a new member here and is a follow-up (this struct carries no size field). */
     const char* (*code_group)(void* user, void* state, bx_ctx* ctx, bx_buf code);
     /* Witness generation for the data group from the SEGMENT'S BYTES — what the reference hands to
      * `prover.prove_segment(&ctx, &segment)` (bento/crates/workflow/src/tasks/prove.rs:41-49) after
@@ -106,8 +109,9 @@ const char* bx_verify_segment_with_circuit(const uint32_t* seal, size_t seal_wor
 
 /* The circuit's control ID for the prover's shape: the Merkle root of the committed code group under the ctx's hash suite
  * (bx_set_hash_suite: Poseidon2 by default, else SHA-256), computed on the
- * device with the kernels of a proof (code_group -> interpolate/zk_shift -> 4x LDE -> hash_rows -> tree).  Deterministic per
- * (circuit, shape).  Upstream ships these as a generated table (risc0-circuit-rv32im `control_id.rs`); an agent builds its
+ * device with the kernels of a proof (code_group -> interpolate/zk_shift -> 4x LDE -> hash_rows -> tree) the first time.  With the
+ * built-in circuit the prover keeps that commitment: later calls, and calls after a proof, return the stored root and launch
+ * nothing, and a call before the first proof spares that proof the work.  Deterministic per (circuit, shape).  Upstream ships these as a generated table (risc0-circuit-rv32im `control_id.rs`); an agent builds its
  * verifier context from this call at start-up (bento/crates/workflow/src/lib.rs:241 `verifier_ctx`).  Blocks; must not run
  * concurrently with a proof on the same prover. */
 const char* bx_prover_control_id(bx_prover* prover, uint32_t id_out[8]);
