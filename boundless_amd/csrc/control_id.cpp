@@ -10,7 +10,7 @@
 //
 // The host computation below shares no code with the device path (ntt.hip / poseidon2.hip) nor with the test oracle: plain
 // iterative radix-2 transforms in natural order — coefficients by an inverse DFT on <w_N>, the coset shift as a_j * 3^j, the 4N
-// evaluations by a zero-padded forward DFT (row i = f(3 * w_4N^i)) — then the row sponge and the pair hashes of transcript.hpp.
+// evaluations by a zero-padded forward DFT (row i = f(3 * w_4N^i)) — then the row and pair hashes of hash_suite.hpp.
 #include <stdio.h>
 #include <string.h>
 
@@ -24,7 +24,7 @@
 #include "circuit.hpp"
 #include "fp.hpp"
 #include "poseidon2_params.hpp"
-#include "transcript.hpp"
+#include "hash_suite.hpp"
 
 namespace {
 using namespace bx;
@@ -117,14 +117,7 @@ const char* host_control_id(uint32_t po2, uint32_t wc, int suite, uint32_t out[8
     });
     ev.clear();
     ev.shrink_to_fit();
-    for (size_t sz = dom; sz > 1; sz >>= 1) {
-        std::vector<uint32_t> next(8 * (sz / 2));
-        parallel_ranges(sz / 2, [&](size_t b, size_t e) {
-            for (size_t i = b; i < e; ++i) h.hash_pair(&next[8 * i], &layer[16 * i], &layer[16 * i + 8]);
-        });
-        layer.swap(next);
-    }
-    memcpy(out, layer.data(), 32);
+    h.merkle_root(out, std::move(layer), dom, [](size_t n, auto&& body) { parallel_ranges(n, body); });
     return nullptr;
 }
 
@@ -178,14 +171,26 @@ const char* synth_check_code_suite(const bx_segment_params* s, const uint32_t ro
     return memcmp(id, root, 32) == 0 ? nullptr : "the code group's root is not this circuit's control ID for the shape (the seal was made with another code group)";
 }
 const char* synth_check_code(void*, const bx_segment_params* s, const uint32_t root[8]) {
-    return synth_check_code_suite(s, root, SUITE_POSEIDON2);
+    return synth_check_code_suite(s, root, SUITE_POSEIDON2);  // a table's check_code has no suite parameter: the default one
 }
 }  // namespace bx
 
 struct bx_verifier_ctx {
-    std::vector<std::pair<uint32_t, Digest>> ids;    // Poseidon2 control IDs
-    std::vector<std::pair<uint32_t, Digest>> sha;    // SHA-256 control IDs (any 32-bit words)
+    struct Id { int suite; uint32_t po2; Digest digest; };
+    std::vector<Id> ids;  // a set, every suite's IDs together
 };
+
+namespace bx {
+// what verify.cpp asks a context: is `root` one of the IDs registered for po2?
+bool verifier_ctx_contains_suite(const bx_verifier_ctx* v, int suite, uint32_t po2, const uint32_t root[8]) {
+    for (auto& e : v->ids)
+        if (e.suite == suite && e.po2 == po2 && memcmp(e.digest.data(), root, 32) == 0) return true;
+    return false;
+}
+bool verifier_ctx_contains(const bx_verifier_ctx* v, uint32_t po2, const uint32_t root[8]) {
+    return verifier_ctx_contains_suite(v, SUITE_POSEIDON2, po2, root);  // the form without a suite means the default one
+}
+}  // namespace bx
 
 extern "C" {
 
@@ -216,58 +221,30 @@ const char* bx_verifier_ctx_create(bx_verifier_ctx** out) {
 }
 void bx_verifier_ctx_destroy(bx_verifier_ctx* v) { delete v; }
 const char* bx_verifier_ctx_add_control_id(bx_verifier_ctx* v, uint32_t po2, const uint32_t id[8]) {
-    if (!v || !id) return "bx_verifier_ctx_add_control_id: null argument";
-    if (po2 < 9 || po2 > 24) return "bx_verifier_ctx_add_control_id: po2 must be in [9, 24]";
-    for (int i = 0; i < 8; ++i)
-        if (id[i] >= bx::P) return "bx_verifier_ctx_add_control_id: a digest word is not a canonical field element";
-    try {
-        Digest d;
-        memcpy(d.data(), id, 32);
-        for (auto& e : v->ids)
-            if (e.first == po2 && e.second == d) return nullptr;  // a set
-        v->ids.emplace_back(po2, d);
-        return nullptr;
-    } catch (const std::exception&) {
-        return "bx_verifier_ctx_add_control_id: out of memory";
-    }
+    return bx_verifier_ctx_add_control_id_hashfn(v, po2, id, "poseidon2");  // the ABI without a hashfn means the default suite
 }
 const char* bx_verifier_ctx_add_control_id_hashfn(bx_verifier_ctx* v, uint32_t po2, const uint32_t id[8], const char* hashfn) {
     const int suite = parse_hash_suite(hashfn);
     if (suite < 0) return "bx_verifier_ctx_add_control_id: unknown hashfn (\"poseidon2\" or \"sha-256\")";
-    if (suite == SUITE_POSEIDON2) return bx_verifier_ctx_add_control_id(v, po2, id);
     if (!v || !id) return "bx_verifier_ctx_add_control_id: null argument";
     if (po2 < 9 || po2 > 24) return "bx_verifier_ctx_add_control_id: po2 must be in [9, 24]";
+    for (int i = 0; i < 8; ++i)
+        if (HostSuite{suite}.digests_are_elems() && id[i] >= bx::P) return "bx_verifier_ctx_add_control_id: a digest word is not a canonical field element";
     try {
-        Digest d;
-        memcpy(d.data(), id, 32);
-        for (auto& e : v->sha)
-            if (e.first == po2 && e.second == d) return nullptr;
-        v->sha.emplace_back(po2, d);
+        bx_verifier_ctx::Id d{suite, po2, {}};
+        memcpy(d.digest.data(), id, 32);
+        if (!bx::verifier_ctx_contains_suite(v, suite, po2, id)) v->ids.push_back(d);
         return nullptr;
     } catch (const std::exception&) {
         return "bx_verifier_ctx_add_control_id: out of memory";
     }
 }
-size_t bx_verifier_ctx_size(const bx_verifier_ctx* v) { return v ? v->ids.size() + v->sha.size() : 0; }
+size_t bx_verifier_ctx_size(const bx_verifier_ctx* v) { return v ? v->ids.size() : 0; }
 size_t bx_verifier_ctx_count(const bx_verifier_ctx* v, uint32_t po2) {
     size_t n = 0;
-    if (v) {
-        for (auto& e : v->ids) n += e.first == po2;
-        for (auto& e : v->sha) n += e.first == po2;
-    }
+    if (v)
+        for (auto& e : v->ids) n += e.po2 == po2;
     return n;
 }
 
 }  // extern "C"
-
-namespace bx {
-// what verify.cpp asks a context: is `root` one of the IDs registered for po2?
-bool verifier_ctx_contains_suite(const bx_verifier_ctx* v, int suite, uint32_t po2, const uint32_t root[8]) {
-    for (auto& e : suite == SUITE_SHA256 ? v->sha : v->ids)
-        if (e.first == po2 && memcmp(e.second.data(), root, 32) == 0) return true;
-    return false;
-}
-bool verifier_ctx_contains(const bx_verifier_ctx* v, uint32_t po2, const uint32_t root[8]) {
-    return verifier_ctx_contains_suite(v, SUITE_POSEIDON2, po2, root);
-}
-}  // namespace bx

@@ -281,11 +281,18 @@ const char* prefix_products_lookback(bx_ctx* c, uint32_t* io, size_t n, size_t c
 const char* ntt_init_tables(bx_ctx* c);
 void ntt_free_tables(bx_ctx* c);
 const char* poseidon2_upload_params(bx_ctx* c);
-// the `sha-256` suite's Merkle work (sha256.hip), dispatched to by the hash entry points of poseidon2.hip on a sha-256 ctx
-const char* sha256_hash_rows(bx_ctx* c, uint32_t* out, const uint32_t* matrix, size_t rows, size_t cols);
-const char* sha256_hash_fold(bx_ctx* c, uint32_t* io, size_t input_size, size_t output_size);
-const char* sha256_fold_layers(bx_ctx* c, uint32_t* nodes, size_t rows);
-const char* hash_rows_suite(bx_ctx* c, bx_buf out, bx_buf matrix, int suite);  // bx_hash_rows under an explicit suite (poseidon2.hip)
+// A hash suite's Merkle launches: what the hash entry points and the layer schedule of hal.hip use, defined beside the suite's
+// kernels (poseidon2.hip, sha256.hip).  fold3 stands before fold2 as in the schedule: a table's initialiser is the first use of
+// the kernel templates, and the order of first use is their order in the code object (device_code_hash).
+struct HashLaunchers {
+    const char* (*rows)(bx_ctx* c, uint32_t* out, const uint32_t* matrix, size_t rows, size_t cols);  // Hal::hash_rows
+    const char* (*fold)(bx_ctx* c, uint32_t* io, size_t input_size, size_t output_size);              // Hal::hash_fold: one layer
+    const char* (*fold3)(bx_ctx* c, uint32_t* io, size_t input_size);  // three levels of a large layer in one launch, depth first per lane
+    const char* (*fold2)(bx_ctx* c, uint32_t* io, size_t input_size);  // two
+    const char* (*fold_small)(bx_ctx* c, uint32_t* io, size_t input_size, size_t per_wg, int levels);  // a small layer through LDS: per_wg = 2^levels <= 512 inputs per workgroup
+};
+HashLaunchers poseidon2_launchers(), sha256_launchers();  // functions, not objects: a namespace-scope constant would be emitted for the device too
+const char* hash_rows_suite(bx_ctx* c, bx_buf out, bx_buf matrix, int suite);  // bx_hash_rows under an explicit suite (hal.hip)
 
 // the synthetic circuit's device stages (circuit.hip), driven by prover.hip
 struct Circuit;

@@ -19,6 +19,7 @@
 
 #include "ctx.hpp"
 #include "groth16.hpp"
+#include "hash_suite.hpp"
 #include "poseidon2_params.hpp"
 
 namespace bx {
@@ -352,10 +353,94 @@ extern "C" const char* bx_device_name(bx_ctx* c, char* out, size_t cap) try {
     return nullptr;
 } BX_ABI_CATCH(c, "bx_device_name")
 
-// The default suite, the reference's `poseidon2` (ProverOpts::default(), bento/crates/workflow/src/lib.rs:246-249); a ctx's own
-// suite is bx_ctx_hash_suite (sha256.hip).  Hal::has_unified_memory: MI355X HBM is not host-coherent unified memory.
-extern "C" const char* bx_hash_suite_name(void) { return "poseidon2"; }
+// Hal::has_unified_memory: MI355X HBM is not host-coherent unified memory.
 extern "C" int bx_has_unified_memory(bx_ctx*) { return 0; }
+
+// ---- the hash suite of a ctx and the Merkle entry points under it; a suite's kernels are reached through its HashLaunchers (ctx.hpp) ----
+// The default suite, the reference's `poseidon2` (ProverOpts::default(), bento/crates/workflow/src/lib.rs:246-249)
+extern "C" const char* bx_hash_suite_name(void) { return hash_suite_name(SUITE_POSEIDON2); }
+extern "C" const char* bx_ctx_hash_suite(bx_ctx* c) { return c ? hash_suite_name(c->hash_suite) : nullptr; }
+extern "C" const char* bx_set_hash_suite(bx_ctx* c, const char* hashfn) try {
+    if (!c) return "bx_set_hash_suite: null ctx";
+    const int s = parse_hash_suite(hashfn);
+    BX_REQUIRE(c, s >= 0, "bx_set_hash_suite: unknown hashfn (\"poseidon2\" or \"sha-256\")");
+    // a prover's trees and its host transcript must agree for its whole life (the same rule as bx_poseidon2_set_params)
+    BX_REQUIRE(c, c->live_provers == 0, "bx_set_hash_suite: destroy the provers of this ctx first (they were created under the current suite)");
+    c->hash_suite = s;
+    return nullptr;
+} BX_ABI_CATCH(c, "bx_set_hash_suite")
+
+namespace bx {
+static HashLaunchers hash_launchers(int suite) { return suite == SUITE_SHA256 ? sha256_launchers() : poseidon2_launchers(); }
+// the rows of a column-major matrix to digests: Hal::hash_rows, and the leaves of bx_merkle_build
+static const char* hash_rows_op(bx_ctx* c, int suite, uint32_t* out, bx_buf matrix, size_t rows) {
+    OpScope op(c, "hash_rows", 4.0 * (double)matrix.len + 32.0 * (double)rows);
+    return hash_launchers(suite).rows(c, out, (const uint32_t*)matrix.dptr, rows, matrix.len / rows);
+}
+// Hal::hash_rows under a given suite (the image ID's leaves are Poseidon2 on every ctx: image.hip)
+const char* hash_rows_suite(bx_ctx* c, bx_buf out, bx_buf matrix, int suite) {
+    BX_REQUIRE(c, out.len % 8 == 0, "hash_rows: digest buffer length not a multiple of 8 words");
+    size_t rows = out.len / 8;
+    BX_REQUIRE(c, rows > 0 && matrix.len % rows == 0, "hash_rows: matrix.len not a multiple of rows");
+    BX_REQUIRE(c, rows <= 0xffffffffu, "hash_rows: too many rows");
+    BX_ENTER(c);
+    return hash_rows_op(c, suite, (uint32_t*)out.dptr, matrix, rows);
+}
+static bool holds_tree(bx_buf nodes, size_t rows) { return is_pow2(rows) && rows <= nodes.len / 16 && nodes.len == 16 * rows; }
+
+// Every layer above the leaves nodes[rows .. 2 rows), down to the root nodes[1]: one schedule, so a tree takes exactly as many launches
+// under every suite.  Large layers: full-utilisation launches (lane = output node, or a lane folds 2^L inputs depth first).  Once a
+// layer no longer fills the chip (<= fold_fuse_below inputs) the remaining levels are latency-bound, so a workgroup folds 512
+// inputs nine levels deep through LDS in one launch.
+static const char* merkle_fold_layers(bx_ctx* c, int suite, bx_buf nodes, size_t rows) {
+    OpScope op(c, "hash_fold", 96.0 * (double)(rows - 1));
+    const HashLaunchers h = hash_launchers(suite);
+    uint32_t* n = (uint32_t*)nodes.dptr;
+    const size_t fuse_below = (size_t)c->fold_fuse_below, min_lanes = (size_t)c->fold_deep_min_lanes;
+    // L levels per launch: while that still leaves a lane per SIMD slot of the chip and lands above the fused kernel's range
+    auto deep = [&](size_t size, int L) { return c->fold_deep >= L && (size >> L) >= min_lanes && (size >> L) >= fuse_below; };
+    for (size_t size = rows; size > 1;) {
+        int levels = deep(size, 3) ? 3 : deep(size, 2) ? 2 : 1;
+        if (size <= fuse_below) {
+            const size_t cap = c->fold_quad ? (size_t)c->fold_quad_wg : 512, per_wg = size < cap ? size : cap;
+            levels = ilog2(per_wg);
+            BX_TRY(h.fold_small(c, n, size, per_wg, levels));
+        } else {
+            BX_TRY(levels == 3 ? h.fold3(c, n, size) : levels == 2 ? h.fold2(c, n, size) : h.fold(c, n, size, size / 2));
+        }
+        size >>= levels;
+    }
+    return nullptr;
+}
+}  // namespace bx
+
+extern "C" const char* bx_hash_rows(bx_ctx* c, bx_buf out, bx_buf matrix) try {
+    if (!c) return "bx_hash_rows: null ctx";
+    return hash_rows_suite(c, out, matrix, c->hash_suite);
+} BX_ABI_CATCH(c, "bx_hash_rows")
+extern "C" const char* bx_hash_fold(bx_ctx* c, bx_buf io, size_t input_size, size_t output_size) try {
+    if (!c) return "bx_hash_fold: null ctx";
+    BX_REQUIRE(c, output_size <= io.len / 32 && input_size == 2 * output_size, "hash_fold: input_size must be 2*output_size, and the buffer hold 2*input_size digests");
+    BX_ENTER(c);
+    OpScope op(c, "hash_fold", 96.0 * (double)output_size);
+    return hash_launchers(c->hash_suite).fold(c, (uint32_t*)io.dptr, input_size, output_size);
+} BX_ABI_CATCH(c, "bx_hash_fold")
+
+extern "C" const char* bx_merkle_build(bx_ctx* c, bx_buf nodes, bx_buf matrix, size_t rows) try {
+    if (!c) return "bx_merkle_build: null ctx";
+    BX_REQUIRE(c, holds_tree(nodes, rows), "merkle_build: nodes must hold 2*rows digests, rows a power of two");
+    BX_REQUIRE(c, matrix.len % rows == 0, "merkle_build: matrix.len not a multiple of rows");
+    BX_ENTER(c);
+    BX_TRY(hash_rows_op(c, c->hash_suite, (uint32_t*)nodes.dptr + 8 * rows, matrix, rows));
+    return merkle_fold_layers(c, c->hash_suite, nodes, rows);
+} BX_ABI_CATCH(c, "bx_merkle_build")
+// Extension: the fold half of bx_merkle_build alone — the leaves are already in nodes[rows .. 2 rows).
+extern "C" const char* bx_merkle_fold(bx_ctx* c, bx_buf nodes, size_t rows) try {
+    if (!c) return "bx_merkle_fold: null ctx";
+    BX_REQUIRE(c, holds_tree(nodes, rows), "merkle_fold: nodes must hold 2*rows digests, rows a power of two");
+    BX_ENTER(c);
+    return merkle_fold_layers(c, c->hash_suite, nodes, rows);
+} BX_ABI_CATCH(c, "bx_merkle_fold")
 
 extern "C" const char* bx_set_stream(bx_ctx* c, void* s) try {
     if (!c) return "bx_set_stream: null ctx";

@@ -18,7 +18,7 @@
 
 #include "ctx.hpp"
 #include "image.hpp"
-#include "sha256_suite.hpp"
+#include "hash_suite.hpp"
 
 namespace bx {
 

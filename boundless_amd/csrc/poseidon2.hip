@@ -11,7 +11,7 @@
 // across the 64 lanes of a wave (lane r reads matrix[c*rows + r]).
 #include "ctx.hpp"
 #include "poseidon2_arith.hpp"
-#include "sha256_suite.hpp"
+#include "hash_suite.hpp"
 #include "../../include/bx_image.h"
 
 namespace bx {
@@ -505,6 +505,24 @@ static const char* launch_hash_fold(bx_ctx* c, uint32_t* io, size_t input_size, 
     BX_LAUNCH_CHECK(c);
     return nullptr;
 }
+template <int L>
+static const char* launch_hash_fold_deep(bx_ctx* c, uint32_t* io, size_t size) {
+    hipLaunchKernelGGL(hash_fold_deep_kernel<L>, dim3((unsigned)(((size >> L) + 255) / 256)), dim3(256), 0, c->stream, io, c->d_p2, (uint32_t)size);
+    BX_LAUNCH_CHECK(c);
+    return nullptr;
+}
+// small layers: four lanes per node (fold_quad, the default) or one
+static const char* launch_hash_fold_small(bx_ctx* c, uint32_t* io, size_t size, size_t per_wg, int levels) {
+    if (c->fold_quad)
+        hipLaunchKernelGGL(hash_fold_quad_kernel, dim3((unsigned)(size / per_wg)), dim3((unsigned)(2 * per_wg)), 0, c->stream, io, c->d_p2,
+                           (uint32_t)size, (uint32_t)per_wg, levels);
+    else
+        hipLaunchKernelGGL(hash_fold_multi_kernel, dim3((unsigned)(size / per_wg)), dim3(256), 0, c->stream, io, c->d_p2, (uint32_t)size,
+                           (uint32_t)per_wg, levels);
+    BX_LAUNCH_CHECK(c);
+    return nullptr;
+}
+HashLaunchers poseidon2_launchers() { return {launch_hash_rows, launch_hash_fold, launch_hash_fold_deep<3>, launch_hash_fold_deep<2>, launch_hash_fold_small}; }
 
 }  // namespace bx
 
@@ -528,32 +546,6 @@ extern "C" const char* bx_poseidon2_get_params(bx_ctx* c, uint32_t* rc213, uint3
     return nullptr;
 } BX_ABI_CATCH(c, "bx_poseidon2_get_params")
 
-// Hal::hash_rows under a given suite (the image ID's leaves are Poseidon2 on every ctx: image.hip)
-const char* bx::hash_rows_suite(bx_ctx* c, bx_buf out, bx_buf matrix, int suite) {
-    BX_REQUIRE(c, out.len % 8 == 0, "hash_rows: digest buffer length not a multiple of 8 words");
-    size_t rows = out.len / 8;
-    BX_REQUIRE(c, rows > 0 && matrix.len % rows == 0, "hash_rows: matrix.len not a multiple of rows");
-    BX_REQUIRE(c, rows <= 0xffffffffu, "hash_rows: too many rows");
-    size_t cols = matrix.len / rows;
-    BX_ENTER(c);
-    OpScope op(c, "hash_rows", 4.0 * (double)matrix.len + 32.0 * (double)rows);
-    if (suite == SUITE_SHA256) return sha256_hash_rows(c, (uint32_t*)out.dptr, (const uint32_t*)matrix.dptr, rows, cols);
-    return launch_hash_rows(c, (uint32_t*)out.dptr, (const uint32_t*)matrix.dptr, rows, cols);
-}
-extern "C" const char* bx_hash_rows(bx_ctx* c, bx_buf out, bx_buf matrix) try {
-    if (!c) return "bx_hash_rows: null ctx";
-    return hash_rows_suite(c, out, matrix, c->hash_suite);
-} BX_ABI_CATCH(c, "bx_hash_rows")
-
-extern "C" const char* bx_hash_fold(bx_ctx* c, bx_buf io, size_t input_size, size_t output_size) try {
-    if (!c) return "bx_hash_fold: null ctx";
-    BX_REQUIRE(c, output_size <= io.len / 32 && input_size == 2 * output_size, "hash_fold: input_size must be 2*output_size, and the buffer hold 2*input_size digests");
-    BX_ENTER(c);
-    OpScope op(c, "hash_fold", 96.0 * (double)output_size);
-    if (c->hash_suite == SUITE_SHA256) return sha256_hash_fold(c, (uint32_t*)io.dptr, input_size, output_size);
-    return launch_hash_fold(c, (uint32_t*)io.dptr, input_size, output_size);
-} BX_ABI_CATCH(c, "bx_hash_fold")
-
 extern "C" const char* bx_hash_fold_indexed(bx_ctx* c, bx_buf out, bx_buf in, bx_buf sel, size_t count) try {
     if (!c) return "bx_hash_fold_indexed: null ctx";
     BX_REQUIRE(c, count <= out.len / 8 && count <= sel.len / 2, "hash_fold_indexed: out or sel too small");
@@ -568,70 +560,9 @@ extern "C" const char* bx_hash_fold_indexed(bx_ctx* c, bx_buf out, bx_buf in, bx
     return nullptr;
 } BX_ABI_CATCH(c, "bx_hash_fold_indexed")
 
-// every layer above the leaves nodes[rows .. 2 rows), down to the root nodes[1]
-static const char* merkle_fold_layers(bx_ctx* c, uint32_t* n, size_t rows) {
-    // Large layers: full-utilisation launches (lane = output node, or a lane folds 2^L inputs depth first).  Once a layer no
-    // longer fills the chip (<= fold_fuse_below inputs) the remaining levels are latency-bound, so a workgroup folds 512 inputs
-    // nine levels deep through LDS in one launch.
-    size_t size = rows;
-    const size_t fuse_below = (size_t)c->fold_fuse_below;
-    while (size > 1) {
-        if (size <= fuse_below) {
-            const size_t cap = c->fold_quad ? (size_t)c->fold_quad_wg : 512;
-            size_t per_wg = size < cap ? size : cap;
-            int levels = ilog2(per_wg);
-            if (c->fold_quad)
-                hipLaunchKernelGGL(hash_fold_quad_kernel, dim3((unsigned)(size / per_wg)), dim3((unsigned)(2 * per_wg)), 0, c->stream, n,
-                                   c->d_p2, (uint32_t)size, (uint32_t)per_wg, levels);
-            else
-                hipLaunchKernelGGL(hash_fold_multi_kernel, dim3((unsigned)(size / per_wg)), dim3(256), 0, c->stream, n, c->d_p2,
-                                   (uint32_t)size, (uint32_t)per_wg, levels);
-            BX_LAUNCH_CHECK(c);
-            size >>= levels;
-        } else if (c->fold_deep >= 3 && (size >> 3) >= (size_t)c->fold_deep_min_lanes && (size >> 3) >= fuse_below) {
-            // three levels per launch while that still leaves a lane per SIMD slot of the chip and lands above the fused kernel's range
-            hipLaunchKernelGGL(hash_fold_deep_kernel<3>, dim3((unsigned)(((size >> 3) + 255) / 256)), dim3(256), 0, c->stream, n, c->d_p2, (uint32_t)size);
-            BX_LAUNCH_CHECK(c);
-            size >>= 3;
-        } else if (c->fold_deep >= 2 && (size >> 2) >= (size_t)c->fold_deep_min_lanes && (size >> 2) >= fuse_below) {
-            hipLaunchKernelGGL(hash_fold_deep_kernel<2>, dim3((unsigned)(((size >> 2) + 255) / 256)), dim3(256), 0, c->stream, n, c->d_p2, (uint32_t)size);
-            BX_LAUNCH_CHECK(c);
-            size >>= 2;
-        } else {
-            BX_TRY(launch_hash_fold(c, n, size, size / 2));
-            size >>= 1;
-        }
-    }
-    return nullptr;
-}
-
-extern "C" const char* bx_merkle_build(bx_ctx* c, bx_buf nodes, bx_buf matrix, size_t rows) try {
-    if (!c) return "bx_merkle_build: null ctx";
-    BX_REQUIRE(c, is_pow2(rows) && rows <= nodes.len / 16 && nodes.len == 16 * rows, "merkle_build: nodes must hold 2*rows digests, rows a power of two");
-    BX_REQUIRE(c, matrix.len % rows == 0, "merkle_build: matrix.len not a multiple of rows");
-    BX_ENTER(c);
-    uint32_t* n = (uint32_t*)nodes.dptr;
-    {
-        OpScope op(c, "hash_rows", 4.0 * (double)matrix.len + 32.0 * (double)rows);
-        if (c->hash_suite == SUITE_SHA256) BX_TRY(sha256_hash_rows(c, n + 8 * rows, (const uint32_t*)matrix.dptr, rows, matrix.len / rows));
-        else BX_TRY(launch_hash_rows(c, n + 8 * rows, (const uint32_t*)matrix.dptr, rows, matrix.len / rows));
-    }
-    OpScope op(c, "hash_fold", 96.0 * (double)(rows - 1));
-    if (c->hash_suite == SUITE_SHA256) return sha256_fold_layers(c, n, rows);
-    return merkle_fold_layers(c, n, rows);
-} BX_ABI_CATCH(c, "bx_merkle_build")
-// Extension: the fold half of bx_merkle_build alone — the leaves are already in nodes[rows .. 2 rows).
-extern "C" const char* bx_merkle_fold(bx_ctx* c, bx_buf nodes, size_t rows) try {
-    if (!c) return "bx_merkle_fold: null ctx";
-    BX_REQUIRE(c, is_pow2(rows) && rows <= nodes.len / 16 && nodes.len == 16 * rows, "merkle_fold: nodes must hold 2*rows digests, rows a power of two");
-    BX_ENTER(c);
-    OpScope op(c, "hash_fold", 96.0 * (double)(rows - 1));
-    if (c->hash_suite == SUITE_SHA256) return sha256_fold_layers(c, (uint32_t*)nodes.dptr, rows);
-    return merkle_fold_layers(c, (uint32_t*)nodes.dptr, rows);
-} BX_ABI_CATCH(c, "bx_merkle_fold")
-
 extern "C" const char* bx_transcript_step(bx_ctx* c, bx_buf state, bx_buf digests, size_t n_commit, bx_buf out_ext, size_t n_ext) try {
     if (!c) return "bx_transcript_step: null ctx";
+    // (no dispatch: the only device-side RNG is Poseidon2's)
     BX_REQUIRE(c, c->hash_suite == SUITE_POSEIDON2, "transcript_step: the device transcript is Poseidon2's (a sha-256 ctx draws on the host)");
     BX_REQUIRE(c, state.dptr != nullptr && state.len >= 25, "transcript_step: the state is 24 cells and the pool counter");
     BX_REQUIRE(c, n_commit <= 64 && n_ext <= 64, "transcript_step: at most 64 commits and 64 challenges per step");

@@ -33,15 +33,6 @@ __global__ void merkle_query_gather_kernel(uint32_t* __restrict__ out, const uin
     }
 }
 
-static inline unsigned top_layer_of(unsigned layers) {
-    unsigned top = 0;
-    for (unsigned i = 1; i < layers; ++i) {
-        if ((1u << i) > BX_QUERIES) break;
-        top = i;
-    }
-    return top;
-}
-
 struct DevBuf {  // owning device allocation; movable, not copyable
     bx_ctx* c = nullptr;
     bx_buf b{nullptr, 0};
@@ -595,7 +586,7 @@ static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t
     if (hipSetDevice(c->device) != hipSuccess) return perr(p, "bx_prove_segment: hipSetDevice failed");
     const size_t N = p->N, D = 4 * N;
     const uint32_t po2 = p->shape.po2;
-    Transcript T(&p->h2, p->hs.suite);
+    Transcript T(p->hs);
     T.seal.reserve(p->seal_bound);
     TraceRange whole(c, "bx:prove_segment");
 
@@ -836,8 +827,8 @@ static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t
             // inside the loop.  Roots, top layers, the drawn challenges and the final coefficients come back in ONE copy after the
             // loop; the host transcript then replays the same commits (it writes the seal) and must draw the same words.
             uint32_t st[25];
-            memcpy(st, T.cells, sizeof T.cells);
-            st[24] = T.pool_used;
+            memcpy(st, T.cells(), 24 * sizeof(uint32_t));
+            st[24] = T.pool_used();
             PV(h2d_staged(c, p->tstate.slice(0, 25), st, 25));
         }
         size_t ri = 0;

@@ -1,5 +1,5 @@
-// sha256.hip — the `sha-256` hash suite's Merkle hashing for gfx950: Hal::{hash_rows, hash_fold} and the Merkle layers of
-// bx_merkle_build / bx_merkle_fold on a ctx switched with bx_set_hash_suite (include/bx_hal.h).
+// sha256.hip — the `sha-256` hash suite's Merkle hashing for gfx950: the kernels behind Hal::{hash_rows, hash_fold} and the Merkle layers
+// on a ctx switched with bx_set_hash_suite, and their launcher table (ctx.hpp: HashLaunchers; entry points and schedule: hal.hip).
 //
 // Restates risc0_zkp's Sha256 HAL kernels `sha_rows` / `sha_fold` with the conventions of sha256_suite.hpp [EXT: risc0-zkp 3.0.3
 // core/hash/sha, recalled].  A compression is pure 32-bit VALU work — 64 rounds of alignbit rotates, bfi Ch / Maj and add3 / xor3
@@ -148,64 +148,29 @@ __global__ __launch_bounds__(256) void sha256_fold_multi_kernel(uint32_t* __rest
     }
 }
 
-const char* sha256_hash_rows(bx_ctx* c, uint32_t* out, const uint32_t* matrix, size_t rows, size_t cols) {
+static const char* sha256_rows(bx_ctx* c, uint32_t* out, const uint32_t* matrix, size_t rows, size_t cols) {
     if (rows == 0) return nullptr;
-    const unsigned bs = 256;
-    hipLaunchKernelGGL(sha256_rows_kernel, dim3((unsigned)((rows + bs - 1) / bs)), dim3(bs), 0, c->stream, out, matrix, (uint32_t)rows,
-                       (uint32_t)cols);
+    hipLaunchKernelGGL(sha256_rows_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, out, matrix, (uint32_t)rows, (uint32_t)cols);
     BX_LAUNCH_CHECK(c);
     return nullptr;
 }
-const char* sha256_hash_fold(bx_ctx* c, uint32_t* io, size_t input_size, size_t output_size) {
+static const char* sha256_fold(bx_ctx* c, uint32_t* io, size_t input_size, size_t output_size) {
     if (output_size == 0) return nullptr;
-    hipLaunchKernelGGL(sha256_fold_kernel, dim3((unsigned)((output_size + 255) / 256)), dim3(256), 0, c->stream, io, (uint32_t)input_size,
-                       (uint32_t)output_size);
+    hipLaunchKernelGGL(sha256_fold_kernel, dim3((unsigned)((output_size + 255) / 256)), dim3(256), 0, c->stream, io, (uint32_t)input_size, (uint32_t)output_size);
     BX_LAUNCH_CHECK(c);
     return nullptr;
 }
-// Every layer above the leaves nodes[rows .. 2 rows) down to the root, on the same schedule as the Poseidon2 layers
-// (poseidon2.hip: merkle_fold_layers) and the same tunables, so a tree takes exactly as many launches under either suite.
-const char* sha256_fold_layers(bx_ctx* c, uint32_t* n, size_t rows) {
-    size_t size = rows;
-    const size_t fuse_below = (size_t)c->fold_fuse_below;
-    while (size > 1) {
-        if (size <= fuse_below) {
-            size_t cap = c->fold_quad ? (size_t)c->fold_quad_wg : 512;
-            if (cap > 512) cap = 512;
-            const size_t per_wg = size < cap ? size : cap;
-            const int levels = ilog2(per_wg);
-            hipLaunchKernelGGL(sha256_fold_multi_kernel, dim3((unsigned)(size / per_wg)), dim3(256), 0, c->stream, n, (uint32_t)size,
-                               (uint32_t)per_wg, levels);
-            BX_LAUNCH_CHECK(c);
-            size >>= levels;
-        } else if (c->fold_deep >= 3 && (size >> 3) >= (size_t)c->fold_deep_min_lanes && (size >> 3) >= fuse_below) {
-            hipLaunchKernelGGL(sha256_fold_deep_kernel<3>, dim3((unsigned)(((size >> 3) + 255) / 256)), dim3(256), 0, c->stream, n, (uint32_t)size);
-            BX_LAUNCH_CHECK(c);
-            size >>= 3;
-        } else if (c->fold_deep >= 2 && (size >> 2) >= (size_t)c->fold_deep_min_lanes && (size >> 2) >= fuse_below) {
-            hipLaunchKernelGGL(sha256_fold_deep_kernel<2>, dim3((unsigned)(((size >> 2) + 255) / 256)), dim3(256), 0, c->stream, n, (uint32_t)size);
-            BX_LAUNCH_CHECK(c);
-            size >>= 2;
-        } else {
-            BX_TRY(sha256_hash_fold(c, n, size, size / 2));
-            size >>= 1;
-        }
-    }
+template <int L>
+static const char* sha256_fold_deep(bx_ctx* c, uint32_t* io, size_t size) {
+    hipLaunchKernelGGL(sha256_fold_deep_kernel<L>, dim3((unsigned)(((size >> L) + 255) / 256)), dim3(256), 0, c->stream, io, (uint32_t)size);
+    BX_LAUNCH_CHECK(c);
     return nullptr;
 }
+static const char* sha256_fold_small(bx_ctx* c, uint32_t* io, size_t size, size_t per_wg, int levels) {
+    hipLaunchKernelGGL(sha256_fold_multi_kernel, dim3((unsigned)(size / per_wg)), dim3(256), 0, c->stream, io, (uint32_t)size, (uint32_t)per_wg, levels);
+    BX_LAUNCH_CHECK(c);
+    return nullptr;
+}
+HashLaunchers sha256_launchers() { return {sha256_rows, sha256_fold, sha256_fold_deep<3>, sha256_fold_deep<2>, sha256_fold_small}; }
 
 }  // namespace bx
-
-using namespace bx;
-
-extern "C" const char* bx_set_hash_suite(bx_ctx* c, const char* hashfn) try {
-    if (!c) return "bx_set_hash_suite: null ctx";
-    const int s = parse_hash_suite(hashfn);
-    BX_REQUIRE(c, s >= 0, "bx_set_hash_suite: unknown hashfn (\"poseidon2\" or \"sha-256\")");
-    // a prover's trees and its host transcript must agree for its whole life (the same rule as bx_poseidon2_set_params)
-    BX_REQUIRE(c, c->live_provers == 0, "bx_set_hash_suite: destroy the provers of this ctx first (they were created under the current suite)");
-    c->hash_suite = s;
-    return nullptr;
-} BX_ABI_CATCH(c, "bx_set_hash_suite")
-
-extern "C" const char* bx_ctx_hash_suite(bx_ctx* c) { return c ? hash_suite_name(c->hash_suite) : nullptr; }

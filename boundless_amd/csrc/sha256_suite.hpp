@@ -27,16 +27,6 @@ namespace bx {
 // the element hash reads canonical values (true) or raw Montgomery words (false): convention 1's one switch
 constexpr bool SHA_ELEM_CANONICAL = true;
 
-// hash suites a ctx / a prover / a verification runs under (bx_set_hash_suite)
-enum HashSuite : int { SUITE_POSEIDON2 = 0, SUITE_SHA256 = 1 };
-inline int parse_hash_suite(const char* name) {  // -1: not a suite this library implements
-    if (!name) return -1;
-    if (strcmp(name, "poseidon2") == 0) return SUITE_POSEIDON2;
-    if (strcmp(name, "sha-256") == 0) return SUITE_SHA256;
-    return -1;
-}
-inline const char* hash_suite_name(int s) { return s == SUITE_SHA256 ? "sha-256" : "poseidon2"; }
-
 BX_HD constexpr uint32_t sha256_k(int t) {
     constexpr uint32_t K[64] = {
         0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be,

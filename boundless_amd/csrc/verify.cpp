@@ -5,7 +5,7 @@
 // merkle::MerkleTreeVerifier} (risc0-zkp 3.0.3, reference Cargo.lock:9155): replay the transcript, check the constraint
 // identity at the random point Z (here: of the synthetic circuit specified in bx_prover.h), then for each query verify the
 // Merkle openings, recompute the DEEP quotient from the opened trace rows and follow the FRI folds to the final polynomial.
-// Pure CPU code (the reference verifies on the CPU as well); it shares only fp.hpp/transcript.hpp with the prover.
+// Pure CPU code (the reference verifies on the CPU as well); it shares only fp.hpp, hash_suite.hpp and transcript.hpp with the prover.
 #include <stdio.h>
 #include <string.h>
 
@@ -59,21 +59,12 @@ unsigned ilog2u(size_t n) {
     while (((size_t)1 << k) < n) k++;
     return k;
 }
-unsigned top_layer_of(unsigned layers) {
-    unsigned top = 0;
-    for (unsigned i = 1; i < layers; ++i) {
-        if ((1u << i) > BX_QUERIES) break;
-        top = i;
-    }
-    return top;
-}
 Fp4 ld(const uint32_t* w) { return Fp4{{w[0], w[1], w[2], w[3]}}; }
 bool eq(const Fp4& a, const Fp4& b) { return a.c[0] == b.c[0] && a.c[1] == b.c[1] && a.c[2] == b.c[2] && a.c[3] == b.c[3]; }
 Fp4 from_base(uint32_t v) { return Fp4{{v, 0, 0, 0}}; }
 uint32_t rou(unsigned k) { return fp_pow(fp_encode(137u), (uint64_t)1 << (27 - k)); }  // w_{2^k}
 
-// digest words: field elements under Poseidon2 (canonical only), any 32-bit value under SHA-256 (sha256_suite.hpp, convention 2)
-const uint32_t* digest_words(Reader& rd, const HostSuite& h, size_t k) { return h.suite == SUITE_SHA256 ? rd.take(k) : rd.take_elems(k); }
+const uint32_t* digest_words(Reader& rd, const HostSuite& h, size_t k) { return h.digests_are_elems() ? rd.take_elems(k) : rd.take(k); }
 
 // MerkleTreeVerifier: top layer read from the seal, root recomputed and committed
 struct TreeV {
@@ -90,14 +81,7 @@ struct TreeV {
         size_t ts = top_size();
         const uint32_t* t = digest_words(rd, h, 8 * ts);
         top.assign(t, t + 8 * ts);
-        // fold the top layer to the root
-        std::vector<uint32_t> layer(top);
-        for (size_t sz = ts; sz > 1; sz >>= 1) {
-            std::vector<uint32_t> next(8 * (sz / 2));
-            for (size_t i = 0; i < sz / 2; ++i) h.hash_pair(&next[8 * i], &layer[16 * i], &layer[16 * i + 8]);
-            layer.swap(next);
-        }
-        memcpy(root, layer.data(), 32);
+        h.merkle_root(root, top, ts, [](size_t n, auto&& body) { body((size_t)0, n); });
         T.commit(root);
     }
     // reads `cols` values + the path from the seal, checks them against the top layer; returns the column values
@@ -145,7 +129,7 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
     HostPoseidon2 h2;
     h2.load(POSEIDON2_RC, POSEIDON2_DIAG);
     const HostSuite h{suite, &h2};
-    Transcript T(&h2, suite);
+    Transcript T(h);
     Reader rd{seal, words};
 
     // ---- header ----
@@ -455,7 +439,7 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
     rd.pos = queries_at + (size_t)BX_QUERIES * per_query;
     if (rd.pos > rd.n) throw Fail{"seal truncated"};
     VCHECK(rd.pos == rd.n, "trailing words after the last query");
-    if (!vctx) {
+    if (!vctx) {  // (the same detour as above: a table's check_code has no suite parameter)
         const char* ce = suite == SUITE_SHA256 ? synth_check_code_suite(&shape, trees[0].root, suite) : circ->check_code(circ->user, &shape, trees[0].root);
         VCHECK(ce == nullptr, std::string("control ID: ") + (ce ? ce : ""));
     }

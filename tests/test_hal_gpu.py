@@ -305,12 +305,29 @@ def test_hash_rows_extreme_values(hal, oracle):
     assert np.array_equal(io.view()[8:16], want)
 
 
-@pytest.fixture(params=[1, 0], ids=["quad", "lane"])
+FOLD_DEFAULTS = {"fold_quad": 1, "fold_deep": 2, "fold_deep_min_lanes": 1 << 17, "fold_fuse_below": 1 << 17}
+# The branches of the Merkle layer schedule.  With fold_deep_min_lanes and fold_fuse_below at 2^10 the sizes of the tests reach every
+# one of them: three levels per launch, two, one layer per launch above the fused range, and the fused small-layer launch; with
+# fold_fuse_below = 0 the fused launch is never taken and single layers run down to the root.
+FOLD_SCHEDULES = {
+    "quad": {"fold_quad": 1},
+    "lane": {"fold_quad": 0},
+    "deep1": {"fold_deep": 1, "fold_deep_min_lanes": 1 << 10, "fold_fuse_below": 1 << 10},
+    "deep2": {"fold_deep": 2, "fold_deep_min_lanes": 1 << 10, "fold_fuse_below": 1 << 10},
+    "deep3": {"fold_deep": 3, "fold_deep_min_lanes": 1 << 10, "fold_fuse_below": 1 << 10},
+    "nofuse": {"fold_deep": 3, "fold_deep_min_lanes": 1 << 10, "fold_fuse_below": 0},
+}
+
+
+@pytest.fixture(params=list(FOLD_SCHEDULES))
 def fold_path(hal, request):
-    """Small Merkle layers on both kernels: four lanes per node (default) and one lane per node."""
-    hal.set_tunable("fold_quad", request.param)
+    """Small Merkle layers on both kernels (four lanes per node, the default, and one lane per node), and the large-layer schedule
+    under each setting of FOLD_SCHEDULES."""
+    for name, value in FOLD_SCHEDULES[request.param].items():
+        hal.set_tunable(name, value)
     yield request.param
-    hal.set_tunable("fold_quad", 1)
+    for name, value in FOLD_DEFAULTS.items():
+        hal.set_tunable(name, value)
 
 
 @pytest.mark.parametrize("rows", [2, 4, 8, 256, 512, 1024, 4096, 1 << 15, 1 << 17, 1 << 19])

@@ -53,8 +53,31 @@ def test_hash_rows_matches_python(shal, rows, cols_list):
             assert np.array_equal(got, want), (rows, cols, off)
 
 
-@pytest.mark.parametrize("log_rows", [1, 2, 6, 10, 14, 17, 18, 20])
-def test_merkle_fold_and_hash_fold_match_python(shal, log_rows):
+FOLD_DEFAULTS = {"fold_deep": 2, "fold_deep_min_lanes": 1 << 17, "fold_fuse_below": 1 << 17}
+# the branches of the Merkle layer schedule, as FOLD_SCHEDULES of tests/test_hal_gpu.py walks them under Poseidon2
+FOLD_SCHEDULES = {
+    "default": {},
+    "deep1": {"fold_deep": 1, "fold_deep_min_lanes": 1 << 10, "fold_fuse_below": 1 << 10},
+    "deep2": {"fold_deep": 2, "fold_deep_min_lanes": 1 << 10, "fold_fuse_below": 1 << 10},
+    "deep3": {"fold_deep": 3, "fold_deep_min_lanes": 1 << 10, "fold_fuse_below": 1 << 10},
+    "nofuse": {"fold_deep": 3, "fold_deep_min_lanes": 1 << 10, "fold_fuse_below": 0},
+}
+FOLD_LOG_ROWS = [1, 2, 6, 10, 14, 17, 18, 20]
+
+
+@pytest.fixture
+def fold_schedule(shal, request):
+    for name, value in FOLD_SCHEDULES[request.param].items():
+        shal.set_tunable(name, value)
+    yield request.param
+    for name, value in FOLD_DEFAULTS.items():
+        shal.set_tunable(name, value)
+
+
+@pytest.mark.parametrize("fold_schedule,log_rows",
+                         [pytest.param(s, n, id=str(n) if s == "default" else f"{s}-{n}") for s in FOLD_SCHEDULES for n in FOLD_LOG_ROWS],
+                         indirect=["fold_schedule"])
+def test_merkle_fold_and_hash_fold_match_python(shal, fold_schedule, log_rows):
     rows = 1 << log_rows
     rng = np.random.default_rng(log_rows)
     leaves = rng.integers(0, 2**32, (rows, 8), dtype=np.uint64).astype(np.uint32)  # digest words: any 32-bit value

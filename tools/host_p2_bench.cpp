@@ -1,8 +1,8 @@
-// host_p2_bench.cpp — the host Poseidon2 permutation (boundless_amd/csrc/transcript.hpp): scalar form vs the run-time selected form, words
+// host_p2_bench.cpp — the host Poseidon2 permutation (boundless_amd/csrc/poseidon2_host.hpp): scalar form vs the run-time selected form, words
 // compared on 20 000 states, then timed.  g++ -O3 -std=c++17 -Iboundless_amd/csrc tools/host_p2_bench.cpp -o /tmp/hp2 && /tmp/hp2
 #include <chrono>
 #include <cstdio>
-#include "transcript.hpp"
+#include "poseidon2_host.hpp"
 #include "poseidon2_params.hpp"
 using namespace bx;
 int main() {
