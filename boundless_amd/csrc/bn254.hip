@@ -531,6 +531,8 @@ const char* key_load(bx_ctx* c, const uint8_t* p, size_t len, bx_groth16_key* k)
         memcpy(&g, z.sec[2] + 340, 128);
         BX_REQUIRE(c, on_curve(g), "bx_groth16_key_load: gamma2 is not on its curve (endianness or Montgomery form?)");
     }
+    k->vk_header.assign(z.sec[2], z.sec[2] + z.sec_len[2]);
+    k->vk_ic.assign(z.sec[3], z.sec[3] + z.sec_len[3]);
     k->pin_bytes = std::min<size_t>((size_t)64 << 20, len + 4096);
     BX_HIP(c, hipHostMalloc(&k->h_pin, k->pin_bytes, hipHostMallocDefault));
     k->n_c = (uint32_t)nc;

@@ -63,4 +63,6 @@ struct bx_groth16_key {
     uint32_t omega2n_mont[8];  // omega_2N (coset generator), Montgomery
     uint32_t ninv_mont[8];     // 1/N, Montgomery
     std::vector<void*> allocs;
+    // host copies of zkey sections 2 (header) and 3 (IC), as the file holds them: what bx_groth16_key_vk answers from
+    std::vector<uint8_t> vk_header, vk_ic;
 };

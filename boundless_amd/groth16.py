@@ -3,8 +3,11 @@
     key = Groth16Key(hal, "circuit.zkey")      # or the zkey's bytes; parsed, uploaded and checked once
     proof = key.prove(witness)                 # witness: ints, or n_vars x 32 bytes little-endian (what a .wtns holds)
     proof.to_json(), proof.seal(selector)      # snarkjs proof JSON; the 260-byte on-chain seal
+    verify(key.vk(), proof)                    # the library's host verifier: returns, or raises HalError naming the failed check
+    verify_seal(VerifyingKey.from_json(text), seal, claim_digest)
 
-A thin ctypes binding: the arithmetic runs in the library's HIP kernels, and there is no CPU fallback.
+A thin ctypes binding: the proving arithmetic runs in the library's HIP kernels, and there is no CPU fallback.  Verification
+(VerifyingKey, verify, verify_seal, pairing_check, Proof.from_seal / from_json) is host C++ in the same library and needs no GPU.
 """
 import ctypes as C
 import struct
@@ -30,6 +33,11 @@ class _Proof(C.Structure):
                 ("public_signals", C.c_uint32 * (MAX_PUBLIC * 8))]
 
 
+class _Vk(C.Structure):
+    _fields_ = [("alpha1", C.c_uint32 * 16), ("beta2", C.c_uint32 * 32), ("gamma2", C.c_uint32 * 32), ("delta2", C.c_uint32 * 32),
+                ("n_public", C.c_uint32), ("ic", C.c_uint32 * ((MAX_PUBLIC + 1) * 16))]
+
+
 _declared = False
 
 
@@ -48,6 +56,17 @@ def _lib():
             "bx_groth16_prove": [vp, vp, vp, sz, vp, C.POINTER(_Proof)],
             "bx_groth16_proof_json": [C.POINTER(_Proof), C.c_char_p, sz],
             "bx_groth16_public_json": [C.POINTER(_Proof), C.c_char_p, sz],
+            "bx_groth16_zkey_vk": [cp, C.POINTER(_Vk)],
+            "bx_groth16_zkey_vk_mem": [vp, sz, C.POINTER(_Vk)],
+            "bx_groth16_key_vk": [vp, C.POINTER(_Vk)],
+            "bx_groth16_vk_json": [C.POINTER(_Vk), C.c_char_p, sz],
+            "bx_groth16_vk_from_json": [cp, sz, C.POINTER(_Vk)],
+            "bx_groth16_proof_from_json": [cp, sz, cp, sz, C.POINTER(_Proof)],
+            "bx_groth16_seal_encode": [C.POINTER(_Proof), cp, C.c_char_p],
+            "bx_groth16_seal_decode": [cp, sz, C.POINTER(_Proof)],
+            "bx_groth16_verify": [C.POINTER(_Vk), C.POINTER(_Proof)],
+            "bx_groth16_verify_seal": [C.POINTER(_Vk), cp, sz, cp],
+            "bx_bn254_pairing_check": [u32p, u32p, sz],
             "bx_bn254_msm_g1": [vp, BxBuf, BxBuf, sz, u32p],
             "bx_bn254_msm_g2": [vp, BxBuf, BxBuf, sz, u32p],
         }
@@ -124,6 +143,35 @@ class Proof:
     def as_tuple(self):
         return self.a, self.b, self.c
 
+    @classmethod
+    def from_seal(cls, seal, public=()):
+        """bx_groth16_seal_decode: a 260-byte seal (or 256 without its selector) back to a proof; the seal carries no public signals,
+        so they are re-attached here"""
+        raw, b = _Proof(), bytes(seal)
+        _check(_lib().bx_groth16_seal_decode(b, len(b), C.byref(raw)))
+        return cls(raw).with_public(public)
+
+    @classmethod
+    def from_json(cls, proof_json, public_json=None):
+        """bx_groth16_proof_from_json: what to_json() and public_json() write"""
+        raw = _Proof()
+        pj = proof_json.encode() if isinstance(proof_json, str) else bytes(proof_json)
+        uj = None if public_json is None else (public_json.encode() if isinstance(public_json, str) else bytes(public_json))
+        _check(_lib().bx_groth16_proof_from_json(pj, len(pj), uj, 0 if uj is None else len(uj), C.byref(raw)))
+        return cls(raw)
+
+    def with_public(self, public):
+        """the same A, B, C with other public signals (ints below 2^256; verification refuses those not below r)"""
+        public = [int(x) for x in public]
+        if len(public) > MAX_PUBLIC:
+            raise ValueError("more public signals than BX_GROTH16_MAX_PUBLIC")
+        raw = _Proof.from_buffer_copy(self._raw)
+        C.memset(raw.public_signals, 0, C.sizeof(raw.public_signals))
+        for i, x in enumerate(public):
+            raw.public_signals[8 * i:8 * i + 8] = [int(w) for w in _words(x)]
+        raw.n_public = len(public)
+        return Proof(raw)
+
     def to_json(self):
         buf = C.create_string_buffer(2048)
         _check(_lib().bx_groth16_proof_json(C.byref(self._raw), buf, len(buf)))
@@ -139,9 +187,95 @@ class Proof:
         sel = bytes(selector)
         if len(sel) != 4:
             raise ValueError("selector must be 4 bytes")
-        a, b, c = self.a or (0, 0), self.b or ((0, 0), (0, 0)), self.c or (0, 0)
-        nums = [a[0], a[1], b[0][1], b[0][0], b[1][1], b[1][0], c[0], c[1]]
-        return sel + b"".join(x.to_bytes(32, "big") for x in nums)
+        out = C.create_string_buffer(260)
+        _check(_lib().bx_groth16_seal_encode(C.byref(self._raw), sel, out))
+        return out.raw
+
+
+def _g1(w):
+    p = (_int(w[0:8]), _int(w[8:16]))
+    return None if p == (0, 0) else p
+
+
+def _g2(w):
+    x, y = (_int(w[0:8]), _int(w[8:16])), (_int(w[16:24]), _int(w[24:32]))
+    return None if x == (0, 0) and y == (0, 0) else (x, y)
+
+
+class VerifyingKey:
+    """bx_groth16_vk: alpha1 (G1), beta2, gamma2, delta2 (G2) and IC_0 .. IC_n_public (G1) as integer affine coordinates.  Every
+    constructor goes through the library, which checks ranges, curves and the G2 subgroup and raises HalError otherwise."""
+
+    def __init__(self, raw):
+        self._raw = raw
+        self.n_public = int(raw.n_public)
+        self.alpha1, self.beta2, self.gamma2, self.delta2 = _g1(raw.alpha1), _g2(raw.beta2), _g2(raw.gamma2), _g2(raw.delta2)
+        self.ic = [_g1(raw.ic[16 * i:16 * i + 16]) for i in range(self.n_public + 1)]
+
+    @classmethod
+    def from_zkey(cls, src):
+        """the verifying key a zkey carries (path or bytes): bx_groth16_zkey_vk(_mem)"""
+        L, raw = _lib(), _Vk()
+        if isinstance(src, (bytes, bytearray, memoryview)):
+            b = bytes(src)
+            _check(L.bx_groth16_zkey_vk_mem(b, len(b), C.byref(raw)))
+        else:
+            _check(L.bx_groth16_zkey_vk(str(src).encode(), C.byref(raw)))
+        return cls(raw)
+
+    @classmethod
+    def from_json(cls, text):
+        """snarkjs verification_key.json: bx_groth16_vk_from_json"""
+        raw = _Vk()
+        b = text.encode() if isinstance(text, str) else bytes(text)
+        _check(_lib().bx_groth16_vk_from_json(b, len(b), C.byref(raw)))
+        return cls(raw)
+
+    def to_json(self):
+        buf = C.create_string_buffer(1024 + 200 * (MAX_PUBLIC + 1))
+        _check(_lib().bx_groth16_vk_json(C.byref(self._raw), buf, len(buf)))
+        return buf.value.decode()
+
+    def as_dict(self):
+        return {"alpha1": self.alpha1, "beta2": self.beta2, "gamma2": self.gamma2, "delta2": self.delta2, "ic": list(self.ic)}
+
+    def __eq__(self, other):
+        return isinstance(other, VerifyingKey) and self.as_dict() == other.as_dict()
+
+
+def verify(vk, proof):
+    """bx_groth16_verify: returns None when the proof is accepted, raises HalError with the library's message (the failed check by
+    name, or "pairing check failed") otherwise"""
+    _check(_lib().bx_groth16_verify(C.byref(vk._raw), C.byref(proof._raw)))
+
+
+def verify_seal(vk, seal, claim_digest):
+    """bx_groth16_verify_seal: the reference's verify_seal — one public input, the 32-byte claim digest as a big-endian number mod r"""
+    s, d = bytes(seal), bytes(claim_digest)
+    if len(d) != 32:
+        raise ValueError("claim digest must be 32 bytes")
+    _check(_lib().bx_groth16_verify_seal(C.byref(vk._raw), s, len(s), d))
+
+
+def pairing_check(g1s, g2s):
+    """bx_bn254_pairing_check: prod e(g1s[i], g2s[i]) == 1 for integer affine points (None = infinity).  True / False; a malformed
+    point (off its curve, outside the subgroup, a coordinate not below q) raises HalError"""
+    if len(g1s) != len(g2s):
+        raise ValueError("as many G1 as G2 points")
+    a, b = np.zeros((len(g1s), 16), np.uint32), np.zeros((len(g2s), 32), np.uint32)
+    for i, p in enumerate(g1s):
+        if p is not None:
+            a[i, :8], a[i, 8:] = _words(p[0], 8), _words(p[1], 8)
+    for i, p in enumerate(g2s):
+        if p is not None:
+            for j, v in enumerate((p[0][0], p[0][1], p[1][0], p[1][1])):
+                b[i, 8 * j:8 * j + 8] = _words(v, 8)
+    u32p = C.POINTER(C.c_uint32)
+    msg = _lib().bx_bn254_pairing_check(a.ctypes.data_as(u32p), b.ctypes.data_as(u32p), len(g1s))
+    if msg and msg.decode().endswith("pairing check failed"):
+        return False
+    _check(msg)
+    return True
 
 
 class Groth16Key:
@@ -166,6 +300,12 @@ class Groth16Key:
         raw = _Proof()
         _check(self.L.bx_groth16_prove(self.hal.ctx, self.key, w, len(w) // 32, rs, C.byref(raw)))
         return Proof(raw)
+
+    def vk(self):
+        """bx_groth16_key_vk: the verifying key of this proving key, from what the load kept on the host (no device access)"""
+        raw = _Vk()
+        _check(self.L.bx_groth16_key_vk(self.key, C.byref(raw)))
+        return VerifyingKey(raw)
 
     def free(self):
         """bx_groth16_key_free; after hal.close() there is nothing left to free (bx_free released the ctx's keys)"""
@@ -229,4 +369,4 @@ def msm_g2(hal, points, scalars, n=None):
     return None if x == (0, 0) and y == (0, 0) else (x, y)
 
 
-__all__ = ["Groth16Key", "Proof", "inspect", "read_wtns", "msm_g1", "msm_g2", "g1_words", "g2_words", "scalar_words", "Q", "R"]
+__all__ = ["Groth16Key", "Proof", "VerifyingKey", "verify", "verify_seal", "pairing_check", "inspect", "read_wtns", "msm_g1", "msm_g2", "g1_words", "g2_words", "scalar_words", "Q", "R"]

@@ -9,8 +9,9 @@
  * them); the output is the snarkjs proof JSON.  INTEGRATION.md shows the Rust call sites.
  *
  * Conventions: those of bx_hal.h (NULL = ok, otherwise a message owned by the library; no call aborts and no exception crosses the
- * ABI).  The host-only calls that take no ctx (bx_groth16_zkey_inspect*, bx_groth16_*_json) return messages in a thread-local
- * buffer, valid until the next such call on the same thread.  A key belongs to the ctx it was loaded on.  Numbers are 8 x u32
+ * ABI).  The host-only calls that take no ctx (bx_groth16_zkey_inspect*, bx_groth16_*_json, and the whole verifier: bx_groth16_vk*,
+ * bx_groth16_*_vk, bx_groth16_seal_*, bx_groth16_verify*, bx_bn254_pairing_check) return messages in a thread-local buffer, valid
+ * until the next such call on the same thread; they need no GPU and may be called from several threads at once.  A key belongs to the ctx it was loaded on.  Numbers are 8 x u32
  * little-endian words; "canonical" means < the modulus and not in Montgomery form.  The file formats and encodings are stated in
  * boundless_amd/csrc/groth16.hpp and DESIGN.md §11.  bx_free releases the keys still loaded on its ctx.
  */
@@ -76,6 +77,52 @@ const char* bx_groth16_public_json(const bx_groth16_proof* proof, char* buf, siz
  * the affine result in canonical coordinates (16 / 32 words), infinity as zeros.  n <= BX_BN254_MSM_MAX_N.  Blocks. */
 const char* bx_bn254_msm_g1(bx_ctx* ctx, bx_buf points, bx_buf scalars, size_t n, uint32_t* out);
 const char* bx_bn254_msm_g2(bx_ctx* ctx, bx_buf points, bx_buf scalars, size_t n, uint32_t* out);
+
+/* ---- Verification: host only (no ctx, no GPU), what the reference's snark task does after proving
+ * (bento/crates/workflow/src/tasks/snark.rs:58-59 and :76-78; blake3_groth16/src/verify.rs:63-77, verify_seal). ---- */
+
+typedef struct bx_groth16_vk {
+    uint32_t alpha1[16];                           /* G1: x, y (canonical Fq) */
+    uint32_t beta2[32], gamma2[32], delta2[32];    /* G2: x.c0, x.c1, y.c0, y.c1 */
+    uint32_t n_public;
+    uint32_t ic[(BX_GROTH16_MAX_PUBLIC + 1) * 16]; /* IC_0 .. IC_n_public */
+} bx_groth16_vk;
+
+/* The verifying key a proving key carries (zkey section 2: alpha1, beta2, gamma2, delta2; section 3: IC).  The zkey readers refuse
+ * what bx_groth16_zkey_inspect refuses and read sections 2 and 3 only.  Every way of building a vk checks that its coordinates are
+ * below q, that alpha1, beta2, gamma2, delta2 and every IC lie on their curves, and that the three G2 points are not infinity and
+ * lie in the subgroup of order r; n_public is at most BX_GROTH16_MAX_PUBLIC.  bx_groth16_key_vk answers from what
+ * bx_groth16_key_load kept on the host: no device access. */
+const char* bx_groth16_zkey_vk(const char* path, bx_groth16_vk* out);
+const char* bx_groth16_zkey_vk_mem(const void* bytes, size_t len, bx_groth16_vk* out);
+const char* bx_groth16_key_vk(const bx_groth16_key* key, bx_groth16_vk* out);
+
+/* snarkjs verification_key.json: {"protocol": "groth16", "curve": "bn128", "nPublic": n, "vk_alpha_1": [x, y, "1"], "vk_beta_2":
+ * [[x.c0, x.c1], [y.c0, y.c1], ["1", "0"]], "vk_gamma_2", "vk_delta_2", "IC": [[x, y, "1"], ...]} with decimal strings.
+ * vk_alphabeta_12 is not written; it and every unknown key are ignored when read.  bx_groth16_proof_from_json reads what
+ * bx_groth16_proof_json and bx_groth16_public_json write. */
+const char* bx_groth16_vk_json(const bx_groth16_vk* vk, char* buf, size_t cap);
+const char* bx_groth16_vk_from_json(const char* json, size_t len, bx_groth16_vk* out);
+const char* bx_groth16_proof_from_json(const char* proof_json, size_t proof_len, const char* public_json, size_t public_len,
+                                       bx_groth16_proof* out);
+
+/* The on-chain seal: [4-byte selector] A.x A.y B.x.c1 B.x.c0 B.y.c1 B.y.c0 C.x C.y, 32 bytes big-endian each.  Decoding takes 260
+ * bytes (the selector is skipped) or 256 (no selector), leaves n_public = 0 and checks nothing about the numbers: verification does. */
+const char* bx_groth16_seal_encode(const bx_groth16_proof* proof, const uint8_t selector[4], uint8_t out[260]);
+const char* bx_groth16_seal_decode(const uint8_t* seal, size_t len, bx_groth16_proof* out);
+
+/* e(-A, B) e(alpha1, beta2) e(IC_0 + sum x_i IC_i, gamma2) e(C, delta2) = 1, by one multi-Miller loop and one final exponentiation.
+ * NULL = accepted; otherwise the first failed check by name.  Strict, as the on-chain verifier is: a coordinate not below q, a
+ * public signal not below r, proof.n_public != vk.n_public, A, B or C at infinity or off its curve and B outside the subgroup of
+ * order r are refused as such; a well-formed proof that fails the equation gives "pairing check failed".  vk: from one of the
+ * builders above (verification re-checks its ranges and curves, not its subgroups). */
+const char* bx_groth16_verify(const bx_groth16_vk* vk, const bx_groth16_proof* proof);
+/* The reference's verify_seal: one public input, claim_digest read as a big-endian number and reduced mod r. */
+const char* bx_groth16_verify_seal(const bx_groth16_vk* vk, const uint8_t* seal, size_t len, const uint8_t claim_digest[32]);
+
+/* prod e(g1[i], g2[i]) == 1 (the EIP-197 question).  g1: n x 16 words, g2: n x 32 words, canonical affine, infinity as zeros (such
+ * a pair contributes 1); points off their curve or outside the subgroup are refused.  n = 0 is accepted.  NULL = yes. */
+const char* bx_bn254_pairing_check(const uint32_t* g1, const uint32_t* g2, size_t n);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

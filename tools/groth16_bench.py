@@ -1,6 +1,7 @@
 """Groth16 proof latency on one GPU (include/bx_groth16.h): synthetic keys at 2^20 and 2^22 constraints, or a real zkey + wtns.
 
-    python tools/groth16_bench.py [--log 20,22] [--steps 10] [--warmup 2] [--key K.zkey --wtns W.wtns]
+    python tools/groth16_bench.py [--log 20,22] [--steps 10] [--warmup 2] [--key K.zkey --wtns W.wtns] [--verify]
+    python tools/groth16_bench.py --verify-only          # host only, no GPU: the reference's seal through bx_groth16_verify_seal
 
 Synthetic key: n_vars = n_constraints = 2^k - 2 (domain 2^k), n_public = 1 as in the blake3 circuit, two A entries and one B entry
 per constraint; its points are a table of a few thousand generated ones tiled (valid curve points, so the key passes the on-curve
@@ -9,6 +10,11 @@ witnesses: uniform values and a circom-like one (45 % zeros, 45 % ones, the rest
 (median of `steps` blocking proofs after `warmup`) and the per-stage split of one more proof from the ctx's profile events
 (bx_profile_enable): upload, coefficient evaluation, NTTs (+ the pointwise kernel), each MSM.  Prints one JSON line per case,
 stamped with `device_code_sha`.
+
+--verify: each case also times bx_groth16_verify (host C++) on the proof it made, against the key's own vk (bx_groth16_key_vk).  A
+synthetic key's proofs do not verify, so the verdict is reported, not asserted; the work is the same up to the final comparison.
+--verify-only: the median of 200 bx_groth16_verify_seal calls (after 20 warm-up) on tests/golden/groth16/blake3_groth16_reference.json,
+and beside it the time of tests/bn254_ref.py's big-integer Python verifier on the same vector, with the CPU model.  One JSON line.
 """
 import argparse
 import json
@@ -74,6 +80,72 @@ def witness(n, rng, skew):
     return w.tobytes()
 
 
+def cpu_model():
+    try:
+        for line in open("/proc/cpuinfo"):
+            if line.startswith("model name"):
+                return line.split(":", 1)[1].strip()
+    except OSError:
+        pass
+    import platform
+
+    return platform.processor() or platform.machine()
+
+
+def time_verify(g16, vk, proof, steps, warmup):
+    """ms per bx_groth16_verify call (median, min, max) and the verdict"""
+    from boundless_amd.hal import HalError
+
+    verdict, ts = "accepted", []
+    for i in range(warmup + steps):
+        t0 = time.perf_counter()
+        try:
+            g16.verify(vk, proof)
+        except HalError as e:
+            verdict = str(e)
+        if i >= warmup:
+            ts.append(1e3 * (time.perf_counter() - t0))
+    return {"verify_ms_median": round(statistics.median(ts), 3), "verify_ms_min": round(min(ts), 3), "verify_ms_max": round(max(ts), 3),
+            "verify_calls": steps, "verify_verdict": verdict}
+
+
+def verify_only(calls=200, warmup=20):
+    import bn254_ref as ref
+
+    from boundless_amd import build, groth16 as g16
+
+    build.build(verbose=False)
+    d = json.load(open(os.path.join(ROOT, "tests", "golden", "groth16", "blake3_groth16_reference.json")))
+    v = {k: int(x) for k, x in d["vk"].items()}
+    g1 = lambda p: [str(v[p + "x"]), str(v[p + "y"]), "1"]
+    g2 = lambda p: [[str(v[p + "x2"]), str(v[p + "x1"])], [str(v[p + "y2"]), str(v[p + "y1"])], ["1", "0"]]
+    vk = g16.VerifyingKey.from_json(json.dumps({"protocol": "groth16", "curve": "bn128", "nPublic": 1, "vk_alpha_1": g1("alpha"),
+                                                "vk_beta_2": g2("beta"), "vk_gamma_2": g2("gamma"), "vk_delta_2": g2("delta"),
+                                                "IC": [g1("IC0"), g1("IC1")]}))
+    seal, digest = bytes.fromhex(d["seal_hex"]), bytes.fromhex(d["claim_digest_hex"])
+    ts = []
+    for i in range(warmup + calls):
+        t0 = time.perf_counter()
+        g16.verify_seal(vk, seal, digest)  # raises if the reference's seal were refused
+        if i >= warmup:
+            ts.append(1e3 * (time.perf_counter() - t0))
+    t0 = time.perf_counter()
+    vk_again = g16.VerifyingKey.from_json(vk.to_json())
+    vk_ms = 1e3 * (time.perf_counter() - t0)
+    assert vk_again == vk
+    proof = g16.Proof.from_seal(seal)
+    rts = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        ok = ref.verify(vk.as_dict(), proof.as_tuple(), [int.from_bytes(digest, "big") % ref.R])
+        rts.append(1e3 * (time.perf_counter() - t0))
+        assert ok
+    print(json.dumps({"case": "bx_groth16_verify_seal on the reference vector", "verify_seal_ms_median": round(statistics.median(ts), 4),
+                      "verify_seal_ms_min": round(min(ts), 4), "verify_seal_ms_max": round(max(ts), 4), "calls": calls, "warmup": warmup,
+                      "vk_from_json_ms": round(vk_ms, 3), "bn254_ref_verify_ms_median": round(statistics.median(rts), 1), "bn254_ref_calls": 3,
+                      "cpu": cpu_model(), "threads": 1}), flush=True)
+
+
 def run(hal, key, wit, steps, warmup, label):
     rs = (12345).to_bytes(32, "little") + (67890).to_bytes(32, "little")
     r, s = int.from_bytes(rs[:32], "little"), int.from_bytes(rs[32:], "little")
@@ -102,7 +174,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--key")
     ap.add_argument("--wtns")
+    ap.add_argument("--verify", action="store_true", help="also time bx_groth16_verify on each case's proof")
+    ap.add_argument("--verify-only", action="store_true", help="host only: time bx_groth16_verify_seal on the reference vector")
     a = ap.parse_args()
+    if a.verify_only:
+        return verify_only()
     from boundless_amd import build, groth16 as g16
     from boundless_amd.hal import HipHal
 
@@ -111,7 +187,10 @@ def main():
     if a.key:
         key = g16.Groth16Key(hal, a.key)
         wit = g16.witness_bytes(g16.read_wtns(a.wtns))
-        print(json.dumps(dict(run(hal, key, wit, a.steps, a.warmup, "real"), info=key.info, device_code_sha=stamp, device=hal.device_name())), flush=True)
+        res = run(hal, key, wit, a.steps, a.warmup, "real")
+        if a.verify:
+            res.update(time_verify(g16, key.vk(), key.prove(wit), a.steps, a.warmup), cpu=cpu_model())
+        print(json.dumps(dict(res, info=key.info, device_code_sha=stamp, device=hal.device_name())), flush=True)
         key.free()
         return
     for log_n in map(int, a.log.split(",")):
@@ -123,7 +202,10 @@ def main():
         t2 = time.perf_counter()
         n = key.info["n_vars"]
         for skew in (False, True):
-            res = run(hal, key, witness(n, rng, skew), a.steps, a.warmup, f"2^{log_n} {'circom-like (90% 0/1)' if skew else 'uniform'} witness")
+            wit = witness(n, rng, skew)
+            res = run(hal, key, wit, a.steps, a.warmup, f"2^{log_n} {'circom-like (90% 0/1)' if skew else 'uniform'} witness")
+            if a.verify:
+                res.update(time_verify(g16, key.vk(), key.prove(wit), a.steps, a.warmup), cpu=cpu_model())
             res.update(info=key.info, key_build_s=round(t1 - t0, 2), key_load_s=round(t2 - t1, 2), device_code_sha=stamp, device=hal.device_name(),
                        synthetic=True)
             print(json.dumps(res), flush=True)
