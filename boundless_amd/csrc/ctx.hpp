@@ -81,7 +81,7 @@ struct bx_ctx {
     uint32_t* d_scan[2] = {nullptr, nullptr};
     size_t scan_cap = 0, scan_used[2] = {0, 0};
     int scan_next = 0;
-    long scan_lookback = 1;  // poly_divide / prefix_products: single-pass decoupled look-back kernels (0 = the three-phase kernels)
+    long scan_lookback = 1;  // poly_divide / prefix_products / prefix_sums / logup_accumulate: single-pass decoupled look-back kernels (0 = the three-phase kernels)
 
     // Deferred Hal::gather_sample calls (poly.hip).  MerkleTreeProver::prove issues one gather per opened row and one per path digest:
     // ~5 000 launches of a few words each per proof, 3.7 us of host time apiece on an idle GPU (19 of the 70 ms of a proof driven
@@ -278,6 +278,7 @@ const char* d2h_batch_add(bx_ctx* c, size_t* used, bx_buf src, size_t words, con
 const char* d2h_batch_wait(bx_ctx* c);
 const char* poly_divide_lookback(bx_ctx* c, uint32_t* polys, size_t size, size_t count, const uint32_t* zs, uint32_t* rems, const uint32_t* which);  // scan.hip
 const char* prefix_products_lookback(bx_ctx* c, uint32_t* io, size_t n, size_t count);
+const char* prefix_sums_three_phase(bx_ctx* c, uint32_t* io, size_t n, size_t count);  // poly.hip: the scan_lookback = 0 form of bx_batch_prefix_sums
 const char* ntt_init_tables(bx_ctx* c);
 void ntt_free_tables(bx_ctx* c);
 const char* poseidon2_upload_params(bx_ctx* c);

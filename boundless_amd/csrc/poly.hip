@@ -576,6 +576,61 @@ __global__ void pp_apply_kernel(uint32_t* __restrict__ io, size_t n, const uint3
             }
     }
 }
+// ---- prefix_sums: inclusive running sum of ext elements; the three-phase shape of prefix_products with the Fp4 sum as the operator
+// (the scan_lookback = 0 form; ps_lookback_kernel of scan.hip is the default) ----
+__global__ void ps_local_kernel(const uint32_t* __restrict__ io, size_t n, size_t seq_stride, uint32_t* __restrict__ agg, size_t chunks,
+                                size_t agg_stride) {
+    size_t ch = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ch >= chunks) return;
+    io += 4 * seq_stride * blockIdx.y;
+    agg += 4 * agg_stride * blockIdx.y;
+    size_t lo = ch * PP_L, hi = lo + PP_L < n ? lo + PP_L : n;
+    Fp4 p = f4_zero();
+    for (size_t b = lo; b < hi; ++b) p = f4_add(p, ld4(io + 4 * b));
+    st4(agg + 4 * ch, p);
+}
+// agg[ch] <- sum of all chunks before ch (exclusive scan), one workgroup per sequence
+__global__ void ps_scan_kernel(uint32_t* __restrict__ agg, size_t chunks, size_t agg_stride) {
+    extern __shared__ uint32_t sh[];
+    agg += 4 * agg_stride * blockIdx.x;
+    const uint32_t nt = blockDim.x, tid = threadIdx.x;
+    size_t per = (chunks + nt - 1) / nt;
+    size_t lo = (size_t)tid * per < chunks ? (size_t)tid * per : chunks;
+    size_t hi = lo + per < chunks ? lo + per : chunks;
+    Fp4 incl = f4_zero();
+    for (size_t ch = lo; ch < hi; ++ch) incl = f4_add(incl, ld4(agg + 4 * ch));
+    for (uint32_t d = 1; d < nt; d <<= 1) {
+        st4(sh + 4 * tid, incl);
+        __syncthreads();
+        if (tid >= d) incl = f4_add(incl, ld4(sh + 4 * (tid - d)));
+        __syncthreads();
+    }
+    st4(sh + 4 * tid, incl);
+    __syncthreads();
+    Fp4 carry = tid == 0 ? f4_zero() : ld4(sh + 4 * (tid - 1));
+    for (size_t ch = lo; ch < hi; ++ch) {
+        Fp4 a = ld4(agg + 4 * ch);
+        st4(agg + 4 * ch, carry);
+        carry = f4_add(carry, a);
+    }
+}
+// io[i] <- carry + sum_{lo <= k < i} io[k] (EXCL, the inner levels) or ... + io[i] (the outer level)
+template <bool EXCL>
+__global__ void ps_apply_kernel(uint32_t* __restrict__ io, size_t n, size_t seq_stride, const uint32_t* __restrict__ carry_in, size_t chunks,
+                                size_t carry_stride) {
+    size_t ch = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ch >= chunks) return;
+    io += 4 * seq_stride * blockIdx.y;
+    carry_in += 4 * carry_stride * blockIdx.y;
+    size_t lo = ch * PP_L, hi = lo + PP_L < n ? lo + PP_L : n;
+    Fp4 p = ld4(carry_in + 4 * ch);
+    for (size_t b = lo; b < hi; ++b) {
+        const Fp4 v = ld4(io + 4 * b);
+        if (EXCL) st4(io + 4 * b, p);
+        p = f4_add(p, v);
+        if (!EXCL) st4(io + 4 * b, p);
+    }
+}
 // entries [index[0], index[last]) are written.  The per-cycle grouping of upstream's scatter only orders writes that hit
 // the same offset, which its circuits never produce, so one pass over the range is equivalent.  Nothing is read back by
 // the host: a bad offset or index range raises a word of the ctx's deferred error flags (reported by the next bx_d2h / bx_sync).
@@ -934,6 +989,38 @@ extern "C" const char* bx_prefix_products(bx_ctx* c, bx_buf io) try {
     if (!c) return "bx_prefix_products: null ctx";
     return bx_batch_prefix_products(c, io, 1);
 } BX_ABI_CATCH(c, "bx_prefix_products")
+
+// exclusive running sums, in place, of `count` sequences of n entries (sequence k at arr + 4 * k * stride)
+static const char* excl_sum_rec(bx_ctx* c, uint32_t* arr, size_t n, size_t stride, size_t count, uint32_t* scratch) {
+    if (n <= PP_DIRECT) {
+        unsigned nt = n >= 1024 ? 1024 : 64;
+        hipLaunchKernelGGL(ps_scan_kernel, dim3((unsigned)count), dim3(nt), nt * 16, c->stream, arr, n, stride);
+        BX_LAUNCH_CHECK(c);
+        return nullptr;
+    }
+    const size_t chunks = (n + PP_L - 1) / PP_L;
+    hipLaunchKernelGGL(ps_local_kernel, dim3((unsigned)((chunks + 255) / 256), (unsigned)count), dim3(256), 0, c->stream, (const uint32_t*)arr, n,
+                       stride, scratch, chunks, chunks);
+    BX_LAUNCH_CHECK(c);
+    BX_TRY(excl_sum_rec(c, scratch, chunks, chunks, count, scratch + 4 * chunks * count));
+    hipLaunchKernelGGL(ps_apply_kernel<true>, dim3((unsigned)((chunks + 255) / 256), (unsigned)count), dim3(256), 0, c->stream, arr, n, stride,
+                       (const uint32_t*)scratch, chunks, chunks);
+    BX_LAUNCH_CHECK(c);
+    return nullptr;
+}
+// chunk sums -> exclusive scan of them (recursively, PP_L per level) -> inclusive replay of every chunk with its carry
+const char* bx::prefix_sums_three_phase(bx_ctx* c, uint32_t* io, size_t n, size_t count) {
+    const size_t chunks = (n + PP_L - 1) / PP_L;
+    BX_TRY(ensure_scratch(c, 4 * chunks * count + scan_scratch_words(chunks, PP_L, PP_DIRECT, count)));
+    hipLaunchKernelGGL(ps_local_kernel, dim3((unsigned)((chunks + 255) / 256), (unsigned)count), dim3(256), 0, c->stream, (const uint32_t*)io, n, n,
+                       c->d_scratch, chunks, chunks);
+    BX_LAUNCH_CHECK(c);
+    BX_TRY(excl_sum_rec(c, c->d_scratch, chunks, chunks, count, c->d_scratch + 4 * chunks * count));
+    hipLaunchKernelGGL(ps_apply_kernel<false>, dim3((unsigned)((chunks + 255) / 256), (unsigned)count), dim3(256), 0, c->stream, io, n, n,
+                       (const uint32_t*)c->d_scratch, chunks, chunks);
+    BX_LAUNCH_CHECK(c);
+    return nullptr;
+}
 
 extern "C" const char* bx_scatter(bx_ctx* c, bx_buf into, bx_buf index, bx_buf offsets, bx_buf values) try {
     if (!c) return "bx_scatter: null ctx";

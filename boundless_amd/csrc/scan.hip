@@ -1,4 +1,5 @@
-// scan.hip — single-pass scans over AoS ext arrays for gfx950: the DEEP quotient (poly_divide) and prefix_products.
+// scan.hip — single-pass scans over AoS ext arrays for gfx950: the DEEP quotient (poly_divide), prefix_products, and the additive
+// half of an accumulate stage (batch inversion, prefix_sums, logup_accumulate: further down, beside the kernels).
 //
 // Restates risc0_zkp::core::poly::poly_divide (run once per tap point of every DEEP combination polynomial by
 // Prover::finalize) and risc0_zkp::hal::Hal::prefix_products (risc0-zkp 3.0.3, reference Cargo.lock:9155), reached from
@@ -290,6 +291,216 @@ __global__ __launch_bounds__(SC_T) void pp_lookback_kernel(uint32_t* __restrict_
     }
 }
 
+// ---- the additive half of an accumulate stage (LogUp): batch inversion, prefix sums, and the two fused ----
+// Montgomery's trick over the K elements a lane holds: running products, ONE inversion of the last of them, and a walk back that
+// peels one element off per step — 3 (K - 1) products and one exponentiation instead of K exponentiations.  A zero element takes part
+// as 1 and comes out as 0 (selects, no branches), so it does not poison its chunk; results are canonical, hence equal word for
+// word to K separate inversions.
+struct InvFp {
+    using T = uint32_t;
+    static __device__ __forceinline__ T one() { return MONT_ONE; }
+    static __device__ __forceinline__ bool is_zero(T a) { return a == 0u; }
+    static __device__ __forceinline__ T mul(T a, T b) { return fp_mul(a, b); }
+    static __device__ __forceinline__ T inv(T a) { return fp_inv(a); }
+    static __device__ __forceinline__ T pick(bool z, T a) { return z ? 0u : a; }
+};
+struct InvFp4 {
+    using T = Fp4;
+    static __device__ __forceinline__ T one() { return f4_one(); }
+    static __device__ __forceinline__ bool is_zero(const T& a) { return f4_is_zero(a); }
+    static __device__ __forceinline__ T mul(const T& a, const T& b) { return f4_mul_lz(a, b); }
+    static __device__ __forceinline__ T inv(const T& a) { return f4_inv(a); }
+    static __device__ __forceinline__ T pick(bool z, const T& a) { return Fp4{{z ? 0u : a.c[0], z ? 0u : a.c[1], z ? 0u : a.c[2], z ? 0u : a.c[3]}}; }
+};
+template <typename F, int K>
+__device__ __forceinline__ void inv_chunk(typename F::T (&x)[K]) {
+    using T = typename F::T;
+    T pre[K];
+    uint32_t zeros = 0u;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const bool z = F::is_zero(x[k]);
+        zeros |= (z ? 1u : 0u) << k;
+        if (z) x[k] = F::one();
+        pre[k] = k ? F::mul(pre[k - 1], x[k]) : x[k];
+    }
+    T inv = F::inv(pre[K - 1]);  // of a product of non-zero elements: never zero
+#pragma unroll
+    for (int k = K - 1; k > 0; --k) {
+        const T o = F::mul(inv, pre[k - 1]);
+        inv = F::mul(inv, x[k]);
+        x[k] = F::pick((zeros >> k) & 1u, o);
+    }
+    x[0] = F::pick(zeros & 1u, inv);
+}
+
+// out[i] = in[i]^-1 (times mults[i] when SCALE) over n AoS ext elements; in == out is allowed.  A workgroup owns a tile of 2048
+// elements, loaded coalesced and transposed through LDS like the scans, so that a lane inverts 8 consecutive elements.  Elements
+// past the end are zeros: they cost a select and are never stored.
+template <bool SCALE>
+__global__ __launch_bounds__(SC_T) void binv_ext_kernel(const uint32_t* in, uint32_t* out, const uint32_t* __restrict__ mults, size_t n) {
+    __shared__ uint4 sh[SC_T * 9];
+    const uint32_t tid = threadIdx.x;
+    const size_t lo = (size_t)blockIdx.x * SC_TILE;
+    const uint32_t valid = n - lo < (size_t)SC_TILE ? (uint32_t)(n - lo) : (uint32_t)SC_TILE;
+    const uint4* src = reinterpret_cast<const uint4*>(in) + lo;
+    uint4* dst = reinterpret_cast<uint4*>(out) + lo;
+#pragma unroll
+    for (int k = 0; k < SC_I; ++k) {
+        const uint32_t u = (uint32_t)k * SC_T + tid;
+        sh[sc_slot(u)] = u < valid ? src[u] : make_uint4(0, 0, 0, 0);
+    }
+    __syncthreads();
+    Fp4 x[SC_I];
+#pragma unroll
+    for (int k = 0; k < SC_I; ++k) {
+        const uint4 w = sh[9 * tid + k];
+        x[k] = Fp4{{w.x, w.y, w.z, w.w}};
+    }
+    inv_chunk<InvFp4, SC_I>(x);
+#pragma unroll
+    for (int k = 0; k < SC_I; ++k) {
+        if (SCALE) {  // a lane reads its own 8 multiplicities: 4-byte loads 32 bytes apart, uncoalesced — this is the scan_lookback = 0 path only
+            const uint32_t u = SC_I * tid + (uint32_t)k;
+            x[k] = f4_scale(x[k], u < valid ? mults[lo + u] : 0u);
+        }
+        sh[9 * tid + k] = make_uint4(x[k].c[0], x[k].c[1], x[k].c[2], x[k].c[3]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SC_I; ++k) {
+        const uint32_t u = (uint32_t)k * SC_T + tid;
+        if (u < valid) dst[u] = sh[sc_slot(u)];
+    }
+}
+// the same over base-field words, in place: a lane owns 8 consecutive words (two 16-byte accesses when the buffer is 16-byte aligned
+// and the chunk is whole, single words otherwise)
+constexpr int BI_K = 8;
+__global__ __launch_bounds__(256) void binv_elem_kernel(uint32_t* __restrict__ io, size_t n, bool aligned16) {
+    const size_t lo = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * BI_K;
+    if (lo >= n) return;
+    const bool whole = aligned16 && n - lo >= (size_t)BI_K;
+    uint32_t x[BI_K];
+    if (whole) {
+        const uint4 a = *reinterpret_cast<const uint4*>(io + lo), b = *reinterpret_cast<const uint4*>(io + lo + 4);
+        x[0] = a.x, x[1] = a.y, x[2] = a.z, x[3] = a.w, x[4] = b.x, x[5] = b.y, x[6] = b.z, x[7] = b.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < BI_K; ++k) x[k] = lo + k < n ? io[lo + k] : 0u;
+    }
+    inv_chunk<InvFp, BI_K>(x);
+    if (whole) {
+        *reinterpret_cast<uint4*>(io + lo) = make_uint4(x[0], x[1], x[2], x[3]);
+        *reinterpret_cast<uint4*>(io + lo + 4) = make_uint4(x[4], x[5], x[6], x[7]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < BI_K; ++k)
+            if (lo + k < n) io[lo + k] = x[k];
+    }
+}
+
+// prefix sums: out[i] <- in[0] + .. + in[i], `count` sequences of n elements back to back — pp_lookback_kernel with the Fp4 sum in
+// place of the Fp4 product (identity zero; an aggregate is a sum, so the look-back adds where that one multiplies).  LOGUP: the
+// element that enters the sum is mults[i] * in[i]^-1, formed in the tile load — a lane's 8 elements are one inversion chunk — so the
+// fused call reads denoms and mults once and writes out once.  in == out is allowed: a tile reads only itself, before it writes.
+__device__ __forceinline__ uint32_t sc_mslot(uint32_t u) { return u + (u >> 5); }  // 8 words per lane, 32 banks: lanes 4 apart shift by one bank
+template <bool LOGUP>
+__global__ __launch_bounds__(SC_T) void ps_lookback_kernel(const uint32_t* in, uint32_t* out, const uint32_t* __restrict__ mults, size_t n,
+                                                           uint32_t* __restrict__ state, uint32_t seq_stride, uint32_t* __restrict__ clear,
+                                                           size_t clear_words) {
+    __shared__ uint4 sh[SC_T * 9];
+    __shared__ uint32_t shm[LOGUP ? SC_TILE + SC_TILE / 32 : 1];
+    __shared__ uint32_t wtot[4 * 4], carry_sh[4], agg_sh[4], sh_tile;
+    const uint32_t q = blockIdx.y, tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    uint32_t* st = state + (size_t)q * seq_stride;
+    const uint32_t tile = sc_begin(st, clear, clear_words, &sh_tile);
+    const size_t lo = (size_t)tile * SC_TILE;
+    const uint4* src = reinterpret_cast<const uint4*>(in) + (size_t)q * n + lo;
+    uint4* dst = reinterpret_cast<uint4*>(out) + (size_t)q * n + lo;
+    const uint32_t valid = n - lo < (size_t)SC_TILE ? (uint32_t)(n - lo) : (uint32_t)SC_TILE;
+#pragma unroll
+    for (int k = 0; k < SC_I; ++k) {
+        const uint32_t u = (uint32_t)k * SC_T + tid;
+        sh[sc_slot(u)] = u < valid ? src[u] : make_uint4(0, 0, 0, 0);  // elements past the end are zeros: they change no sum
+        if (LOGUP) shm[sc_mslot(u)] = u < valid ? mults[(size_t)q * n + lo + u] : 0u;
+    }
+    __syncthreads();
+    Fp4 pre[SC_I];  // this lane's elements, then their running sums
+#pragma unroll
+    for (int k = 0; k < SC_I; ++k) {
+        const uint4 w = sh[9 * tid + k];
+        pre[k] = Fp4{{w.x, w.y, w.z, w.w}};
+    }
+    if (LOGUP) {
+        inv_chunk<InvFp4, SC_I>(pre);
+#pragma unroll
+        for (int k = 0; k < SC_I; ++k) pre[k] = f4_scale(pre[k], shm[sc_mslot(SC_I * tid + (uint32_t)k)]);
+    }
+#pragma unroll
+    for (int k = 1; k < SC_I; ++k) pre[k] = f4_add(pre[k - 1], pre[k]);
+    Fp4 I = pre[SC_I - 1];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const Fp4 prev = sc_shfl_up(I, 1 << k);
+        if (lane >= (1u << k)) I = f4_add(I, prev);
+    }
+    if (lane == 63) *reinterpret_cast<uint4*>(wtot + 4 * wv) = make_uint4(I.c[0], I.c[1], I.c[2], I.c[3]);
+    __syncthreads();
+    Fp4 cw = f4_zero();
+    for (uint32_t w = 0; w < wv; ++w) cw = f4_add(cw, sc_ld4(wtot + 4 * w));
+    Fp4 excl = sc_shfl_up(I, 1);
+    if (lane == 0) excl = f4_zero();
+    excl = f4_add(excl, cw);
+    if (tid == SC_T - 1) {
+        const Fp4 agg = f4_add(I, cw);
+        *reinterpret_cast<uint4*>(agg_sh) = make_uint4(agg.c[0], agg.c[1], agg.c[2], agg.c[3]);
+        if (tile > 0) sc_publish(st + SC_HDR + 8 * (size_t)tile, agg);
+    }
+    __syncthreads();
+    if (wv == 0) {
+        Fp4 carry = f4_zero();
+        int base = (int)tile - 1;
+        while (tile > 0) {
+            const int id = base - (int)lane;
+            Fp4 val = f4_zero();
+            bool is_incl = true;
+            if (id >= 0) {
+                const uint32_t* slot = st + SC_HDR + 8 * (size_t)id;
+                for (;;) {
+                    if (sc_try_read(slot + 4, val)) { is_incl = true; break; }
+                    if (sc_try_read(slot, val)) { is_incl = false; break; }
+                    __builtin_amdgcn_s_sleep(1);
+                }
+            }
+            const unsigned long long m = __ballot(is_incl);
+            const uint32_t first = m ? (uint32_t)__ffsll((long long)m) - 1u : 64u;
+            Fp4 part = lane <= first ? val : f4_zero();
+#pragma unroll
+            for (int d = 32; d > 0; d >>= 1) part = f4_add(part, sc_shfl_xor(part, d));
+            carry = f4_add(carry, part);
+            if (first < 64u) break;
+            base -= 64;
+        }
+        if (lane == 0) {
+            sc_publish(st + SC_HDR + 8 * (size_t)tile + 4, f4_add(carry, sc_ld4(agg_sh)));
+            *reinterpret_cast<uint4*>(carry_sh) = make_uint4(carry.c[0], carry.c[1], carry.c[2], carry.c[3]);
+        }
+    }
+    __syncthreads();
+    const Fp4 e = f4_add(excl, sc_ld4(carry_sh));
+#pragma unroll
+    for (int k = 0; k < SC_I; ++k) {
+        const Fp4 o = f4_add(e, pre[k]);
+        sh[9 * tid + k] = make_uint4(o.c[0], o.c[1], o.c[2], o.c[3]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SC_I; ++k) {
+        const uint32_t u = (uint32_t)k * SC_T + tid;
+        if (u < valid) dst[u] = sh[sc_slot(u)];
+    }
+}
+
 // two alternating state buffers; returns the one to use and what to clear in the other
 const char* scan_state(bx_ctx* c, size_t words, uint32_t** use, uint32_t** clear, size_t* clear_words) {
     if (c->scan_cap < words) {
@@ -399,3 +610,92 @@ extern "C" const char* bx_poly_divide_batch_indexed(bx_ctx* c, bx_buf polys, siz
     OpScope op(c, "poly_divide", 32.0 * (double)size * (double)count);
     return poly_divide_lookback(c, (uint32_t*)polys.dptr, size, count, zs, (uint32_t*)rems_out.dptr, which);
 } BX_ABI_CATCH(c, "bx_poly_divide_batch_indexed")
+
+// ---- LogUp helpers: batch inversion, prefix sums, and both in one pass ----
+static const char* launch_sums(bx_ctx* c, bool logup, const uint32_t* in, uint32_t* out, const uint32_t* mults, size_t n, size_t count) {
+    const size_t tiles = (n + SC_TILE - 1) / SC_TILE;
+    const uint32_t seq_stride = SC_HDR + 8 * (uint32_t)tiles;
+    uint32_t *use, *clear;
+    size_t clear_words;
+    BX_TRY(scan_state(c, (size_t)seq_stride * count, &use, &clear, &clear_words));
+    if (logup)
+        hipLaunchKernelGGL(ps_lookback_kernel<true>, dim3((unsigned)tiles, (unsigned)count), dim3(SC_T), 0, c->stream, in, out, mults, n, use, seq_stride,
+                           clear, clear_words);
+    else
+        hipLaunchKernelGGL(ps_lookback_kernel<false>, dim3((unsigned)tiles, (unsigned)count), dim3(SC_T), 0, c->stream, in, out, mults, n, use, seq_stride,
+                           clear, clear_words);
+    BX_LAUNCH_CHECK(c);
+    return nullptr;
+}
+// out[i] = in[i]^-1 (* mults[i]) over n ext elements, one launch
+static const char* launch_invert_ext(bx_ctx* c, const uint32_t* in, uint32_t* out, const uint32_t* mults, size_t n) {
+    const unsigned tiles = (unsigned)((n + SC_TILE - 1) / SC_TILE);
+    if (mults)
+        hipLaunchKernelGGL(binv_ext_kernel<true>, dim3(tiles), dim3(SC_T), 0, c->stream, in, out, mults, n);
+    else
+        hipLaunchKernelGGL(binv_ext_kernel<false>, dim3(tiles), dim3(SC_T), 0, c->stream, in, out, mults, n);
+    BX_LAUNCH_CHECK(c);
+    return nullptr;
+}
+constexpr size_t SC_MAX_ELEMS = (size_t)SC_TILE << 28;  // tiles of one launch fit a grid dimension, and 8 state words per tile a 32-bit stride
+
+extern "C" const char* bx_batch_invert_ext(bx_ctx* c, bx_buf io) try {
+    if (!c) return "bx_batch_invert_ext: null ctx";
+    BX_REQUIRE(c, io.len % 4 == 0, "batch_invert_ext: buffer must hold AoS ext elements");
+    BX_REQUIRE(c, io.len / 4 <= SC_MAX_ELEMS, "batch_invert_ext: too many elements");
+    BX_REQUIRE(c, ((uintptr_t)io.dptr & 15u) == 0, "batch_invert_ext: buffers must be 16-byte aligned");
+    BX_ENTER(c);
+    if (!io.len) return nullptr;
+    OpScope op(c, "batch_invert_ext", 8.0 * (double)io.len);
+    return launch_invert_ext(c, (const uint32_t*)io.dptr, (uint32_t*)io.dptr, nullptr, io.len / 4);
+} BX_ABI_CATCH(c, "bx_batch_invert_ext")
+extern "C" const char* bx_batch_invert_elem(bx_ctx* c, bx_buf io) try {
+    if (!c) return "bx_batch_invert_elem: null ctx";
+    BX_REQUIRE(c, io.len <= SC_MAX_ELEMS, "batch_invert_elem: too many elements");
+    BX_REQUIRE(c, ((uintptr_t)io.dptr & 3u) == 0, "batch_invert_elem: buffer must be word aligned");
+    BX_ENTER(c);
+    if (!io.len) return nullptr;
+    OpScope op(c, "batch_invert_elem", 8.0 * (double)io.len);
+    const size_t lanes = (io.len + BI_K - 1) / BI_K;
+    hipLaunchKernelGGL(binv_elem_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, c->stream, (uint32_t*)io.dptr, io.len,
+                       ((uintptr_t)io.dptr & 15u) == 0);
+    BX_LAUNCH_CHECK(c);
+    return nullptr;
+} BX_ABI_CATCH(c, "bx_batch_invert_elem")
+extern "C" const char* bx_batch_prefix_sums(bx_ctx* c, bx_buf io, size_t count) try {
+    if (!c) return "bx_batch_prefix_sums: null ctx";
+    BX_REQUIRE(c, io.len % 4 == 0, "prefix_sums: buffer must hold AoS ext elements");
+    BX_REQUIRE(c, count >= 1 && count <= 65535, "prefix_sums: the number of sequences must be in [1, 65535]");
+    BX_REQUIRE(c, (io.len / 4) % count == 0, "prefix_sums: the buffer does not split into `count` equal sequences");
+    BX_REQUIRE(c, io.len / 4 / count <= SC_MAX_ELEMS, "prefix_sums: sequences too long");
+    BX_REQUIRE(c, ((uintptr_t)io.dptr & 15u) == 0, "prefix_sums: buffers must be 16-byte aligned");
+    BX_ENTER(c);
+    const size_t n = io.len / 4 / count;
+    if (n < 2) return nullptr;
+    OpScope op(c, "prefix_sums", 8.0 * (double)io.len);
+    if (c->scan_lookback) return launch_sums(c, false, (const uint32_t*)io.dptr, (uint32_t*)io.dptr, nullptr, n, count);
+    return prefix_sums_three_phase(c, (uint32_t*)io.dptr, n, count);
+} BX_ABI_CATCH(c, "bx_batch_prefix_sums")
+extern "C" const char* bx_prefix_sums(bx_ctx* c, bx_buf io) try {
+    if (!c) return "bx_prefix_sums: null ctx";
+    return bx_batch_prefix_sums(c, io, 1);
+} BX_ABI_CATCH(c, "bx_prefix_sums")
+extern "C" const char* bx_logup_accumulate(bx_ctx* c, bx_buf out, bx_buf denoms, bx_buf mults, size_t count) try {
+    if (!c) return "bx_logup_accumulate: null ctx";
+    BX_REQUIRE(c, out.len % 4 == 0 && denoms.len == out.len, "logup_accumulate: out and denoms must hold the same number of AoS ext elements");
+    BX_REQUIRE(c, count >= 1 && count <= 65535, "logup_accumulate: the number of sequences must be in [1, 65535]");
+    BX_REQUIRE(c, (out.len / 4) % count == 0, "logup_accumulate: the buffers do not split into `count` equal sequences");
+    const size_t n = out.len / 4 / count;
+    BX_REQUIRE(c, out.len / 4 <= SC_MAX_ELEMS, "logup_accumulate: too many elements");  // bounds n, and the one-launch inversion over all sequences
+    BX_REQUIRE(c, mul_le(count, n, mults.len), "logup_accumulate: one multiplicity per denominator");
+    BX_REQUIRE(c, ((uintptr_t)out.dptr & 15u) == 0 && ((uintptr_t)denoms.dptr & 15u) == 0 && ((uintptr_t)mults.dptr & 3u) == 0,
+               "logup_accumulate: ext buffers must be 16-byte aligned");
+    BX_ENTER(c);
+    if (!n) return nullptr;
+    OpScope op(c, "logup_accumulate", 8.0 * (double)out.len + 4.0 * (double)(count * n));
+    if (c->scan_lookback) return launch_sums(c, true, (const uint32_t*)denoms.dptr, (uint32_t*)out.dptr, (const uint32_t*)mults.dptr, n, count);
+    // the three-phase form: invert and scale into out, then the three-phase running sums over out
+    BX_TRY(launch_invert_ext(c, (const uint32_t*)denoms.dptr, (uint32_t*)out.dptr, (const uint32_t*)mults.dptr, n * count));
+    if (n < 2) return nullptr;
+    return prefix_sums_three_phase(c, (uint32_t*)out.dptr, n, count);
+} BX_ABI_CATCH(c, "bx_logup_accumulate")

@@ -100,6 +100,11 @@ def load_library():
         "bx_poly_divide_batch": [ctx, BxBuf, sz, u32p, BxBuf],
         "bx_prefix_products": [ctx, BxBuf],
         "bx_batch_prefix_products": [ctx, BxBuf, sz],
+        "bx_batch_invert_ext": [ctx, BxBuf],
+        "bx_batch_invert_elem": [ctx, BxBuf],
+        "bx_prefix_sums": [ctx, BxBuf],
+        "bx_batch_prefix_sums": [ctx, BxBuf, sz],
+        "bx_logup_accumulate": [ctx, BxBuf, BxBuf, BxBuf, sz],
         "bx_scatter": [ctx, BxBuf, BxBuf, BxBuf, BxBuf],
         "bx_timer_start": [ctx],
         "bx_timer_stop": [ctx, C.POINTER(C.c_float)],
@@ -373,6 +378,25 @@ class HipHal:
 
     def batch_prefix_products(self, io, count):
         self._check(self.lib.bx_batch_prefix_products(self.ctx, io.raw, count))
+
+    # the additive half of an accumulate stage (LogUp): extensions, see include/bx_hal.h
+    def batch_invert_ext(self, io):
+        """io[i] = io[i]^-1 over AoS ext elements, in place; zero maps to zero."""
+        self._check(self.lib.bx_batch_invert_ext(self.ctx, io.raw))
+
+    def batch_invert_elem(self, io):
+        """The same over base-field words."""
+        self._check(self.lib.bx_batch_invert_elem(self.ctx, io.raw))
+
+    def prefix_sums(self, io):
+        self._check(self.lib.bx_prefix_sums(self.ctx, io.raw))
+
+    def batch_prefix_sums(self, io, count):
+        self._check(self.lib.bx_batch_prefix_sums(self.ctx, io.raw, count))
+
+    def logup_accumulate(self, out, denoms, mults, count=1):
+        """out[s][i] = sum_{j <= i} mults[s][j] / denoms[s][j] for `count` sequences back to back; `out` may be `denoms`."""
+        self._check(self.lib.bx_logup_accumulate(self.ctx, out.raw, denoms.raw, mults.raw, count))
 
     def scatter(self, into, index, offsets, values):
         self._check(self.lib.bx_scatter(self.ctx, into.raw, index.raw, offsets.raw, values.raw))

@@ -206,6 +206,29 @@ const char* bx_prefix_products(bx_ctx* ctx, bx_buf io_ext);
 /* Extension: `count` independent sequences of io_ext.len/4/count ext elements each, laid out back to back, scanned in one
  * set of launches (the accumulate step runs one sequence per accumulator). */
 const char* bx_batch_prefix_products(bx_ctx* ctx, bx_buf io_ext, size_t count);
+/* Extensions: the additive half of an accumulate stage — what a logarithmic-derivative (LogUp) argument needs where a grand-product
+ * argument needs prefix_products: per row a sum of terms m / (beta + v) in the extension field, then a running sum over the rows.
+ * All five are enqueued on the ctx's stream like prefix_products; ext buffers are AoS (4 words per element) and must be 16-byte
+ * aligned; every word written is canonical (< BX_P), so two ways of computing the same thing agree word for word.
+ *
+ * bx_batch_invert_ext: io[i] = io[i]^-1 in Fp4 = Fp[X]/(X^4 + 11), in place.  ZERO MAPS TO ZERO (risc0's ExtElem::inv and Elem::inv
+ * compute x^(order - 2), which sends 0 to 0); a zero does not disturb its neighbours.  One field exponentiation per 8 elements
+ * (Montgomery's trick per lane), not one per element.
+ * bx_batch_invert_elem: the same over base-field words (multiplicities, the vanishing-polynomial division); any length. */
+const char* bx_batch_invert_ext(bx_ctx* ctx, bx_buf io_ext);
+const char* bx_batch_invert_elem(bx_ctx* ctx, bx_buf io);
+/* bx_prefix_sums: io[i] = io[0] + .. + io[i] over AoS ext elements (inclusive running sum), in place.
+ * bx_batch_prefix_sums: `count` independent sequences of io_ext.len/4/count elements each, back to back, in one set of launches.
+ * The tunable "scan_lookback" chooses between the one-launch look-back kernel and the three-phase kernels as it does for
+ * prefix_products; both give the same words. */
+const char* bx_prefix_sums(bx_ctx* ctx, bx_buf io_ext);
+const char* bx_batch_prefix_sums(bx_ctx* ctx, bx_buf io_ext, size_t count);
+/* bx_logup_accumulate: out[s][i] = sum_{j <= i} mults[s][j] * denoms[s][j]^-1 for `count` sequences of n = out_ext.len/4/count
+ * elements: denoms_ext (same length as out_ext) holds the ext denominators, mults (at least count * n words, sequence s at s * n) the
+ * base-field multiplicities.  A zero denominator contributes zero.  Word for word what bx_batch_invert_ext, an element-wise
+ * scale by mults and bx_batch_prefix_sums give, with one read of denoms and mults and one write of out; out may be denoms itself
+ * (any other overlap of out with denoms or mults is the caller's error). */
+const char* bx_logup_accumulate(bx_ctx* ctx, bx_buf out_ext, bx_buf denoms_ext, bx_buf mults, size_t count);
 /* Hal::scatter(into, index, offsets, values): for cycle c < index.len - 1, every entry e in [index[c], index[c+1])
  * writes into[offsets[e]] = values[e].  All four are device buffers.  Asynchronous: an offset outside `into` or an index
  * range outside offsets/values is detected on the device and reported by the next blocking call on the ctx (bx_d2h,
