@@ -276,9 +276,6 @@ const char* h2d_staged(bx_ctx* c, bx_buf dst, const uint32_t* src, size_t words)
 // where it will land; the data is there after d2h_batch_wait.  `used` starts at 0; nothing else may use bx_d2h in between.
 const char* d2h_batch_add(bx_ctx* c, size_t* used, bx_buf src, size_t words, const uint32_t** host);
 const char* d2h_batch_wait(bx_ctx* c);
-const char* poly_divide_lookback(bx_ctx* c, uint32_t* polys, size_t size, size_t count, const uint32_t* zs, uint32_t* rems, const uint32_t* which);  // scan.hip
-const char* prefix_products_lookback(bx_ctx* c, uint32_t* io, size_t n, size_t count);
-const char* prefix_sums_three_phase(bx_ctx* c, uint32_t* io, size_t n, size_t count);  // poly.hip: the scan_lookback = 0 form of bx_batch_prefix_sums
 const char* ntt_init_tables(bx_ctx* c);
 void ntt_free_tables(bx_ctx* c);
 const char* poseidon2_upload_params(bx_ctx* c);

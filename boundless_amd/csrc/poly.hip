@@ -1,10 +1,11 @@
-// poly.hip — FRI fold, DEEP mixing/evaluation/division and element-wise helpers for gfx950.
+// poly.hip — FRI fold, DEEP mixing/evaluation and element-wise helpers for gfx950 (the scans — poly_divide, prefix_products,
+// prefix_sums — are scan.hip).
 //
-// Restates risc0_zkp::hal::Hal::{fri_fold, mix_poly_coeffs, batch_evaluate_any, eltwise_*, gather_sample} and
-// risc0_zkp::core::poly::poly_divide (risc0-zkp 3.0.3, reference Cargo.lock:9155), reached from
+// Restates risc0_zkp::hal::Hal::{fri_fold, mix_poly_coeffs, batch_evaluate_any, eltwise_*, gather_sample, scatter}
+// (risc0-zkp 3.0.3, reference Cargo.lock:9155), reached from
 // bento/crates/workflow/src/tasks/prove.rs:41-49 through Prover::finalize / fri_prove.
-// All of these stream each input word once; they are HBM-bound except batch_evaluate_any and
-// poly_divide, whose Fp4 products make them VALU-bound.
+// All of these stream each input word once; they are HBM-bound except batch_evaluate_any,
+// whose Fp4 products make it VALU-bound.
 #define BX_PLAIN_MAD 1  // the signed multiply-adds of lazy_ext.hpp are left to the compiler here (no loop-carried cell state)
 #include <algorithm>
 
@@ -393,244 +394,6 @@ __global__ __launch_bounds__(64) void gather_batch_kernel(const uint4* __restric
     for (uint32_t i = threadIdx.x; i < size; i += 64u) dst[i] = src[(size_t)i * stride];
 }
 
-// The chunk walks below are chains of dependent Fp4 products; their loads are independent, so they are issued eight at a
-// time (SCAN_B elements = 128 bytes per lane in flight) instead of one per product.
-constexpr int SCAN_B = 8;
-
-// ---- poly_divide: q_{i-1} = p_i + z q_i (top down), in place; remainder = p_0 + z q_0 ----
-// Three phases over chunks of DIV_L coefficients: (1) each chunk's carry-out assuming zero carry-in,
-// (2) sequential composition of the chunk maps carry -> local + z^L * carry (one workgroup), (3) replay.
-// The phases nest: the chunk values are themselves an array to be divided by (x - z^L) — "the carry entering chunk ch" is
-// that division's quotient coefficient — so arrays longer than DIV_DIRECT recurse with chunks of DIV_L and the one-workgroup
-// kernel only ever sees <= DIV_DIRECT entries (2^20 -> 2^15 -> 2^10: five launches, 123 -> 40 us per 2^20 coefficients).
-constexpr int DIV_L = 32;
-constexpr size_t DIV_DIRECT = 2048;
-__global__ void div_local_kernel(const uint32_t* __restrict__ poly, size_t size, Fp4 z, uint32_t* __restrict__ local,
-                                 size_t chunks) {
-    size_t ch = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch >= chunks) return;
-    size_t lo = ch * DIV_L, hi = lo + DIV_L < size ? lo + DIV_L : size;
-    Fp4 cur = f4_zero();
-    for (size_t top = hi; top > lo;) {
-        const size_t nb = top - lo < (size_t)SCAN_B ? top - lo : (size_t)SCAN_B;
-        Fp4 v[SCAN_B];
-#pragma unroll
-        for (int k = 0; k < SCAN_B; ++k)
-            if ((size_t)k < nb) v[k] = ld4(poly + 4 * (top - 1 - k));
-#pragma unroll
-        for (int k = 0; k < SCAN_B; ++k)
-            if ((size_t)k < nb) cur = f4_add(f4_mul(z, cur), v[k]);
-        top -= nb;
-    }
-    st4(local + 4 * ch, cur);
-}
-// carry_in[ch] = value of `cur` entering chunk ch from above.  One workgroup: thread t owns a contiguous run of chunks
-// (thread 0 the highest), reduces it to the affine map carry -> a*carry + b, the maps are composed across threads with a
-// log-step (Hillis-Steele) scan in LDS, and each thread replays its run with the carry that enters it.
-__global__ void div_scan_kernel(uint32_t* __restrict__ local_then_carry, size_t chunks, Fp4 zL, uint32_t* __restrict__ rem) {
-    extern __shared__ uint32_t sh[];  // per thread: a (4 words) | b (4 words)
-    const uint32_t nt = blockDim.x, tid = threadIdx.x;
-    size_t per = (chunks + nt - 1) / nt;
-    size_t hi = chunks > (size_t)tid * per ? chunks - (size_t)tid * per : 0;
-    size_t lo = hi > per ? hi - per : 0;
-    Fp4 a = f4_one(), b = f4_zero();
-    for (size_t ch = hi; ch-- > lo;) {
-        b = f4_add(f4_mul(zL, b), ld4(local_then_carry + 4 * ch));
-        a = f4_mul(a, zL);
-    }
-    // inclusive scan of F_t = f_t o f_(t-1) o ... o f_0 with (a2,b2) o (a1,b1) = (a2*a1, a2*b1 + b2)
-    for (uint32_t d = 1; d < nt; d <<= 1) {
-        st4(sh + 8 * tid, a);
-        st4(sh + 8 * tid + 4, b);
-        __syncthreads();
-        if (tid >= d) {
-            Fp4 pa = ld4(sh + 8 * (tid - d)), pb = ld4(sh + 8 * (tid - d) + 4);
-            b = f4_add(f4_mul(a, pb), b);
-            a = f4_mul(a, pa);
-        }
-        __syncthreads();
-    }
-    st4(sh + 8 * tid + 4, b);
-    __syncthreads();
-    if (tid == nt - 1) st4(rem, b);  // composition of every run applied to carry 0 = the remainder
-    Fp4 carry = tid == 0 ? f4_zero() : ld4(sh + 8 * (tid - 1) + 4);
-    for (size_t ch = hi; ch-- > lo;) {
-        Fp4 l = ld4(local_then_carry + 4 * ch);
-        st4(local_then_carry + 4 * ch, carry);
-        carry = f4_add(f4_mul(zL, carry), l);
-    }
-}
-__global__ void div_apply_kernel(uint32_t* __restrict__ poly, size_t size, Fp4 z, const uint32_t* __restrict__ carry_in,
-                                 size_t chunks) {
-    size_t ch = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch >= chunks) return;
-    size_t lo = ch * DIV_L, hi = lo + DIV_L < size ? lo + DIV_L : size;
-    Fp4 cur = ld4(carry_in + 4 * ch);
-    for (size_t top = hi; top > lo;) {
-        const size_t nb = top - lo < (size_t)SCAN_B ? top - lo : (size_t)SCAN_B;
-        Fp4 v[SCAN_B];
-#pragma unroll
-        for (int k = 0; k < SCAN_B; ++k)
-            if ((size_t)k < nb) v[k] = ld4(poly + 4 * (top - 1 - k));
-#pragma unroll
-        for (int k = 0; k < SCAN_B; ++k)
-            if ((size_t)k < nb) {
-                st4(poly + 4 * (top - 1 - k), cur);
-                cur = f4_add(f4_mul(z, cur), v[k]);
-            }
-        top -= nb;
-    }
-}
-
-// ---- prefix_products: inclusive running product of ext elements, same three-phase shape as poly_divide ----
-constexpr int PP_L = 64;
-constexpr size_t PP_DIRECT = 2048;
-// blockIdx.y = sequence of a batch (each with its own n elements of io and `chunks` aggregates)
-__global__ void pp_local_kernel(const uint32_t* __restrict__ io, size_t n, size_t seq_stride, uint32_t* __restrict__ agg, size_t chunks,
-                                size_t agg_stride) {
-    size_t ch = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch >= chunks) return;
-    io += 4 * seq_stride * blockIdx.y;
-    agg += 4 * agg_stride * blockIdx.y;
-    size_t lo = ch * PP_L, hi = lo + PP_L < n ? lo + PP_L : n;
-    Fp4 p = f4_one();
-    for (size_t b = lo; b < hi; b += SCAN_B) {
-        const size_t nb = hi - b < (size_t)SCAN_B ? hi - b : (size_t)SCAN_B;
-        Fp4 v[SCAN_B];
-#pragma unroll
-        for (int k = 0; k < SCAN_B; ++k)
-            if ((size_t)k < nb) v[k] = ld4(io + 4 * (b + k));
-#pragma unroll
-        for (int k = 0; k < SCAN_B; ++k)
-            if ((size_t)k < nb) p = f4_mul(p, v[k]);
-    }
-    st4(agg + 4 * ch, p);
-}
-// agg[ch] <- product of all chunks before ch (exclusive scan), one workgroup, log-step scan across threads
-__global__ void pp_scan_kernel(uint32_t* __restrict__ agg, size_t chunks, size_t agg_stride) {
-    extern __shared__ uint32_t sh[];
-    agg += 4 * agg_stride * blockIdx.x;
-    const uint32_t nt = blockDim.x, tid = threadIdx.x;
-    size_t per = (chunks + nt - 1) / nt;
-    size_t lo = (size_t)tid * per < chunks ? (size_t)tid * per : chunks;
-    size_t hi = lo + per < chunks ? lo + per : chunks;
-    Fp4 mine = f4_one();
-    for (size_t ch = lo; ch < hi; ++ch) mine = f4_mul(mine, ld4(agg + 4 * ch));
-    Fp4 incl = mine;
-    for (uint32_t d = 1; d < nt; d <<= 1) {
-        st4(sh + 4 * tid, incl);
-        __syncthreads();
-        if (tid >= d) incl = f4_mul(incl, ld4(sh + 4 * (tid - d)));
-        __syncthreads();
-    }
-    st4(sh + 4 * tid, incl);
-    __syncthreads();
-    Fp4 carry = tid == 0 ? f4_one() : ld4(sh + 4 * (tid - 1));
-    for (size_t ch = lo; ch < hi; ++ch) {
-        Fp4 a = ld4(agg + 4 * ch);
-        st4(agg + 4 * ch, carry);
-        carry = f4_mul(carry, a);
-    }
-}
-// exclusive form for the inner levels: io[i] <- carry * prod_{lo <= k < i} io[k]
-__global__ void pp_apply_excl_kernel(uint32_t* __restrict__ io, size_t n, size_t seq_stride, const uint32_t* __restrict__ carry_in,
-                                     size_t chunks, size_t carry_stride) {
-    size_t ch = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch >= chunks) return;
-    io += 4 * seq_stride * blockIdx.y;
-    carry_in += 4 * carry_stride * blockIdx.y;
-    size_t lo = ch * PP_L, hi = lo + PP_L < n ? lo + PP_L : n;
-    Fp4 p = ld4(carry_in + 4 * ch);
-    for (size_t b = lo; b < hi; b += SCAN_B) {
-        const size_t nb = hi - b < (size_t)SCAN_B ? hi - b : (size_t)SCAN_B;
-        Fp4 v[SCAN_B];
-#pragma unroll
-        for (int k = 0; k < SCAN_B; ++k)
-            if ((size_t)k < nb) v[k] = ld4(io + 4 * (b + k));
-#pragma unroll
-        for (int k = 0; k < SCAN_B; ++k)
-            if ((size_t)k < nb) {
-                st4(io + 4 * (b + k), p);
-                p = f4_mul(p, v[k]);
-            }
-    }
-}
-__global__ void pp_apply_kernel(uint32_t* __restrict__ io, size_t n, const uint32_t* __restrict__ carry_in, size_t chunks) {
-    size_t ch = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch >= chunks) return;
-    io += 4 * n * blockIdx.y;
-    carry_in += 4 * chunks * blockIdx.y;
-    size_t lo = ch * PP_L, hi = lo + PP_L < n ? lo + PP_L : n;
-    Fp4 p = ld4(carry_in + 4 * ch);
-    for (size_t b = lo; b < hi; b += SCAN_B) {
-        const size_t nb = hi - b < (size_t)SCAN_B ? hi - b : (size_t)SCAN_B;
-        Fp4 v[SCAN_B];
-#pragma unroll
-        for (int k = 0; k < SCAN_B; ++k)
-            if ((size_t)k < nb) v[k] = ld4(io + 4 * (b + k));
-#pragma unroll
-        for (int k = 0; k < SCAN_B; ++k)
-            if ((size_t)k < nb) {
-                p = f4_mul(p, v[k]);
-                st4(io + 4 * (b + k), p);
-            }
-    }
-}
-// ---- prefix_sums: inclusive running sum of ext elements; the three-phase shape of prefix_products with the Fp4 sum as the operator
-// (the scan_lookback = 0 form; ps_lookback_kernel of scan.hip is the default) ----
-__global__ void ps_local_kernel(const uint32_t* __restrict__ io, size_t n, size_t seq_stride, uint32_t* __restrict__ agg, size_t chunks,
-                                size_t agg_stride) {
-    size_t ch = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch >= chunks) return;
-    io += 4 * seq_stride * blockIdx.y;
-    agg += 4 * agg_stride * blockIdx.y;
-    size_t lo = ch * PP_L, hi = lo + PP_L < n ? lo + PP_L : n;
-    Fp4 p = f4_zero();
-    for (size_t b = lo; b < hi; ++b) p = f4_add(p, ld4(io + 4 * b));
-    st4(agg + 4 * ch, p);
-}
-// agg[ch] <- sum of all chunks before ch (exclusive scan), one workgroup per sequence
-__global__ void ps_scan_kernel(uint32_t* __restrict__ agg, size_t chunks, size_t agg_stride) {
-    extern __shared__ uint32_t sh[];
-    agg += 4 * agg_stride * blockIdx.x;
-    const uint32_t nt = blockDim.x, tid = threadIdx.x;
-    size_t per = (chunks + nt - 1) / nt;
-    size_t lo = (size_t)tid * per < chunks ? (size_t)tid * per : chunks;
-    size_t hi = lo + per < chunks ? lo + per : chunks;
-    Fp4 incl = f4_zero();
-    for (size_t ch = lo; ch < hi; ++ch) incl = f4_add(incl, ld4(agg + 4 * ch));
-    for (uint32_t d = 1; d < nt; d <<= 1) {
-        st4(sh + 4 * tid, incl);
-        __syncthreads();
-        if (tid >= d) incl = f4_add(incl, ld4(sh + 4 * (tid - d)));
-        __syncthreads();
-    }
-    st4(sh + 4 * tid, incl);
-    __syncthreads();
-    Fp4 carry = tid == 0 ? f4_zero() : ld4(sh + 4 * (tid - 1));
-    for (size_t ch = lo; ch < hi; ++ch) {
-        Fp4 a = ld4(agg + 4 * ch);
-        st4(agg + 4 * ch, carry);
-        carry = f4_add(carry, a);
-    }
-}
-// io[i] <- carry + sum_{lo <= k < i} io[k] (EXCL, the inner levels) or ... + io[i] (the outer level)
-template <bool EXCL>
-__global__ void ps_apply_kernel(uint32_t* __restrict__ io, size_t n, size_t seq_stride, const uint32_t* __restrict__ carry_in, size_t chunks,
-                                size_t carry_stride) {
-    size_t ch = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch >= chunks) return;
-    io += 4 * seq_stride * blockIdx.y;
-    carry_in += 4 * carry_stride * blockIdx.y;
-    size_t lo = ch * PP_L, hi = lo + PP_L < n ? lo + PP_L : n;
-    Fp4 p = ld4(carry_in + 4 * ch);
-    for (size_t b = lo; b < hi; ++b) {
-        const Fp4 v = ld4(io + 4 * b);
-        if (EXCL) st4(io + 4 * b, p);
-        p = f4_add(p, v);
-        if (!EXCL) st4(io + 4 * b, p);
-    }
-}
 // entries [index[0], index[last]) are written.  The per-cycle grouping of upstream's scatter only orders writes that hit
 // the same offset, which its circuits never produce, so one pass over the range is equivalent.  Nothing is read back by
 // the host: a bad offset or index range raises a word of the ctx's deferred error flags (reported by the next bx_d2h / bx_sync).
@@ -902,125 +665,6 @@ const char* gather_flush(bx_ctx* c) {
     return nullptr;
 }
 }  // namespace bx
-
-// in-place division of the AoS ext array `arr` (n entries) by (x - z); `scratch` has room for every level's chunk values
-static const char* divide_rec(bx_ctx* c, uint32_t* arr, size_t n, Fp4 z, uint32_t* scratch, uint32_t* rem) {
-    if (n <= DIV_DIRECT) {
-        // one workgroup: thread t owns a run of entries; the "chunk" multiplier of the kernel is z itself here
-        unsigned nt = n >= 1024 ? 1024 : 64;
-        hipLaunchKernelGGL(div_scan_kernel, dim3(1), dim3(nt), nt * 32, c->stream, arr, n, z, rem);
-        BX_LAUNCH_CHECK(c);
-        return nullptr;
-    }
-    const size_t chunks = (n + DIV_L - 1) / DIV_L;
-    hipLaunchKernelGGL(div_local_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, c->stream, (const uint32_t*)arr, n, z, scratch,
-                       chunks);
-    BX_LAUNCH_CHECK(c);
-    BX_TRY(divide_rec(c, scratch, chunks, f4_pow(z, DIV_L), scratch + 4 * chunks, rem));  // chunk values -> carries entering the chunks
-    hipLaunchKernelGGL(div_apply_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, c->stream, arr, n, z, (const uint32_t*)scratch,
-                       chunks);
-    BX_LAUNCH_CHECK(c);
-    return nullptr;
-}
-static size_t scan_scratch_words(size_t n, size_t L, size_t direct, size_t count) {
-    size_t words = 8;
-    while (n > direct) {
-        n = (n + L - 1) / L;
-        words += 4 * n * count;
-    }
-    return words;
-}
-
-extern "C" const char* bx_poly_divide(bx_ctx* c, bx_buf poly, const uint32_t z[4], bx_buf rem_out) try {
-    if (!c) return "bx_poly_divide: null ctx";
-    BX_REQUIRE(c, poly.len % 4 == 0 && rem_out.len >= 4, "poly_divide: poly must be AoS ext, remainder buffer >= 4 words");
-    BX_ENTER(c);
-    size_t size = poly.len / 4;
-    if (!size) return nullptr;
-    OpScope op(c, "poly_divide", 8.0 * (double)poly.len);
-    if (c->scan_lookback && ((uintptr_t)poly.dptr & 15u) == 0 && ((uintptr_t)rem_out.dptr & 15u) == 0)
-        return poly_divide_lookback(c, (uint32_t*)poly.dptr, size, 1, z, (uint32_t*)rem_out.dptr, nullptr);
-    BX_TRY(ensure_scratch(c, scan_scratch_words(size, DIV_L, DIV_DIRECT, 1)));
-    return divide_rec(c, (uint32_t*)poly.dptr, size, host4(z), c->d_scratch, (uint32_t*)rem_out.dptr);
-} BX_ABI_CATCH(c, "bx_poly_divide")
-
-// exclusive running products, in place, of `count` sequences of n entries (sequence k at arr + 4 * k * stride)
-static const char* excl_scan_rec(bx_ctx* c, uint32_t* arr, size_t n, size_t stride, size_t count, uint32_t* scratch) {
-    if (n <= PP_DIRECT) {
-        unsigned nt = n >= 1024 ? 1024 : 64;
-        hipLaunchKernelGGL(pp_scan_kernel, dim3((unsigned)count), dim3(nt), nt * 16, c->stream, arr, n, stride);
-        BX_LAUNCH_CHECK(c);
-        return nullptr;
-    }
-    const size_t chunks = (n + PP_L - 1) / PP_L;
-    hipLaunchKernelGGL(pp_local_kernel, dim3((unsigned)((chunks + 255) / 256), (unsigned)count), dim3(256), 0, c->stream, (const uint32_t*)arr, n,
-                       stride, scratch, chunks, chunks);
-    BX_LAUNCH_CHECK(c);
-    BX_TRY(excl_scan_rec(c, scratch, chunks, chunks, count, scratch + 4 * chunks * count));
-    hipLaunchKernelGGL(pp_apply_excl_kernel, dim3((unsigned)((chunks + 255) / 256), (unsigned)count), dim3(256), 0, c->stream, arr, n, stride,
-                       (const uint32_t*)scratch, chunks, chunks);
-    BX_LAUNCH_CHECK(c);
-    return nullptr;
-}
-
-extern "C" const char* bx_batch_prefix_products(bx_ctx* c, bx_buf io, size_t count) try {
-    if (!c) return "bx_batch_prefix_products: null ctx";
-    BX_REQUIRE(c, io.len % 4 == 0, "prefix_products: buffer must hold AoS ext elements");
-    BX_REQUIRE(c, count >= 1 && (io.len / 4) % count == 0, "prefix_products: the buffer does not split into `count` equal sequences");
-    BX_REQUIRE(c, count <= 65535, "prefix_products: too many sequences");
-    BX_ENTER(c);
-    size_t n = io.len / 4 / count;
-    if (n < 2) return nullptr;
-    OpScope op(c, "prefix_products", 8.0 * (double)io.len);
-    if (c->scan_lookback && ((uintptr_t)io.dptr & 15u) == 0) return prefix_products_lookback(c, (uint32_t*)io.dptr, n, count);
-    // chunk products -> exclusive scan of them (recursively, PP_L per level) -> inclusive replay of every chunk with its carry
-    size_t chunks = (n + PP_L - 1) / PP_L;
-    BX_TRY(ensure_scratch(c, 4 * chunks * count + scan_scratch_words(chunks, PP_L, PP_DIRECT, count)));
-    hipLaunchKernelGGL(pp_local_kernel, dim3((unsigned)((chunks + 255) / 256), (unsigned)count), dim3(256), 0, c->stream,
-                       (const uint32_t*)io.dptr, n, n, c->d_scratch, chunks, chunks);
-    BX_LAUNCH_CHECK(c);
-    BX_TRY(excl_scan_rec(c, c->d_scratch, chunks, chunks, count, c->d_scratch + 4 * chunks * count));
-    hipLaunchKernelGGL(pp_apply_kernel, dim3((unsigned)((chunks + 255) / 256), (unsigned)count), dim3(256), 0, c->stream, (uint32_t*)io.dptr, n,
-                       c->d_scratch, chunks);
-    BX_LAUNCH_CHECK(c);
-    return nullptr;
-} BX_ABI_CATCH(c, "bx_batch_prefix_products")
-extern "C" const char* bx_prefix_products(bx_ctx* c, bx_buf io) try {
-    if (!c) return "bx_prefix_products: null ctx";
-    return bx_batch_prefix_products(c, io, 1);
-} BX_ABI_CATCH(c, "bx_prefix_products")
-
-// exclusive running sums, in place, of `count` sequences of n entries (sequence k at arr + 4 * k * stride)
-static const char* excl_sum_rec(bx_ctx* c, uint32_t* arr, size_t n, size_t stride, size_t count, uint32_t* scratch) {
-    if (n <= PP_DIRECT) {
-        unsigned nt = n >= 1024 ? 1024 : 64;
-        hipLaunchKernelGGL(ps_scan_kernel, dim3((unsigned)count), dim3(nt), nt * 16, c->stream, arr, n, stride);
-        BX_LAUNCH_CHECK(c);
-        return nullptr;
-    }
-    const size_t chunks = (n + PP_L - 1) / PP_L;
-    hipLaunchKernelGGL(ps_local_kernel, dim3((unsigned)((chunks + 255) / 256), (unsigned)count), dim3(256), 0, c->stream, (const uint32_t*)arr, n,
-                       stride, scratch, chunks, chunks);
-    BX_LAUNCH_CHECK(c);
-    BX_TRY(excl_sum_rec(c, scratch, chunks, chunks, count, scratch + 4 * chunks * count));
-    hipLaunchKernelGGL(ps_apply_kernel<true>, dim3((unsigned)((chunks + 255) / 256), (unsigned)count), dim3(256), 0, c->stream, arr, n, stride,
-                       (const uint32_t*)scratch, chunks, chunks);
-    BX_LAUNCH_CHECK(c);
-    return nullptr;
-}
-// chunk sums -> exclusive scan of them (recursively, PP_L per level) -> inclusive replay of every chunk with its carry
-const char* bx::prefix_sums_three_phase(bx_ctx* c, uint32_t* io, size_t n, size_t count) {
-    const size_t chunks = (n + PP_L - 1) / PP_L;
-    BX_TRY(ensure_scratch(c, 4 * chunks * count + scan_scratch_words(chunks, PP_L, PP_DIRECT, count)));
-    hipLaunchKernelGGL(ps_local_kernel, dim3((unsigned)((chunks + 255) / 256), (unsigned)count), dim3(256), 0, c->stream, (const uint32_t*)io, n, n,
-                       c->d_scratch, chunks, chunks);
-    BX_LAUNCH_CHECK(c);
-    BX_TRY(excl_sum_rec(c, c->d_scratch, chunks, chunks, count, c->d_scratch + 4 * chunks * count));
-    hipLaunchKernelGGL(ps_apply_kernel<false>, dim3((unsigned)((chunks + 255) / 256), (unsigned)count), dim3(256), 0, c->stream, io, n, n,
-                       (const uint32_t*)c->d_scratch, chunks, chunks);
-    BX_LAUNCH_CHECK(c);
-    return nullptr;
-}
 
 extern "C" const char* bx_scatter(bx_ctx* c, bx_buf into, bx_buf index, bx_buf offsets, bx_buf values) try {
     if (!c) return "bx_scatter: null ctx";

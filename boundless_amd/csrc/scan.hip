@@ -1,18 +1,21 @@
-// scan.hip — single-pass scans over AoS ext arrays for gfx950: the DEEP quotient (poly_divide), prefix_products, and the additive
-// half of an accumulate stage (batch inversion, prefix_sums, logup_accumulate: further down, beside the kernels).
+// scan.hip — every scan over AoS ext arrays for gfx950: the DEEP quotient (poly_divide*), prefix_products, prefix_sums, and the
+// additive half of an accumulate stage (batch inversion, logup_accumulate).
 //
 // Restates risc0_zkp::core::poly::poly_divide (run once per tap point of every DEEP combination polynomial by
 // Prover::finalize) and risc0_zkp::hal::Hal::prefix_products (risc0-zkp 3.0.3, reference Cargo.lock:9155), reached from
 // bento/crates/workflow/src/tasks/prove.rs:41-49.
 //
-// Both are first-order recurrences over 16-byte elements whose algorithmic traffic is one read and one write of the array.
-// Round 2 ran them as reduce / scan-the-chunk-values (recursively, down to one workgroup) / replay: five launches per call, every
-// element read twice with 512-byte strides between lanes, 5-17 % of the HBM roofline.  Here each is ONE launch: a workgroup owns
-// a tile of 2048 elements (loaded coalesced, transposed through LDS so that a lane owns 8 consecutive elements), scans it in
-// registers and wave shuffles, publishes its aggregate, and obtains the carry entering the tile by DECOUPLED LOOK-BACK: wave 0
-// inspects the 64 preceding tiles at once, takes the nearest published inclusive value and the aggregates after it, and moves
-// on 64 tiles at a time until it finds one.  Tiles are handed out by a ticket counter, so a tile's predecessors are always
-// running or finished and the spin terminates.  Each array is read once and written once.
+// All are first-order recurrences over 16-byte elements whose algorithmic traffic is one read and one write of the array.  Each has
+// two forms, and every entry point reads the same way: validate, open the OpScope, then "look-back if enabled (the scan_lookback
+// tunable) and 16-byte aligned, else three-phase".
+//
+// LOOK-BACK, the default: ONE launch.  A workgroup owns a tile of 2048 elements (loaded coalesced, transposed through LDS so that a
+// lane owns 8 consecutive elements), scans it in registers and wave shuffles, publishes its aggregate, and obtains the carry entering
+// the tile by DECOUPLED LOOK-BACK: wave 0 inspects the 64 preceding tiles at once, takes the nearest published inclusive value and
+// the aggregates after it, and moves on 64 tiles at a time until it finds one.  Tiles are handed out by a ticket counter, so a
+// tile's predecessors are always running or finished and the spin terminates.  Each array is read once and written once.
+// The tile load, the tile store and the look-back loop are written once (sc_tile_load, sc_tile_store, sc_look_back); products, sums
+// and the fused LogUp sum are one kernel over an operator (ScanMul, ScanSum); the division keeps its own body between the shared pieces.
 //
 // Publication protocol.  An ext value is four words < 2^31, so bit 31 of every word is free: a slot is written with four
 // relaxed agent-scope atomic stores of (word | 2^31) and read with four relaxed agent-scope atomic loads; the value is taken
@@ -23,6 +26,9 @@
 // poly_divide specifics: the recurrence runs from the top coefficient down, cur <- z cur + p_i with out_i = cur before the
 // update; an element's map is affine with a known slope (z), so a span of L elements is (z^L, B) and only B is scanned or
 // published — the slopes z^8, z^16 .. z^2048, z^(2048*64) come from the host as kernel arguments.
+//
+// THREE-PHASE (further down): chunk values / scan of the chunk values (recursively, down to one workgroup) / replay.  Five launches
+// per call, every element read twice with 512-byte or 1-KiB strides between lanes; it needs 4-byte alignment only.
 #define BX_PLAIN_MAD 1  // the signed multiply-adds of lazy_ext.hpp are left to the compiler here
 #include <algorithm>
 #include <vector>
@@ -40,6 +46,8 @@ __device__ __forceinline__ Fp4 sc_ld4(const uint32_t* p) {
     uint4 v = *reinterpret_cast<const uint4*>(p);
     return Fp4{{v.x, v.y, v.z, v.w}};
 }
+__device__ __forceinline__ uint4 sc_u4(const Fp4& a) { return make_uint4(a.c[0], a.c[1], a.c[2], a.c[3]); }
+__device__ __forceinline__ void sc_st4(uint32_t* p, const Fp4& a) { *reinterpret_cast<uint4*>(p) = sc_u4(a); }
 __device__ __forceinline__ void sc_publish(uint32_t* slot, const Fp4& v) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) __hip_atomic_store(slot + k, v.c[k] | SC_VALID, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -70,6 +78,110 @@ __device__ __forceinline__ uint32_t sc_begin(uint32_t* __restrict__ seq_state, u
     return *sh_tile;
 }
 
+// ---- the two scan operators.  combine is the generic product, combine_lz the lazy one of the chains inside a tile (the same canonical
+// words, so published values keep bit 31 free; the sum has one body for both, on purpose); pad is what an element past the end of a tile reads as; carry / apply are the last step,
+// a lane's carry-in applied to its 8 running values: the product centres the carry once ----
+struct ScanMul {
+    using Carry = C4;
+    static __device__ __forceinline__ Fp4 identity() { return f4_one(); }
+    static __device__ __forceinline__ Fp4 combine(const Fp4& a, const Fp4& b) { return f4_mul(a, b); }
+    static __device__ __forceinline__ Fp4 combine_lz(const Fp4& a, const Fp4& b) { return f4_mul_lz(a, b); }
+    static __device__ __forceinline__ uint4 pad() { return make_uint4(MONT_ONE, 0, 0, 0); }
+    static __device__ __forceinline__ Carry carry(const Fp4& e) { return f4_centre(e); }
+    static __device__ __forceinline__ Fp4 apply(const Carry& e, const Fp4& x) { return f4_mul_cc(e, f4_centre(x)); }
+};
+struct ScanSum {
+    using Carry = Fp4;
+    static __device__ __forceinline__ Fp4 identity() { return f4_zero(); }
+    static __device__ __forceinline__ Fp4 combine(const Fp4& a, const Fp4& b) { return f4_add(a, b); }
+    static __device__ __forceinline__ Fp4 combine_lz(const Fp4& a, const Fp4& b) { return f4_add(a, b); }
+    static __device__ __forceinline__ uint4 pad() { return make_uint4(0, 0, 0, 0); }
+    static __device__ __forceinline__ Carry carry(const Fp4& e) { return e; }
+    static __device__ __forceinline__ Fp4 apply(const Carry& e, const Fp4& x) { return f4_add(e, x); }
+};
+
+// ---- the pieces every tile kernel shares ----
+// LDS layout of a tile: lane t's 8 elements at [9 t, 9 t + 8) (in 16-byte units): the pad makes the blocked accesses conflict-free
+__device__ __forceinline__ uint32_t sc_slot(uint32_t u) { return (u >> 3) * 9u + (u & 7u); }
+// Where element u of a tile lies in its sequence: ascending from `lo`, or (the division) descending from below `hi`.
+struct TileUp {
+    size_t lo;
+    __device__ __forceinline__ size_t operator()(uint32_t u) const { return lo + u; }
+};
+struct TileDown {
+    size_t hi;
+    __device__ __forceinline__ size_t operator()(uint32_t u) const { return hi - 1 - u; }
+};
+// Coalesced load, transposed through LDS: element u of the tile is seq[at(u)], elements past `valid` read as `pad`; x[] returns the
+// lane's 8 consecutive elements.  also(u) runs beside each element's load, so that whatever else a kernel stages per element (the
+// LogUp multiplicities) is in flight together with the tile and behind the same barrier.
+template <typename At, typename Also>
+__device__ __forceinline__ void sc_tile_load(uint4* sh, const uint4* seq, At at, uint32_t valid, const uint4 pad, Fp4 (&x)[SC_I], Also also) {
+    const uint32_t tid = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < SC_I; ++k) {
+        const uint32_t u = (uint32_t)k * SC_T + tid;
+        also(u);
+        sh[sc_slot(u)] = u < valid ? seq[at(u)] : uint4(pad);  // a copy: between two lvalues the choice would be of addresses, one of them in scratch
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SC_I; ++k) {
+        const uint4 w = sh[9 * tid + k];
+        x[k] = Fp4{{w.x, w.y, w.z, w.w}};
+    }
+}
+template <typename At>
+__device__ __forceinline__ void sc_tile_load(uint4* sh, const uint4* seq, At at, uint32_t valid, const uint4 pad, Fp4 (&x)[SC_I]) {
+    sc_tile_load(sh, seq, at, valid, pad, x, [](uint32_t) {});
+}
+// the way back: lane t has left its results at sh[9 t + k]
+template <typename At>
+__device__ __forceinline__ void sc_tile_store(const uint4* sh, uint4* seq, At at, uint32_t valid) {
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SC_I; ++k) {
+        const uint32_t u = (uint32_t)k * SC_T + threadIdx.x;
+        if (u < valid) seq[at(u)] = sh[sc_slot(u)];
+    }
+}
+// The look-back of wave 0 (tile > 0): lane l inspects tile (base - l); tiles before the first one count as "inclusive, identity".
+// Returns the carry entering `tile`.  W weighs what is read: W::lane a lane's value, W::window the combined window, W::next steps
+// back one window — nothing for a plain operator, the known slopes for the division.
+struct NoWeight {
+    __device__ __forceinline__ Fp4 lane(const Fp4& v) const { return v; }
+    __device__ __forceinline__ Fp4 window(const Fp4& p) const { return p; }
+    __device__ __forceinline__ void next() {}
+};
+template <typename Op, typename W>
+__device__ __forceinline__ Fp4 sc_look_back(const uint32_t* st, uint32_t tile, uint32_t lane, W w) {
+    Fp4 carry = Op::identity();
+    int base = (int)tile - 1;
+    while (tile > 0) {
+        const int id = base - (int)lane;
+        Fp4 val = Op::identity();
+        bool is_incl = true;
+        if (id >= 0) {
+            const uint32_t* slot = st + SC_HDR + 8 * (size_t)id;
+            for (;;) {
+                if (sc_try_read(slot + 4, val)) { is_incl = true; break; }
+                if (sc_try_read(slot, val)) { is_incl = false; break; }
+                __builtin_amdgcn_s_sleep(1);
+            }
+        }
+        const unsigned long long m = __ballot(is_incl);
+        const uint32_t first = m ? (uint32_t)__ffsll((long long)m) - 1u : 64u;  // nearest tile whose inclusive value is known
+        Fp4 part = lane <= first ? w.lane(val) : Op::identity();
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) part = Op::combine_lz(part, sc_shfl_xor(part, d));
+        carry = Op::combine_lz(carry, w.window(part));
+        if (first < 64u) break;
+        w.next();
+        base -= 64;
+    }
+    return carry;
+}
+
 struct DivSeq {
     Fp4 z;      // the point
     Fp4 zp[6];  // z^(8 * 2^k), k < 6: slopes of spans of 1, 2, .. 32 lanes
@@ -92,9 +204,14 @@ __device__ __forceinline__ Fp4 sc_lane_pow(const Fp4 (&tab)[6], uint32_t lane) {
 struct DivArgs {
     DivSeq s[8];
 };
-
-// LDS layout of a tile: lane t's 8 elements at [9 t, 9 t + 8) (in 16-byte units): the pad makes the blocked accesses conflict-free
-__device__ __forceinline__ uint32_t sc_slot(uint32_t u) { return (u >> 3) * 9u + (u & 7u); }
+// the division's look-back is a sum whose terms carry slopes: tile (base - l) weighs zL^l, the window `wbase`, 64 tiles zL64
+struct DivWeight {
+    const DivSeq& S;
+    Fp4 lpow, wbase;
+    __device__ __forceinline__ Fp4 lane(const Fp4& v) const { return f4_mul_lz(lpow, v); }
+    __device__ __forceinline__ Fp4 window(const Fp4& p) const { return f4_mul(wbase, p); }
+    __device__ __forceinline__ void next() { wbase = f4_mul(wbase, S.zL64); }
+};
 
 __global__ __launch_bounds__(SC_T) void div_lookback_kernel(uint32_t* __restrict__ polys, size_t size, DivArgs args, uint32_t* __restrict__ state,
                                                             uint32_t seq_stride, uint32_t tiles, uint32_t* __restrict__ clear, size_t clear_words,
@@ -108,19 +225,8 @@ __global__ __launch_bounds__(SC_T) void div_lookback_kernel(uint32_t* __restrict
     uint4* poly = reinterpret_cast<uint4*>(polys) + (size_t)S.poly * size;
     const size_t hi = size - (size_t)tile * SC_TILE;                    // positions [hi - valid, hi), top first: u = hi - 1 - pos
     const uint32_t valid = hi < (size_t)SC_TILE ? (uint32_t)hi : (uint32_t)SC_TILE;  // elements of this tile that exist
-    // coalesced load (descending addresses), transposed through LDS
-#pragma unroll
-    for (int k = 0; k < SC_I; ++k) {
-        const uint32_t u = (uint32_t)k * SC_T + tid;
-        sh[sc_slot(u)] = u < valid ? poly[hi - 1 - u] : make_uint4(0, 0, 0, 0);
-    }
-    __syncthreads();
     Fp4 v[SC_I];
-#pragma unroll
-    for (int k = 0; k < SC_I; ++k) {
-        const uint4 w = sh[9 * tid + k];
-        v[k] = Fp4{{w.x, w.y, w.z, w.w}};
-    }
+    sc_tile_load(sh, poly, TileDown{hi}, valid, make_uint4(0, 0, 0, 0), v);
     const uint32_t mine = valid > SC_I * tid ? (valid - SC_I * tid < (uint32_t)SC_I ? valid - SC_I * tid : (uint32_t)SC_I) : 0u;
     const C4 zc = f4_centre(S.z);
     Fp4 cur = f4_zero();
@@ -134,7 +240,7 @@ __global__ __launch_bounds__(SC_T) void div_lookback_kernel(uint32_t* __restrict
         const Fp4 prev = sc_shfl_up(I, 1 << k);
         if (lane >= (1u << k)) I = f4_add(I, f4_mul_lz(S.zp[k], prev));
     }
-    if (lane == 63) *reinterpret_cast<uint4*>(wtot + 4 * wv) = make_uint4(I.c[0], I.c[1], I.c[2], I.c[3]);
+    if (lane == 63) sc_st4(wtot + 4 * wv, I);
     __syncthreads();
     Fp4 cw = f4_zero();  // carry entering this wave from the waves above it (tile carry still zero)
     for (uint32_t w = 0; w < wv; ++w) cw = f4_add(f4_mul_lz(S.z512, cw), sc_ld4(wtot + 4 * w));
@@ -144,41 +250,16 @@ __global__ __launch_bounds__(SC_T) void div_lookback_kernel(uint32_t* __restrict
     excl = f4_add(excl, f4_mul_lz(zlane, cw));
     if (tid == SC_T - 1) {
         const Fp4 agg = f4_add(I, f4_mul(S.z512, cw));  // the whole tile with zero carry-in
-        *reinterpret_cast<uint4*>(agg_sh) = make_uint4(agg.c[0], agg.c[1], agg.c[2], agg.c[3]);
+        sc_st4(agg_sh, agg);
         if (tile > 0) sc_publish(st + SC_HDR + 8 * (size_t)tile, agg);
     }
     __syncthreads();
     if (wv == 0) {
-        // look back: lane l inspects tile (base - l); tiles above the first one count as "inclusive, zero"
-        Fp4 carry = f4_zero(), wbase = f4_one();
-        const Fp4 lpow = sc_lane_pow(S.zLp, lane);
-        int base = (int)tile - 1;
-        while (tile > 0) {
-            const int id = base - (int)lane;
-            Fp4 val = f4_zero();
-            bool is_incl = true;
-            if (id >= 0) {
-                const uint32_t* slot = st + SC_HDR + 8 * (size_t)id;
-                for (;;) {
-                    if (sc_try_read(slot + 4, val)) { is_incl = true; break; }
-                    if (sc_try_read(slot, val)) { is_incl = false; break; }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-            }
-            const unsigned long long m = __ballot(is_incl);
-            const uint32_t first = m ? (uint32_t)__ffsll((long long)m) - 1u : 64u;  // nearest tile whose inclusive value is known
-            Fp4 part = lane <= first ? f4_mul_lz(lpow, val) : f4_zero();
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) part = f4_add(part, sc_shfl_xor(part, d));
-            carry = f4_add(carry, f4_mul(wbase, part));
-            if (first < 64u) break;
-            wbase = f4_mul(wbase, S.zL64);
-            base -= 64;
-        }
+        const Fp4 carry = sc_look_back<ScanSum>(st, tile, lane, DivWeight{S, sc_lane_pow(S.zLp, lane), f4_one()});
         if (lane == 0) {
             const Fp4 incl = f4_add(f4_mul(S.zL, carry), sc_ld4(agg_sh));
             sc_publish(st + SC_HDR + 8 * (size_t)tile + 4, incl);
-            *reinterpret_cast<uint4*>(carry_sh) = make_uint4(carry.c[0], carry.c[1], carry.c[2], carry.c[3]);
+            sc_st4(carry_sh, carry);
         }
     }
     __syncthreads();
@@ -188,114 +269,20 @@ __global__ __launch_bounds__(SC_T) void div_lookback_kernel(uint32_t* __restrict
     cur = f4_add(excl, f4_mul_lz(zt, sc_ld4(carry_sh)));
 #pragma unroll
     for (int k = 0; k < SC_I; ++k) {
-        if ((uint32_t)k < mine) {
-            sh[9 * tid + k] = make_uint4(cur.c[0], cur.c[1], cur.c[2], cur.c[3]);
+        if (SC_I * tid + (uint32_t)k < valid) {  // k < mine, said again from `valid`: the eight masks of the first pass are not kept across the look-back
+            sh[9 * tid + k] = sc_u4(cur);
             cur = f4_add(f4_mul_cc(zc, f4_centre(cur)), v[k]);
         }
     }
     // the lane that owns coefficient 0 leaves the division with the remainder in `cur`
-    if (tile == tiles - 1 && mine > 0 && SC_I * tid + mine == valid) *reinterpret_cast<uint4*>(rems + 4 * (size_t)q) = make_uint4(cur.c[0], cur.c[1], cur.c[2], cur.c[3]);
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < SC_I; ++k) {
-        const uint32_t u = (uint32_t)k * SC_T + tid;
-        if (u < valid) poly[hi - 1 - u] = sh[sc_slot(u)];
-    }
+    if (tile == tiles - 1 && mine > 0 && SC_I * tid + mine == valid) sc_st4(rems + 4 * (size_t)q, cur);
+    sc_tile_store(sh, poly, TileDown{hi}, valid);
 }
 
-// prefix_products: io[i] <- io[0] * .. * io[i], `count` sequences of n elements back to back; forward, multiplicative
-__global__ __launch_bounds__(SC_T) void pp_lookback_kernel(uint32_t* __restrict__ io, size_t n, uint32_t* __restrict__ state, uint32_t seq_stride,
-                                                           uint32_t* __restrict__ clear, size_t clear_words) {
-    __shared__ uint4 sh[SC_T * 9];
-    __shared__ uint32_t wtot[4 * 4], carry_sh[4], agg_sh[4], sh_tile;
-    const uint32_t q = blockIdx.y, tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    uint32_t* st = state + (size_t)q * seq_stride;
-    const uint32_t tile = sc_begin(st, clear, clear_words, &sh_tile);
-    uint4* seq = reinterpret_cast<uint4*>(io) + (size_t)q * n;
-    const size_t lo = (size_t)tile * SC_TILE;
-    const uint32_t valid = n - lo < (size_t)SC_TILE ? (uint32_t)(n - lo) : (uint32_t)SC_TILE;
-    const uint4 one4 = make_uint4(MONT_ONE, 0, 0, 0);
-#pragma unroll
-    for (int k = 0; k < SC_I; ++k) {
-        const uint32_t u = (uint32_t)k * SC_T + tid;
-        sh[sc_slot(u)] = u < valid ? seq[lo + u] : one4;  // elements past the end are ones: they change no product
-    }
-    __syncthreads();
-    Fp4 pre[SC_I];  // running products of this lane's elements
-#pragma unroll
-    for (int k = 0; k < SC_I; ++k) {
-        const uint4 w = sh[9 * tid + k];
-        const Fp4 x = Fp4{{w.x, w.y, w.z, w.w}};
-        pre[k] = k ? f4_mul_lz(pre[k - 1], x) : x;
-    }
-    Fp4 I = pre[SC_I - 1];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const Fp4 prev = sc_shfl_up(I, 1 << k);
-        if (lane >= (1u << k)) I = f4_mul_lz(I, prev);
-    }
-    if (lane == 63) *reinterpret_cast<uint4*>(wtot + 4 * wv) = make_uint4(I.c[0], I.c[1], I.c[2], I.c[3]);
-    __syncthreads();
-    Fp4 cw = f4_one();
-    for (uint32_t w = 0; w < wv; ++w) cw = f4_mul_lz(cw, sc_ld4(wtot + 4 * w));
-    Fp4 excl = sc_shfl_up(I, 1);
-    if (lane == 0) excl = f4_one();
-    excl = f4_mul_lz(excl, cw);
-    if (tid == SC_T - 1) {
-        const Fp4 agg = f4_mul(I, cw);
-        *reinterpret_cast<uint4*>(agg_sh) = make_uint4(agg.c[0], agg.c[1], agg.c[2], agg.c[3]);
-        if (tile > 0) sc_publish(st + SC_HDR + 8 * (size_t)tile, agg);
-    }
-    __syncthreads();
-    if (wv == 0) {
-        Fp4 carry = f4_one();
-        int base = (int)tile - 1;
-        while (tile > 0) {
-            const int id = base - (int)lane;
-            Fp4 val = f4_one();
-            bool is_incl = true;
-            if (id >= 0) {
-                const uint32_t* slot = st + SC_HDR + 8 * (size_t)id;
-                for (;;) {
-                    if (sc_try_read(slot + 4, val)) { is_incl = true; break; }
-                    if (sc_try_read(slot, val)) { is_incl = false; break; }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-            }
-            const unsigned long long m = __ballot(is_incl);
-            const uint32_t first = m ? (uint32_t)__ffsll((long long)m) - 1u : 64u;
-            Fp4 part = lane <= first ? val : f4_one();
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) part = f4_mul_lz(part, sc_shfl_xor(part, d));
-            carry = f4_mul_lz(carry, part);
-            if (first < 64u) break;
-            base -= 64;
-        }
-        if (lane == 0) {
-            sc_publish(st + SC_HDR + 8 * (size_t)tile + 4, f4_mul(carry, sc_ld4(agg_sh)));
-            *reinterpret_cast<uint4*>(carry_sh) = make_uint4(carry.c[0], carry.c[1], carry.c[2], carry.c[3]);
-        }
-    }
-    __syncthreads();
-    const C4 e = f4_centre(f4_mul_lz(excl, sc_ld4(carry_sh)));
-#pragma unroll
-    for (int k = 0; k < SC_I; ++k) {
-        const Fp4 o = f4_mul_cc(e, f4_centre(pre[k]));
-        sh[9 * tid + k] = make_uint4(o.c[0], o.c[1], o.c[2], o.c[3]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < SC_I; ++k) {
-        const uint32_t u = (uint32_t)k * SC_T + tid;
-        if (u < valid) seq[lo + u] = sh[sc_slot(u)];
-    }
-}
-
-// ---- the additive half of an accumulate stage (LogUp): batch inversion, prefix sums, and the two fused ----
-// Montgomery's trick over the K elements a lane holds: running products, ONE inversion of the last of them, and a walk back that
-// peels one element off per step — 3 (K - 1) products and one exponentiation instead of K exponentiations.  A zero element takes part
-// as 1 and comes out as 0 (selects, no branches), so it does not poison its chunk; results are canonical, hence equal word for
-// word to K separate inversions.
+// ---- batch inversion: Montgomery's trick over the K elements a lane holds: running products, ONE inversion of the last of them, and
+// a walk back that peels one element off per step — 3 (K - 1) products and one exponentiation instead of K exponentiations.  A zero
+// element takes part as 1 and comes out as 0 (selects, no branches), so it does not poison its chunk; results are canonical, hence
+// equal word for word to K separate inversions.
 struct InvFp {
     using T = uint32_t;
     static __device__ __forceinline__ T one() { return MONT_ONE; }
@@ -334,6 +321,69 @@ __device__ __forceinline__ void inv_chunk(typename F::T (&x)[K]) {
     x[0] = F::pick(zeros & 1u, inv);
 }
 
+// The scan of `count` sequences of n elements back to back, forward: out[i] <- in[0] op .. op in[i] (prefix_products with ScanMul,
+// prefix_sums with ScanSum).  LOGUP (sums only): the element that enters the sum is mults[i] * in[i]^-1, formed in the tile load — a
+// lane's 8 elements are one inversion chunk — so the fused call reads denoms and mults once and writes out once.  in == out is
+// allowed: a tile reads only itself, before it writes.
+__device__ __forceinline__ uint32_t sc_mslot(uint32_t u) { return u + (u >> 5); }  // 8 words per lane, 32 banks: lanes 4 apart shift by one bank
+template <typename Op, bool LOGUP>
+__global__ __launch_bounds__(SC_T) void scan_lookback_kernel(const uint32_t* in, uint32_t* out, const uint32_t* __restrict__ mults, size_t n,
+                                                             uint32_t* __restrict__ state, uint32_t seq_stride, uint32_t* __restrict__ clear,
+                                                             size_t clear_words) {
+    __shared__ uint4 sh[SC_T * 9];
+    __shared__ uint32_t shm[LOGUP ? SC_TILE + SC_TILE / 32 : 1];
+    __shared__ uint32_t wtot[4 * 4], carry_sh[4], agg_sh[4], sh_tile;
+    const uint32_t q = blockIdx.y, tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    uint32_t* st = state + (size_t)q * seq_stride;
+    const uint32_t tile = sc_begin(st, clear, clear_words, &sh_tile);
+    const size_t lo = (size_t)tile * SC_TILE;
+    const uint4* src = reinterpret_cast<const uint4*>(in) + (size_t)q * n;
+    uint4* dst = reinterpret_cast<uint4*>(out) + (size_t)q * n;
+    const uint32_t valid = n - lo < (size_t)SC_TILE ? (uint32_t)(n - lo) : (uint32_t)SC_TILE;
+    Fp4 pre[SC_I];  // this lane's elements, then their running values; elements past the end are identities: they change no running value
+    sc_tile_load(sh, src, TileUp{lo}, valid, Op::pad(), pre, [=](uint32_t u) {
+        if (LOGUP) shm[sc_mslot(u)] = u < valid ? mults[(size_t)q * n + lo + u] : 0u;
+    });
+    if (LOGUP) {
+        inv_chunk<InvFp4, SC_I>(pre);
+#pragma unroll
+        for (int k = 0; k < SC_I; ++k) pre[k] = f4_scale(pre[k], shm[sc_mslot(SC_I * tid + (uint32_t)k)]);
+    }
+#pragma unroll
+    for (int k = 1; k < SC_I; ++k) pre[k] = Op::combine_lz(pre[k - 1], pre[k]);
+    Fp4 I = pre[SC_I - 1];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const Fp4 prev = sc_shfl_up(I, 1 << k);
+        if (lane >= (1u << k)) I = Op::combine_lz(I, prev);
+    }
+    if (lane == 63) sc_st4(wtot + 4 * wv, I);
+    __syncthreads();
+    Fp4 cw = Op::identity();
+    for (uint32_t w = 0; w < wv; ++w) cw = Op::combine_lz(cw, sc_ld4(wtot + 4 * w));
+    Fp4 excl = sc_shfl_up(I, 1);
+    if (lane == 0) excl = Op::identity();
+    excl = Op::combine_lz(excl, cw);
+    if (tid == SC_T - 1) {
+        const Fp4 agg = Op::combine(I, cw);
+        sc_st4(agg_sh, agg);
+        if (tile > 0) sc_publish(st + SC_HDR + 8 * (size_t)tile, agg);
+    }
+    __syncthreads();
+    if (wv == 0) {
+        const Fp4 carry = sc_look_back<Op>(st, tile, lane, NoWeight{});
+        if (lane == 0) {
+            sc_publish(st + SC_HDR + 8 * (size_t)tile + 4, Op::combine(carry, sc_ld4(agg_sh)));
+            sc_st4(carry_sh, carry);
+        }
+    }
+    __syncthreads();
+    const typename Op::Carry e = Op::carry(Op::combine_lz(excl, sc_ld4(carry_sh)));
+#pragma unroll
+    for (int k = 0; k < SC_I; ++k) sh[9 * tid + k] = sc_u4(Op::apply(e, pre[k]));
+    sc_tile_store(sh, dst, TileUp{lo}, valid);
+}
+
 // out[i] = in[i]^-1 (times mults[i] when SCALE) over n AoS ext elements; in == out is allowed.  A workgroup owns a tile of 2048
 // elements, loaded coalesced and transposed through LDS like the scans, so that a lane inverts 8 consecutive elements.  Elements
 // past the end are zeros: they cost a select and are never stored.
@@ -343,20 +393,8 @@ __global__ __launch_bounds__(SC_T) void binv_ext_kernel(const uint32_t* in, uint
     const uint32_t tid = threadIdx.x;
     const size_t lo = (size_t)blockIdx.x * SC_TILE;
     const uint32_t valid = n - lo < (size_t)SC_TILE ? (uint32_t)(n - lo) : (uint32_t)SC_TILE;
-    const uint4* src = reinterpret_cast<const uint4*>(in) + lo;
-    uint4* dst = reinterpret_cast<uint4*>(out) + lo;
-#pragma unroll
-    for (int k = 0; k < SC_I; ++k) {
-        const uint32_t u = (uint32_t)k * SC_T + tid;
-        sh[sc_slot(u)] = u < valid ? src[u] : make_uint4(0, 0, 0, 0);
-    }
-    __syncthreads();
     Fp4 x[SC_I];
-#pragma unroll
-    for (int k = 0; k < SC_I; ++k) {
-        const uint4 w = sh[9 * tid + k];
-        x[k] = Fp4{{w.x, w.y, w.z, w.w}};
-    }
+    sc_tile_load(sh, reinterpret_cast<const uint4*>(in), TileUp{lo}, valid, make_uint4(0, 0, 0, 0), x);
     inv_chunk<InvFp4, SC_I>(x);
 #pragma unroll
     for (int k = 0; k < SC_I; ++k) {
@@ -364,14 +402,9 @@ __global__ __launch_bounds__(SC_T) void binv_ext_kernel(const uint32_t* in, uint
             const uint32_t u = SC_I * tid + (uint32_t)k;
             x[k] = f4_scale(x[k], u < valid ? mults[lo + u] : 0u);
         }
-        sh[9 * tid + k] = make_uint4(x[k].c[0], x[k].c[1], x[k].c[2], x[k].c[3]);
+        sh[9 * tid + k] = sc_u4(x[k]);
     }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < SC_I; ++k) {
-        const uint32_t u = (uint32_t)k * SC_T + tid;
-        if (u < valid) dst[u] = sh[sc_slot(u)];
-    }
+    sc_tile_store(sh, reinterpret_cast<uint4*>(out), TileUp{lo}, valid);
 }
 // the same over base-field words, in place: a lane owns 8 consecutive words (two 16-byte accesses when the buffer is 16-byte aligned
 // and the chunk is whole, single words otherwise)
@@ -399,105 +432,170 @@ __global__ __launch_bounds__(256) void binv_elem_kernel(uint32_t* __restrict__ i
     }
 }
 
-// prefix sums: out[i] <- in[0] + .. + in[i], `count` sequences of n elements back to back — pp_lookback_kernel with the Fp4 sum in
-// place of the Fp4 product (identity zero; an aggregate is a sum, so the look-back adds where that one multiplies).  LOGUP: the
-// element that enters the sum is mults[i] * in[i]^-1, formed in the tile load — a lane's 8 elements are one inversion chunk — so the
-// fused call reads denoms and mults once and writes out once.  in == out is allowed: a tile reads only itself, before it writes.
-__device__ __forceinline__ uint32_t sc_mslot(uint32_t u) { return u + (u >> 5); }  // 8 words per lane, 32 banks: lanes 4 apart shift by one bank
-template <bool LOGUP>
-__global__ __launch_bounds__(SC_T) void ps_lookback_kernel(const uint32_t* in, uint32_t* out, const uint32_t* __restrict__ mults, size_t n,
-                                                           uint32_t* __restrict__ state, uint32_t seq_stride, uint32_t* __restrict__ clear,
-                                                           size_t clear_words) {
-    __shared__ uint4 sh[SC_T * 9];
-    __shared__ uint32_t shm[LOGUP ? SC_TILE + SC_TILE / 32 : 1];
-    __shared__ uint32_t wtot[4 * 4], carry_sh[4], agg_sh[4], sh_tile;
-    const uint32_t q = blockIdx.y, tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    uint32_t* st = state + (size_t)q * seq_stride;
-    const uint32_t tile = sc_begin(st, clear, clear_words, &sh_tile);
-    const size_t lo = (size_t)tile * SC_TILE;
-    const uint4* src = reinterpret_cast<const uint4*>(in) + (size_t)q * n + lo;
-    uint4* dst = reinterpret_cast<uint4*>(out) + (size_t)q * n + lo;
-    const uint32_t valid = n - lo < (size_t)SC_TILE ? (uint32_t)(n - lo) : (uint32_t)SC_TILE;
+// ---- the three-phase forms ----
+// The chunk walks below are chains of dependent Fp4 products; their loads are independent, so they are issued eight at a
+// time (SCAN_B elements = 128 bytes per lane in flight) instead of one per product.
+constexpr int SCAN_B = 8;
+
+// poly_divide: q_{i-1} = p_i + z q_i (top down), in place; remainder = p_0 + z q_0.
+// Three phases over chunks of DIV_L coefficients: (1) each chunk's carry-out assuming zero carry-in,
+// (2) sequential composition of the chunk maps carry -> local + z^L * carry (one workgroup), (3) replay.
+// The phases nest: the chunk values are themselves an array to be divided by (x - z^L) — "the carry entering chunk ch" is
+// that division's quotient coefficient — so arrays longer than DIV_DIRECT recurse with chunks of DIV_L and the one-workgroup
+// kernel only ever sees <= DIV_DIRECT entries (2^20 -> 2^15 -> 2^10: five launches).
+constexpr int DIV_L = 32;
+constexpr size_t DIV_DIRECT = 2048;
+__global__ void div_local_kernel(const uint32_t* __restrict__ poly, size_t size, Fp4 z, uint32_t* __restrict__ local,
+                                 size_t chunks) {
+    size_t ch = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ch >= chunks) return;
+    size_t lo = ch * DIV_L, hi = lo + DIV_L < size ? lo + DIV_L : size;
+    Fp4 cur = f4_zero();
+    for (size_t top = hi; top > lo;) {
+        const size_t nb = top - lo < (size_t)SCAN_B ? top - lo : (size_t)SCAN_B;
+        Fp4 v[SCAN_B];
 #pragma unroll
-    for (int k = 0; k < SC_I; ++k) {
-        const uint32_t u = (uint32_t)k * SC_T + tid;
-        sh[sc_slot(u)] = u < valid ? src[u] : make_uint4(0, 0, 0, 0);  // elements past the end are zeros: they change no sum
-        if (LOGUP) shm[sc_mslot(u)] = u < valid ? mults[(size_t)q * n + lo + u] : 0u;
+        for (int k = 0; k < SCAN_B; ++k)
+            if ((size_t)k < nb) v[k] = sc_ld4(poly + 4 * (top - 1 - k));
+#pragma unroll
+        for (int k = 0; k < SCAN_B; ++k)
+            if ((size_t)k < nb) cur = f4_add(f4_mul(z, cur), v[k]);
+        top -= nb;
     }
+    sc_st4(local + 4 * ch, cur);
+}
+// carry_in[ch] = value of `cur` entering chunk ch from above.  One workgroup: thread t owns a contiguous run of chunks
+// (thread 0 the highest), reduces it to the affine map carry -> a*carry + b, the maps are composed across threads with a
+// log-step (Hillis-Steele) scan in LDS, and each thread replays its run with the carry that enters it.
+__global__ void div_scan_kernel(uint32_t* __restrict__ local_then_carry, size_t chunks, Fp4 zL, uint32_t* __restrict__ rem) {
+    extern __shared__ uint32_t sh[];  // per thread: a (4 words) | b (4 words)
+    const uint32_t nt = blockDim.x, tid = threadIdx.x;
+    size_t per = (chunks + nt - 1) / nt;
+    size_t hi = chunks > (size_t)tid * per ? chunks - (size_t)tid * per : 0;
+    size_t lo = hi > per ? hi - per : 0;
+    Fp4 a = f4_one(), b = f4_zero();
+    for (size_t ch = hi; ch-- > lo;) {
+        b = f4_add(f4_mul(zL, b), sc_ld4(local_then_carry + 4 * ch));
+        a = f4_mul(a, zL);
+    }
+    // inclusive scan of F_t = f_t o f_(t-1) o ... o f_0 with (a2,b2) o (a1,b1) = (a2*a1, a2*b1 + b2)
+    for (uint32_t d = 1; d < nt; d <<= 1) {
+        sc_st4(sh + 8 * tid, a);
+        sc_st4(sh + 8 * tid + 4, b);
+        __syncthreads();
+        if (tid >= d) {
+            Fp4 pa = sc_ld4(sh + 8 * (tid - d)), pb = sc_ld4(sh + 8 * (tid - d) + 4);
+            b = f4_add(f4_mul(a, pb), b);
+            a = f4_mul(a, pa);
+        }
+        __syncthreads();
+    }
+    sc_st4(sh + 8 * tid + 4, b);
     __syncthreads();
-    Fp4 pre[SC_I];  // this lane's elements, then their running sums
-#pragma unroll
-    for (int k = 0; k < SC_I; ++k) {
-        const uint4 w = sh[9 * tid + k];
-        pre[k] = Fp4{{w.x, w.y, w.z, w.w}};
+    if (tid == nt - 1) sc_st4(rem, b);  // composition of every run applied to carry 0 = the remainder
+    Fp4 carry = tid == 0 ? f4_zero() : sc_ld4(sh + 8 * (tid - 1) + 4);
+    for (size_t ch = hi; ch-- > lo;) {
+        Fp4 l = sc_ld4(local_then_carry + 4 * ch);
+        sc_st4(local_then_carry + 4 * ch, carry);
+        carry = f4_add(f4_mul(zL, carry), l);
     }
-    if (LOGUP) {
-        inv_chunk<InvFp4, SC_I>(pre);
+}
+__global__ void div_apply_kernel(uint32_t* __restrict__ poly, size_t size, Fp4 z, const uint32_t* __restrict__ carry_in,
+                                 size_t chunks) {
+    size_t ch = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ch >= chunks) return;
+    size_t lo = ch * DIV_L, hi = lo + DIV_L < size ? lo + DIV_L : size;
+    Fp4 cur = sc_ld4(carry_in + 4 * ch);
+    for (size_t top = hi; top > lo;) {
+        const size_t nb = top - lo < (size_t)SCAN_B ? top - lo : (size_t)SCAN_B;
+        Fp4 v[SCAN_B];
 #pragma unroll
-        for (int k = 0; k < SC_I; ++k) pre[k] = f4_scale(pre[k], shm[sc_mslot(SC_I * tid + (uint32_t)k)]);
-    }
+        for (int k = 0; k < SCAN_B; ++k)
+            if ((size_t)k < nb) v[k] = sc_ld4(poly + 4 * (top - 1 - k));
 #pragma unroll
-    for (int k = 1; k < SC_I; ++k) pre[k] = f4_add(pre[k - 1], pre[k]);
-    Fp4 I = pre[SC_I - 1];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const Fp4 prev = sc_shfl_up(I, 1 << k);
-        if (lane >= (1u << k)) I = f4_add(I, prev);
-    }
-    if (lane == 63) *reinterpret_cast<uint4*>(wtot + 4 * wv) = make_uint4(I.c[0], I.c[1], I.c[2], I.c[3]);
-    __syncthreads();
-    Fp4 cw = f4_zero();
-    for (uint32_t w = 0; w < wv; ++w) cw = f4_add(cw, sc_ld4(wtot + 4 * w));
-    Fp4 excl = sc_shfl_up(I, 1);
-    if (lane == 0) excl = f4_zero();
-    excl = f4_add(excl, cw);
-    if (tid == SC_T - 1) {
-        const Fp4 agg = f4_add(I, cw);
-        *reinterpret_cast<uint4*>(agg_sh) = make_uint4(agg.c[0], agg.c[1], agg.c[2], agg.c[3]);
-        if (tile > 0) sc_publish(st + SC_HDR + 8 * (size_t)tile, agg);
-    }
-    __syncthreads();
-    if (wv == 0) {
-        Fp4 carry = f4_zero();
-        int base = (int)tile - 1;
-        while (tile > 0) {
-            const int id = base - (int)lane;
-            Fp4 val = f4_zero();
-            bool is_incl = true;
-            if (id >= 0) {
-                const uint32_t* slot = st + SC_HDR + 8 * (size_t)id;
-                for (;;) {
-                    if (sc_try_read(slot + 4, val)) { is_incl = true; break; }
-                    if (sc_try_read(slot, val)) { is_incl = false; break; }
-                    __builtin_amdgcn_s_sleep(1);
-                }
+        for (int k = 0; k < SCAN_B; ++k)
+            if ((size_t)k < nb) {
+                sc_st4(poly + 4 * (top - 1 - k), cur);
+                cur = f4_add(f4_mul(z, cur), v[k]);
             }
-            const unsigned long long m = __ballot(is_incl);
-            const uint32_t first = m ? (uint32_t)__ffsll((long long)m) - 1u : 64u;
-            Fp4 part = lane <= first ? val : f4_zero();
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) part = f4_add(part, sc_shfl_xor(part, d));
-            carry = f4_add(carry, part);
-            if (first < 64u) break;
-            base -= 64;
-        }
-        if (lane == 0) {
-            sc_publish(st + SC_HDR + 8 * (size_t)tile + 4, f4_add(carry, sc_ld4(agg_sh)));
-            *reinterpret_cast<uint4*>(carry_sh) = make_uint4(carry.c[0], carry.c[1], carry.c[2], carry.c[3]);
-        }
+        top -= nb;
     }
-    __syncthreads();
-    const Fp4 e = f4_add(excl, sc_ld4(carry_sh));
+}
+
+// prefix_products / prefix_sums: the same three-phase shape over an operator, chunks of PP_L elements, one lane per chunk.
+constexpr int PP_L = 64;
+constexpr size_t PP_DIRECT = 2048;
+// agg[ch] <- the chunk's aggregate.  blockIdx.y = sequence of a batch (each with its own n elements of io and `chunks` aggregates)
+template <typename Op>
+__global__ void tp_local_kernel(const uint32_t* __restrict__ io, size_t n, size_t seq_stride, uint32_t* __restrict__ agg, size_t chunks,
+                                size_t agg_stride) {
+    size_t ch = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ch >= chunks) return;
+    io += 4 * seq_stride * blockIdx.y;
+    agg += 4 * agg_stride * blockIdx.y;
+    size_t lo = ch * PP_L, hi = lo + PP_L < n ? lo + PP_L : n;
+    Fp4 p = Op::identity();
+    for (size_t b = lo; b < hi; b += SCAN_B) {
+        const size_t nb = hi - b < (size_t)SCAN_B ? hi - b : (size_t)SCAN_B;
+        Fp4 v[SCAN_B];
 #pragma unroll
-    for (int k = 0; k < SC_I; ++k) {
-        const Fp4 o = f4_add(e, pre[k]);
-        sh[9 * tid + k] = make_uint4(o.c[0], o.c[1], o.c[2], o.c[3]);
+        for (int k = 0; k < SCAN_B; ++k)
+            if ((size_t)k < nb) v[k] = sc_ld4(io + 4 * (b + k));
+#pragma unroll
+        for (int k = 0; k < SCAN_B; ++k)
+            if ((size_t)k < nb) p = Op::combine(p, v[k]);
     }
+    sc_st4(agg + 4 * ch, p);
+}
+// agg[ch] <- aggregate of all chunks before ch (exclusive scan), one workgroup per sequence, log-step scan across threads
+template <typename Op>
+__global__ void tp_scan_kernel(uint32_t* __restrict__ agg, size_t chunks, size_t agg_stride) {
+    extern __shared__ uint32_t sh[];
+    agg += 4 * agg_stride * blockIdx.x;
+    const uint32_t nt = blockDim.x, tid = threadIdx.x;
+    size_t per = (chunks + nt - 1) / nt;
+    size_t lo = (size_t)tid * per < chunks ? (size_t)tid * per : chunks;
+    size_t hi = lo + per < chunks ? lo + per : chunks;
+    Fp4 incl = Op::identity();
+    for (size_t ch = lo; ch < hi; ++ch) incl = Op::combine(incl, sc_ld4(agg + 4 * ch));
+    for (uint32_t d = 1; d < nt; d <<= 1) {
+        sc_st4(sh + 4 * tid, incl);
+        __syncthreads();
+        if (tid >= d) incl = Op::combine(incl, sc_ld4(sh + 4 * (tid - d)));
+        __syncthreads();
+    }
+    sc_st4(sh + 4 * tid, incl);
     __syncthreads();
+    Fp4 carry = tid == 0 ? Op::identity() : sc_ld4(sh + 4 * (tid - 1));
+    for (size_t ch = lo; ch < hi; ++ch) {
+        Fp4 a = sc_ld4(agg + 4 * ch);
+        sc_st4(agg + 4 * ch, carry);
+        carry = Op::combine(carry, a);
+    }
+}
+// io[i] <- carry op io[lo] op .. op io[i - 1] (EXCL, the inner levels) or .. op io[i] (the caller's array)
+template <typename Op, bool EXCL>
+__global__ void tp_apply_kernel(uint32_t* __restrict__ io, size_t n, size_t seq_stride, const uint32_t* __restrict__ carry_in, size_t chunks,
+                                size_t carry_stride) {
+    size_t ch = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ch >= chunks) return;
+    io += 4 * seq_stride * blockIdx.y;
+    carry_in += 4 * carry_stride * blockIdx.y;
+    size_t lo = ch * PP_L, hi = lo + PP_L < n ? lo + PP_L : n;
+    Fp4 p = sc_ld4(carry_in + 4 * ch);
+    for (size_t b = lo; b < hi; b += SCAN_B) {
+        const size_t nb = hi - b < (size_t)SCAN_B ? hi - b : (size_t)SCAN_B;
+        Fp4 v[SCAN_B];
 #pragma unroll
-    for (int k = 0; k < SC_I; ++k) {
-        const uint32_t u = (uint32_t)k * SC_T + tid;
-        if (u < valid) dst[u] = sh[sc_slot(u)];
+        for (int k = 0; k < SCAN_B; ++k)
+            if ((size_t)k < nb) v[k] = sc_ld4(io + 4 * (b + k));
+#pragma unroll
+        for (int k = 0; k < SCAN_B; ++k)
+            if ((size_t)k < nb) {
+                if (EXCL) sc_st4(io + 4 * (b + k), p);
+                p = Op::combine(p, v[k]);
+                if (!EXCL) sc_st4(io + 4 * (b + k), p);
+            }
     }
 }
 
@@ -547,7 +645,7 @@ static DivSeq div_seq(const uint32_t z[4]) {
 }
 
 // `count` polynomials of `size` AoS ext coefficients back to back, polynomial q divided in place by (x - zs[q]); rems[4q..] = remainder
-const char* poly_divide_lookback(bx_ctx* c, uint32_t* polys, size_t size, size_t count, const uint32_t* zs, uint32_t* rems, const uint32_t* which) {
+static const char* poly_divide_lookback(bx_ctx* c, uint32_t* polys, size_t size, size_t count, const uint32_t* zs, uint32_t* rems, const uint32_t* which) {
     const size_t tiles = (size + SC_TILE - 1) / SC_TILE;
     const uint32_t seq_stride = SC_HDR + 8 * (uint32_t)tiles;
     for (size_t q0 = 0; q0 < count; q0 += 8) {
@@ -566,21 +664,91 @@ const char* poly_divide_lookback(bx_ctx* c, uint32_t* polys, size_t size, size_t
     }
     return nullptr;
 }
-const char* prefix_products_lookback(bx_ctx* c, uint32_t* io, size_t n, size_t count) {
+// the look-back scan of `count` sequences of n elements, `in` to `out` (the same buffer, or denoms and mults to out for LOGUP)
+template <typename Op, bool LOGUP>
+static const char* scan_lookback(bx_ctx* c, const uint32_t* in, uint32_t* out, const uint32_t* mults, size_t n, size_t count) {
     const size_t tiles = (n + SC_TILE - 1) / SC_TILE;
     const uint32_t seq_stride = SC_HDR + 8 * (uint32_t)tiles;
     uint32_t *use, *clear;
     size_t clear_words;
     BX_TRY(scan_state(c, (size_t)seq_stride * count, &use, &clear, &clear_words));
-    hipLaunchKernelGGL(pp_lookback_kernel, dim3((unsigned)tiles, (unsigned)count), dim3(SC_T), 0, c->stream, io, n, use, seq_stride, clear, clear_words);
+    hipLaunchKernelGGL((scan_lookback_kernel<Op, LOGUP>), dim3((unsigned)tiles, (unsigned)count), dim3(SC_T), 0, c->stream, in, out, mults, n, use,
+                       seq_stride, clear, clear_words);
     BX_LAUNCH_CHECK(c);
     return nullptr;
+}
+
+// in-place division of the AoS ext array `arr` (n entries) by (x - z); `scratch` has room for every level's chunk values
+static const char* divide_rec(bx_ctx* c, uint32_t* arr, size_t n, Fp4 z, uint32_t* scratch, uint32_t* rem) {
+    if (n <= DIV_DIRECT) {
+        // one workgroup: thread t owns a run of entries; the "chunk" multiplier of the kernel is z itself here
+        unsigned nt = n >= 1024 ? 1024 : 64;
+        hipLaunchKernelGGL(div_scan_kernel, dim3(1), dim3(nt), nt * 32, c->stream, arr, n, z, rem);
+        BX_LAUNCH_CHECK(c);
+        return nullptr;
+    }
+    const size_t chunks = (n + DIV_L - 1) / DIV_L;
+    hipLaunchKernelGGL(div_local_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, c->stream, (const uint32_t*)arr, n, z, scratch,
+                       chunks);
+    BX_LAUNCH_CHECK(c);
+    BX_TRY(divide_rec(c, scratch, chunks, f4_pow(z, DIV_L), scratch + 4 * chunks, rem));  // chunk values -> carries entering the chunks
+    hipLaunchKernelGGL(div_apply_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, c->stream, arr, n, z, (const uint32_t*)scratch,
+                       chunks);
+    BX_LAUNCH_CHECK(c);
+    return nullptr;
+}
+static size_t scan_scratch_words(size_t n, size_t L, size_t direct, size_t count) {
+    size_t words = 8;
+    while (n > direct) {
+        n = (n + L - 1) / L;
+        words += 4 * n * count;
+    }
+    return words;
+}
+// The running Op, in place, over `count` sequences of n entries (sequence k at arr + 4 * k * stride): chunk aggregates -> exclusive scan
+// of them (recursively, PP_L per level, one workgroup per sequence at the bottom) -> replay of every chunk with its carry.  EXCL: the
+// exclusive scan, which the inner levels are; the caller's array is the inclusive one.
+template <typename Op, bool EXCL>
+static const char* three_phase_rec(bx_ctx* c, uint32_t* arr, size_t n, size_t stride, size_t count, uint32_t* scratch) {
+    if (EXCL && n <= PP_DIRECT) {
+        unsigned nt = n >= 1024 ? 1024 : 64;
+        hipLaunchKernelGGL((tp_scan_kernel<Op>), dim3((unsigned)count), dim3(nt), nt * 16, c->stream, arr, n, stride);
+        BX_LAUNCH_CHECK(c);
+        return nullptr;
+    }
+    const size_t chunks = (n + PP_L - 1) / PP_L;
+    hipLaunchKernelGGL((tp_local_kernel<Op>), dim3((unsigned)((chunks + 255) / 256), (unsigned)count), dim3(256), 0, c->stream, (const uint32_t*)arr, n,
+                       stride, scratch, chunks, chunks);
+    BX_LAUNCH_CHECK(c);
+    BX_TRY((three_phase_rec<Op, true>(c, scratch, chunks, chunks, count, scratch + 4 * chunks * count)));
+    hipLaunchKernelGGL((tp_apply_kernel<Op, EXCL>), dim3((unsigned)((chunks + 255) / 256), (unsigned)count), dim3(256), 0, c->stream, arr, n, stride,
+                       (const uint32_t*)scratch, chunks, chunks);
+    BX_LAUNCH_CHECK(c);
+    return nullptr;
+}
+template <typename Op>
+static const char* scan_three_phase(bx_ctx* c, uint32_t* io, size_t n, size_t count) {
+    const size_t chunks = (n + PP_L - 1) / PP_L;
+    BX_TRY(ensure_scratch(c, 4 * chunks * count + scan_scratch_words(chunks, PP_L, PP_DIRECT, count)));
+    return three_phase_rec<Op, false>(c, io, n, n, count, c->d_scratch);
 }
 
 }  // namespace bx
 
 using namespace bx;
 
+extern "C" const char* bx_poly_divide(bx_ctx* c, bx_buf poly, const uint32_t z[4], bx_buf rem_out) try {
+    if (!c) return "bx_poly_divide: null ctx";
+    BX_REQUIRE(c, poly.len % 4 == 0 && rem_out.len >= 4, "poly_divide: poly must be AoS ext, remainder buffer >= 4 words");
+    BX_ENTER(c);
+    size_t size = poly.len / 4;
+    if (!size) return nullptr;
+    OpScope op(c, "poly_divide", 8.0 * (double)poly.len);
+    if (c->scan_lookback && ((uintptr_t)poly.dptr & 15u) == 0 && ((uintptr_t)rem_out.dptr & 15u) == 0)
+        return poly_divide_lookback(c, (uint32_t*)poly.dptr, size, 1, z, (uint32_t*)rem_out.dptr, nullptr);
+    BX_TRY(ensure_scratch(c, scan_scratch_words(size, DIV_L, DIV_DIRECT, 1)));
+    return divide_rec(c, (uint32_t*)poly.dptr, size, Fp4{{z[0], z[1], z[2], z[3]}}, c->d_scratch, (uint32_t*)rem_out.dptr);
+} BX_ABI_CATCH(c, "bx_poly_divide")
 extern "C" const char* bx_poly_divide_batch(bx_ctx* c, bx_buf polys, size_t count, const uint32_t* zs, bx_buf rems_out) try {
     if (!c) return "bx_poly_divide_batch: null ctx";
     BX_REQUIRE(c, count >= 1 && count <= 65535 && polys.len % (4 * count) == 0, "poly_divide_batch: the buffer does not split into `count` AoS ext polynomials");
@@ -611,22 +779,25 @@ extern "C" const char* bx_poly_divide_batch_indexed(bx_ctx* c, bx_buf polys, siz
     return poly_divide_lookback(c, (uint32_t*)polys.dptr, size, count, zs, (uint32_t*)rems_out.dptr, which);
 } BX_ABI_CATCH(c, "bx_poly_divide_batch_indexed")
 
+extern "C" const char* bx_batch_prefix_products(bx_ctx* c, bx_buf io, size_t count) try {
+    if (!c) return "bx_batch_prefix_products: null ctx";
+    BX_REQUIRE(c, io.len % 4 == 0, "prefix_products: buffer must hold AoS ext elements");
+    BX_REQUIRE(c, count >= 1 && (io.len / 4) % count == 0, "prefix_products: the buffer does not split into `count` equal sequences");
+    BX_REQUIRE(c, count <= 65535, "prefix_products: too many sequences");
+    BX_ENTER(c);
+    size_t n = io.len / 4 / count;
+    if (n < 2) return nullptr;
+    OpScope op(c, "prefix_products", 8.0 * (double)io.len);
+    if (c->scan_lookback && ((uintptr_t)io.dptr & 15u) == 0)
+        return scan_lookback<ScanMul, false>(c, (const uint32_t*)io.dptr, (uint32_t*)io.dptr, nullptr, n, count);
+    return scan_three_phase<ScanMul>(c, (uint32_t*)io.dptr, n, count);
+} BX_ABI_CATCH(c, "bx_batch_prefix_products")
+extern "C" const char* bx_prefix_products(bx_ctx* c, bx_buf io) try {
+    if (!c) return "bx_prefix_products: null ctx";
+    return bx_batch_prefix_products(c, io, 1);
+} BX_ABI_CATCH(c, "bx_prefix_products")
+
 // ---- LogUp helpers: batch inversion, prefix sums, and both in one pass ----
-static const char* launch_sums(bx_ctx* c, bool logup, const uint32_t* in, uint32_t* out, const uint32_t* mults, size_t n, size_t count) {
-    const size_t tiles = (n + SC_TILE - 1) / SC_TILE;
-    const uint32_t seq_stride = SC_HDR + 8 * (uint32_t)tiles;
-    uint32_t *use, *clear;
-    size_t clear_words;
-    BX_TRY(scan_state(c, (size_t)seq_stride * count, &use, &clear, &clear_words));
-    if (logup)
-        hipLaunchKernelGGL(ps_lookback_kernel<true>, dim3((unsigned)tiles, (unsigned)count), dim3(SC_T), 0, c->stream, in, out, mults, n, use, seq_stride,
-                           clear, clear_words);
-    else
-        hipLaunchKernelGGL(ps_lookback_kernel<false>, dim3((unsigned)tiles, (unsigned)count), dim3(SC_T), 0, c->stream, in, out, mults, n, use, seq_stride,
-                           clear, clear_words);
-    BX_LAUNCH_CHECK(c);
-    return nullptr;
-}
 // out[i] = in[i]^-1 (* mults[i]) over n ext elements, one launch
 static const char* launch_invert_ext(bx_ctx* c, const uint32_t* in, uint32_t* out, const uint32_t* mults, size_t n) {
     const unsigned tiles = (unsigned)((n + SC_TILE - 1) / SC_TILE);
@@ -673,8 +844,8 @@ extern "C" const char* bx_batch_prefix_sums(bx_ctx* c, bx_buf io, size_t count) 
     const size_t n = io.len / 4 / count;
     if (n < 2) return nullptr;
     OpScope op(c, "prefix_sums", 8.0 * (double)io.len);
-    if (c->scan_lookback) return launch_sums(c, false, (const uint32_t*)io.dptr, (uint32_t*)io.dptr, nullptr, n, count);
-    return prefix_sums_three_phase(c, (uint32_t*)io.dptr, n, count);
+    if (c->scan_lookback) return scan_lookback<ScanSum, false>(c, (const uint32_t*)io.dptr, (uint32_t*)io.dptr, nullptr, n, count);
+    return scan_three_phase<ScanSum>(c, (uint32_t*)io.dptr, n, count);
 } BX_ABI_CATCH(c, "bx_batch_prefix_sums")
 extern "C" const char* bx_prefix_sums(bx_ctx* c, bx_buf io) try {
     if (!c) return "bx_prefix_sums: null ctx";
@@ -693,9 +864,10 @@ extern "C" const char* bx_logup_accumulate(bx_ctx* c, bx_buf out, bx_buf denoms,
     BX_ENTER(c);
     if (!n) return nullptr;
     OpScope op(c, "logup_accumulate", 8.0 * (double)out.len + 4.0 * (double)(count * n));
-    if (c->scan_lookback) return launch_sums(c, true, (const uint32_t*)denoms.dptr, (uint32_t*)out.dptr, (const uint32_t*)mults.dptr, n, count);
+    if (c->scan_lookback)
+        return scan_lookback<ScanSum, true>(c, (const uint32_t*)denoms.dptr, (uint32_t*)out.dptr, (const uint32_t*)mults.dptr, n, count);
     // the three-phase form: invert and scale into out, then the three-phase running sums over out
     BX_TRY(launch_invert_ext(c, (const uint32_t*)denoms.dptr, (uint32_t*)out.dptr, (const uint32_t*)mults.dptr, n * count));
     if (n < 2) return nullptr;
-    return prefix_sums_three_phase(c, (uint32_t*)out.dptr, n, count);
+    return scan_three_phase<ScanSum>(c, (uint32_t*)out.dptr, n, count);
 } BX_ABI_CATCH(c, "bx_logup_accumulate")

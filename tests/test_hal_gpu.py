@@ -783,6 +783,44 @@ def test_scans_single_pass_and_three_phase_agree_with_the_oracle_across_tile_bou
         hal.set_tunable("scan_lookback", 1)
 
 
+@pytest.mark.parametrize("off", [1, 3])
+@pytest.mark.parametrize("size", [1, 65, 2049, 131073])
+def test_scans_fall_back_to_three_phase_on_buffers_that_are_only_word_aligned(hal, oracle, size, off):
+    """poly_divide / prefix_products under the default scan_lookback = 1 on operands sliced at a word offset that is not a multiple of
+    four: the look-back kernels need 16-byte accesses, so these calls take the three-phase kernels.  Words around the slices stay."""
+    hal.set_tunable("scan_lookback", 1)
+    pad = 8
+    host = np.random.default_rng(size + off).integers(0, 1 << 32, off + 4 * size + pad, dtype=np.uint32)
+    rem_host = np.random.default_rng(7 * size + off).integers(0, 1 << 32, off + 4 + pad, dtype=np.uint32)
+    poly, z = rnd(size, 4 * size), rnd(size + 1, 4)
+    host[off:off + 4 * size] = poly
+    whole, rem_whole = hal.copy_from(host), hal.copy_from(rem_host)
+    buf, rem = whole.slice(off, 4 * size), rem_whole.slice(off, 4)
+    assert buf.raw.dptr % 16 == 4 * off and rem.raw.dptr % 16 == 4 * off
+    hal.poly_divide(buf, z, rem)
+    ref, ref_rem = poly.copy(), np.zeros(4, np.uint32)
+    oracle.bxo_poly_divide(ref, size, c(z), ref_rem)
+    got, got_rem = whole.view(), rem_whole.view()
+    assert np.array_equal(got[off:off + 4 * size], ref) and np.array_equal(got_rem[off:off + 4], ref_rem), ("divide", size, off)
+    assert np.array_equal(got[:off], host[:off]) and np.array_equal(got[off + 4 * size:], host[off + 4 * size:]), ("divide: around the polynomial", size, off)
+    assert np.array_equal(got_rem[:off], rem_host[:off]) and np.array_equal(got_rem[off + 4:], rem_host[off + 4:]), ("divide: around the remainder", size, off)
+    for count in (1, 3):
+        x = rnd(size + 2, 4 * size * count)
+        host2 = np.random.default_rng(size + count).integers(0, 1 << 32, off + 4 * size * count + pad, dtype=np.uint32)
+        host2[off:off + x.size] = x
+        whole2 = hal.copy_from(host2)
+        if count == 1:
+            hal.prefix_products(whole2.slice(off, x.size))
+        else:
+            hal.batch_prefix_products(whole2.slice(off, x.size), count)
+        r2 = x.copy().reshape(count, 4 * size)
+        for seq in r2:
+            oracle.bxo_prefix_products(seq, size)
+        got2 = whole2.view()
+        assert np.array_equal(got2[off:off + x.size], r2.ravel()), ("prefix", size, off, count)
+        assert np.array_equal(got2[:off], host2[:off]) and np.array_equal(got2[off + x.size:], host2[off + x.size:]), ("prefix: around", size, off, count)
+
+
 def test_poly_divide_batch_divides_every_polynomial_by_its_own_point(hal, oracle):
     for size, count in ((5000, 3), (1 << 16, 9), (2048, 1), (100, 16)):
         polys = rnd(size + count, 4 * size * count)

@@ -172,6 +172,30 @@ def test_logup_accumulate(hal, lookback, n, count, alias):
     mul.free()
 
 
+@pytest.mark.parametrize("count", [1, 3])
+@pytest.mark.parametrize("n", [2047, 2048, 2049, 131072, 131073])
+def test_sums_at_the_tile_and_window_edges(hal, lookback, n, count):
+    """the sizes the products are tested at: around the 2048-element tile, and the 64-tile look-back window (131072), which is also
+    where the three-phase driver first recurses (131072 / 64 chunks > 2048)"""
+    d = cached(("x", n * count), lambda: rand_ext(100 + n * count, n * count))
+    m = cached(("e", n * count), lambda: rand_elem(200 + n * count, n * count))
+    rng = np.random.default_rng(n + count)
+    io = Placed(hal, rng, d, 4)
+    hal.batch_prefix_sums(io.buf, count)
+    io.check(R.batch_prefix_sums(d, count), f"batch_prefix_sums n={n} count={count}")
+    io.free()
+    want = cached(("logup", n, count), lambda: R.logup_accumulate_big(d, m, count))
+    den = Placed(hal, rng, d, 4)
+    mul = Placed(hal, rng, m, 1)
+    out = Placed(hal, rng, np.zeros(4 * n * count, np.uint32), 4)
+    hal.logup_accumulate(out.buf, den.buf, mul.buf, count)
+    out.check(want, f"logup_accumulate n={n} count={count}")
+    den.unchanged("logup_accumulate: denoms")
+    mul.unchanged("logup_accumulate: mults")
+    for b in (den, mul, out):
+        b.free()
+
+
 def test_two_to_the_22_once(hal):
     n = 1 << 22
     x = rand_ext(22, n)
