@@ -125,3 +125,29 @@ def synthetic_circuit():
     lib = load_library()
     lib.bx_synthetic_circuit.restype = C.POINTER(CircuitOps)
     return lib.bx_synthetic_circuit()
+
+
+def lookup_circuit():
+    """Pointer to the library's lookup circuit (bx_lookup_circuit, include/bx_lookup.h): a range check proved with LogUp running sums."""
+    lib = load_library()
+    lib.bx_lookup_circuit.restype = C.POINTER(CircuitOps)
+    return lib.bx_lookup_circuit()
+
+
+def builtin_circuit(name):
+    """"synthetic" or "lookup" -> pointer to the library's table"""
+    if name == "synthetic":
+        return synthetic_circuit()
+    if name == "lookup":
+        return lookup_circuit()
+    raise ValueError(f"unknown built-in circuit {name!r} (\"synthetic\" or \"lookup\")")
+
+
+def encode_cell_records(records):
+    """The payload of a lookup-circuit segment (include/bx_lookup.h, "segment"): an iterable of (col, row, value) -> 12 bytes each,
+    little endian.  `value` is the field value the data cell (col, row) is to hold (not its Montgomery word)."""
+    out = bytearray()
+    for col, row, value in records:
+        for v in (col, row, value):
+            out += int(v).to_bytes(4, "little")
+    return bytes(out)

@@ -320,7 +320,9 @@ __global__ void mix_table_kernel(uint32_t* __restrict__ out, Fp4 base, uint32_t 
     }
 }
 const char* circuit_mix_table(bx_ctx* c, const Circuit& cc, bx_buf mixpows, const uint32_t poly_mix[4]) {
-    const uint32_t n = (uint32_t)cc.constraints();
+    return mix_power_table(c, mixpows, poly_mix, (uint32_t)cc.constraints());
+}
+const char* mix_power_table(bx_ctx* c, bx_buf mixpows, const uint32_t poly_mix[4], uint32_t n) {
     BX_REQUIRE(c, mixpows.len >= 8 * (size_t)n, "circuit_mix_table: table too small");
     if (!n) return nullptr;
     hipLaunchKernelGGL(mix_table_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, (uint32_t*)mixpows.dptr,
@@ -453,17 +455,21 @@ const char* synth_eval_check(void*, void* state, bx_ctx* c, bx_buf check, bx_buf
     const Circuit& cc = st->cc;
     BX_TRY(synth_betas(c, st, mix));
     BX_TRY(circuit_mix_table(c, cc, st->mixpows, poly_mix));
-    // 1 / ((3x)^N - 1) takes four values on the domain x = w_4N^row: (3x)^N = 3^N w_4^(row mod 4)
     uint32_t zinv[4];
-    const uint32_t t3n = fp_pow(MONT_THREE, (uint64_t)1 << cc.po2), w4 = fp_pow(fp_encode(137u), (uint64_t)1 << 25);  // ROU_FWD[2]
+    vanishing_inverses(cc.po2, zinv);
+    return circuit_eval_check(c, cc, check, ecode, edata, eacc, st->mixpows, st->betas, zinv, globals);
+}
+}  // namespace
+
+// 1 / ((3x)^N - 1) takes four values on the domain x = w_4N^row: (3x)^N = 3^N w_4^(row mod 4)
+void vanishing_inverses(uint32_t po2, uint32_t zinv[4]) {
+    const uint32_t t3n = fp_pow(MONT_THREE, (uint64_t)1 << po2), w4 = fp_pow(fp_encode(137u), (uint64_t)1 << 25);  // ROU_FWD[2]
     uint32_t cur = MONT_ONE;
     for (int m = 0; m < 4; ++m) {
         zinv[m] = fp_inv(fp_sub(fp_mul(t3n, cur), MONT_ONE));
         cur = fp_mul(cur, w4);
     }
-    return circuit_eval_check(c, cc, check, ecode, edata, eacc, st->mixpows, st->betas, zinv, globals);
 }
-}  // namespace
 
 const char* synthetic_constraints_at(void*, const bx_segment_params* shape, const bx_tap_reader* taps, const uint32_t poly_mix[4],
                                      const uint32_t mix[4], const uint32_t* globals, uint32_t out[4]);  // verify.cpp (host arithmetic only)

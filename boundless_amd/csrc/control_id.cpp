@@ -22,6 +22,7 @@
 
 #include "../../include/bx_circuit.h"
 #include "circuit.hpp"
+#include "lookup.hpp"
 #include "fp.hpp"
 #include "poseidon2_params.hpp"
 #include "hash_suite.hpp"
@@ -76,12 +77,23 @@ void parallel_ranges(size_t n, F&& body) {  // body(begin, end)
     for (auto& x : th) x.join();
 }
 
-// Merkle root of the committed code group of the synthetic circuit for (po2, w_code) under a hash suite
-const char* host_control_id(uint32_t po2, uint32_t wc, int suite, uint32_t out[8]) {
-    if (po2 < 9 || po2 > 24 || wc < 1 || wc >= 65536) return "bx_synthetic_control_id_host: shape out of range";
+// Merkle root of the committed code group of a built-in circuit for (po2, w_code) under a hash suite; cell(col, row) is the
+// circuit's code cell
+// (a functor: the call is inlined into the column loop); `who` holds the entry point's two refusals
+struct HostIdErrors {
+    const char *range, *too_large;
+};
+constexpr HostIdErrors SYNTH_ID_ERRORS = {
+    "bx_synthetic_control_id_host: shape out of range",
+    "bx_synthetic_control_id_host: the code group is too large for the host computation (build a verifier context from bx_prover_control_id instead)"};
+constexpr HostIdErrors LOOKUP_ID_ERRORS = {
+    "bx_lookup_control_id_host: shape out of range (po2 in [9, 24], w_code >= 3 and below 65536)",
+    "bx_lookup_control_id_host: the code group is too large for the host computation (build a verifier context from bx_prover_control_id instead)"};
+template <class CodeCell>
+const char* host_control_id(uint32_t po2, uint32_t wc, int suite, const CodeCell& cell, const HostIdErrors& who, uint32_t out[8]) {
+    if (po2 < 9 || po2 > 24 || wc < 1 || wc >= 65536) return who.range;
     const size_t n = (size_t)1 << po2, dom = 4 * n;
-    if ((double)wc * (double)dom * 4.0 > 6.0e9) return "bx_synthetic_control_id_host: the code group is too large for the host computation (build a verifier context from bx_prover_control_id instead)";
-    const Circuit cc(po2, wc, 1, 1, 1, 1);  // only po2 / w_code enter the code group
+    if ((double)wc * (double)dom * 4.0 > 6.0e9) return who.too_large;
     std::vector<uint32_t> ev((size_t)wc * dom);
     const uint32_t w_n_inv = fp_inv(root_of_unity(po2)), w_dom = root_of_unity(po2 + 2), n_inv = fp_inv(fp_encode((uint32_t)n));
     {
@@ -91,7 +103,7 @@ const char* host_control_id(uint32_t po2, uint32_t wc, int suite, uint32_t out[8
             th.emplace_back([&, k] {
                 for (uint32_t c = k; c < wc; c += t) {
                     uint32_t* col = &ev[(size_t)c * dom];
-                    for (size_t r = 0; r < n; ++r) col[r] = synth_code_cell(cc, c, (uint32_t)r);
+                    for (size_t r = 0; r < n; ++r) col[r] = cell(c, (uint32_t)r);
                     dft_natural(col, po2, w_n_inv);  // coefficients * N
                     uint32_t shift = n_inv;          // 3^j / N
                     for (size_t j = 0; j < n; ++j) {
@@ -137,7 +149,36 @@ const size_t N_TABLE = 0;
 #endif
 
 std::mutex cache_mu;
-std::map<std::array<uint32_t, 3>, Digest> cache;  // (po2, w_code, suite) -> host-computed control ID
+enum BuiltIn : uint32_t { BUILTIN_SYNTHETIC = 0, BUILTIN_LOOKUP = 1 };
+std::map<std::array<uint32_t, 4>, Digest> cache;  // (circuit, po2, w_code, suite) -> host-computed control ID
+
+// the cached host computation for one of the built-in circuits
+const char* cached_control_id(BuiltIn which, uint32_t po2, uint32_t wc, int suite, uint32_t out[8]) {
+    const std::array<uint32_t, 4> key{(uint32_t)which, po2, wc, (uint32_t)suite};
+    {
+        std::lock_guard<std::mutex> g(cache_mu);
+        auto it = cache.find(key);
+        if (it != cache.end()) {
+            memcpy(out, it->second.data(), 32);
+            return nullptr;
+        }
+    }
+    Digest d;
+    const char* e;
+    if (which == BUILTIN_LOOKUP) {
+        if (wc < 3) return LOOKUP_ID_ERRORS.range;
+        const Lookup lk(po2, wc, 4, 12);  // only po2 / w_code enter the code group
+        e = host_control_id(po2, wc, suite, [&lk](uint32_t c, uint32_t r) { return lookup_code_cell(lk, c, r); }, LOOKUP_ID_ERRORS, d.data());
+    } else {
+        const Circuit cc(po2, wc, 1, 1, 1, 1);
+        e = host_control_id(po2, wc, suite, [&cc](uint32_t c, uint32_t r) { return synth_code_cell(cc, c, r); }, SYNTH_ID_ERRORS, d.data());
+    }
+    if (e) return e;
+    std::lock_guard<std::mutex> g(cache_mu);
+    cache[key] = d;
+    memcpy(out, d.data(), 32);
+    return nullptr;
+}
 
 const char* synth_control_id(uint32_t po2, uint32_t wc, int suite, uint32_t out[8], bool use_table) {
     if (use_table && wc == 16 && suite == SUITE_POSEIDON2)  // the generated table holds Poseidon2 IDs
@@ -146,20 +187,7 @@ const char* synth_control_id(uint32_t po2, uint32_t wc, int suite, uint32_t out[
                 memcpy(out, SYNTH_CONTROL_IDS_W16[i].id, 32);
                 return nullptr;
             }
-    {
-        std::lock_guard<std::mutex> g(cache_mu);
-        auto it = cache.find({po2, wc, (uint32_t)suite});
-        if (it != cache.end()) {
-            memcpy(out, it->second.data(), 32);
-            return nullptr;
-        }
-    }
-    Digest d;
-    if (const char* e = host_control_id(po2, wc, suite, d.data())) return e;
-    std::lock_guard<std::mutex> g(cache_mu);
-    cache[{po2, wc, (uint32_t)suite}] = d;
-    memcpy(out, d.data(), 32);
-    return nullptr;
+    return cached_control_id(BUILTIN_SYNTHETIC, po2, wc, suite, out);
 }
 }  // namespace
 
@@ -172,6 +200,22 @@ const char* synth_check_code_suite(const bx_segment_params* s, const uint32_t ro
 }
 const char* synth_check_code(void*, const bx_segment_params* s, const uint32_t root[8]) {
     return synth_check_code_suite(s, root, SUITE_POSEIDON2);  // a table's check_code has no suite parameter: the default one
+}
+const char* lookup_check_code_suite(const bx_segment_params* s, const uint32_t root[8], int suite) {
+    if (!s || !root) return "check_code: null argument";
+    uint32_t id[8];
+    if (const char* e = cached_control_id(BUILTIN_LOOKUP, s->po2, s->w_code, suite, id)) return e;
+    return memcmp(id, root, 32) == 0 ? nullptr : "the code group's root is not the lookup circuit's control ID for the shape (the seal was made with another code group)";
+}
+const char* lookup_check_code(void*, const bx_segment_params* s, const uint32_t root[8]) {
+    return lookup_check_code_suite(s, root, SUITE_POSEIDON2);
+}
+// the built-in circuits' control IDs follow the hash suite (a table's check_code has no suite parameter): what verify.cpp asks under a
+// suite other than the default when it has no context.  Any other table (a plug-in circuit) is refused.
+const char* builtin_check_code_suite(const bx_circuit_ops* circ, const bx_segment_params* s, const uint32_t root[8], int suite) {
+    if (circ == bx_synthetic_circuit()) return synth_check_code_suite(s, root, suite);
+    if (circ && circ->check_code == lookup_check_code) return lookup_check_code_suite(s, root, suite);  // bx_lookup_circuit(), without linking its device half
+    return "no control IDs of this suite for the circuit (a plug-in circuit needs a verifier context)";
 }
 }  // namespace bx
 
@@ -210,6 +254,23 @@ const char* bx_synthetic_control_id_host_hashfn(uint32_t po2, uint32_t w_code, c
         return nullptr;
     } catch (const std::exception& e) {
         snprintf(err, sizeof err, "bx_synthetic_control_id_host: %s", e.what());
+        return err;
+    }
+}
+
+const char* bx_lookup_control_id_host_hashfn(uint32_t po2, uint32_t w_code, const char* hashfn, uint32_t id_out[8]) {
+    static thread_local char err[256];
+    const int suite = parse_hash_suite(hashfn);
+    if (suite < 0) return "bx_lookup_control_id_host: unknown hashfn (\"poseidon2\" or \"sha-256\")";
+    if (!id_out) return "bx_lookup_control_id_host: null output";
+    try {
+        if (const char* e = cached_control_id(BUILTIN_LOOKUP, po2, w_code, suite, id_out)) {
+            snprintf(err, sizeof err, "%s", e);
+            return err;
+        }
+        return nullptr;
+    } catch (const std::exception& e) {
+        snprintf(err, sizeof err, "bx_lookup_control_id_host: %s", e.what());
         return err;
     }
 }

@@ -151,6 +151,8 @@ struct bx_ctx {
     long deep_bitrev = 1;            // segment prover: keep trace coefficients bit-reversed through the DEEP phase (read at bx_prover_create)
     long code_commit_once = 1;       // segment prover, built-in circuit: commit the code group with a prover's first proof and keep it
                                      // (0 = commit it again with every proof; read at bx_prover_create)
+    long lookup_hist_lds = 1;        // lookup circuit, multiplicity histogram: per-workgroup LDS bins flushed with one atomic per non-zero
+                                     // bin (0 = one global atomic per limb; same words, lookup.hip)
 
     // timing
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -301,6 +303,10 @@ const char* circuit_witness(bx_ctx* c, const Circuit& cc, bx_buf code, bx_buf da
 const char* circuit_accum_gather(bx_ctx* c, const Circuit& cc, bx_buf srcvals, bx_buf data);
 const char* circuit_accumulate(bx_ctx* c, const Circuit& cc, bx_buf accum, bx_buf run, bx_buf srcvals, bx_buf betas_dev, uint64_t seed_accum);
 const char* circuit_mix_table(bx_ctx* c, const Circuit& cc, bx_buf mixpows, const uint32_t poly_mix[4]);
+// what every eval_check shares (circuit.hip): the table of n mix powers (canonical, then centred: 8n words), and the four values
+// 1 / ((3x)^N - 1) takes on the domain x = w_4N^row, indexed by row mod 4
+const char* mix_power_table(bx_ctx* c, bx_buf mixpows, const uint32_t poly_mix[4], uint32_t n);
+void vanishing_inverses(uint32_t po2, uint32_t zinv[4]);
 const char* circuit_eval_check(bx_ctx* c, const Circuit& cc, bx_buf check, bx_buf ecode, bx_buf edata, bx_buf eacc, bx_buf mixpows, bx_buf betas_dev,
                                const uint32_t zinv[4], const uint32_t* globals);
 

@@ -725,6 +725,8 @@ extern "C" const char* bx_set_tunable(bx_ctx* c, const char* name, long value) t
         c->deep_bitrev = value != 0;
     } else if (!strcmp(name, "code_commit_once")) {
         c->code_commit_once = value != 0;
+    } else if (!strcmp(name, "lookup_hist_lds")) {
+        c->lookup_hist_lds = value != 0;
     } else if (!strcmp(name, "fold_deep")) {
         BX_REQUIRE(c, value >= 1 && value <= 3, "fold_deep must be 1, 2 or 3");
         c->fold_deep = value;

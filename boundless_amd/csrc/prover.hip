@@ -13,7 +13,7 @@
 #include "circuit.hpp"
 #include "ctx.hpp"
 #include "transcript.hpp"
-#include "../../include/bx_circuit.h"
+#include "../../include/bx_lookup.h"
 
 namespace bx {
 
@@ -277,9 +277,9 @@ extern "C" const char* bx_prover_create_with_circuit(bx_ctx* c, const bx_segment
         if (const char* e = circuit->normalize(circuit->user, &p->shape)) return set_msg(c, e);
     p->N = (size_t)1 << shape->po2;
     p->coeffs_bitrev = shape->po2 >= 15 && c->deep_bitrev;
-    // only the built-in circuit is known to the library to be shape-only (synth_code_cell with a constant seed); a plug-in's code_group
-    // is opaque and is called for every proof
-    p->code_once = circuit == bx_synthetic_circuit() && c->code_commit_once;
+    // only the built-in circuits are known to the library to be shape-only (synth_code_cell / lookup_code_cell with a constant seed); a
+    // plug-in's code_group is opaque and is called for every proof
+    p->code_once = (circuit == bx_synthetic_circuit() || circuit == bx_lookup_circuit()) && c->code_commit_once;
     p->err[0] = 0;
     p->h2.load(c->h_rc, c->h_diag);
     p->hs = HostSuite{c->hash_suite, &p->h2};

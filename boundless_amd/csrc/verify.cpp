@@ -19,6 +19,7 @@
 #include "../../include/bx_circuit.h"
 #include "../../include/bx_prover.h"
 #include "circuit.hpp"
+#include "lookup.hpp"
 #include "fp.hpp"
 #include "poseidon2_params.hpp"
 #include "transcript.hpp"
@@ -106,7 +107,7 @@ struct TreeV {
 }  // namespace
 namespace bx {
 bool verifier_ctx_contains_suite(const bx_verifier_ctx* v, int suite, uint32_t po2, const uint32_t root[8]);  // control_id.cpp
-const char* synth_check_code_suite(const bx_segment_params* s, const uint32_t root[8], int suite);
+const char* builtin_check_code_suite(const bx_circuit_ops* circ, const bx_segment_params* s, const uint32_t root[8], int suite);
 }
 namespace {
 
@@ -123,6 +124,12 @@ int verify_threads() {
     if (from_env) return from_env;
     unsigned hw = std::thread::hardware_concurrency();
     return hw >= 4 ? 4 : hw >= 1 ? (int)hw : 1;
+}
+
+// the lookup circuit's table, recognised without linking its device half (host-only builds of the verifier): like the synthetic
+// circuit's, its control IDs follow the suite (control_id.cpp: builtin_check_code_suite)
+bool builtin_sha256_ids(const bx_circuit_ops* circ) {
+    return circ->check_code != nullptr && circ->check_code == bx::lookup_check_code;
 }
 
 void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, const bx_verifier_ctx* vctx, int suite) {
@@ -173,8 +180,8 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
     //      An explicit context is a lookup and is asked at once; the circuit's own check may have to compute the ID (seconds for
     //      a shape outside its table), so it runs last: only a seal that is otherwise a valid proof can make the verifier pay ----
     if (vctx) VCHECK(verifier_ctx_contains_suite(vctx, suite, po2, trees[0].root), "the code group's root is not one of the verifier context's control IDs for this po2");
-    else if (suite == SUITE_SHA256)  // a table's check_code knows one suite (it has no suite parameter): only the built-in circuit's IDs follow it
-        VCHECK(circ == bx_synthetic_circuit(), "no control IDs to check the code root against (sha-256: a plug-in circuit needs a verifier context)");
+    else if (suite == SUITE_SHA256)  // a table's check_code knows one suite (it has no suite parameter): only the built-in circuits' IDs follow it
+        VCHECK(circ == bx_synthetic_circuit() || builtin_sha256_ids(circ), "no control IDs to check the code root against (sha-256: a plug-in circuit needs a verifier context)");
     else VCHECK(circ->check_code != nullptr, "no control IDs to check the code root against (the circuit table has no check_code: pass a verifier context)");
     trees[1].read_and_commit(rd, T, h, D, widths[1]);
     const Fp4 beta = T.random_ext();  // the accumulators' mix
@@ -440,7 +447,7 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
     if (rd.pos > rd.n) throw Fail{"seal truncated"};
     VCHECK(rd.pos == rd.n, "trailing words after the last query");
     if (!vctx) {  // (the same detour as above: a table's check_code has no suite parameter)
-        const char* ce = suite == SUITE_SHA256 ? synth_check_code_suite(&shape, trees[0].root, suite) : circ->check_code(circ->user, &shape, trees[0].root);
+        const char* ce = suite == SUITE_SHA256 ? builtin_check_code_suite(circ, &shape, trees[0].root, suite) : circ->check_code(circ->user, &shape, trees[0].root);
         VCHECK(ce == nullptr, std::string("control ID: ") + (ce ? ce : ""));
     }
 }

@@ -175,18 +175,34 @@ def _declare(lib):
     lib.bx_verifier_ctx_add_control_id_hashfn.restype = C.c_char_p
     lib.bx_synthetic_control_id_host_hashfn.argtypes = [C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]
     lib.bx_synthetic_control_id_host_hashfn.restype = C.c_char_p
+    lib.bx_lookup_control_id_host_hashfn.argtypes = [C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]
+    lib.bx_lookup_control_id_host_hashfn.restype = C.c_char_p
     lib._bx_prover_declared = True
+
+
+def _circuit_pointer(circuit):
+    """None (the synthetic circuit), the name of a built-in circuit ("synthetic", "lookup"), a CircuitOps table or a pointer to one
+    -> what the C entry points take"""
+    if circuit is None:
+        return None
+    if isinstance(circuit, str):
+        from .circuit import builtin_circuit
+
+        circuit = builtin_circuit(circuit)
+    if isinstance(circuit, C.Structure):
+        return C.addressof(circuit)
+    return C.cast(circuit, C.c_void_p)
 
 
 def verify_seal(seal_words, circuit=None, ctx=None, hashfn="poseidon2"):
     """Host-side verifier (include/bx_prover.h: bx_verify_segment); needs no GPU.  `circuit` = a bx_circuit_ops table
     (boundless_amd.circuit.CircuitOps) when the seal was made for another circuit than the built-in synthetic one; `ctx` = a
     VerifierContext holding the control IDs the code root may be (None = the circuit's own check_code); `hashfn` = the suite the
-    seal was made under ("poseidon2" or "sha-256")."""
+    seal was made under ("poseidon2" or "sha-256").  `circuit` may also name a built-in circuit: "synthetic" or "lookup"."""
     lib = load_library()
     _declare(lib)
     a = np.ascontiguousarray(seal_words, dtype=np.uint32)
-    circ, vctx = C.addressof(circuit) if circuit is not None else None, ctx.handle if ctx is not None else None
+    circ, vctx = _circuit_pointer(circuit), ctx.handle if ctx is not None else None
     if hashfn == "poseidon2":
         msg = lib.bx_verify_segment_with_context(a.ctypes.data, a.size, circ, vctx)
     else:
@@ -221,6 +237,17 @@ def synthetic_control_id_host(po2, w_code, hashfn="poseidon2"):
     return out
 
 
+def lookup_control_id_host(po2, w_code, hashfn="poseidon2"):
+    """The lookup circuit's control ID for (po2, w_code) under a hash suite, computed on the host (include/bx_lookup.h); no GPU."""
+    lib = load_library()
+    _declare(lib)
+    out = np.zeros(8, np.uint32)
+    msg = lib.bx_lookup_control_id_host_hashfn(po2, w_code, str(hashfn).encode(), out.ctypes.data)
+    if msg:
+        raise HalError(msg.decode())
+    return out
+
+
 class HipProverServer:
     """`impl ProverServer` for one GPU.  `widths` = (code, data, accum) trace-group widths of the synthetic circuit (include/bx_prover.h)."""
 
@@ -228,7 +255,9 @@ class HipProverServer:
 
     def __init__(self, device=0, po2=20, widths=DEFAULT_WIDTHS, hal=None, terms=0, degree=0, circuit=None, hashfn=None):
         """terms / degree: the circuit's knobs (synthetic circuit: product terms per constraint, factors per term); 0 = defaults.
-        circuit: a bx_circuit_ops table (boundless_amd.circuit.CircuitOps) to prove another circuit than the built-in one.
+        circuit: None or "synthetic" = the synthetic circuit; "lookup" = the library's lookup circuit (include/bx_lookup.h; its segments
+        carry cell records as their payload: boundless_amd.circuit.encode_cell_records); or a bx_circuit_ops table
+        (boundless_amd.circuit.CircuitOps, or a pointer to one) to prove a circuit written outside the library.
         hashfn: `ProverOpts::hashfn`, "poseidon2" or "sha-256"; None = the suite of `hal` (a context created here: "poseidon2").
         A `hal` of another suite is switched (refused while another prover lives on it)."""
         self._own_hal = hal is None  # a context created here is released by close(); a caller's is the caller's
@@ -243,8 +272,7 @@ class HipProverServer:
         shape = SegmentParams(po2, *self.widths, terms, degree)
         handle = C.c_void_p()
         self._circuit = circuit  # the table must outlive the prover
-        msg = self.lib.bx_prover_create_with_circuit(self.hal.ctx, C.byref(shape), C.addressof(circuit) if circuit is not None else None,
-                                                     C.byref(handle))
+        msg = self.lib.bx_prover_create_with_circuit(self.hal.ctx, C.byref(shape), _circuit_pointer(circuit), C.byref(handle))
         if msg:
             raise HalError(msg.decode())
         self.handle = handle
