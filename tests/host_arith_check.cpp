@@ -98,7 +98,8 @@ static int check_ntt_butterflies() {
 }
 
 // LazyExtAcc (mix_poly_coeffs, batch_evaluate_any, eval_check's mixing): sum_k w_k * x_k against f4_scale + f4_add, for term
-// counts around every fold boundary, worst-case magnitudes (weights +-P/2, x = P - 1) and random operands
+// counts around every fold boundary, worst-case magnitudes (weights +-P/2, x = P - 1) and random operands; then the same through
+// add_centred
 static int check_lazy_ext_acc() {
     const int counts[] = {0, 1, 2, 3, 15, 16, 17, 31, 32, 33, 100, 336, 1000};
     for (int mode = 0; mode < 3; ++mode)
@@ -123,11 +124,78 @@ static int check_lazy_ext_acc() {
                     return 1;
                 }
         }
+    // add_centred (eval_partial_x4_kernel of poly.hip): w and x both centred, the first-level fold every FOUR terms.  The term counts
+    // above plus those around the four-term fold and around the 8 x 4 = 32-term second-level fold; weights +-P/2 with xc +-P/2 in
+    // modes 1 and 2 (mode 1: every product +P^2/4 or -P^2/4 by the draw; mode 2: all of one sign, the accumulators' full worst case)
+    const int counts_c[] = {0, 1, 2, 3, 4, 5, 15, 16, 17, 31, 32, 33, 63, 64, 65, 100, 336, 1000};
+    for (int mode = 0; mode < 4; ++mode)
+        for (int n : counts_c) {
+            LazyExtAcc acc;
+            acc.reset();
+            Fp4 want = f4_zero();
+            for (int k = 0; k < n; ++k) {
+                Fp4 w;
+                uint32_t x;
+                for (int c = 0; c < 4; ++c)
+                    w.c[c] = mode == 0 ? (uint32_t)(rnd64() % P) : mode == 1 ? ((rnd64() & 1) ? P / 2 : P / 2 + 1) : (c & 1) == (mode & 1) ? P / 2 : P / 2 + 1;
+                x = mode == 0 ? (uint32_t)(rnd64() % P) : mode == 1 ? ((rnd64() & 1) ? P / 2 : P / 2 + 1) : mode == 2 ? P / 2 : P / 2 + 1;
+                const i32 wc[4] = {fp_centre_w(w.c[0]), fp_centre_w(w.c[1]), fp_centre_w(w.c[2]), fp_centre_w(w.c[3])};
+                acc.add_centred(wc, fp_centre_w(x));
+                want = f4_add(want, f4_scale(w, x));
+            }
+            const Fp4 got = acc.finish();
+            for (int c = 0; c < 4; ++c)
+                if (got.c[c] != want.c[c] || got.c[c] >= P) {
+                    fprintf(stderr, "LazyExtAcc::add_centred mismatch: mode %d, %d terms, component %d\n", mode, n, c);
+                    return 1;
+                }
+        }
+    return 0;
+}
+
+// The ext x ext product on centred operands (lazy_ext.hpp: every scan of scan.hip, the lookup circuit's eval_check) against fp.hpp's
+// canonical f4_mul, component for component; BX_CHECK_BOUNDS asserts each of its seven sredc operands against SREDC_MAX.  The
+// largest accumulators come from operands of magnitude P/2, so: every sign choice of +-P/2 over the eight components, every pair of
+// elements made of the extreme words, every such element against random ones, and random pairs.
+static int check_f4_mul_one(const Fp4& a, const Fp4& b) {
+    const Fp4 want = f4_mul(a, b), lz = f4_mul_lz(a, b), cc = f4_mul_cc(f4_centre(a), f4_centre(b));
+    for (int c = 0; c < 4; ++c)
+        if (lz.c[c] != want.c[c] || cc.c[c] != want.c[c] || lz.c[c] >= P) {
+            fprintf(stderr, "f4_mul_cc mismatch: a = {%u,%u,%u,%u} b = {%u,%u,%u,%u} component %d: lz %u cc %u want %u\n", a.c[0], a.c[1], a.c[2], a.c[3],
+                    b.c[0], b.c[1], b.c[2], b.c[3], c, lz.c[c], cc.c[c], want.c[c]);
+            return 1;
+        }
+    return 0;
+}
+static int check_f4_mul_cc() {
+    const uint32_t edge[] = {0, 1, P - 1, P / 2, P / 2 + 1, P / 2 - 1, MONT_ONE, P - MONT_ONE};
+    const auto edge_elem = [&](unsigned i) { return Fp4{{edge[i & 7], edge[(i >> 3) & 7], edge[(i >> 6) & 7], edge[(i >> 9) & 7]}}; };
+    const auto rand_elem = [] { return Fp4{{(uint32_t)(rnd64() % P), (uint32_t)(rnd64() % P), (uint32_t)(rnd64() % P), (uint32_t)(rnd64() % P)}}; };
+    for (unsigned s = 0; s < 256; ++s) {  // centred: bit set -> -P/2 (the word P/2 + 1), clear -> +P/2
+        Fp4 a, b;
+        for (int c = 0; c < 4; ++c) {
+            a.c[c] = P / 2 + ((s >> c) & 1);
+            b.c[c] = P / 2 + ((s >> (4 + c)) & 1);
+        }
+        REQUIRE(fp_centre_w(a.c[0]) == ((s & 1) ? -(i32)(P / 2) : (i32)(P / 2)));
+        if (check_f4_mul_one(a, b)) return 1;
+    }
+    for (unsigned i = 0; i < 4096; ++i)
+        for (unsigned j = 0; j < 4096; ++j)
+            if (check_f4_mul_one(edge_elem(i), edge_elem(j))) return 1;
+    Fp4 rnd_elems[64];
+    for (Fp4& e : rnd_elems) e = rand_elem();
+    for (unsigned i = 0; i < 4096; ++i)
+        for (const Fp4& e : rnd_elems)
+            if (check_f4_mul_one(edge_elem(i), e) || check_f4_mul_one(e, edge_elem(i))) return 1;
+    for (int i = 0; i < 1000000; ++i)
+        if (check_f4_mul_one(rand_elem(), rand_elem())) return 1;
     return 0;
 }
 
 int main() {
     if (check_lazy_ext_acc()) return 1;
+    if (check_f4_mul_cc()) return 1;
     if (check_ntt_butterflies()) return 1;
     if (check_cons_sum<64, 4>() || check_cons_sum<48, 3>() || check_cons_sum<16, 3>() || check_cons_sum<32, 3>() || check_cons_sum<8, 2>() || check_cons_sum<5, 1>() ||
         check_cons_sum<7, 4>() || check_cons_sum<64, 5>() || check_cons_sum<1, 1>() || check_cons_sum<25, 2>())

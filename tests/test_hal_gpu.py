@@ -1082,3 +1082,153 @@ def test_eltwise_copy_elem_slice_places_a_host_region_with_strides(hal):
             hal.eltwise_copy_elem_slice(dst, src, *bad)
     assert not dst.view().any()
     hal.eltwise_copy_elem_slice(dst, src, 0, 5, 0, 0, 0, 0)  # nothing to copy: not an error
+
+
+# ------------------------------------------------------------------ worst-case operands of the centred arithmetic
+# mix_poly_coeffs, batch_evaluate_any, the scans and Poseidon2 run on signed, centred Montgomery arithmetic (lazy_ext.hpp,
+# poseidon2_arith.hpp): the words of largest magnitude are P//2 and P//2 + 1 (tests/extreme_words.py), and — the argument of
+# adversarial_columns above — they have to go through the COMPILED kernels, not only through tests/host_arith_check.cpp.
+import sys  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from extreme_words import EDGE, HALF, MONT_ONE, NAMES, pattern  # noqa: E402
+
+HALF_W, HALF1_W = np.full(4, HALF, np.uint32), np.full(4, HALF + 1, np.uint32)
+ONE_W, ZERO_W = np.array([MONT_ONE, 0, 0, 0], np.uint32), np.zeros(4, np.uint32)
+MINUS_ONE_W = np.array([P - MONT_ONE, 0, 0, 0], np.uint32)
+EDGE_W = np.array([HALF, HALF + 1, HALF - 1, P - 1], np.uint32)
+
+
+@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("count,npoly,ncombo", [(1001, 33, 3), (1 << 12, 35, 3)])
+def test_mix_poly_coeffs_extreme_operands(hal, oracle, count, npoly, ncombo, name):
+    """The one-word kernel (count = 1001) and the x4 kernel with its odd tail (4096, 35 polynomials).  mix = 1 makes every weight
+    mix_start: all +P/2, then all -P/2; with inputs all P - 1 that is the largest every accumulator of LazyExtAcc::add can get."""
+    inp = c(pattern(name, (npoly, count), seed=count).reshape(-1))
+    combos = np.random.default_rng(count).integers(0, ncombo, npoly, dtype=np.uint32)
+    d_inp, d_combos = hal.copy_from(inp), hal.copy_from(combos)
+    for mix, start in ((ONE_W, HALF_W), (ONE_W, HALF1_W), (EDGE_W, HALF1_W), (HALF1_W, EDGE_W), (rnd(3, 4), rnd(4, 4))):
+        for init in (np.zeros(ncombo * count * 4, np.uint32), np.full(ncombo * count * 4, P - 1, np.uint32)):
+            out = hal.copy_from(init)
+            hal.mix_poly_coeffs(out, start, mix, d_inp, d_combos, npoly, count)
+            ref = init.copy()
+            oracle.bxo_mix_poly_coeffs(ref, c(start), c(mix), inp, c(combos), npoly, count)
+            assert np.array_equal(out.view(), ref), (mix.tolist(), start.tolist(), int(init[0]))
+
+
+@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("n", [8, 15])
+def test_batch_evaluate_any_extreme_operands(hal, oracle, n, name):
+    """Coefficients at +-P/2 (only the data side can be forced: the weights are the powers of the point) at 2^8 and at 2^15, where the x4
+    partial kernel and LazyExtAcc::add_centred run; natural storage, bit-reversed storage and the pointer form."""
+    size, npoly = 1 << n, 2
+    coeffs = c(pattern(name, (npoly, size), seed=n).reshape(-1))
+    points = [ZERO_W, ONE_W, MINUS_ONE_W, HALF_W, HALF1_W, rnd(11, 4)]
+    xs = c(np.concatenate(points + points))
+    which = np.array([0] * 6 + [1] * 6, np.uint32)
+    ref = np.zeros(4 * 12, np.uint32)
+    oracle.bxo_batch_evaluate_any(coeffs, size, c(which), xs, ref, 12)
+    d_coeffs, d_xs, d_which = hal.copy_from(coeffs), hal.copy_from(xs), hal.copy_from(which)
+    out = hal.alloc(4 * 12)
+    hal.batch_evaluate_any(d_coeffs, npoly, d_which, d_xs, out)
+    assert np.array_equal(out.view(), ref), "batch_evaluate_any"
+    rev = _bitrev_perm(n)
+    d_stored = hal.copy_from(c(coeffs.reshape(npoly, size)[:, rev].reshape(-1)))  # position j holds the coefficient of x^rev(j)
+    if n >= 15:
+        out = hal.alloc(4 * 12)
+        hal.batch_evaluate_any_bitrev(d_stored, npoly, d_which, d_xs, out)
+        assert np.array_equal(out.view(), ref), "batch_evaluate_any_bitrev"
+    if n < 15:  # the bit-reversed and the pointer form start at 2^15
+        return
+    ptrs, flags = [], []
+    for e in range(12):
+        bitrev = e % 2
+        addr = (d_stored if bitrev else d_coeffs).raw.dptr + 4 * int(which[e]) * size
+        ptrs += [addr & 0xFFFFFFFF, addr >> 32]
+        flags.append(bitrev)
+    out = hal.alloc(4 * 12)
+    hal.batch_evaluate_ptrs(hal.copy_from(np.array(ptrs, np.uint32)), hal.copy_from(np.array(flags, np.uint32)), size, d_xs, out)
+    assert np.array_equal(out.view(), ref), "batch_evaluate_ptrs"
+
+
+@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("count", [1, 1000])
+def test_fri_fold_extreme_operands(hal, oracle, count, name):
+    """fri_fold multiplies with the canonical f4_mul today; this holds it to the same words should it move to the lazy product."""
+    x = c(pattern(name, (4, 16 * count), seed=count).reshape(-1))
+    d_x = hal.copy_from(x)
+    for mix in (HALF_W, HALF1_W, EDGE_W, rnd(9, 4)):
+        out = hal.alloc(4 * count)
+        hal.fri_fold(out, d_x, mix)
+        ref = np.zeros(4 * count, np.uint32)
+        oracle.bxo_fri_fold(ref, x, c(mix), count)
+        assert np.array_equal(out.view(), ref), mix.tolist()
+
+
+@pytest.mark.parametrize("size", [2, 65, 2049, 131073])
+@pytest.mark.parametrize("lookback", [1, 0])
+def test_scans_extreme_operands(hal, oracle, lookback, size):
+    """poly_divide(_batch) and (batch_)prefix_products — every combine is the ext x ext product on centred operands (f4_mul_cc) —
+    over a chunk edge, a wave edge, a tile edge and the edge of the look-back window, under both scan_lookback settings: elements and
+    the point z at +-P/2, where the product's accumulators are largest."""
+    zs = [HALF_W, HALF1_W, ONE_W, ZERO_W]
+    hal.set_tunable("scan_lookback", lookback)
+    try:
+        for name in NAMES:
+            polys = c(pattern(name, (4, size, 4), seed=size).reshape(-1))
+            want = polys.copy().reshape(4, 4 * size)
+            want_rems = np.zeros((4, 4), np.uint32)
+            for q, z in enumerate(zs):
+                oracle.bxo_poly_divide(want[q], size, c(z), want_rems[q])
+                buf, rem = hal.copy_from(polys.reshape(4, -1)[q]), hal.alloc(4)
+                hal.poly_divide(buf, z, rem)
+                assert np.array_equal(buf.view(), want[q]) and np.array_equal(rem.view(), want_rems[q]), ("poly_divide", name, z.tolist())
+            buf, rems = hal.copy_from(polys), hal.alloc(16)
+            hal.poly_divide_batch(buf, 4, c(np.concatenate(zs)), rems)
+            assert np.array_equal(buf.view(), want.reshape(-1)) and np.array_equal(rems.view(), want_rems.reshape(-1)), ("poly_divide_batch", name)
+            want = polys.copy().reshape(4, 4 * size)
+            for seq in want:
+                oracle.bxo_prefix_products(seq, size)
+            buf = hal.copy_from(polys.reshape(4, -1)[0])
+            hal.prefix_products(buf)
+            assert np.array_equal(buf.view(), want[0]), ("prefix_products", name)
+            buf = hal.copy_from(polys)
+            hal.batch_prefix_products(buf, 4)
+            assert np.array_equal(buf.view(), want.reshape(-1)), ("batch_prefix_products", name)
+    finally:
+        hal.set_tunable("scan_lookback", 1)
+
+
+def test_poseidon2_extreme_operands(hal, oracle):
+    """hash_rows, hash_fold and merkle_build on the words that are largest for Poseidon2's centred cells: rows drawn from every
+    extreme word, whole rows of P//2, of P//2 + 1 and of their alternation (along the row and from row to row)."""
+    rows, cols = 256, 48
+    m = pattern("edge_mix", (cols, rows), seed=7)  # column-major: m[:, r] is row r
+    m[:, 0], m[:, 1], m[:, 2] = HALF, HALF + 1, P - 1
+    m[:, 3] = pattern("alt_half", cols)
+    m[:, 4] = pattern("alt_half", cols + 1)[1:]
+    m[:, 100:140] = pattern("alt_half", (cols, 40))  # whole rows of P//2 and of P//2 + 1 in turn
+    assert set(EDGE) == set(m[:, 5:100].ravel().tolist())
+    x = c(m.reshape(-1))
+    leaves = np.zeros(8 * rows, np.uint32)
+    oracle.bxo_hash_rows(leaves, x, rows, cols)
+    out = hal.alloc_digest(rows)
+    hal.hash_rows(out, hal.copy_from(x))
+    assert np.array_equal(out.view(), leaves), "hash_rows"
+    ref = np.zeros(16 * rows, np.uint32)
+    ref[8 * rows:] = leaves
+    size = rows
+    while size > 1:
+        oracle.bxo_hash_fold(ref, size, size // 2)
+        size //= 2
+    nodes = hal.alloc_digest(2 * rows)
+    nodes.copy_from(np.zeros(16 * rows, np.uint32))
+    hal.merkle_build(nodes, hal.copy_from(x), rows)
+    assert np.array_equal(nodes.view()[8:], ref[8:]), "merkle_build"
+    for name in NAMES:  # digests are never extreme by themselves: one layer of 256 nodes made of the patterns
+        layer = np.zeros(16 * rows, np.uint32)
+        layer[8 * rows:] = pattern(name, (rows, 8), seed=9).reshape(-1)
+        io = hal.copy_from(layer)
+        hal.hash_fold(io, rows, rows // 2)
+        oracle.bxo_hash_fold(layer, rows, rows // 2)
+        assert np.array_equal(io.view()[8 * (rows // 2):], layer[8 * (rows // 2):]), ("hash_fold", name)

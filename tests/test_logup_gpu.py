@@ -16,6 +16,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import extreme_words  # noqa: E402
 import logup_ref as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -250,6 +251,8 @@ def adversarial(kind, n, width):
         x[2048:2056] = 0
     elif kind == "whole_tile_zero":
         x[2048:4096] = 0
+    elif kind in CENTRED:  # the words of largest magnitude for the centred arithmetic (tests/extreme_words.py)
+        x = extreme_words.pattern(kind, (n, width) if width > 1 else n, seed=5).reshape(n, width)  # alt_half: within an ext element, else from element to element
     else:
         raise ValueError(kind)
     return x.ravel()
@@ -298,6 +301,24 @@ def test_adversarial_logup(hal, lookback, kind, alias):
     hal.prefix_sums(s.buf)
     s.check(R.prefix_sums(d), f"prefix_sums {kind}")
     s.free()
+
+
+# The ext inversion, the running sums and the fused LogUp call multiply and accumulate on centred operands: +-P/2 everywhere, +-P/2
+# alternating within an element, and a draw from every extreme word, through the adversarial tests above — same N_ADV, same references
+# ("all_p_minus_1" and friends centre to -1, 0 and 1: the smallest magnitudes).  An ext element of four equal words is no zero, and
+# edge_mix holds zero words (zero base-field elements, and now and then a zero ext element).
+CENTRED = ["all_half", "all_half1", "alt_half", "edge_mix"]
+
+
+@pytest.mark.parametrize("kind", CENTRED)
+def test_centred_extremes_inversion(hal, kind):
+    test_adversarial_inversion(hal, kind)
+
+
+@pytest.mark.parametrize("alias", [False, True], ids=["distinct", "alias"])
+@pytest.mark.parametrize("kind", CENTRED)
+def test_centred_extremes_logup(hal, lookback, kind, alias):
+    test_adversarial_logup(hal, lookback, kind, alias)
 
 
 # ---- relations between the calls ----

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import extreme_words  # noqa: E402
 import logup_ref as lr  # noqa: E402
 import lookup_ref as ref  # noqa: E402
 
@@ -154,6 +155,32 @@ def test_eval_check_is_the_references_quotient(hal, po2, widths):
         host = [e.view().reshape(w, 4 * sh.N) for e, w in zip(evals, (sh.wc, sh.wd, sh.wa))]
         want = ref.check_quotient(sh, host[0], host[1], host[2], POLY_MIX, ALPHA, g)
         assert np.array_equal(check.view().reshape(4, 4 * sh.N), want)
+    finally:
+        st.close()
+
+
+@pytest.mark.parametrize("name", extreme_words.NAMES)
+def test_eval_check_is_the_references_quotient_on_extreme_matrices(hal, name):
+    """eval_check takes any evaluation matrices: filled with the words of largest magnitude for the centred arithmetic
+    (tests/extreme_words.py), the ext x ext product step * den of every running-sum constraint sees +-P/2 on both sides — with
+    alpha = (0, h, h', h) and limbs of -P/2 every word of den is +-P/2."""
+    po2, widths = 9, (3, 4, 12)
+    st = Stages(hal, po2, widths)
+    try:
+        sh = st.sh
+        dom = 4 * sh.N
+        host = [extreme_words.pattern(name, (w, dom), seed=q) for q, w in enumerate(widths)]
+        dev = [hal.copy_from(np.ascontiguousarray(m.reshape(-1))) for m in host]
+        half = extreme_words.HALF
+        for poly_mix, alpha, g in ((POLY_MIX, ALPHA, (half, half + 1)), ([half + 1] * 4, [0, half, half + 1, half], (P - 1, half))):
+            check = hal.alloc(16 * sh.N)
+            msg = st.ops.eval_check(None, st.state, hal.ctx, check.raw, dev[0].raw, dev[1].raw, dev[2].raw, (C.c_uint32 * 4)(*poly_mix),
+                                    (C.c_uint32 * 4)(*alpha), (C.c_uint32 * 2)(*g))
+            assert not msg, _text(msg)
+            got = check.view().reshape(4, dom)
+            want = ref.check_quotient(sh, host[0], host[1], host[2], poly_mix, alpha, g)
+            bad = np.argwhere(got != want)
+            assert bad.size == 0, f"{len(bad)} check words differ, first at (plane, point) {tuple(bad[0])}; alpha {alpha}"
     finally:
         st.close()
 
