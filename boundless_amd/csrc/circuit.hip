@@ -4,12 +4,15 @@
 // rules shared with the host verifier.  Upstream's counterparts are the machine-generated `witgen`/`step_exec`, `accum`
 // and `eval_check` kernels of risc0-circuit-rv32im-sys 4.0.1 (reference Cargo.lock:8996), which are not vendored.
 //
-// All three stages are VALU-bound (no HBM or MFMA roofline applies): a derived cell / a constraint costs T*(G-1)
-// Montgomery products, the loads around it are one coalesced dword per lane and column.
+// All three stages are VALU-bound (no HBM or MFMA roofline applies): a derived cell / a constraint costs T*(G-2) reduced
+// products and T multiply-adds for the terms, then one reduction and one multiply-add per group of terms that share their
+// first factor (circuit_dev.hpp, the factored form: 32 groups at (64, 4), 16 at (48, 3)); for G <= 2, T*(G-1) products term by
+// term.  The loads around it are one coalesced dword per lane and column.
 // The signed multiply-adds are left to the compiler in this translation unit (poseidon2.hip pins them as single asm
 // statements because its loop-carried cells get widened): here the terms of a cell share their inner products (7 pool entries
-// give at most 28 distinct pairs), and only un-pinned code lets hipcc find them: 446 instead of 605 instructions per cell
-// for (T, G) = (48, 3), and none of the s_nops it places between adjacent asm statements.
+// give at most 28 distinct pairs), and only un-pinned code lets hipcc find them, with none of the s_nops it places between
+// adjacent asm statements.  Per cell, compiled: 486 VALU instructions (368 multiply-class) at (T, G) = (64, 4) and 265 (127)
+// at (48, 3); term by term they were 630 (474) and 389 (218).  DESIGN.md §4 has the table.
 #define BX_PLAIN_MAD 1
 #include "circuit.hpp"
 #include "ctx.hpp"
