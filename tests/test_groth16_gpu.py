@@ -10,6 +10,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bn254_ref as ref  # noqa: E402
+import bn254_tiled as tiled  # noqa: E402
 
 from boundless_amd import groth16 as g16  # noqa: E402
 from boundless_amd.hal import HalError, HipHal  # noqa: E402
@@ -78,11 +79,8 @@ T = 1024
 
 @pytest.fixture(scope="module")
 def tables():
-    rng = random.Random(99)
-    k1 = [rng.randrange(1, R) for _ in range(T)]
-    k2 = k1[:256]
-    p1 = ref.fixed_base(1).many(k1)
-    p2 = ref.fixed_base(2).many(k2)
+    k1, p1, k2, p2 = tiled.tables()
+    assert len(k1) == T
     return k1, p1, g16.g1_words(p1), k2, p2, g16.g2_words(p2)
 
 
@@ -145,13 +143,8 @@ def test_msm_g1_large_by_linearity(hal, tables, log_n, skew):
     pts = hal.copy_from(np.tile(w1, n // T))
     scb = hal.copy_from(sc.ravel())
     got = g16.msm_g1(hal, pts, scb, n)
-    # sum_i s_i k_(i mod T): per table entry, limb sums in uint64 (n / T values below 2^32 each), then Python integers
-    limb = sc.reshape(n // T, T, 8).astype(np.uint64).sum(axis=0)
-    total = 0
-    for t in range(T):
-        st = sum(int(limb[t, l]) << (32 * l) for l in range(8))
-        total += st * k1[t]
-    assert got == ref.mul(ref.G1F, ref.G1_GEN, total % R)
+    # sum_i s_i k_(i mod T) mod r
+    assert got == ref.mul(ref.G1F, ref.G1_GEN, tiled.tiled_total(k1, sc))
     pts.free()
     scb.free()
 
@@ -243,9 +236,7 @@ def test_msm_g2_wide_window_reduction(hal, tables):
     pts = hal.copy_from(np.tile(w2, n // t))
     scb = hal.copy_from(sc.ravel())
     got = g16.msm_g2(hal, pts, scb, n)
-    limb = sc.reshape(n // t, t, 8).astype(np.uint64).sum(axis=0)
-    total = sum(sum(int(limb[j, l]) << (32 * l) for l in range(8)) * k2[j] for j in range(t))
-    assert got == ref.mul(ref.G2F, ref.G2_GEN, total % R)
+    assert got == ref.mul(ref.G2F, ref.G2_GEN, tiled.tiled_total(k2, sc))
     pts.free()
     scb.free()
 
