@@ -1,11 +1,12 @@
 // circuit.hpp — shape of the synthetic circuit that stands in for risc0-circuit-rv32im (include/bx_prover.h, "The
 // synthetic circuit", is the normative text): which columns are free / derived / accumulators, which have a tap one row
-// back, which pool entry is factor f of term t.  Shared by the prover (prover.hip, circuit.hip) and the host verifier
-// (verify.cpp).  The test oracle under oracle/ restates the same rules independently.
+// back, which pool entry is factor f of term t.  Shared by the device stages (circuit.hip) and the verifier-side constraint
+// evaluation (circuit_host.cpp).  The test oracle under oracle/ restates the same rules independently.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/bx_circuit.h"
 #include "../../include/bx_prover.h"
 
 #if defined(__HIPCC__)
@@ -121,6 +122,9 @@ inline uint32_t synth_taps(void*, const bx_segment_params* s, int group, uint32_
 inline uint32_t synth_n_globals(void*, const bx_segment_params* s) { return circuit_of(s).globals(); }
 // verifier side of the code-group binding (control_id.cpp): the built-in table, else the cached host computation
 const char* synth_check_code(void*, const bx_segment_params* s, const uint32_t root[8]);
+// sum_i poly_mix^i C_i from the tap values (circuit_host.cpp)
+const char* synthetic_constraints_at(void*, const bx_segment_params* shape, const bx_tap_reader* taps, const uint32_t poly_mix[4], const uint32_t mix[4],
+                                     const uint32_t* globals, uint32_t out[4]);
 // cell (col, row) of the synthetic circuit's code group (bx_prover.h, "code")
 BX_CIRC_HD inline uint32_t synth_code_cell(const Circuit& cc, uint32_t col, uint32_t row) {
     return col == 0 ? (row == 0 ? 268435454u : 0u) : col == 1 ? (row == cc.active_rows() - 1 ? 268435454u : 0u) : synth_word(SYNTH_CODE_SEED, col, row);

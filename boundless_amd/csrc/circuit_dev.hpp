@@ -43,9 +43,6 @@
 namespace bx {
 inline namespace BX_MAD_FLAVOUR {
 
-// canonical [0, P) -> the representative in [-P/2, P/2]
-BX_HD i32 fp_centre(uint32_t v) { return (i32)v - (v > P / 2 ? (i32)P : 0); }
-
 // largest sredc operand whose result is < P in magnitude: ub(FINAL_MAX) = P - 1
 constexpr i64 FINAL_MAX = ((i64)(P / 2) - 1) * ((i64)1 << 32);
 static_assert(ub(FINAL_MAX) < (i64)P && FINAL_MAX <= SREDC_MAX, "FINAL_MAX");
@@ -213,6 +210,30 @@ BX_HD uint32_t cons_sum(const uint32_t (&pool_u)[Circuit::POOL], uint32_t T, uin
         return sum;
     }
 }
+
+// The walk over the derived columns j = 0 .. J-1 that witness generation (one thread per row) and eval_check (one thread per domain
+// point) share keeps the pool of column F+j in registers from one column to the next: the eight previous derived columns in `ring`
+// (csel(0..7) before the first), free columns j, j+1, j+2 in `u`, code csel(j..j+3) in `k`.  Slot 1 alone is loaded per column,
+// where Circuit::slot1_back asks for a row back (else it repeats slot 0).  Circuit::pool_src states the same rule for the host.
+struct DerivedRegs {
+    uint32_t ring[8], u[3], k[4];
+    // the pool of the column the walk stands at
+    BX_HD void fill(uint32_t (&pool)[Circuit::POOL], uint32_t slot1) const {
+        pool[0] = u[0]; pool[1] = slot1; pool[2] = u[1]; pool[3] = u[2];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) pool[4 + q] = ring[q];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) pool[12 + q] = k[q];
+    }
+    // on to column j+1: d = the value of column F+j, next_u = free column (j+3) mod F, next_k = code csel(j+4)
+    BX_HD void shift(uint32_t d, uint32_t next_u, uint32_t next_k) {
+#pragma unroll
+        for (int q = 7; q > 0; --q) ring[q] = ring[q - 1];
+        ring[0] = d;
+        u[0] = u[1]; u[1] = u[2]; u[2] = next_u;
+        k[0] = k[1]; k[1] = k[2]; k[2] = k[3]; k[3] = next_k;
+    }
+};
 
 }  // inline namespace BX_MAD_FLAVOUR
 }  // namespace bx

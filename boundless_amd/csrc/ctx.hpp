@@ -294,20 +294,32 @@ struct HashLaunchers {
 HashLaunchers poseidon2_launchers(), sha256_launchers();  // functions, not objects: a namespace-scope constant would be emitted for the device too
 const char* hash_rows_suite(bx_ctx* c, bx_buf out, bx_buf matrix, int suite);  // bx_hash_rows under an explicit suite (hal.hip)
 
-// the synthetic circuit's device stages (circuit.hip), driven by prover.hip
-struct Circuit;
-const char* circuit_perm_tables(bx_ctx* c, const Circuit& cc, bx_buf offsets, bx_buf index);
-const char* circuit_code(bx_ctx* c, const Circuit& cc, bx_buf code);
-const char* circuit_witness(bx_ctx* c, const Circuit& cc, bx_buf code, bx_buf data, uint64_t seed_data, uint64_t seed_noise, bx_buf perm_offsets,
-                            bx_buf perm_index);
-const char* circuit_accum_gather(bx_ctx* c, const Circuit& cc, bx_buf srcvals, bx_buf data);
-const char* circuit_accumulate(bx_ctx* c, const Circuit& cc, bx_buf accum, bx_buf run, bx_buf srcvals, bx_buf betas_dev, uint64_t seed_accum);
-const char* circuit_mix_table(bx_ctx* c, const Circuit& cc, bx_buf mixpows, const uint32_t poly_mix[4]);
-// what every eval_check shares (circuit.hip): the table of n mix powers (canonical, then centred: 8n words), and the four values
-// 1 / ((3x)^N - 1) takes on the domain x = w_4N^row, indexed by row mod 4
-const char* mix_power_table(bx_ctx* c, bx_buf mixpows, const uint32_t poly_mix[4], uint32_t n);
-void vanishing_inverses(uint32_t po2, uint32_t zinv[4]);
-const char* circuit_eval_check(bx_ctx* c, const Circuit& cc, bx_buf check, bx_buf ecode, bx_buf edata, bx_buf eacc, bx_buf mixpows, bx_buf betas_dev,
-                               const uint32_t zinv[4], const uint32_t* globals);
+// An owning device allocation over raw_alloc, for buffers that live as long as their owner (a prover, a circuit's state): freed with
+// hipFree in the destructor, not pooled; movable, not copyable.
+struct DevBuf {
+    bx_ctx* c = nullptr;
+    bx_buf b{nullptr, 0};
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : c(o.c), b(o.b) { o.b = bx_buf{nullptr, 0}; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            if (b.dptr) (void)hipFree(b.dptr);
+            c = o.c;
+            b = o.b;
+            o.b = bx_buf{nullptr, 0};
+        }
+        return *this;
+    }
+    const char* alloc(bx_ctx* ctx, size_t words) {
+        c = ctx;
+        return raw_alloc(ctx, words, &b);
+    }
+    ~DevBuf() {
+        if (b.dptr) (void)hipFree(b.dptr);
+    }
+    bx_buf slice(size_t off, size_t len) const { return bx_buf{(uint32_t*)b.dptr + off, len}; }
+};
 
 }  // namespace bx

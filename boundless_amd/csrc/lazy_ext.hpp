@@ -20,8 +20,6 @@
 namespace bx {
 inline namespace BX_MAD_FLAVOUR {
 
-BX_HD i32 fp_centre_w(uint32_t v) { return (i32)v - (v > P / 2 ? (i32)P : 0); }  // canonical -> [-P/2, P/2]
-
 // ---- ext x ext product on the signed lazy arithmetic: 40 multiply-class instructions instead of the 69 (+62 cheap ones) of
 // fp.hpp's f4_mul, which reduces and conditionally subtracts after every one of its 19 base products.  Operands are CENTRED
 // (|.| <= P/2), so four raw products fit one 64-bit accumulator (4 (P/2)^2 = P^2 <= SREDC_MAX = 1.2 P^2): every output
@@ -31,7 +29,7 @@ BX_HD i32 fp_centre_w(uint32_t v) { return (i32)v - (v > P / 2 ? (i32)P : 0); } 
 struct C4 {
     i32 c[4];
 };
-BX_HD C4 f4_centre(const Fp4& a) { return C4{{fp_centre_w(a.c[0]), fp_centre_w(a.c[1]), fp_centre_w(a.c[2]), fp_centre_w(a.c[3])}}; }
+BX_HD C4 f4_centre(const Fp4& a) { return C4{{fp_centre(a.c[0]), fp_centre(a.c[1]), fp_centre(a.c[2]), fp_centre(a.c[3])}}; }
 BX_HD Fp4 f4_mul_cc(const C4& a, const C4& b) {
     constexpr i32 NB = (i32)MONT_NBETA - (i32)P;  // Montgomery form of -11, centred
     const i64 t3 = smad(a.c[0], b.c[3], smad(a.c[1], b.c[2], smad(a.c[2], b.c[1], smul(a.c[3], b.c[0]))));

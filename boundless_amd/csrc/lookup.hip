@@ -13,13 +13,13 @@
 // eval_check costs two ext x ext products per sequence and domain point (f4_mul_lz, lazy_ext.hpp) and is VALU-bound like the
 // synthetic circuit's; everything else here streams.
 #define BX_PLAIN_MAD 1
+#include <memory>
 #include <new>
 #include <unordered_map>
 #include <vector>
 
+#include "circuit_common.hpp"
 #include "lookup.hpp"
-#include "ctx.hpp"
-#include "lazy_ext.hpp"
 
 namespace bx {
 
@@ -135,28 +135,11 @@ __global__ void lookup_build_kernel(uint32_t* __restrict__ denoms, uint32_t* __r
         *reinterpret_cast<uint4*>(denoms + 4 * i) = make_uint4(fp_sub(alpha.c[0], a), alpha.c[1], alpha.c[2], alpha.c[3]);
     }
 }
-// sequence s, component k -> accum column 4s + k; columns >= 4S are filler
-__global__ void lookup_store_kernel(uint32_t* __restrict__ accum, const uint32_t* __restrict__ run, Lookup lk, uint64_t gseed) {
-    const uint32_t n = 1u << lk.po2;
-    const size_t total = (size_t)n * lk.S, stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        const uint32_t s = (uint32_t)(i >> lk.po2), r = (uint32_t)(i & (n - 1));
-        const uint4 v = *reinterpret_cast<const uint4*>(run + 4 * i);
-        uint32_t* o = accum + (size_t)(4 * s) * n + r;
-        o[0] = v.x; o[n] = v.y; o[2 * (size_t)n] = v.z; o[3 * (size_t)n] = v.w;
-    }
-    const size_t filler = (size_t)n * (lk.wa - 4 * lk.S);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < filler; i += stride) {
-        const uint32_t c = 4 * lk.S + (uint32_t)(i >> lk.po2), r = (uint32_t)(i & (n - 1));
-        accum[(size_t)c * n + r] = synth_word(gseed, c, r);
-    }
-}
 
 // ---- eval_check: sum_i poly_mix^i C_i(x) / ((3x)^N - 1) on the 4N domain, one thread per domain point ----
 struct LookupPoint {
-    uint32_t zinv[4];  // 1 / (3^N w_4^m - 1), m = row mod 4
-    uint32_t g[2];     // the statement's public words
-    uint32_t mont_b;   // B
+    EvalPoint at;
+    uint32_t mont_b;  // B
     Fp4 alpha;
 };
 __global__ __launch_bounds__(256) void lookup_eval_check_kernel(uint32_t* __restrict__ check, const uint32_t* __restrict__ ecode,
@@ -169,22 +152,14 @@ __global__ __launch_bounds__(256) void lookup_eval_check_kernel(uint32_t* __rest
     const uint32_t ib = (i + dom - 4u) & (dom - 1u);  // one row back: x * w_N^-1 = w_4N^(row - 4)
     const uint32_t first = ecode[i], last = ecode[(size_t)dom + i], table = ecode[2 * (size_t)dom + i];
     const uint32_t not_first = fp_sub(MONT_ONE, first);
-    const auto mix_at = [&](size_t k) {
-        const uint4 m = *reinterpret_cast<const uint4*>(mixpows + 4 * k);  // wave-uniform
-        return Fp4{{m.x, m.y, m.z, m.w}};
-    };
     // (S_s(x) - (1 - first) S_s(x w_N^-1)) * (alpha - a) + add, weighted poly_mix^(V + s); returns S_s(x) for the closing sum
     Fp4 tot = f4_zero(), closing = f4_zero();
     const auto sequence = [&](uint32_t s, uint32_t a, const Fp4& add) {
         Fp4 cur, back;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            cur.c[k] = eacc[(size_t)(4 * s + k) * dom + i];
-            back.c[k] = eacc[(size_t)(4 * s + k) * dom + ib];
-        }
+        ext_column_at(eacc, s, dom, i, ib, cur, back);
         const Fp4 step = f4_sub(cur, f4_scale(back, not_first));
         const Fp4 den{{fp_sub(pt.alpha.c[0], a), pt.alpha.c[1], pt.alpha.c[2], pt.alpha.c[3]}};
-        tot = f4_add(tot, f4_mul_lz(mix_at(lk.V + s), f4_add(f4_mul_lz(step, den), add)));
+        tot = f4_add(tot, f4_mul_lz(mix_power(mixpows, lk.V + s), f4_add(f4_mul_lz(step, den), add)));
         closing = f4_add(closing, cur);
     };
     LazyExtAcc mixacc;  // the base-valued constraints v - lo - B hi (ext weight x base value)
@@ -192,48 +167,33 @@ __global__ __launch_bounds__(256) void lookup_eval_check_kernel(uint32_t* __rest
     const Fp4 minus_one{{fp_neg(MONT_ONE), 0u, 0u, 0u}};
     for (uint32_t j = 0; j < lk.V; ++j) {
         const uint32_t v = edata[(size_t)(3 * j) * dom + i], lo = edata[(size_t)(3 * j + 1) * dom + i], hi = edata[(size_t)(3 * j + 2) * dom + i];
-        const uint4 m = *reinterpret_cast<const uint4*>(mixpows_c + 4 * (size_t)j);
-        const i32 w[4] = {(i32)m.x, (i32)m.y, (i32)m.z, (i32)m.w};
-        mixacc.add(w, fp_sub(fp_sub(v, lo), fp_mul(pt.mont_b, hi)));
+        mix_add(mixacc, mixpows_c, j, fp_sub(fp_sub(v, lo), fp_mul(pt.mont_b, hi)));
         sequence(2 * j, lo, minus_one);
         sequence(2 * j + 1, hi, minus_one);
     }
     sequence(2 * lk.V, table, Fp4{{edata[(size_t)lk.mult_col() * dom + i], 0u, 0u, 0u}});
     tot = f4_add(tot, mixacc.finish());
     const size_t k0 = 3 * (size_t)lk.V + 1;
-    tot = f4_add(tot, f4_mul_lz(mix_at(k0), f4_scale(closing, last)));
+    tot = f4_add(tot, f4_mul_lz(mix_power(mixpows, k0), f4_scale(closing, last)));
     const uint32_t v0 = edata[i];
-    tot = f4_add(tot, f4_scale(mix_at(k0 + 1), fp_mul(first, fp_sub(v0, pt.g[0]))));
-    tot = f4_add(tot, f4_scale(mix_at(k0 + 2), fp_mul(last, fp_sub(v0, pt.g[1]))));
-    tot = f4_scale(tot, pt.zinv[i & 3u]);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) check[(size_t)k * dom + i] = tot.c[k];
+    tot = f4_add(tot, f4_scale(mix_power(mixpows, k0 + 1), fp_mul(first, fp_sub(v0, pt.at.g[0]))));
+    tot = f4_add(tot, f4_scale(mix_power(mixpows, k0 + 2), fp_mul(last, fp_sub(v0, pt.at.g[1]))));
+    store_check(check, tot, pt.at, dom, i);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // the lookup circuit as a bx_circuit_ops table (include/bx_circuit.h)
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
-constexpr uint64_t GOLDEN64 = 0x9E3779B97F4A7C15ull;
-inline unsigned grid_for(size_t n, unsigned bs = 256, size_t cap = 1 << 16) {
-    size_t b = (n + bs - 1) / bs;
-    return (unsigned)(b > cap ? cap : (b ? b : 1));
-}
 struct LookupState {
     Lookup lk;
-    uint64_t seed = 0, noise_seed = 0;
-    bool noise_set = false;
+    uint64_t seed = 0;
+    NoiseSeed noise;
     // limbs: the 2V limb columns; mcol: the multiplicity column; counts: B bins; run: S AoS ext sequences (denominators, then sums);
     // mults: S sequences of multiplicities; records: the segment's cell records; mixpows: eval_check's weights
-    bx_buf limbs{nullptr, 0}, mcol{nullptr, 0}, counts{nullptr, 0}, run{nullptr, 0}, mults{nullptr, 0}, records{nullptr, 0}, mixpows{nullptr, 0};
+    DevBuf limbs, mcol, counts, run, mults, records, mixpows;
 };
-void lookup_destroy(void*, void* state) {
-    auto* st = (LookupState*)state;
-    if (!st) return;
-    for (bx_buf* b : {&st->limbs, &st->mcol, &st->counts, &st->run, &st->mults, &st->records, &st->mixpows})
-        if (b->dptr) (void)hipFree(b->dptr);
-    delete st;
-}
+void lookup_destroy(void*, void* state) { delete (LookupState*)state; }
 __global__ void fill_words_kernel(uint32_t* __restrict__ out, uint32_t value, size_t n) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = value;
@@ -241,32 +201,26 @@ __global__ void fill_words_kernel(uint32_t* __restrict__ out, uint32_t value, si
 const char* lookup_create(void*, bx_ctx* c, const bx_segment_params* shape, void** state) {
     bx_segment_params checked = *shape;  // the prover normalised it already; a direct caller of the table may not have
     if (const char* e = lookup_normalize(nullptr, &checked)) return set_msg(c, e);
-    auto* st = new (std::nothrow) LookupState();
+    std::unique_ptr<LookupState> st(new (std::nothrow) LookupState());
     BX_REQUIRE(c, st != nullptr, "lookup circuit: out of host memory");
     st->lk = lookup_of(shape);
     const Lookup& lk = st->lk;
     const size_t n = (size_t)1 << lk.po2;
-    const char* e = nullptr;
-    if (!e) e = raw_alloc(c, 8 * (lk.constraints() + 1), &st->mixpows);
-    if (!e) e = raw_alloc(c, n * 2 * lk.V, &st->limbs);
-    if (!e) e = raw_alloc(c, n, &st->mcol);
-    if (!e) e = raw_alloc(c, lk.B, &st->counts);
-    if (!e) e = raw_alloc(c, 4 * n * lk.S, &st->run);
-    if (!e) e = raw_alloc(c, n * lk.S, &st->mults);
-    if (!e) e = raw_alloc(c, 3 * (size_t)BX_LOOKUP_MAX_RECORDS, &st->records);
+    BX_TRY(st->mixpows.alloc(c, 8 * (lk.constraints() + 1)));
+    BX_TRY(st->limbs.alloc(c, n * 2 * lk.V));
+    BX_TRY(st->mcol.alloc(c, n));
+    BX_TRY(st->counts.alloc(c, lk.B));
+    BX_TRY(st->run.alloc(c, 4 * n * lk.S));
+    BX_TRY(st->mults.alloc(c, n * lk.S));
+    BX_TRY(st->records.alloc(c, 3 * (size_t)BX_LOOKUP_MAX_RECORDS));
     // a table of 2^15 bins needs more dynamic LDS than a kernel may use by default (set once per process and kernel; cheap to repeat)
-    if (!e && (size_t)lk.B * 4 > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)lookup_hist_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lk.B * 4)) != hipSuccess)
-        e = set_msg(c, "lookup circuit: the histogram's LDS bins could not be reserved");
-    if (!e) {  // every limb is looked up once: the multiplicities of the 2V limb sequences are the constant 1
-        hipLaunchKernelGGL(fill_words_kernel, dim3(grid_for(n * 2 * lk.V)), dim3(256), 0, c->stream, (uint32_t*)st->mults.dptr, MONT_ONE, n * 2 * lk.V);
-        if (hipGetLastError() != hipSuccess) e = set_msg(c, "lookup circuit: launch failed");
-    }
-    if (e) {
-        lookup_destroy(nullptr, st);
-        return e;
-    }
-    *state = st;
+    BX_REQUIRE(c, (size_t)lk.B * 4 <= 64 * 1024 ||
+                      hipFuncSetAttribute((const void*)lookup_hist_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lk.B * 4)) == hipSuccess,
+               "lookup circuit: the histogram's LDS bins could not be reserved");
+    // every limb is looked up once: the multiplicities of the 2V limb sequences are the constant 1
+    hipLaunchKernelGGL(fill_words_kernel, dim3(grid_for(n * 2 * lk.V)), dim3(256), 0, c->stream, (uint32_t*)st->mults.b.dptr, MONT_ONE, n * 2 * lk.V);
+    BX_REQUIRE(c, hipGetLastError() == hipSuccess, "lookup circuit: launch failed");
+    *state = st.release();
     return nullptr;
 }
 const char* lookup_code_group(void*, void* state, bx_ctx* c, bx_buf code) {
@@ -278,16 +232,12 @@ const char* lookup_code_group(void*, void* state, bx_ctx* c, bx_buf code) {
     BX_LAUNCH_CHECK(c);
     return nullptr;
 }
-void lookup_set_noise_seed(void*, void* state, uint64_t noise_seed) {
-    auto* st = (LookupState*)state;
-    st->noise_seed = noise_seed;
-    st->noise_set = true;
-}
+void lookup_set_noise_seed(void*, void* state, uint64_t noise_seed) { ((LookupState*)state)->noise.set(noise_seed); }
 
 const char* lookup_histogram(bx_ctx* c, LookupState* st) {
     const Lookup& lk = st->lk;
     const size_t total = ((size_t)2 * lk.V) << lk.po2;
-    BX_HIP(c, hipMemsetAsync(st->counts.dptr, 0, (size_t)lk.B * 4, c->stream));
+    BX_HIP(c, hipMemsetAsync(st->counts.b.dptr, 0, (size_t)lk.B * 4, c->stream));
     OpScope op(c, "lookup_hist", 4.0 * (double)total);  // the histogram kernel alone
     if (c->lookup_hist_lds) {
         const size_t lds = (size_t)lk.B * 4;
@@ -295,11 +245,11 @@ const char* lookup_histogram(bx_ctx* c, LookupState* st) {
         size_t wgs = (total + 8 * HIST_T - 1) / (8 * HIST_T);
         if (wgs > (size_t)c->cu_count) wgs = (size_t)c->cu_count;
         const size_t per_wg = ((total + wgs - 1) / wgs + HIST_T - 1) / HIST_T * HIST_T;
-        hipLaunchKernelGGL(lookup_hist_lds_kernel, dim3((unsigned)wgs), dim3(HIST_T), lds, c->stream, (uint32_t*)st->counts.dptr,
-                           (const uint32_t*)st->limbs.dptr, lk, total, per_wg);
+        hipLaunchKernelGGL(lookup_hist_lds_kernel, dim3((unsigned)wgs), dim3(HIST_T), lds, c->stream, (uint32_t*)st->counts.b.dptr,
+                           (const uint32_t*)st->limbs.b.dptr, lk, total, per_wg);
     } else {
-        hipLaunchKernelGGL(lookup_hist_atomic_kernel, dim3(grid_for(total)), dim3(256), 0, c->stream, (uint32_t*)st->counts.dptr,
-                           (const uint32_t*)st->limbs.dptr, lk, total);
+        hipLaunchKernelGGL(lookup_hist_atomic_kernel, dim3(grid_for(total)), dim3(256), 0, c->stream, (uint32_t*)st->counts.b.dptr,
+                           (const uint32_t*)st->limbs.b.dptr, lk, total);
     }
     BX_LAUNCH_CHECK(c);
     return nullptr;
@@ -309,18 +259,12 @@ const char* lookup_histogram(bx_ctx* c, LookupState* st) {
 // (the last record of a cell wins) and uploaded through the pinned ring; the HBM copy of the segment is not needed.
 const char* lookup_witgen_impl(LookupState* st, bx_ctx* c, bx_buf data, const uint8_t* segment, size_t segment_len, uint32_t* globals_out) {
     const Lookup& lk = st->lk;
-    // a noise seed given through set_noise_seed belongs to THIS witgen, accepted or refused
-    const bool noise_given = st->noise_set;
-    st->noise_set = false;
     const size_t n = (size_t)1 << lk.po2;
     const uint32_t act = lk.active_rows();
     uint64_t seed = 0;
-    uint32_t seg_po2 = 0;
-    if (const char* e = bx_segment_decode(segment, segment_len, nullptr, &seg_po2, &seed)) return set_msg(c, e);
-    if (seg_po2 != lk.po2) {
-        snprintf(c->err, sizeof c->err, "prove_segment: the segment has po2 %u, this prover was created for po2 %u", seg_po2, lk.po2);
-        return c->err;
-    }
+    const char* refused = segment_header(c, segment, segment_len, lk.po2, &seed);
+    const uint64_t noise = st->noise.take(seed);  // a noise seed given through set_noise_seed belongs to THIS witgen, accepted or refused
+    if (refused) return refused;
     BX_REQUIRE(c, data.len == n * lk.wd, "lookup witgen: data group buffer size mismatch");
     const uint8_t* payload = segment + BX_SEGMENT_WIRE_BYTES;
     const size_t payload_len = segment_len - BX_SEGMENT_WIRE_BYTES;
@@ -345,8 +289,7 @@ const char* lookup_witgen_impl(LookupState* st, bx_ctx* c, bx_buf data, const ui
         recs[3 * ins.first->second + 2] = fp_encode(w[2]);
     }
     st->seed = seed;
-    const uint64_t noise = noise_given ? st->noise_seed : splitmix64(seed ^ 0x5A4B4E4F49534521ull);
-    const uint64_t gseed = seed + GOLDEN64 * 2, nseed = noise + GOLDEN64 * 2;
+    const uint64_t gseed = data_seed(seed), nseed = data_seed(noise);
     // the statement's public words v_0[0], v_0[A-1]: a generated cell, or the record that replaced it
     for (int q = 0; q < 2; ++q) {
         const uint32_t r = q ? act - 1 : 0u;
@@ -355,24 +298,24 @@ const char* lookup_witgen_impl(LookupState* st, bx_ctx* c, bx_buf data, const ui
                                            : fp_encode((synth_word(gseed, 1, r) & (lk.B - 1u)) + lk.B * (synth_word(gseed, 2, r) & (lk.B - 1u)));
     }
     const uint32_t count = (uint32_t)(recs.size() / 3);
-    if (count) BX_TRY(h2d_staged(c, bx_buf{st->records.dptr, recs.size()}, recs.data(), recs.size()));
+    if (count) BX_TRY(h2d_staged(c, bx_buf{st->records.b.dptr, recs.size()}, recs.data(), recs.size()));
     {
         OpScope op(c, "lookup_fill", 4.0 * (double)(n * lk.wd) + 8.0 * (double)(n * 2 * lk.V));
         hipLaunchKernelGGL(lookup_fill_kernel, dim3(grid_for(n * lk.wd)), dim3(256), 0, c->stream, (uint32_t*)data.dptr, lk, gseed, nseed);
         BX_LAUNCH_CHECK(c);
         if (count) {
             hipLaunchKernelGGL(lookup_records_kernel, dim3((count + 255) / 256), dim3(256), 0, c->stream, (uint32_t*)data.dptr,
-                               (const uint32_t*)st->records.dptr, count, lk);
+                               (const uint32_t*)st->records.b.dptr, count, lk);
             BX_LAUNCH_CHECK(c);
         }
-        hipLaunchKernelGGL(lookup_gather_kernel, dim3(grid_for(n * 2 * lk.V)), dim3(256), 0, c->stream, (uint32_t*)st->limbs.dptr,
+        hipLaunchKernelGGL(lookup_gather_kernel, dim3(grid_for(n * 2 * lk.V)), dim3(256), 0, c->stream, (uint32_t*)st->limbs.b.dptr,
                            (const uint32_t*)data.dptr, lk);
         BX_LAUNCH_CHECK(c);
     }
     BX_TRY(lookup_histogram(c, st));
     OpScope op(c, "lookup_mult", 12.0 * (double)n);
-    hipLaunchKernelGGL(lookup_mult_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (uint32_t*)data.dptr, (uint32_t*)st->mcol.dptr,
-                       (const uint32_t*)st->counts.dptr, lk);
+    hipLaunchKernelGGL(lookup_mult_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (uint32_t*)data.dptr, (uint32_t*)st->mcol.b.dptr,
+                       (const uint32_t*)st->counts.b.dptr, lk);
     BX_LAUNCH_CHECK(c);
     return nullptr;
 }
@@ -392,16 +335,13 @@ const char* lookup_accumulate(void*, void* state, bx_ctx* c, bx_buf accum, const
     BX_REQUIRE(c, accum.len == n * lk.wa, "lookup accumulate: accum group buffer size mismatch");
     {
         OpScope op(c, "lookup_build", 24.0 * (double)(n * lk.S));
-        hipLaunchKernelGGL(lookup_build_kernel, dim3(grid_for(n * lk.S)), dim3(256), 0, c->stream, (uint32_t*)st->run.dptr, (uint32_t*)st->mults.dptr,
-                           (const uint32_t*)st->limbs.dptr, (const uint32_t*)st->mcol.dptr, lk, Fp4{{mix[0], mix[1], mix[2], mix[3]}});
+        hipLaunchKernelGGL(lookup_build_kernel, dim3(grid_for(n * lk.S)), dim3(256), 0, c->stream, (uint32_t*)st->run.b.dptr, (uint32_t*)st->mults.b.dptr,
+                           (const uint32_t*)st->limbs.b.dptr, (const uint32_t*)st->mcol.b.dptr, lk, Fp4{{mix[0], mix[1], mix[2], mix[3]}});
         BX_LAUNCH_CHECK(c);
     }
-    BX_TRY(bx_logup_accumulate(c, st->run, st->run, st->mults, lk.S));  // in place: the sums replace the denominators
-    const uint64_t gseed = (st->seed + GOLDEN64 * 3) ^ (((uint64_t)mix[0] << 32) | mix[1]);
+    BX_TRY(bx_logup_accumulate(c, st->run.b, st->run.b, st->mults.b, lk.S));  // in place: the sums replace the denominators
     OpScope op(c, "lookup_store", 4.0 * (double)(n * lk.wa) + 16.0 * (double)(n * lk.S));
-    hipLaunchKernelGGL(lookup_store_kernel, dim3(grid_for(n * lk.wa)), dim3(256), 0, c->stream, (uint32_t*)accum.dptr, (const uint32_t*)st->run.dptr, lk, gseed);
-    BX_LAUNCH_CHECK(c);
-    return nullptr;
+    return store_ext_columns(c, accum, st->run.b, lk.po2, lk.S, lk.wa, filler_seed(st->seed, mix));
 }
 
 const char* lookup_eval_check(void*, void* state, bx_ctx* c, bx_buf check, bx_buf ecode, bx_buf edata, bx_buf eacc, const uint32_t poly_mix[4],
@@ -411,18 +351,18 @@ const char* lookup_eval_check(void*, void* state, bx_ctx* c, bx_buf check, bx_bu
     const size_t dom = (size_t)4 << lk.po2;
     BX_REQUIRE(c, check.len == 4 * dom && ecode.len == dom * lk.wc && edata.len == dom * lk.wd && eacc.len == dom * lk.wa,
                "lookup eval_check: buffer size mismatch");
-    BX_TRY(mix_power_table(c, st->mixpows, poly_mix, (uint32_t)lk.constraints()));
+    BX_TRY(mix_power_table(c, st->mixpows.b, poly_mix, (uint32_t)lk.constraints()));
     LookupPoint pt;
-    vanishing_inverses(lk.po2, pt.zinv);
-    pt.g[0] = globals[0];
-    pt.g[1] = globals[1];
+    vanishing_inverses(lk.po2, pt.at.zinv);
+    pt.at.g[0] = globals[0];
+    pt.at.g[1] = globals[1];
     pt.mont_b = fp_encode(lk.B);
     pt.alpha = Fp4{{mix[0], mix[1], mix[2], mix[3]}};
     // every evaluation the constraints name is read once, the running sums twice (the tap one row back); four planes are written
     OpScope op(c, "lookup_eval_check", 4.0 * (double)dom * (3.0 + 3.0 * lk.V + 1.0 + 8.0 * lk.S + 4.0));
     hipLaunchKernelGGL(lookup_eval_check_kernel, dim3((unsigned)((dom + 255) / 256)), dim3(256), 0, c->stream, (uint32_t*)check.dptr,
-                       (const uint32_t*)ecode.dptr, (const uint32_t*)edata.dptr, (const uint32_t*)eacc.dptr, lk, (const uint32_t*)st->mixpows.dptr,
-                       (const uint32_t*)st->mixpows.dptr + 4 * lk.constraints(), pt);
+                       (const uint32_t*)ecode.dptr, (const uint32_t*)edata.dptr, (const uint32_t*)eacc.dptr, lk, (const uint32_t*)st->mixpows.b.dptr,
+                       (const uint32_t*)st->mixpows.b.dptr + 4 * lk.constraints(), pt);
     BX_LAUNCH_CHECK(c);
     return nullptr;
 }

@@ -55,8 +55,8 @@ __global__ void mix_prep_kernel(const uint32_t* __restrict__ combos, uint32_t in
                                 Fp4 mix_start, Fp4 mix) {
     for (uint32_t i = threadIdx.x; i < input_size; i += blockDim.x) {  // stored centred: the weights of a LazyExtAcc
         const Fp4 w = f4_mul(mix_start, f4_pow(mix, i));
-        st4(pows + 4 * (size_t)i, Fp4{{(uint32_t)fp_centre_w(w.c[0]), (uint32_t)fp_centre_w(w.c[1]), (uint32_t)fp_centre_w(w.c[2]),
-                                       (uint32_t)fp_centre_w(w.c[3])}});
+        st4(pows + 4 * (size_t)i, Fp4{{(uint32_t)fp_centre(w.c[0]), (uint32_t)fp_centre(w.c[1]), (uint32_t)fp_centre(w.c[2]),
+                                       (uint32_t)fp_centre(w.c[3])}});
     }
     // order[] = a counting sort of the columns by combo.  Up to 1024 columns every thread ranks its own columns against an LDS copy
     // of the combo ids (the single-thread loop this replaces walked n_combos x input_size dependent global loads: 23 us per call,
@@ -191,8 +191,8 @@ __global__ __launch_bounds__(EV_T) void eval_partial_kernel(const uint32_t* __re
     // the (x^256)^i table becomes the centred weights of a LazyExtAcc: 10 instead of 32 instructions per coefficient
     if (tid < EV_K) {
         const Fp4 w = ld4(ypow + 4 * tid);
-        st4(ypow + 4 * tid, Fp4{{(uint32_t)fp_centre_w(w.c[0]), (uint32_t)fp_centre_w(w.c[1]), (uint32_t)fp_centre_w(w.c[2]),
-                                 (uint32_t)fp_centre_w(w.c[3])}});
+        st4(ypow + 4 * tid, Fp4{{(uint32_t)fp_centre(w.c[0]), (uint32_t)fp_centre(w.c[1]), (uint32_t)fp_centre(w.c[2]),
+                                 (uint32_t)fp_centre(w.c[3])}});
     }
     __syncthreads();
     LazyExtAcc lz;
@@ -281,8 +281,8 @@ __global__ __launch_bounds__(EV_T) void eval_tables_kernel(const uint32_t* __res
     powers(Cc, 32);
     if (tid < 32) {
         const Fp4 w = ld4(pw + 4 * (brev_log ? (__brev(tid) >> 27) : tid));
-        st4(T + EVT_IW + 4 * tid, Fp4{{(uint32_t)fp_centre_w(w.c[0]), (uint32_t)fp_centre_w(w.c[1]), (uint32_t)fp_centre_w(w.c[2]),
-                                       (uint32_t)fp_centre_w(w.c[3])}});
+        st4(T + EVT_IW + 4 * tid, Fp4{{(uint32_t)fp_centre(w.c[0]), (uint32_t)fp_centre(w.c[1]), (uint32_t)fp_centre(w.c[2]),
+                                       (uint32_t)fp_centre(w.c[3])}});
     }
     if (tid == 0) {
         const Fp4 A2 = f4_mul(A, A), A3 = f4_mul(A2, A);
@@ -330,8 +330,8 @@ __global__ __launch_bounds__(EV_T) void eval_partial_x4_kernel(const uint32_t* _
 #pragma unroll
         for (int u = 0; u < EV_B; ++u) {
             const W4 w = ldw4(T + EVT_IW + 4 * (ib + u));  // wave-uniform
-            lz[0].add_centred(w.c, fp_centre_w(cur[u].x)); lz[1].add_centred(w.c, fp_centre_w(cur[u].y));
-            lz[2].add_centred(w.c, fp_centre_w(cur[u].z)); lz[3].add_centred(w.c, fp_centre_w(cur[u].w));
+            lz[0].add_centred(w.c, fp_centre(cur[u].x)); lz[1].add_centred(w.c, fp_centre(cur[u].y));
+            lz[2].add_centred(w.c, fp_centre(cur[u].z)); lz[3].add_centred(w.c, fp_centre(cur[u].w));
         }
 #pragma unroll
         for (int u = 0; u < EV_B; ++u) cur[u] = nxt[u];

@@ -431,6 +431,8 @@ BX_HD void internal_round(i32* s, const uint32_t* diag, const uint32_t* rc) {
     for (int i = 0; i < P2_CELLS; ++i) BX_ASSERT_BOUND(iabs64(s[i]) <= B_INT, "internal cell");
 }
 
+// canonical word -> the representative in [-P/2, P/2] (pool entries of cons_sum, the weights and operands of lazy_ext.hpp)
+BX_HD i32 fp_centre(uint32_t v) { return (i32)v - (v > P / 2 ? (i32)P : 0); }
 // signed cell -> canonical word (|v| < P)
 BX_HD uint32_t canon(i32 v) {
     BX_ASSERT_BOUND(iabs64(v) < (i64)P, "canonicalisation input");

@@ -5,7 +5,8 @@
 // poly_group::PolyGroup} (risc0-zkp 3.0.3, reference Cargo.lock:9155) as called by
 // bento/crates/workflow/src/tasks/prove.rs:41-49.  The call sequence, constants (INV_RATE 4, FRI_FOLD 16,
 // FRI_MIN_DEGREE 256, QUERIES 50, CHECK_SIZE 16), Merkle top-layer rule and transcript order are upstream's; the
-// circuit (witness generation, accumulate, eval_check: circuit.hip) is the synthetic one specified in bx_prover.h.
+// circuit (witness generation, accumulate, eval_check) is reached through its bx_circuit_ops table only (bx_circuit.h); the default
+// is the synthetic one specified in bx_prover.h (circuit.hip).
 #include <algorithm>
 #include <memory>
 #include <mutex>
@@ -32,32 +33,6 @@ __global__ void merkle_query_gather_kernel(uint32_t* __restrict__ out, const uin
         o[cols + w] = nodes[(size_t)idx * 8 + (w & 7u)];
     }
 }
-
-struct DevBuf {  // owning device allocation; movable, not copyable
-    bx_ctx* c = nullptr;
-    bx_buf b{nullptr, 0};
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : c(o.c), b(o.b) { o.b = bx_buf{nullptr, 0}; }
-    DevBuf& operator=(DevBuf&& o) noexcept {
-        if (this != &o) {
-            if (b.dptr) (void)hipFree(b.dptr);
-            c = o.c;
-            b = o.b;
-            o.b = bx_buf{nullptr, 0};
-        }
-        return *this;
-    }
-    const char* alloc(bx_ctx* ctx, size_t words) {
-        c = ctx;
-        return raw_alloc(ctx, words, &b);  // long-lived (the prover's lifetime), freed with hipFree in the destructor: not pooled
-    }
-    ~DevBuf() {
-        if (b.dptr) (void)hipFree(b.dptr);
-    }
-    bx_buf slice(size_t off, size_t len) const { return bx_buf{(uint32_t*)b.dptr + off, len}; }
-};
 
 struct Tree {
     size_t rows = 0, cols = 0;

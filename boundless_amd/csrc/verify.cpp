@@ -454,70 +454,6 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
 
 }  // namespace
 
-// sum_i poly_mix^i C_i of the synthetic circuit (include/bx_prover.h) from the tap values: the verifier-side half of the
-// bx_circuit_ops table built in circuit.hip.  Host arithmetic only.
-namespace bx {
-const char* synthetic_constraints_at(void*, const bx_segment_params* shape, const bx_tap_reader* taps, const uint32_t poly_mix_w[4],
-                                     const uint32_t mix_w[4], const uint32_t* globals, uint32_t out[4]) {
-    const Circuit cc(shape->po2, shape->w_code, shape->w_data, shape->w_accum, shape->cons_terms, shape->cons_degree);
-    const Fp4 poly_mix = ld(poly_mix_w), beta = ld(mix_w);
-    const char* err = nullptr;
-    auto at = [&](int g, uint32_t c, int back) -> Fp4 {
-        Fp4 v = f4_zero();
-        if (const char* e = taps->at(taps->ctx, g, c, back, v.c)) err = e;
-        return v;
-    };
-    Fp4 rhs = f4_zero(), cur = f4_one();
-    for (uint32_t j = 0; j < cc.J; ++j) {
-        Fp4 pool[Circuit::POOL];
-        for (unsigned slot = 0; slot < Circuit::POOL; ++slot) {
-            const Circuit::Src src = cc.pool_src(j, slot);
-            pool[slot] = src.group < 0 ? f4_one() : at(src.group, src.col, src.back);
-        }
-        Fp4 sum = f4_zero();
-        for (uint32_t t = 0; t < cc.T; ++t) {
-            Fp4 prod = pool[Circuit::pool_idx(t, 0)];
-            for (uint32_t f = 1; f < cc.G; ++f) prod = f4_mul(prod, pool[Circuit::pool_idx(t, f)]);
-            sum = f4_add(sum, prod);
-        }
-        rhs = f4_add(rhs, f4_mul(cur, f4_sub(at(1, cc.F + j, 0), sum)));
-        cur = f4_mul(cur, poly_mix);
-    }
-    auto acc_at = [&](uint32_t e, int back) -> Fp4 {  // the ext-valued accumulator: sum_k X^k * column(4e+k)
-        Fp4 r = f4_zero();
-        for (int k = 0; k < 4; ++k) {
-            Fp4 xk = f4_zero();
-            xk.c[k] = MONT_ONE;
-            r = f4_add(r, f4_mul(xk, at(2, 4 * e + k, back)));
-        }
-        return r;
-    };
-    const Fp4 first = at(0, 0, 0);
-    Fp4 be = beta;
-    for (uint32_t e = 0; e < cc.E; ++e) {
-        Fp4 inner = f4_add(first, f4_mul(f4_sub(f4_one(), first), acc_at(e, 1)));
-        Fp4 cons = f4_sub(acc_at(e, 0), f4_mul(inner, f4_add(be, at(1, cc.acc_src(e), 0))));
-        rhs = f4_add(rhs, f4_mul(cur, cons));
-        cur = f4_mul(cur, poly_mix);
-        if (e & 1) be = f4_mul(be, beta);  // beta^(floor(e/2)+1)
-    }
-    for (uint32_t p = 0; p < cc.pairs; ++p) {
-        Fp4 cons = f4_mul(at(0, 1, 0), f4_sub(acc_at(2 * p + 1, 0), acc_at(2 * p, 0)));
-        rhs = f4_add(rhs, f4_mul(cur, cons));
-        cur = f4_mul(cur, poly_mix);
-    }
-    // boundary constraints tying the public words to the trace
-    rhs = f4_add(rhs, f4_mul(cur, f4_mul(first, f4_sub(at(1, 0, 0), from_base(globals[0])))));
-    cur = f4_mul(cur, poly_mix);
-    if (cc.globals() > 1) {
-        rhs = f4_add(rhs, f4_mul(cur, f4_mul(at(0, 1, 0), f4_sub(at(1, cc.wd - 1, 0), from_base(globals[1])))));
-        cur = f4_mul(cur, poly_mix);
-    }
-    memcpy(out, rhs.c, 16);
-    return err;
-}
-}  // namespace bx
-
 // The compiled-in Poseidon2 table (canonical integers): what bx_init loads into every new ctx and what the verifier uses.
 // Needs no ctx and no GPU, so that the fixture manifest (tests/golden/MANIFEST.json) can pin its SHA-256 on any host.
 extern "C" const char* bx_poseidon2_default_params(uint32_t* rc213, uint32_t* diag24) {

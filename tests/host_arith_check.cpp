@@ -113,7 +113,7 @@ static int check_lazy_ext_acc() {
                 for (int c = 0; c < 4; ++c)
                     w.c[c] = mode == 0 ? (uint32_t)(rnd64() % P) : ((rnd64() & 1) ? P / 2 : P / 2 + 1);  // centred: +P/2 or -P/2
                 x = mode == 0 ? (uint32_t)(rnd64() % P) : (mode == 1 ? P - 1 : (uint32_t)(rnd64() % 3) * (P / 2));
-                const i32 wc[4] = {fp_centre_w(w.c[0]), fp_centre_w(w.c[1]), fp_centre_w(w.c[2]), fp_centre_w(w.c[3])};
+                const i32 wc[4] = {fp_centre(w.c[0]), fp_centre(w.c[1]), fp_centre(w.c[2]), fp_centre(w.c[3])};
                 acc.add(wc, x);
                 want = f4_add(want, f4_scale(w, x));
             }
@@ -139,8 +139,8 @@ static int check_lazy_ext_acc() {
                 for (int c = 0; c < 4; ++c)
                     w.c[c] = mode == 0 ? (uint32_t)(rnd64() % P) : mode == 1 ? ((rnd64() & 1) ? P / 2 : P / 2 + 1) : (c & 1) == (mode & 1) ? P / 2 : P / 2 + 1;
                 x = mode == 0 ? (uint32_t)(rnd64() % P) : mode == 1 ? ((rnd64() & 1) ? P / 2 : P / 2 + 1) : mode == 2 ? P / 2 : P / 2 + 1;
-                const i32 wc[4] = {fp_centre_w(w.c[0]), fp_centre_w(w.c[1]), fp_centre_w(w.c[2]), fp_centre_w(w.c[3])};
-                acc.add_centred(wc, fp_centre_w(x));
+                const i32 wc[4] = {fp_centre(w.c[0]), fp_centre(w.c[1]), fp_centre(w.c[2]), fp_centre(w.c[3])};
+                acc.add_centred(wc, fp_centre(x));
                 want = f4_add(want, f4_scale(w, x));
             }
             const Fp4 got = acc.finish();
@@ -177,7 +177,7 @@ static int check_f4_mul_cc() {
             a.c[c] = P / 2 + ((s >> c) & 1);
             b.c[c] = P / 2 + ((s >> (4 + c)) & 1);
         }
-        REQUIRE(fp_centre_w(a.c[0]) == ((s & 1) ? -(i32)(P / 2) : (i32)(P / 2)));
+        REQUIRE(fp_centre(a.c[0]) == ((s & 1) ? -(i32)(P / 2) : (i32)(P / 2)));
         if (check_f4_mul_one(a, b)) return 1;
     }
     for (unsigned i = 0; i < 4096; ++i)

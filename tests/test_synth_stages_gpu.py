@@ -54,15 +54,15 @@ class Stages:
         self.hal.sync()
         self.ops.destroy(None, self.state)
 
-    def witgen(self, seed, noise_seed=None):
-        """-> (code, data) device buffers and the public words"""
+    def witgen(self, seed, noise_seed=None, seg_po2=None):
+        """-> (code, data) device buffers and the public words; seg_po2: what the segment's header says, if not the shape's po2"""
         sh = self.sh
         code, data = self.hal.alloc(sh.N * sh.wc), self.hal.alloc(sh.N * sh.wd)
         msg = self.ops.code_group(None, self.state, self.hal.ctx, code.raw)
         assert not msg, _text(msg)
         if noise_seed is not None:
             _SET_NOISE(self.ops.set_noise_seed)(None, self.state, noise_seed)
-        blob = Segment(index=0, po2=sh.po2, seed=seed).to_bytes()
+        blob = Segment(index=0, po2=sh.po2 if seg_po2 is None else seg_po2, seed=seed).to_bytes()
         seg = (C.c_uint8 * len(blob)).from_buffer_copy(blob)
         g = (C.c_uint32 * 2)()
         msg = self.ops.witgen(None, self.state, self.hal.ctx, code.raw, data.raw, seg, len(blob), BxBuf(None, 0), g)
@@ -132,6 +132,21 @@ def test_witgen_with_a_given_noise_seed_and_in_a_single_workgroup(hal):
     _witness_equals_reference(hal, PO2, BIG, (64, 4), seed=5, noise_seed=0xFEEDFACE12345678)
     _witness_equals_reference(hal, PO2, ODD, (48, 3), seed=6, noise_seed=1)
     _witness_equals_reference(hal, 6, BIG, (64, 4), seed=7)  # 64 rows: one 256-lane workgroup, a quarter of it idle in witgen
+
+
+def test_a_refused_segment_uses_up_the_noise_seed_given_for_it(hal):
+    """set_noise_seed is for the NEXT witgen, accepted or refused (bx_circuit.h): after a segment of the wrong po2 the following witgen
+    draws its ZK rows from the default generator, not from the seed given for the refused one."""
+    st = Stages(hal, PO2, BIG, (0, 0))
+    try:
+        with pytest.raises(HalError, match=f"was created for po2 {PO2}"):
+            st.witgen(31, noise_seed=0xDEC0DE5EED, seg_po2=PO2 + 1)
+        _, data, g = st.witgen(31)
+        want_data, want_g = ref.data_columns(st.sh, 31)
+        assert_same_matrix("witgen after a refused segment", data.view().reshape(st.sh.wd, -1), want_data)
+        assert g == want_g
+    finally:
+        st.close()
 
 
 # ---- eval_check on the honest committed evaluations ----

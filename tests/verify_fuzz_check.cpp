@@ -16,10 +16,6 @@
 #include "../boundless_amd/csrc/circuit.hpp"
 #include "../include/bx_circuit.h"
 
-namespace bx {
-const char* synthetic_constraints_at(void*, const bx_segment_params* shape, const bx_tap_reader* taps, const uint32_t poly_mix[4],
-                                     const uint32_t mix[4], const uint32_t* globals, uint32_t out[4]);
-}
 // the library's table lives in circuit.hip next to the device stages; the verifier only needs the host entries
 extern "C" const bx_circuit_ops* bx_synthetic_circuit(void) {
     static const bx_circuit_ops ops = {nullptr, "synthetic (host entries only)", bx::synth_normalize, bx::synth_taps, bx::synth_n_globals,
