@@ -38,3 +38,15 @@ def pattern(name, shape, seed=0):
 def patterns(shape, seed=0):
     for name in NAMES:
         yield name, pattern(name, shape, seed)
+
+
+def poseidon2_extreme_matrix(rows=256, cols=48):
+    """A column-major (cols, rows) matrix for hash_rows (m[:, r] is row r): rows drawn from every extreme word, whole rows of P//2,
+    of P//2 + 1 and of P - 1, and rows of their alternation (along the row and from row to row)."""
+    m = pattern("edge_mix", (cols, rows), seed=7)
+    m[:, 0], m[:, 1], m[:, 2] = HALF, HALF + 1, P - 1
+    m[:, 3] = pattern("alt_half", cols)
+    m[:, 4] = pattern("alt_half", cols + 1)[1:]
+    m[:, 100:140] = pattern("alt_half", (cols, 40))  # whole rows of P//2 and of P//2 + 1 in turn
+    assert set(EDGE) == set(m[:, 5:100].ravel().tolist())
+    return m

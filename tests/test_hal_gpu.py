@@ -1,12 +1,16 @@
 """GPU parity: every HAL entry point (through the C ABI) against the CPU oracle, bit-exact."""
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
 
 from oracle import np_oracle as npo
 from oracle import oracle_lib as ol
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from ntt_columns import N_ADV, adversarial_columns  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 P = ol.P
@@ -21,31 +25,12 @@ def hal():
     h.close()
 
 
-oracle_P = 2013265921
-
-
 def rnd(seed, n):
     return ol.random_elems(np.random.default_rng(seed), n)
 
 
 def c(a):
     return np.ascontiguousarray(a, dtype=np.uint32)
-
-
-def adversarial_columns(n):
-    """Extreme columns of n rows for the NTT kernels (the default kernels carry values in [0, 2P) across their LDS regroupings, so
-    the words that sit at the ends of every intermediate range must go through the COMPILED kernels, not only through the host
-    check of the arithmetic source): all 0, all P - 1, an impulse at row 0, an impulse at row n - 1, alternating 0 / P - 1."""
-    z = np.zeros(n, np.uint32)
-    top = np.full(n, oracle_P - 1, np.uint32)
-    first, last, alt = z.copy(), z.copy(), z.copy()
-    first[0] = oracle_P - 1
-    last[n - 1] = oracle_P - 1
-    alt[1::2] = oracle_P - 1
-    return np.concatenate([z, top, first, last, alt])
-
-
-N_ADV = 5
 
 
 # ------------------------------------------------------------------ NTT family
@@ -995,23 +980,29 @@ def test_wait_policies_return_the_same_words(hal):
     n = 1 << 22
     src = rnd(920, n)
     try:
-        for blocking, spin in [(2, 60), (2, 0), (2, 5000), (0, 60), (1, 60)]:
+        # the last two: the sleep-poll period at both ends of what a caller would set (the short read-backs below outlast the spin)
+        for blocking, spin, poll in [(2, 60, 50), (2, 0, 50), (2, 5000, 50), (0, 60, 50), (1, 60, 50), (2, 60, 1), (2, 60, 1000)]:
             hal.set_tunable("wait_blocking", blocking)
             hal.set_tunable("wait_spin_us", spin)
+            hal.set_tunable("wait_poll_us", poll)
             a, out = hal.copy_from(src), hal.alloc(n)
             for _ in range(8):  # a few ms of device work in front of the read-back
                 hal.eltwise_copy_elem(out, a)
                 hal.batch_bit_reverse(out, 1)
                 hal.batch_bit_reverse(out, 1)
-            assert np.array_equal(out.view(), src), (blocking, spin)
+            assert np.array_equal(out.view(), src), (blocking, spin, poll)
             for i in range(0, 4096, 97):  # short waits: 8 words each on an idle stream
-                assert np.array_equal(out.slice(i, 8).view(), src[i:i + 8]), (blocking, spin, i)
+                assert np.array_equal(out.slice(i, 8).view(), src[i:i + 8]), (blocking, spin, poll, i)
             a.free(), out.free()
         with pytest.raises(HalError, match="wait_spin_us out of range"):
             hal.set_tunable("wait_spin_us", -1)
+        for bad in (0, 10001):
+            with pytest.raises(HalError, match="wait_poll_us out of range"):
+                hal.set_tunable("wait_poll_us", bad)
     finally:
         hal.set_tunable("wait_blocking", 2)
         hal.set_tunable("wait_spin_us", 60)
+        hal.set_tunable("wait_poll_us", 50)
 
 
 def test_scalars_whose_products_wrap_are_refused(hal):
@@ -1088,10 +1079,7 @@ def test_eltwise_copy_elem_slice_places_a_host_region_with_strides(hal):
 # mix_poly_coeffs, batch_evaluate_any, the scans and Poseidon2 run on signed, centred Montgomery arithmetic (lazy_ext.hpp,
 # poseidon2_arith.hpp): the words of largest magnitude are P//2 and P//2 + 1 (tests/extreme_words.py), and — the argument of
 # adversarial_columns above — they have to go through the COMPILED kernels, not only through tests/host_arith_check.cpp.
-import sys  # noqa: E402
-
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from extreme_words import EDGE, HALF, MONT_ONE, NAMES, pattern  # noqa: E402
+from extreme_words import HALF, MONT_ONE, NAMES, pattern, poseidon2_extreme_matrix  # noqa: E402
 
 HALF_W, HALF1_W = np.full(4, HALF, np.uint32), np.full(4, HALF + 1, np.uint32)
 ONE_W, ZERO_W = np.array([MONT_ONE, 0, 0, 0], np.uint32), np.zeros(4, np.uint32)
@@ -1203,13 +1191,7 @@ def test_poseidon2_extreme_operands(hal, oracle):
     """hash_rows, hash_fold and merkle_build on the words that are largest for Poseidon2's centred cells: rows drawn from every
     extreme word, whole rows of P//2, of P//2 + 1 and of their alternation (along the row and from row to row)."""
     rows, cols = 256, 48
-    m = pattern("edge_mix", (cols, rows), seed=7)  # column-major: m[:, r] is row r
-    m[:, 0], m[:, 1], m[:, 2] = HALF, HALF + 1, P - 1
-    m[:, 3] = pattern("alt_half", cols)
-    m[:, 4] = pattern("alt_half", cols + 1)[1:]
-    m[:, 100:140] = pattern("alt_half", (cols, 40))  # whole rows of P//2 and of P//2 + 1 in turn
-    assert set(EDGE) == set(m[:, 5:100].ravel().tolist())
-    x = c(m.reshape(-1))
+    x = c(poseidon2_extreme_matrix(rows, cols).reshape(-1))  # column-major: m[:, r] is row r
     leaves = np.zeros(8 * rows, np.uint32)
     oracle.bxo_hash_rows(leaves, x, rows, cols)
     out = hal.alloc_digest(rows)

@@ -205,23 +205,40 @@ def op_mix_poly(hal, O, rng):
     return f"mix_poly_coeffs {count} x {npoly} -> {ncombo}"
 
 
+EVAL_RAGGED = [100, 257, (1 << 15) - 1, (1 << 15) + 1, 40000, 3 * (1 << 15) + 77]  # no multiple of the 2^15-coefficient segment
+
+
 def op_evaluate_any(hal, O, rng):
-    size = 1 << int(rng.integers(0, 18))
+    """one time in three a ragged size; from 2^15 on, one time in four (powers of two) the bit-reversed entry point on the
+    permuted array.  With the random word offset of the coefficients this takes every kernel of poly.hip's batch_evaluate_any."""
+    if rng.random() < 1 / 3:
+        size = EVAL_RAGGED[int(rng.integers(0, len(EVAL_RAGGED)))]
+    else:
+        size = 1 << int(rng.integers(0, 18))
+    bitrev = size >= (1 << 15) and size & (size - 1) == 0 and rng.random() < 0.25
     npoly, evals = int(rng.integers(1, 9)), int(rng.integers(1, 40))
     coeffs_h = elems(rng, npoly * size)
     which_h = rng.integers(0, npoly, evals, dtype=np.uint32)
     xs_h = elems(rng, 4 * evals)
-    coeffs = Placed(hal, rng, coeffs_h)
+    stored_h = coeffs_h
+    if bitrev:  # position j holds the coefficient of x^bitrev(j)
+        perm = np.zeros(1, np.int64)
+        while perm.size < size:
+            perm = np.concatenate([2 * perm, 2 * perm + 1])
+        stored_h = c(coeffs_h.reshape(npoly, size)[:, perm].reshape(-1))
+    coeffs = Placed(hal, rng, stored_h)
     which = Placed(hal, rng, which_h)
     xs = Placed(hal, rng, xs_h, granule=4)
     out = Placed(hal, rng, np.zeros(4 * evals, np.uint32), granule=4)
-    hal.batch_evaluate_any(coeffs.buf, npoly, which.buf, xs.buf, out.buf)
+    name = "batch_evaluate_any_bitrev" if bitrev else "batch_evaluate_any"
+    getattr(hal, name)(coeffs.buf, npoly, which.buf, xs.buf, out.buf)
     ref = np.zeros(4 * evals, np.uint32)
     O.bxo_batch_evaluate_any(coeffs_h, size, c(which_h), xs_h, ref, evals)
-    out.check(ref, f"batch_evaluate_any size={size} npoly={npoly} evals={evals}")
+    out.check(ref, f"{name} size={size} npoly={npoly} evals={evals}")
+    coeffs.check(stored_h, f"{name} (coefficients)")
     for p in (coeffs, which, xs, out):
         p.free()
-    return f"batch_evaluate_any {size} x {npoly}, {evals} points"
+    return f"{name} {size} x {npoly}, {evals} points"
 
 
 def op_eltwise(hal, O, rng):
