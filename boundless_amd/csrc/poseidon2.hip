@@ -18,6 +18,7 @@ namespace bx {
 
 constexpr int CELLS = 24, RATE = 16, RF_HALF = 4, RP = 21;
 constexpr int DIAG_OFF = 216;  // diagonal starts 16-byte aligned in the device parameter table
+constexpr int PAIR_OFF = DIAG_OFF + 24, P2_TABLE = PAIR_OFF + 2 * CELLS;  // behind it: the paired rounds' E[24], A[24] (centred)
 
 // ---------------------------------------------------------------------------------------------------------------
 // Instruction budget.  The kernel is VALU-issue-bound and on gfx950 a 32-bit multiply-class op (v_mad_[iu]64_[iu]32,
@@ -36,7 +37,7 @@ constexpr int DIAG_OFF = 216;  // diagonal starts 16-byte aligned in the device 
 //     constants are stored pre-scaled, and only the two layers that must hand back Montgomery form (before the internal
 //     rounds, and at the end) multiply by a correction constant (poseidon2_arith.hpp: representation tracking).
 // Results are congruent mod P at every step and the words that leave the permutation are canonical, so the output is
-// bit-identical to the reduce-everywhere form (6.6 k VALU instructions per permutation by PMC, down from ~14.5 k).
+// bit-identical to the reduce-everywhere form (6.3 k VALU instructions per permutation by PMC, down from ~14.5 k).
 //
 // Magnitude bounds (rho = P / 2^32 = 0.46875; sredc(t) in [t/2^32 - P/2, t/2^32 + P/2); int32 holds 1.0667 P):
 //   redc64s output                     |x| <= 57 + P/2                           (external rounds' S-box input)
@@ -46,10 +47,14 @@ constexpr int DIAG_OFF = 216;  // diagonal starts 16-byte aligned in the device 
 //   internal rounds                    cell i: sredc(d_i s_i + sum_r [+ rc]) with d_i < P: B -> rho B + P/2 + 2 has its fixed
 //                                      point at 0.9412 P, 0.945 P is invariant; |sum| < 22.7 P < 2^37; |sum_r| < 0.791 P thanks to
 //                                      the balanced low word of sum.
+//   paired internal rounds             (rounds 1..20, poseidon2_arith.hpp: internal_round_pair) constants centred to +-P/2; dot-product
+//                                      groups < 2.2 P^2 < 2^63, folded to < 0.14 P^2; |sig1| <= P/2 + 4, |sig2| < 0.57 P; cell operands
+//                                      <= 0.73 P^2, cells < 0.85 P
 // ---------------------------------------------------------------------------------------------------------------
 // Device parameter table (round constants scaled by p2_rc_scale(i) so that they can ride in a REDC accumulator of the
 // round's representation): [0,96) external rounds 0-3 | [96,117) internal rounds | [117,213) external rounds 4-7 |
-// [216,240) internal diagonal (plain Montgomery form, used as a multiplier; 16-byte aligned).
+// [216,240) internal diagonal (plain Montgomery form, used as a multiplier; 16-byte aligned) | [240,288) the constants of the
+// paired internal rounds derived from it (p2_pair_consts: E[24], A[24], centred, as two's-complement words).
 // Input: cells < P (canonical).  Output: canonical.
 __device__ __forceinline__ void poseidon2_mix(uint32_t* io, const uint32_t* __restrict__ prm) {
     i32 s[CELLS];
@@ -72,17 +77,35 @@ __device__ __forceinline__ void poseidon2_mix(uint32_t* io, const uint32_t* __re
             red64ks_all<K1_MID, K2_MID, true>(y, prm[96], s);
         }
     }
-    // internal rounds: cells[i] = sum + diag[i]*cells[i].  sum is accumulated in 64 bits, turned into
-    // sum_r = sum * 2^32 mod P by one reduction, and rides in each cell's REDC accumulator (cell 0: together with the next
-    // constant).
+    // internal rounds: cells[i] = sum + diag[i]*cells[i].  Rounds 1..20 go two at a time (internal_round_pair: cells 1..23 return
+    // to 32 bits once per pair); in the last one sum is accumulated in 64 bits, turned into sum_r = sum * 2^32 mod P by one
+    // reduction, and rides in each cell's REDC accumulator together with external round 4's constants.
     // The 24 diagonal words are wave-uniform.  Loaded as scalars the compiler re-issues the s_load (+ s_waitcnt stall) in every
     // internal round; held in VGPRs they cost 24 registers.  So: six 16-byte vector loads through an offset the compiler cannot prove uniform (an opaque zero), issued once,
     // then v_readfirstlane into SGPRs — values the compiler can neither rematerialise from memory nor widen, and that the
     // multiply-adds read as their one scalar operand.
+    // The constants of the paired rounds (E, A: poseidon2_arith.hpp) are fetched the same way in front of the pairs, the diagonal
+    // itself only behind them, for the single last round: 48 + a few SGPRs are live in the loop, not 72.
+    uint32_t zero;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
+    {
+        i32 pk[2 * CELLS];
+        const uint4* kp = reinterpret_cast<const uint4*>(prm + PAIR_OFF + zero);
+#pragma unroll
+        for (int i = 0; i < 2 * CELLS / 4; ++i) {
+            const uint4 v = kp[i];
+            pk[4 * i] = (i32)__builtin_amdgcn_readfirstlane(v.x);
+            pk[4 * i + 1] = (i32)__builtin_amdgcn_readfirstlane(v.y);
+            pk[4 * i + 2] = (i32)__builtin_amdgcn_readfirstlane(v.z);
+            pk[4 * i + 3] = (i32)__builtin_amdgcn_readfirstlane(v.w);
+        }
+#pragma unroll 1
+        for (int r = 0; r < RP - 1; r += 2) {
+            internal_round_pair(s, pk, pk + CELLS, prm + 97 + r);
+        }
+    }
     uint32_t diag[CELLS];
     {
-        uint32_t zero;
-        asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
         const uint4* dp = reinterpret_cast<const uint4*>(prm + DIAG_OFF + zero);
 #pragma unroll
         for (int i = 0; i < CELLS / 4; ++i) {
@@ -92,10 +115,6 @@ __device__ __forceinline__ void poseidon2_mix(uint32_t* io, const uint32_t* __re
             diag[4 * i + 2] = __builtin_amdgcn_readfirstlane(v.z);
             diag[4 * i + 3] = __builtin_amdgcn_readfirstlane(v.w);
         }
-    }
-#pragma unroll 1
-    for (int r = 0; r < RP - 1; ++r) {
-        internal_round<false>(s, diag, prm + 97 + r);
     }
     internal_round<true>(s, diag, prm + 117);  // external round 4's constants ride in the last internal round
     // external rounds 4..7
@@ -199,7 +218,12 @@ __device__ __forceinline__ void fold_pair(uint32_t* out8, const uint32_t* a8, co
     for (int k = 0; k < 8; ++k) s[k] = a8[k], s[8 + k] = b8[k];
 #pragma unroll
     for (int k = 16; k < CELLS; ++k) s[k] = 0u;
-    poseidon2_mix(s, prm);
+    // Every permutation of a subtree fetches its constants at an offset of its own: sharing one address, the compiler keeps the first
+    // permutation's round constants in SGPRs for the later ones and, with the paired rounds' 48 words beside them, spills.
+    // (a scalar zero the compiler cannot see through, added to the pointer: the loads stay scalar loads of the same table)
+    uint32_t z;
+    asm volatile("s_mov_b32 %0, 0" : "=s"(z));
+    poseidon2_mix(s, prm + z);
 #pragma unroll
     for (int k = 0; k < 8; ++k) out8[k] = s[k];
 }
@@ -480,10 +504,13 @@ __global__ __launch_bounds__(64) void transcript_step_kernel(uint32_t* __restric
 }
 
 const char* poseidon2_upload_params(bx_ctx* c) {
-    uint32_t h[DIAG_OFF + 24] = {0};
+    uint32_t h[P2_TABLE] = {0};
     // round constants ride in REDC accumulators, pre-scaled to the representation of the round they are added in
     for (int i = 0; i < 213; ++i) h[i] = (uint32_t)((uint64_t)(c->h_rc[i] % P) * p2_rc_scale(i) % P);
     for (int i = 0; i < 24; ++i) h[DIAG_OFF + i] = fp_encode(c->h_diag[i]);
+    i32 pe[CELLS], pa[CELLS];
+    p2_pair_consts(h + DIAG_OFF, pe, pa);
+    for (int i = 0; i < CELLS; ++i) h[PAIR_OFF + i] = (uint32_t)pe[i], h[PAIR_OFF + CELLS + i] = (uint32_t)pa[i];
     if (!c->d_p2) BX_HIP(c, hipMalloc(&c->d_p2, sizeof h));
     BX_HIP(c, hipMemcpyAsync(c->d_p2, h, sizeof h, hipMemcpyHostToDevice, c->stream));
     BX_HIP(c, stream_wait(c));

@@ -138,6 +138,26 @@ BX_HD i64 smul_k(i32 a, uint32_t k, int alt = 0) {  // a*k
     return (i64)a * (i64)k;
 #endif
 }
+BX_HD i64 smad_s(i32 a, i32 k, i64 c, int alt = 0) {  // a*k + c, k a SIGNED wave-uniform constant (scalar operand): centred constants
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(BX_PLAIN_MAD)
+    i64 r;
+    BX_MAD_ASM("v_mad_i64_i32", "%1, %2, %3", "v"(a), "s"(k), "v"(c));
+    return r;
+#else
+    (void)alt;
+    return (i64)a * (i64)k + c;
+#endif
+}
+BX_HD i64 smul_s(i32 a, i32 k, int alt = 0) {  // a*k, k signed and wave-uniform
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(BX_PLAIN_MAD)
+    i64 r;
+    BX_MAD_ASM("v_mad_i64_i32", "%1, %2, 0", "v"(a), "s"(k));
+    return r;
+#else
+    (void)alt;
+    return (i64)a * (i64)k;
+#endif
+}
 template <int K>
 BX_HD i64 smadc(i32 a, i64 c, int alt = 0) {  // a*K + c, K an inline constant
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(BX_PLAIN_MAD)
@@ -433,6 +453,166 @@ BX_HD void internal_round(i32* s, const uint32_t* diag, const uint32_t* rc) {
 
 // canonical word -> the representative in [-P/2, P/2] (pool entries of cons_sum, the weights and operands of lazy_ext.hpp)
 BX_HD i32 fp_centre(uint32_t v) { return (i32)v - (v > P / 2 ? (i32)P : 0); }
+
+// ---- two internal rounds in one step ------------------------------------------------------------------------------------
+// Cells 1..23 are linear in the internal rounds: with v the cell values, d the diagonal and V1, V2 the sums of rounds A and B,
+// two rounds give  z_i = d_i^2 v_i + d_i V1 + V2  (i >= 1), so those cells return to 32 bits once per TWO rounds: two
+// multiply-adds and one reduction per cell instead of two of each.  Cell 0 (the S-box) is materialised in every round as before.
+// Per-cell constants, CENTRED to [-P/2, P/2] (scalar operands like diag[]; p2_pair_consts derives them from the diagonal):
+//   E_i = d_i^2 R,  A_i = d_i R^2  (i >= 1);  E_0 = the centred diagonal word of cell 0 (its multiplier in both rounds), A_0 unused.
+// With x the cells before round A (x_i == v_i R), x0' = sbox(x0):
+//   sum1 = x0' + sum_{i>=1} x_i  (64 bits)        sig1 = sredc(fold64(sum1))                   == V1
+//   y0 = sredc(E_0 x0' + sig1 R2 + rcA)           y0' = sbox(y0)
+//   t2 = sum_{i>=1} A_i x_i + sig1 (23 R3) + y0' R2                                             == V2 R^3
+//   sig2 = sredc(t2) == V2 R^2                    z0 = sredc(E_0 y0' + sig2 + rcB)
+//   z_i = sredc(E_i x_i + A_i sig1 + sig2)
+// The dot product does not depend on the S-boxes and is issued between their instructions, as two chains of groups of four
+// products.  A group (< 2^63) is FOLDED, g -> hi(g) R + lo(g) (congruent, < 0.14 P^2), and the next group accumulates on top
+// of the folded value; the last group takes both chains, three products and the late term y0' R2.
+// Every magnitude below is a static_assert; the host build asserts them per value (BX_CHECK_BOUNDS, tests/p2_paired_check.cpp).
+constexpr i64 fold_ub(i64 T) { return ((T >> 32) + 1) * (i64)MONT_ONE + ((i64)1 << 32); }  // |fold64(g)| for |g| <= T
+constexpr i64 B_K = (i64)(P / 2);                                                                // centred constants
+constexpr i64 B_SBOX = ub(ub(ub(B_INT * B_INT) * B_INT) * ub(ub(B_INT * B_INT) * ub(B_INT * B_INT)));  // sbox7s output: 0.881 P
+constexpr i64 B_SIG1 = ub(fold_ub((i64)1 << 37));                                                // P/2 + 4
+constexpr i64 T_DOT = 4 * B_K * B_INT + B_K * B_SIG1;  // a group: four products and (first group) the sig1 term, or a folded group below four products
+static_assert(T_DOT <= INT64_MAX && fold_ub(T_DOT) + 4 * B_K * B_INT <= T_DOT, "dot-product group overflows 64 bits");
+constexpr i64 T_LAST = 2 * fold_ub(T_DOT) + 3 * B_K * B_INT + B_SBOX * (i64)R2;  // both chains, three products, the late term
+static_assert(T_LAST <= INT64_MAX && fold_ub(T_LAST) <= SREDC_MAX, "last dot-product group overflows");
+constexpr i64 B_SIG2 = ub(fold_ub(T_LAST));                                                      // 0.563 P
+constexpr i64 T_PAIR0 = B_K * B_SBOX + B_SIG1 * (i64)R2 + (i64)P;                                // cell 0, either round
+constexpr i64 T_PAIRI = B_K * B_INT + B_K * B_SIG1 + B_SIG2;                                     // cells 1..23
+static_assert(B_SIG2 <= B_SIG1 * (i64)R2 && T_PAIR0 <= SREDC_MAX && ub(T_PAIR0) <= B_INT, "paired rounds: cell 0 leaves the internal-round bound");
+static_assert(T_PAIRI <= SREDC_MAX && ub(T_PAIRI) <= B_INT, "paired rounds: cells 1..23 leave the internal-round bound");
+constexpr i32 K23R3 = (i32)cx_mul(23u, R3) - (cx_mul(23u, R3) > P / 2 ? (i32)P : 0);             // 23 R^3, centred
+
+// g -> hi(g) * R + lo(g) with lo unsigned: congruent to g mod P, one multiply-add
+BX_HD i64 fold64(i64 g, int alt = 0) { return smad_k((i32)(g >> 32), MONT_ONE, (i64)(uint32_t)g, alt); }
+// the constants of the paired rounds from the Montgomery diagonal: E[24] then A[24]
+BX_HD void p2_pair_consts(const uint32_t* diag, i32* E, i32* A) {
+    E[0] = fp_centre(diag[0]);
+    A[0] = 0;
+    for (int i = 1; i < P2_CELLS; ++i) {
+        E[i] = fp_centre(fp_mul(diag[i], diag[i]));
+        A[i] = fp_centre(fp_mul(diag[i], R2));
+    }
+}
+// rounds A and B on all cells; rc[0], rc[1]: their constants (cell 0), scaled like internal_round's
+BX_HD void internal_round_pair(i32* s, const i32* E, const i32* A, const uint32_t* rc) {
+    // Stage-wise like internal_round: the two S-box chains are dependent instruction by instruction, and the sum, the dot product
+    // and its folds are issued in between.  The trailing argument is the carry-out pair rotation.
+    BX_ASSERT_BOUND(iabs64(s[0]) <= B_INT, "sbox input");
+    i64 pa = smulc<1>(s[1], 0), pb = smulc<1>(s[2], 1);
+    i64 t = smul(s[0], s[0], 2);                                    // x^2
+    pa = smadc<1>(s[3], pa, 3);
+    i32 m = mont_m(t);
+    pb = smadc<1>(s[4], pb, 0);
+    i32 x2 = (i32)(smad_k(m, P, t, 1) >> 32);
+    pa = smadc<1>(s[5], pa, 2);
+    t = smul(x2, s[0], 3);                                          // x^3
+    pb = smadc<1>(s[6], pb, 0);
+    i64 u = smul(x2, x2, 1);                                        // x^4
+    pa = smadc<1>(s[7], pa, 2);
+    m = mont_m(t);
+    pb = smadc<1>(s[8], pb, 3);
+    i32 m2 = mont_m(u);
+    pa = smadc<1>(s[9], pa, 0);
+    i32 x3 = (i32)(smad_k(m, P, t, 1) >> 32);
+    pb = smadc<1>(s[10], pb, 2);
+    i32 x4 = (i32)(smad_k(m2, P, u, 3) >> 32);
+    pa = smadc<1>(s[11], pa, 0);
+    t = smul(x3, x4, 1);                                            // x^7
+    pb = smadc<1>(s[12], pb, 2);
+    pa = smadc<1>(s[13], pa, 3);
+    m = mont_m(t);
+    pb = smadc<1>(s[14], pb, 0);
+    pa = smadc<1>(s[15], pa, 1);
+    const i32 x0 = (i32)(smad_k(m, P, t, 2) >> 32);                 // round A's S-box output
+#pragma unroll
+    for (int i = 16; i < P2_CELLS; ++i) {
+        if (i & 1) pa = smadc<1>(s[i], pa, i + 3);
+        else pb = smadc<1>(s[i], pb, i + 3);
+    }
+    pa = smadc<1>(x0, pa, 3);
+    i64 gx = smul_s(s[1], A[1], 0), gy = smul_s(s[5], A[5], 1);     // the two chains of the dot product
+    const i64 sum1 = pa + pb;
+    BX_ASSERT_BOUND(iabs64(sum1) < ((i64)1 << 37) && iabs64(x0) <= B_SBOX, "internal sum < 2^37");
+    i64 a0 = smul_s(x0, E[0], 2);
+    i64 f = fold64(sum1, 3);
+    gx = smad_s(s[2], A[2], gx, 0);
+    m = mont_m(f);
+    gy = smad_s(s[6], A[6], gy, 1);
+    const i32 sig1 = (i32)(smad_k(m, P, f, 2) >> 32);
+    BX_ASSERT_BOUND(iabs64(sig1) <= B_SIG1, "sig1");
+    gx = smad_s(s[3], A[3], gx, 3);
+    gy = smad_s(s[7], A[7], gy, 0);
+    a0 = smad_k(sig1, R2, a0, 1);
+    gx = smad_s(s[4], A[4], gx, 2);
+    a0 = add_u32(a0, rc[0], 3);
+    BX_ASSERT_BOUND(iabs64(a0) <= T_PAIR0, "cell 0, round A");
+    gy = smad_s(s[8], A[8], gy, 0);
+    m = mont_m(a0);
+    gx = smad_s(sig1, K23R3, gx, 1);
+    const i32 y0 = (i32)(smad_k(m, P, a0, 2) >> 32);
+    BX_ASSERT_BOUND(iabs64(y0) <= B_INT && iabs64(gx) <= T_DOT && iabs64(gy) <= T_DOT, "sbox input");
+    i64 fx = fold64(gx, 3);
+    t = smul(y0, y0, 0);                                            // round B's S-box
+    i64 fy = fold64(gy, 1);
+    gx = smad_s(s[9], A[9], fx, 2);
+    m = mont_m(t);
+    gy = smad_s(s[13], A[13], fy, 3);
+    x2 = (i32)(smad_k(m, P, t, 0) >> 32);
+    gx = smad_s(s[10], A[10], gx, 1);
+    gy = smad_s(s[14], A[14], gy, 2);
+    t = smul(x2, y0, 3);
+    gx = smad_s(s[11], A[11], gx, 0);
+    u = smul(x2, x2, 1);
+    gy = smad_s(s[15], A[15], gy, 2);
+    m = mont_m(t);
+    gx = smad_s(s[12], A[12], gx, 3);
+    m2 = mont_m(u);
+    gy = smad_s(s[16], A[16], gy, 0);
+    x3 = (i32)(smad_k(m, P, t, 1) >> 32);
+    BX_ASSERT_BOUND(iabs64(gx) <= T_DOT && iabs64(gy) <= T_DOT, "dot-product group");
+    fx = fold64(gx, 2);
+    x4 = (i32)(smad_k(m2, P, u, 3) >> 32);
+    fy = fold64(gy, 0);
+    t = smul(x3, x4, 1);
+    gx = smad_s(s[17], A[17], fx, 2);
+    gx = smad_s(s[18], A[18], gx, 3);
+    m = mont_m(t);
+    gx = smad_s(s[19], A[19], gx, 0);
+    gx = smad_s(s[20], A[20], gx, 1);
+    const i32 y0s = (i32)(smad_k(m, P, t, 2) >> 32);                // round B's S-box output
+    BX_ASSERT_BOUND(iabs64(gx) <= T_DOT && iabs64(y0s) <= B_SBOX, "dot-product group");
+    fx = fold64(gx, 3);
+    gy = smad_s(s[21], A[21], fy, 0);
+    gy = smad_s(s[22], A[22], gy, 1);
+    gy = smad_s(s[23], A[23], gy, 2);
+    gy = smad_k(y0s, R2, gy + fx, 3);
+    BX_ASSERT_BOUND(iabs64(gy) <= T_LAST, "last dot-product group");
+    const i32 sig2 = sredc(fold64(gy, 0), 1);
+    BX_ASSERT_BOUND(iabs64(sig2) <= B_SIG2, "sig2");
+    const i64 c = smulc<1>(sig2, 2);
+    constexpr int H = P2_CELLS / 2;
+#pragma unroll
+    for (int h = 0; h < P2_CELLS; h += H) {
+        i64 tt[H];
+#pragma unroll
+        for (int i = 0; i < H; ++i) {
+            if (h + i == 0)
+                tt[i] = smad_s(y0s, E[0], add_u32(c, rc[1], 2), 3);
+            else
+                tt[i] = smad_s(s[h + i], E[h + i], c, i + 2);
+        }
+#pragma unroll
+        for (int i = 0; i < H; ++i)
+            if (h + i != 0) tt[i] = smad_s(sig1, A[h + i], tt[i], i + 1);
+        sredc_n<H>(tt, s + h);
+    }
+#pragma unroll
+    for (int i = 0; i < P2_CELLS; ++i) BX_ASSERT_BOUND(iabs64(s[i]) <= B_INT, "internal cell");
+}
+
 // signed cell -> canonical word (|v| < P)
 BX_HD uint32_t canon(i32 v) {
     BX_ASSERT_BOUND(iabs64(v) < (i64)P, "canonicalisation input");
@@ -441,7 +621,8 @@ BX_HD uint32_t canon(i32 v) {
 }
 
 // The whole permutation in the exact order and arithmetic of the device kernel (poseidon2.hip: poseidon2_mix); the device
-// version differs only in pinning the internal-round sum to v_mad_i64_i32 and keeping the diagonal in VGPRs.
+// version differs only in pinning the internal-round sum to v_mad_i64_i32 and in reading the diagonal and the paired rounds'
+// constants from its parameter table (where poseidon2_upload_params put what p2_pair_consts derives) into SGPRs.
 // prm: [0,96) | [96,117) | [117,213) round constants * p2_rc_scale(i) (canonical), [DIAG..DIAG+24) diagonal (Montgomery).
 // Input and output: canonical Montgomery words.
 template <int DIAG>
@@ -465,7 +646,9 @@ BX_HD void poseidon2_mix_bounded(uint32_t* io, const uint32_t* prm) {
             for (int i = 0; i < P2_CELLS; ++i) BX_ASSERT_BOUND(iabs64(s[i]) <= B_MIDOUT, "mid transition output");
         }
     }
-    for (int r = 0; r < 20; ++r) internal_round<false>(s, diag, prm + 97 + r);
+    i32 pair_e[P2_CELLS], pair_a[P2_CELLS];  // the device reads these from its parameter table behind the diagonal
+    p2_pair_consts(diag, pair_e, pair_a);
+    for (int r = 0; r < 20; r += 2) internal_round_pair(s, pair_e, pair_a, prm + 97 + r);
     internal_round<true>(s, diag, prm + 117);
     for (int r = 0; r < 4; ++r) {
         sbox7s_n<P2_CELLS>(s);
