@@ -151,3 +151,239 @@ def encode_cell_records(records):
         for v in (col, row, value):
             out += int(v).to_bytes(4, "little")
     return bytes(out)
+
+
+# ---- constraint programs (include/bx_program.h): a circuit's eval_check and constraints_at from one description ----
+class ConsStep(C.Structure):
+    _fields_ = [("op", C.c_uint32), ("a", C.c_uint32), ("b", C.c_uint32), ("c", C.c_uint32), ("d", C.c_uint32)]
+
+
+class ConsTap(C.Structure):
+    _fields_ = [("group", C.c_uint32), ("col", C.c_uint32), ("back", C.c_uint32)]
+
+
+class ConsProgramDesc(C.Structure):
+    _fields_ = [("steps", C.POINTER(ConsStep)), ("n_steps", C.c_size_t), ("taps", C.POINTER(ConsTap)), ("n_taps", C.c_size_t),
+                ("n_globals", C.c_uint32), ("ret", C.c_uint32)]
+
+
+class ConsProgramInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("steps", "constraints", "degree", "narrow", "wide", "instructions", "taps", "n_globals")]
+
+
+(OP_CONST, OP_CONST_EXT, OP_GET, OP_GET_GLOBAL, OP_ADD, OP_SUB, OP_MUL, OP_TRUE, OP_AND_EQZ, OP_AND_COND) = range(10)  # enum bx_cons_op
+CONS_MAX_STEPS, CONS_MAX_DEGREE, CONS_MAX_NARROW, CONS_MAX_WIDE = 65536, 5, 32, 24  # BX_CONS_MAX_*
+
+
+def _cons_lib():
+    lib = load_library()
+    if not getattr(lib, "_cons_bound", False):
+        u32p, vp = C.POINTER(C.c_uint32), C.c_void_p
+        lib.bx_cons_program_create.argtypes = [C.POINTER(ConsProgramDesc), C.POINTER(vp)]
+        lib.bx_cons_program_destroy.argtypes = [vp]
+        lib.bx_cons_program_destroy.restype = None
+        lib.bx_cons_program_info_get.argtypes = [vp, C.POINTER(ConsProgramInfo)]
+        lib.bx_cons_program_taps.argtypes = [vp, C.c_int, C.c_uint32, u32p]
+        lib.bx_cons_program_taps.restype = C.c_uint32
+        lib.bx_cons_program_constraints_at.argtypes = [vp, C.POINTER(TapReader), u32p, u32p, u32p, u32p]
+        lib.bx_cons_program_load.argtypes = [vp, vp, C.POINTER(vp)]
+        lib.bx_cons_program_unload.argtypes = [vp]
+        lib.bx_cons_program_eval_check.argtypes = [vp, vp, C.c_uint32, BxBuf, BxBuf, C.c_uint32, BxBuf, C.c_uint32, BxBuf, C.c_uint32, u32p, u32p, u32p,
+                                                   C.c_uint32]
+        lib.bx_cons_circuit_create.argtypes = [vp, vp, C.POINTER(vp)]
+        lib.bx_cons_circuit_ops.argtypes = [vp]
+        lib.bx_cons_circuit_ops.restype = C.POINTER(CircuitOps)
+        lib.bx_cons_circuit_destroy.argtypes = [vp]
+        lib.bx_cons_circuit_destroy.restype = None
+        for name in ("bx_cons_program_create", "bx_cons_program_info_get", "bx_cons_program_constraints_at", "bx_cons_program_load", "bx_cons_program_unload",
+                     "bx_cons_program_eval_check", "bx_cons_circuit_create"):
+            getattr(lib, name).restype = C.c_char_p
+        lib._cons_bound = True
+    return lib
+
+
+def _u32x(words, n=None):
+    words = [int(w) for w in words]
+    assert n is None or len(words) == n
+    return (C.c_uint32 * max(len(words), 1))(*words)
+
+
+class CompiledConsProgram:
+    """A compiled constraint program (bx_cons_program): host only until `load`ed on a HipHal."""
+
+    def __init__(self, lib, handle, n_globals):
+        self.lib, self.handle, self.n_globals = lib, handle, n_globals
+
+    @property
+    def info(self):
+        out = ConsProgramInfo()
+        msg = self.lib.bx_cons_program_info_get(self.handle, C.byref(out))
+        assert not msg, msg
+        return {n: int(getattr(out, n)) for n, _ in ConsProgramInfo._fields_}
+
+    def taps(self, group, col):
+        out = (C.c_uint32 * MAX_TAPS)()
+        n = self.lib.bx_cons_program_taps(self.handle, int(group), int(col), out)
+        return list(out[:n])
+
+    def constraints_at(self, tap, poly_mix, mix, globals_=()):
+        """tap(group, col, back) -> 4 Montgomery words (raise to refuse); poly_mix, mix: 4 Montgomery words; -> 4 Montgomery words.
+        A refused tap reads as zero and its message is raised as HalError once the evaluation is through."""
+        from .hal import HalError
+
+        errs = []
+
+        def at(_ctx, group, col, back, out):
+            try:
+                v = tap(group, col, back)
+                for i in range(4):
+                    out[i] = int(v[i])
+                return None
+            except Exception as e:  # noqa: BLE001 - crosses the ABI as a string
+                errs.append(C.create_string_buffer(f"{type(e).__name__}: {e}".encode()))
+                return C.cast(errs[-1], C.c_void_p).value
+
+        reader = TapReader(None, _TAP_AT(at))
+        out = (C.c_uint32 * 4)()
+        g = list(globals_)
+        assert len(g) >= self.n_globals, "fewer globals than the program names"
+        msg = self.lib.bx_cons_program_constraints_at(self.handle, C.byref(reader), _u32x(poly_mix, 4), _u32x(mix, 4), _u32x(g), out)
+        if msg:
+            raise HalError(msg.decode())
+        return list(out)
+
+    def load(self, hal):
+        dev = C.c_void_p()
+        hal._check(self.lib.bx_cons_program_load(hal.ctx, self.handle, C.byref(dev)))
+        return LoadedConsProgram(self, hal, dev)
+
+    def close(self):
+        if self.handle:
+            self.lib.bx_cons_program_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LoadedConsProgram:
+    """A constraint program on a ctx (bx_cons_program_dev); hal.cons_program_eval_check runs it."""
+
+    def __init__(self, program, hal, dev):
+        self.program, self.hal, self.dev = program, hal, dev
+
+    def unload(self):
+        if self.dev:
+            dev, self.dev = self.dev, None
+            self.hal._check(self.program.lib.bx_cons_program_unload(dev))
+
+
+class ConsProgram:
+    """Builder of a constraint program (include/bx_program.h, "Values"): every method appends one step and returns the index of the
+    fp var or mix var it made, which later steps take as operands.
+
+        p = ConsProgram(n_globals=1)
+        x = p.get(1, 0, 0)
+        top = p.and_eqz(p.true(), p.sub(p.mul(x, x), p.get(1, 1, 0)))
+        prog = p.compile(ret=top)
+    """
+
+    def __init__(self, n_globals=0):
+        self.n_globals = n_globals
+        self.steps, self.tap_list, self._tap_index = [], [], {}
+        self.n_fp = self.n_mix = 0
+
+    def _fp(self, op, a=0, b=0, c=0, d=0):
+        self.steps.append((op, a, b, c, d))
+        self.n_fp += 1
+        return self.n_fp - 1
+
+    def _mix(self, op, a=0, b=0, c=0):
+        self.steps.append((op, a, b, c, 0))
+        self.n_mix += 1
+        return self.n_mix - 1
+
+    def const(self, a):
+        return self._fp(OP_CONST, a)
+
+    def const_ext(self, a, b, c, d):
+        return self._fp(OP_CONST_EXT, a, b, c, d)
+
+    def tap(self, group, col, back=0):
+        """index of (group, col, back) in the tap list (added on first use)"""
+        key = (int(group), int(col), int(back))
+        if key not in self._tap_index:
+            self._tap_index[key] = len(self.tap_list)
+            self.tap_list.append(key)
+        return self._tap_index[key]
+
+    def get(self, group, col, back=0):
+        return self._fp(OP_GET, self.tap(group, col, back))
+
+    def get_tap(self, index):
+        """GET of a raw tap-list index (not checked here: bx_cons_program_create is the judge)"""
+        return self._fp(OP_GET, index)
+
+    def global_(self, index):
+        return self._fp(OP_GET_GLOBAL, 0, index)
+
+    def mix(self, component):
+        return self._fp(OP_GET_GLOBAL, 1, component)
+
+    def add(self, a, b):
+        return self._fp(OP_ADD, a, b)
+
+    def sub(self, a, b):
+        return self._fp(OP_SUB, a, b)
+
+    def mul(self, a, b):
+        return self._fp(OP_MUL, a, b)
+
+    def true(self):
+        return self._mix(OP_TRUE)
+
+    def and_eqz(self, x, y):
+        return self._mix(OP_AND_EQZ, x, y)
+
+    def and_cond(self, x, cond, inner):
+        return self._mix(OP_AND_COND, x, cond, inner)
+
+    def compile(self, ret=None):
+        """-> CompiledConsProgram; ret = the mix var whose tot is the result (default: the last one).  A refusal raises HalError."""
+        from .hal import HalError
+
+        lib = _cons_lib()
+        steps = (ConsStep * max(len(self.steps), 1))(*[ConsStep(*s) for s in self.steps])
+        taps = (ConsTap * max(len(self.tap_list), 1))(*[ConsTap(*t) for t in self.tap_list])
+        desc = ConsProgramDesc(steps, len(self.steps), taps, len(self.tap_list), self.n_globals, (self.n_mix - 1 if ret is None else ret) & 0xFFFFFFFF)
+        handle = C.c_void_p()
+        msg = lib.bx_cons_program_create(C.byref(desc), C.byref(handle))
+        if msg:
+            raise HalError(msg.decode())
+        return CompiledConsProgram(lib, handle, self.n_globals)
+
+
+def _from_program(program, base):
+    """CircuitOps.from_program(program, base): the table whose taps, eval_check and constraints_at come from `program` (a
+    CompiledConsProgram) and everything else from `base` (a CircuitOps: from_object, lookup_circuit() or synthetic_circuit()).
+    The result is used like any other table (HipProverServer(circuit=...), verify_seal(circuit=...)); it keeps program and base alive."""
+    import weakref
+
+    from .hal import HalError
+
+    lib = _cons_lib()
+    base_ptr = C.addressof(base) if isinstance(base, C.Structure) else C.cast(base, C.c_void_p).value
+    cc = C.c_void_p()
+    msg = lib.bx_cons_circuit_create(base_ptr, program.handle, C.byref(cc))
+    if msg:
+        raise HalError(msg.decode())
+    ops = lib.bx_cons_circuit_ops(cc).contents
+    ops._keepalive = (program, base)
+    weakref.finalize(ops, lib.bx_cons_circuit_destroy, cc)
+    return ops
+
+
+CircuitOps.from_program = staticmethod(_from_program)

@@ -1,0 +1,399 @@
+// cons_program.hip — device half of constraint programs (include/bx_program.h is the normative text; cons_program.hpp the compiled
+// form): a kernel that INTERPRETS a program's instruction stream over the 4N domain, and the bx_circuit_ops table made of a program
+// and a base table.
+//   lanes     one lane per domain point, 256 per workgroup
+//   slots     the two slot files live in LDS, slot-major: narrow slot s is words [256 s, 256 s + 256) (1 KiB), wide slot s four such
+//             planes (4 KiB).  A wave's access to a slot is 64 consecutive dwords: conflict-free.  A lane only ever touches its own
+//             column, so there is NO barrier, and lanes past the domain return at once.  The dynamic LDS is sized per program
+//             (narrow + 4 wide KiB; at most 32 + 96 = 128 KiB of the CU's 160), so a small program keeps several workgroups per CU.
+//   state     nothing per lane is held in an array indexed at run time (that would be scratch): a value is in LDS or in flight
+//   stream    wave-uniform: fetched through a const __restrict__ pointer indexed by the loop counter, CP_FETCH instructions per
+//             fetch, so that it comes through the scalar cache; decode and dispatch are scalar (readfirstlane makes it explicit)
+//   values    canonical throughout: fp_add / fp_sub / fp_mul, f4_scale and f4_mul_lz (canonical in, canonical out — its lazy
+//             accumulators do not outlive one product, lazy_ext.hpp).  Nothing lazy is kept across instructions, so there is no bound
+//             to carry.  Mix powers come from the canonical half of mix_power_table.
+#define BX_PLAIN_MAD 1
+#include <map>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <set>
+#include <vector>
+
+#include "circuit_common.hpp"
+#include "cons_program.hpp"
+
+namespace bx {
+
+constexpr uint32_t CP_LANES = 256;
+
+struct ConsLaunch {
+    uint32_t zinv[4];  // 1 / (3^N w_4^m - 1), m = row mod 4
+    uint32_t dom, n_fetch, n_narrow, ret_slot;
+};
+
+__device__ __forceinline__ Fp4 cp_ldw(const uint32_t* wid, uint32_t s) {
+    const uint32_t* p = wid + 4 * s * CP_LANES;
+    return Fp4{{p[0], p[CP_LANES], p[2 * CP_LANES], p[3 * CP_LANES]}};
+}
+__device__ __forceinline__ void cp_stw(uint32_t* wid, uint32_t s, const Fp4& v) {
+    uint32_t* p = wid + 4 * s * CP_LANES;
+    p[0] = v.c[0];
+    p[CP_LANES] = v.c[1];
+    p[2 * CP_LANES] = v.c[2];
+    p[3 * CP_LANES] = v.c[3];
+}
+
+// one instruction for one lane; everything decoded from w0 / w1 is wave-uniform
+__device__ __forceinline__ void cp_exec(uint32_t w0v, uint32_t w1v, uint32_t* nar, uint32_t* wid, const uint32_t* __restrict__ ecode,
+                                        const uint32_t* __restrict__ edata, const uint32_t* __restrict__ eacc, const uint2* __restrict__ taps,
+                                        const uint32_t* __restrict__ scal, const uint32_t* __restrict__ mixpows, uint32_t dom, uint32_t i) {
+    const uint32_t w0 = __builtin_amdgcn_readfirstlane(w0v), w1 = __builtin_amdgcn_readfirstlane(w1v);
+    const uint32_t op = w0 & 0xFFu, dst = (w0 >> 8) & 0xFFu, a = (w0 >> 16) & 0xFFu, b = w0 >> 24, c = w1 & 0xFFu, imm = w1 >> 8;
+    switch (op) {
+    case CP_NOP: break;
+    case CP_LD_B: nar[dst * CP_LANES] = scal[imm]; break;
+    case CP_LD_E: {
+        const uint32_t* s = scal + imm;
+        cp_stw(wid, dst, Fp4{{s[0], s[1], s[2], s[3]}});
+        break;
+    }
+    case CP_TAP: {
+        const uint2 t = taps[imm];
+        const uint32_t g = t.y >> 30, back = t.y & 0x3FFFFFFFu;
+        const uint32_t* __restrict__ col = (g == 0 ? ecode : (g == 1 ? edata : eacc)) + (size_t)t.x * dom;
+        nar[dst * CP_LANES] = col[(i - 4u * back) & (dom - 1u)];  // dom divides 2^32: the wrapped difference reduces properly
+        break;
+    }
+    case CP_ADD_BB: nar[dst * CP_LANES] = fp_add(nar[a * CP_LANES], nar[b * CP_LANES]); break;
+    case CP_SUB_BB: nar[dst * CP_LANES] = fp_sub(nar[a * CP_LANES], nar[b * CP_LANES]); break;
+    case CP_MUL_BB: nar[dst * CP_LANES] = fp_mul(nar[a * CP_LANES], nar[b * CP_LANES]); break;
+    case CP_ADD_EB: {
+        Fp4 x = cp_ldw(wid, a);
+        x.c[0] = fp_add(x.c[0], nar[b * CP_LANES]);
+        cp_stw(wid, dst, x);
+        break;
+    }
+    case CP_SUB_EB: {
+        Fp4 x = cp_ldw(wid, a);
+        x.c[0] = fp_sub(x.c[0], nar[b * CP_LANES]);
+        cp_stw(wid, dst, x);
+        break;
+    }
+    case CP_SUB_BE: {
+        const Fp4 y = cp_ldw(wid, b);
+        cp_stw(wid, dst, Fp4{{fp_sub(nar[a * CP_LANES], y.c[0]), fp_neg(y.c[1]), fp_neg(y.c[2]), fp_neg(y.c[3])}});
+        break;
+    }
+    case CP_MUL_EB: cp_stw(wid, dst, f4_scale(cp_ldw(wid, a), nar[b * CP_LANES])); break;
+    case CP_ADD_EE: cp_stw(wid, dst, f4_add(cp_ldw(wid, a), cp_ldw(wid, b))); break;
+    case CP_SUB_EE: cp_stw(wid, dst, f4_sub(cp_ldw(wid, a), cp_ldw(wid, b))); break;
+    case CP_MUL_EE: cp_stw(wid, dst, f4_mul_lz(cp_ldw(wid, a), cp_ldw(wid, b))); break;
+    case CP_ZERO: cp_stw(wid, dst, f4_zero()); break;
+    case CP_EQZ_B: cp_stw(wid, dst, f4_add(cp_ldw(wid, a), f4_scale(mix_power(mixpows, imm), nar[b * CP_LANES]))); break;
+    case CP_EQZ_E: cp_stw(wid, dst, f4_add(cp_ldw(wid, a), f4_mul_lz(mix_power(mixpows, imm), cp_ldw(wid, b)))); break;
+    case CP_COND_B: {
+        const Fp4 w = f4_mul_lz(mix_power(mixpows, imm), cp_ldw(wid, c));
+        cp_stw(wid, dst, f4_add(cp_ldw(wid, a), f4_scale(w, nar[b * CP_LANES])));
+        break;
+    }
+    case CP_COND_E: {
+        const Fp4 w = f4_mul_lz(mix_power(mixpows, imm), cp_ldw(wid, c));
+        cp_stw(wid, dst, f4_add(cp_ldw(wid, a), f4_mul_lz(w, cp_ldw(wid, b))));
+        break;
+    }
+    default: break;
+    }
+}
+
+__global__ __launch_bounds__(256) void cons_program_kernel(uint32_t* __restrict__ check, const uint32_t* __restrict__ ecode,
+                                                           const uint32_t* __restrict__ edata, const uint32_t* __restrict__ eacc,
+                                                           const uint4* __restrict__ code, const uint2* __restrict__ taps,
+                                                           const uint32_t* __restrict__ scal, const uint32_t* __restrict__ mixpows, ConsLaunch L) {
+    extern __shared__ uint32_t slots[];
+    const uint32_t dom = L.dom;
+    const uint32_t i = blockIdx.x * CP_LANES + threadIdx.x;
+    if (i >= dom) return;
+    uint32_t* const nar = slots + threadIdx.x;                          // narrow slot s: nar[256 s]
+    uint32_t* const wid = slots + L.n_narrow * CP_LANES + threadIdx.x;  // wide slot s, plane k: wid[256 (4 s + k)]
+
+    static_assert(CP_FETCH == 4, "the fetch below reads two uint4 = four instructions");
+    for (uint32_t f = 0; f < L.n_fetch; ++f) {
+        const uint4 lo = code[2 * (size_t)f], hi = code[2 * (size_t)f + 1];
+        cp_exec(lo.x, lo.y, nar, wid, ecode, edata, eacc, taps, scal, mixpows, dom, i);
+        cp_exec(lo.z, lo.w, nar, wid, ecode, edata, eacc, taps, scal, mixpows, dom, i);
+        cp_exec(hi.x, hi.y, nar, wid, ecode, edata, eacc, taps, scal, mixpows, dom, i);
+        cp_exec(hi.z, hi.w, nar, wid, ecode, edata, eacc, taps, scal, mixpows, dom, i);
+    }
+    const Fp4 q = f4_scale(cp_ldw(wid, L.ret_slot), L.zinv[i & 3u]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) check[(size_t)k * dom + i] = q.c[k];
+}
+
+}  // namespace bx
+
+// a program loaded on a ctx
+struct bx_cons_program_dev {
+    bx_ctx* ctx = nullptr;
+    bx_cons_program_info info{};
+    uint32_t n_pows = 1, ret_slot = 0, n_fetch = 0, max_col[3] = {0, 0, 0};
+    size_t lds = 0;
+    bx::DevBuf code, taps, scal, mixpows;
+};
+
+namespace bx {
+namespace {
+std::mutex g_loaded_mu;
+std::map<bx_ctx*, std::set<bx_cons_program_dev*>> g_loaded;  // what bx_free still has to release
+}  // namespace
+
+void cons_programs_release(bx_ctx* c) {
+    std::set<bx_cons_program_dev*> ds;
+    {
+        std::lock_guard<std::mutex> g(g_loaded_mu);
+        auto it = g_loaded.find(c);
+        if (it == g_loaded.end()) return;
+        ds.swap(it->second);
+        g_loaded.erase(it);
+    }
+    for (bx_cons_program_dev* d : ds) delete d;  // the caller has drained the stream
+}
+}  // namespace bx
+
+extern "C" const char* bx_cons_program_load(bx_ctx* c, const bx_cons_program* prog, bx_cons_program_dev** out) try {
+    using namespace bx;
+    if (!c) return "bx_cons_program_load: null ctx";
+    BX_REQUIRE(c, prog && out, "bx_cons_program_load: null argument");
+    BX_ENTER(c);
+    *out = nullptr;
+    std::unique_ptr<bx_cons_program_dev> d(new bx_cons_program_dev());
+    d->ctx = c;
+    d->info = prog->info;
+    d->n_pows = prog->n_pows;
+    d->ret_slot = prog->ret_slot;
+    d->n_fetch = (uint32_t)(prog->code.size() / (2 * CP_FETCH));
+    for (int g = 0; g < 3; ++g) d->max_col[g] = prog->max_col[g];
+    // the compiler refuses what does not fit; a stream from anywhere else must not reach the kernel
+    BX_REQUIRE(c, prog->info.narrow <= BX_CONS_MAX_NARROW && prog->info.wide >= 1 && prog->info.wide <= BX_CONS_MAX_WIDE && prog->ret_slot < prog->info.wide &&
+                      prog->code.size() % (2 * CP_FETCH) == 0,
+               "bx_cons_program_load: the program's slot counts are outside the device limits");
+    d->lds = (size_t)(prog->info.narrow + 4 * prog->info.wide) * CP_LANES * 4;
+    const size_t n_scal = prog->info.n_globals + 4 + prog->consts.size();
+    BX_TRY(d->code.alloc(c, prog->code.size() ? prog->code.size() : 1));
+    BX_TRY(d->taps.alloc(c, prog->taps.empty() ? 2 : 2 * prog->taps.size()));
+    BX_TRY(d->scal.alloc(c, n_scal));
+    BX_TRY(d->mixpows.alloc(c, 8 * (size_t)prog->n_pows));
+    std::vector<uint32_t> tapw(2 * prog->taps.size()), scal(n_scal, 0u);
+    for (size_t t = 0; t < prog->taps.size(); ++t) {
+        tapw[2 * t] = prog->taps[t].col;
+        tapw[2 * t + 1] = prog->taps[t].back | prog->taps[t].group << 30;
+    }
+    std::copy(prog->consts.begin(), prog->consts.end(), scal.begin() + prog->info.n_globals + 4);
+    if (!prog->code.empty()) BX_HIP(c, hipMemcpyAsync(d->code.b.dptr, prog->code.data(), prog->code.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (!tapw.empty()) BX_HIP(c, hipMemcpyAsync(d->taps.b.dptr, tapw.data(), tapw.size() * 4, hipMemcpyHostToDevice, c->stream));
+    BX_HIP(c, hipMemcpyAsync(d->scal.b.dptr, scal.data(), scal.size() * 4, hipMemcpyHostToDevice, c->stream));
+    BX_HIP(c, stream_wait(c));  // the host vectors go away
+    // more dynamic LDS than a kernel may use by default (set once per process and kernel; cheap to repeat)
+    BX_REQUIRE(c, d->lds <= 64 * 1024 ||
+                      hipFuncSetAttribute((const void*)cons_program_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BX_CONS_MAX_NARROW * 1024 + BX_CONS_MAX_WIDE * 4096) == hipSuccess,
+               "bx_cons_program_load: the slot files' LDS could not be reserved");
+    {
+        std::lock_guard<std::mutex> g(g_loaded_mu);
+        g_loaded[c].insert(d.get());
+    }
+    *out = d.release();
+    return nullptr;
+} BX_ABI_CATCH(c, "bx_cons_program_load")
+
+extern "C" const char* bx_cons_program_unload(bx_cons_program_dev* dev) try {
+    using namespace bx;
+    if (!dev) return nullptr;
+    bx_ctx* c = nullptr;
+    {
+        // found by address, without reading *dev: a handle unloaded twice, or one whose ctx was freed, names freed memory
+        std::lock_guard<std::mutex> g(g_loaded_mu);
+        for (auto it = g_loaded.begin(); it != g_loaded.end() && !c; ++it)
+            if (it->second.erase(dev)) {
+                c = it->first;
+                if (it->second.empty()) g_loaded.erase(it);
+                break;
+            }
+    }
+    if (!c) return "bx_cons_program_unload: not a loaded program (unloaded twice, or its ctx was freed)";
+    (void)hipSetDevice(c->device);
+    (void)stream_wait(c);  // a launch may still read the tables
+    delete dev;
+    return nullptr;
+} BX_ABI_CATCH(nullptr, "bx_cons_program_unload")
+
+extern "C" const char* bx_cons_program_eval_check(bx_ctx* c, bx_cons_program_dev* dev, uint32_t po2, bx_buf check, bx_buf code_eval, uint32_t w_code,
+                                                  bx_buf data_eval, uint32_t w_data, bx_buf accum_eval, uint32_t w_accum, const uint32_t poly_mix[4],
+                                                  const uint32_t mix[4], const uint32_t* globals, uint32_t n_globals) try {
+    using namespace bx;
+    if (!c) return "bx_cons_program_eval_check: null ctx";
+    BX_REQUIRE(c, dev && poly_mix && mix, "bx_cons_program_eval_check: null argument");
+    BX_REQUIRE(c, dev->ctx == c, "bx_cons_program_eval_check: the program was loaded on another ctx");
+    BX_REQUIRE(c, po2 >= 1 && po2 <= 24, "bx_cons_program_eval_check: po2 must be in [1, 24]");
+    BX_ENTER(c);
+    const size_t dom = (size_t)4 << po2;
+    BX_REQUIRE(c, check.len == 4 * dom && code_eval.len == dom * w_code && data_eval.len == dom * w_data && accum_eval.len == dom * w_accum,
+               "bx_cons_program_eval_check: buffer size mismatch (check 16N, groups 4N x width)");
+    const uint32_t widths[3] = {w_code, w_data, w_accum};
+    for (int g = 0; g < 3; ++g)
+        if (dev->max_col[g] > widths[g]) {
+            snprintf(c->err, sizeof c->err, "bx_cons_program_eval_check: the program taps column %u of group %d, which has %u columns", dev->max_col[g] - 1, g, widths[g]);
+            return c->err;
+        }
+    const uint32_t ng = dev->info.n_globals;
+    if (n_globals < ng || (ng && !globals)) {
+        snprintf(c->err, sizeof c->err, "bx_cons_program_eval_check: %u globals given, the program needs %u", globals ? n_globals : 0u, ng);
+        return c->err;
+    }
+    uint32_t dyn[BX_MAX_GLOBALS + 4];
+    for (uint32_t k = 0; k < ng; ++k) dyn[k] = globals[k];
+    for (uint32_t k = 0; k < 4; ++k) dyn[ng + k] = mix[k];
+    BX_TRY(h2d_staged(c, dev->scal.slice(0, ng + 4), dyn, ng + 4));
+    BX_TRY(mix_power_table(c, dev->mixpows.b, poly_mix, dev->n_pows));
+    ConsLaunch L;
+    vanishing_inverses(po2, L.zinv);
+    L.dom = (uint32_t)dom;
+    L.n_fetch = dev->n_fetch;
+    L.n_narrow = dev->info.narrow;
+    L.ret_slot = dev->ret_slot;
+    // every tap is read once, four planes are written
+    OpScope op(c, "cons_program_eval_check", 4.0 * (double)dom * ((double)dev->info.taps + 4.0));
+    hipLaunchKernelGGL(cons_program_kernel, dim3((unsigned)((dom + CP_LANES - 1) / CP_LANES)), dim3(CP_LANES), dev->lds, c->stream, (uint32_t*)check.dptr,
+                       (const uint32_t*)code_eval.dptr, (const uint32_t*)data_eval.dptr, (const uint32_t*)accum_eval.dptr, (const uint4*)dev->code.b.dptr,
+                       (const uint2*)dev->taps.b.dptr, (const uint32_t*)dev->scal.b.dptr, (const uint32_t*)dev->mixpows.b.dptr, L);
+    BX_LAUNCH_CHECK(c);
+    return nullptr;
+} BX_ABI_CATCH(c, "bx_cons_program_eval_check")
+
+// ---------------------------------------------------------------------------------------------------------------------
+// a bx_circuit_ops made of a program (taps, eval_check, constraints_at) and a base table (everything else)
+// ---------------------------------------------------------------------------------------------------------------------
+struct bx_cons_circuit {
+    bx_circuit_ops ops{};
+    const bx_circuit_ops* base = nullptr;
+    const bx_cons_program* prog = nullptr;
+};
+
+namespace bx {
+namespace {
+struct ConsState {
+    void* base_state = nullptr;
+    bx_cons_program_dev* dev = nullptr;
+    bx_segment_params shape{};
+    uint32_t n_globals = 0;
+};
+const char* cc_normalize(void* u, bx_segment_params* shape) {
+    const bx_circuit_ops* b = ((bx_cons_circuit*)u)->base;
+    return b->normalize ? b->normalize(b->user, shape) : nullptr;
+}
+uint32_t cc_taps(void* u, const bx_segment_params*, int group, uint32_t col, uint32_t* backs_out) {
+    return bx_cons_program_taps(((bx_cons_circuit*)u)->prog, group, col, backs_out);
+}
+uint32_t cc_n_globals(void* u, const bx_segment_params* shape) {
+    const bx_circuit_ops* b = ((bx_cons_circuit*)u)->base;
+    return b->n_globals ? b->n_globals(b->user, shape) : 0;
+}
+void cc_destroy(void* u, void* state) {
+    const bx_circuit_ops* b = ((bx_cons_circuit*)u)->base;
+    ConsState* st = (ConsState*)state;
+    if (!st) return;
+    (void)bx_cons_program_unload(st->dev);
+    if (st->base_state && b->destroy) b->destroy(b->user, st->base_state);
+    delete st;
+}
+const char* cc_create(void* u, bx_ctx* c, const bx_segment_params* shape, void** state) {
+    bx_cons_circuit* cc = (bx_cons_circuit*)u;
+    const bx_circuit_ops* b = cc->base;
+    const uint32_t widths[3] = {shape->w_code, shape->w_data, shape->w_accum};
+    for (int g = 0; g < 3; ++g)
+        if (cc->prog->max_col[g] > widths[g]) {
+            snprintf(c->err, sizeof c->err, "cons circuit: the program taps column %u of group %d, the shape has %u columns there", cc->prog->max_col[g] - 1, g, widths[g]);
+            return c->err;
+        }
+    const uint32_t ng = cc_n_globals(u, shape);
+    if (ng != cc->prog->info.n_globals) {
+        snprintf(c->err, sizeof c->err, "cons circuit: the program has %u globals, the base circuit %u", cc->prog->info.n_globals, ng);
+        return c->err;
+    }
+    std::unique_ptr<ConsState> st(new (std::nothrow) ConsState());
+    BX_REQUIRE(c, st != nullptr, "cons circuit: out of host memory");
+    st->shape = *shape;
+    st->n_globals = ng;
+    BX_TRY(bx_cons_program_load(c, cc->prog, &st->dev));
+    if (b->create)
+        if (const char* e = b->create(b->user, c, shape, &st->base_state)) {
+            const char* kept = e == c->err ? e : set_msg(c, e);
+            (void)bx_cons_program_unload(st->dev);
+            return kept;
+        }
+    *state = st.release();
+    return nullptr;
+}
+const char* cc_code_group(void* u, void* state, bx_ctx* c, bx_buf code) {
+    const bx_circuit_ops* b = ((bx_cons_circuit*)u)->base;
+    BX_REQUIRE(c, b->code_group != nullptr, "cons circuit: the base circuit has no code_group");
+    return b->code_group(b->user, ((ConsState*)state)->base_state, c, code);
+}
+const char* cc_witgen(void* u, void* state, bx_ctx* c, bx_buf code, bx_buf data, const uint8_t* segment, size_t segment_len, bx_buf segment_dev,
+                      uint32_t* globals_out) {
+    const bx_circuit_ops* b = ((bx_cons_circuit*)u)->base;
+    BX_REQUIRE(c, b->witgen != nullptr, "cons circuit: the base circuit has no witgen");
+    return b->witgen(b->user, ((ConsState*)state)->base_state, c, code, data, segment, segment_len, segment_dev, globals_out);
+}
+const char* cc_accumulate(void* u, void* state, bx_ctx* c, bx_buf accum, const uint32_t mix[4]) {
+    const bx_circuit_ops* b = ((bx_cons_circuit*)u)->base;
+    BX_REQUIRE(c, b->accumulate != nullptr, "cons circuit: the base circuit has no accumulate");
+    return b->accumulate(b->user, ((ConsState*)state)->base_state, c, accum, mix);
+}
+const char* cc_eval_check(void*, void* state, bx_ctx* c, bx_buf check, bx_buf ecode, bx_buf edata, bx_buf eacc, const uint32_t poly_mix[4], const uint32_t mix[4],
+                          const uint32_t* globals) {
+    const ConsState* st = (const ConsState*)state;
+    return bx_cons_program_eval_check(c, st->dev, st->shape.po2, check, ecode, st->shape.w_code, edata, st->shape.w_data, eacc, st->shape.w_accum, poly_mix, mix,
+                                      globals, st->n_globals);
+}
+const char* cc_constraints_at(void* u, const bx_segment_params*, const bx_tap_reader* taps, const uint32_t poly_mix[4], const uint32_t mix[4],
+                              const uint32_t* globals, uint32_t out[4]) {
+    return bx_cons_program_constraints_at(((bx_cons_circuit*)u)->prog, taps, poly_mix, mix, globals, out);
+}
+void cc_set_noise_seed(void* u, void* state, uint64_t noise_seed) {
+    const bx_circuit_ops* b = ((bx_cons_circuit*)u)->base;
+    b->set_noise_seed(b->user, ((ConsState*)state)->base_state, noise_seed);
+}
+const char* cc_check_code(void* u, const bx_segment_params* shape, const uint32_t root[8]) {
+    const bx_circuit_ops* b = ((bx_cons_circuit*)u)->base;
+    return b->check_code(b->user, shape, root);
+}
+}  // namespace
+}  // namespace bx
+
+extern "C" const char* bx_cons_circuit_create(const bx_circuit_ops* base, const bx_cons_program* prog, bx_cons_circuit** out) try {
+    if (!base || !prog || !out) return "bx_cons_circuit_create: null argument";
+    bx_cons_circuit* cc = new bx_cons_circuit();
+    cc->base = base;
+    cc->prog = prog;
+    // the optional members stay NULL when the base has none: a table without check_code verifies only against an explicit context
+    cc->ops = bx_circuit_ops{cc,
+                             "bx-cons-program",
+                             bx::cc_normalize,
+                             bx::cc_taps,
+                             bx::cc_n_globals,
+                             bx::cc_create,
+                             bx::cc_destroy,
+                             bx::cc_code_group,
+                             bx::cc_witgen,
+                             bx::cc_accumulate,
+                             bx::cc_eval_check,
+                             bx::cc_constraints_at,
+                             base->set_noise_seed ? bx::cc_set_noise_seed : nullptr,
+                             base->check_code ? bx::cc_check_code : nullptr};
+    *out = cc;
+    return nullptr;
+} catch (...) {
+    return "bx_cons_circuit_create: out of host memory";
+}
+extern "C" const bx_circuit_ops* bx_cons_circuit_ops(bx_cons_circuit* cc) { return cc ? &cc->ops : nullptr; }
+extern "C" void bx_cons_circuit_destroy(bx_cons_circuit* cc) { delete cc; }

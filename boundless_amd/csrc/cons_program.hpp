@@ -1,0 +1,60 @@
+// cons_program.hpp — the compiled form of a constraint program (include/bx_program.h is the normative text): ONE instruction
+// stream that the host executor (cons_program_host.cpp, the verifier's side) and the device kernel (cons_program.hip) both read.
+// Plain C++: the host half compiles without HIP.
+//
+// An instruction is two words:
+//   w0 = opcode | dst << 8 | a << 16 | b << 24      dst, a, b: slot numbers (narrow or wide, as the opcode says)
+//   w1 = c | imm << 8                               c: a third slot (AND_COND's inner); imm: table index (24 bits)
+// Values live in two slot files: NARROW (one word, a base value) and WIDE (four words: an ext value or the tot of a mix var).
+// dst may be a slot one of the sources is read from: an executor reads every source before it writes.
+// Tables: `scal` = [globals (n_globals) | mix (4) | constants]: Montgomery words; an ext constant takes four consecutive ones.
+//         `taps` = (col, back | group << 30) per entry of the program's tap list.
+//         mix powers poly_mix^e, e < n_pows, canonical (mix_power_table).
+// The stream is padded with NOPs to a multiple of CP_FETCH instructions: the kernel fetches that many at a time.
+#pragma once
+#include <stdint.h>
+
+#include <vector>
+
+#include "../../include/bx_program.h"
+
+namespace bx {
+
+enum ConsOpcode : uint32_t {
+    CP_NOP = 0,
+    CP_LD_B,     // narrow[dst] = scal[imm]
+    CP_LD_E,     // wide[dst] = scal[imm .. imm+3]
+    CP_TAP,      // narrow[dst] = tap imm
+    CP_ADD_BB,   // narrow[dst] = narrow[a] + narrow[b]
+    CP_SUB_BB,
+    CP_MUL_BB,
+    CP_ADD_EB,   // wide[dst] = wide[a] + narrow[b]
+    CP_SUB_EB,   // wide[dst] = wide[a] - narrow[b]
+    CP_SUB_BE,   // wide[dst] = narrow[a] - wide[b]
+    CP_MUL_EB,   // wide[dst] = wide[a] * narrow[b]
+    CP_ADD_EE,   // wide[dst] = wide[a] + wide[b]
+    CP_SUB_EE,
+    CP_MUL_EE,
+    CP_ZERO,     // wide[dst] = 0                                                    (TRUE)
+    CP_EQZ_B,    // wide[dst] = wide[a] + pow[imm] * narrow[b]                       (AND_EQZ, base y)
+    CP_EQZ_E,    // wide[dst] = wide[a] + pow[imm] * wide[b]                         (AND_EQZ, ext y)
+    CP_COND_B,   // wide[dst] = wide[a] + (pow[imm] * wide[c]) * narrow[b]           (AND_COND, base cond)
+    CP_COND_E,   // wide[dst] = wide[a] + (pow[imm] * wide[c]) * wide[b]             (AND_COND, ext cond)
+    CP_OPCODES
+};
+constexpr uint32_t CP_FETCH = 4;  // instructions per fetch of the kernel (8 dwords)
+
+inline uint32_t cp_w0(uint32_t op, uint32_t dst, uint32_t a, uint32_t b) { return op | dst << 8 | a << 16 | b << 24; }
+inline uint32_t cp_w1(uint32_t c, uint32_t imm) { return c | imm << 8; }
+
+}  // namespace bx
+
+struct bx_cons_program {
+    bx_cons_program_info info{};
+    std::vector<uint32_t> code;    // 2 words per instruction, padded to CP_FETCH instructions
+    std::vector<uint32_t> consts;  // Montgomery words: the tail of `scal`
+    std::vector<bx_cons_tap> taps;
+    uint32_t n_pows = 1;           // mix powers the stream names (at least 1: a table is never empty)
+    uint32_t ret_slot = 0;         // the wide slot that holds mix[ret].tot at the end
+    uint32_t max_col[3] = {0, 0, 0};  // 1 + the largest tap column per group (0 = the group is not named)
+};

@@ -1,0 +1,375 @@
+// cons_program_host.cpp — host half of constraint programs (include/bx_program.h is the normative text): the compiler from a step list
+// to the instruction stream of cons_program.hpp, and the host executor of that stream over Fp4 (the verifier's constraints_at).
+// No HIP: this translation unit compiles with plain g++ (tests/cons_program_check.cpp runs it under sanitizers).
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <map>
+#include <new>
+#include <set>
+#include <utility>
+
+#include "cons_program.hpp"
+#include "fp.hpp"
+
+namespace bx {
+namespace {
+
+thread_local char g_msg[512];
+const char* refuse(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_msg, sizeof g_msg, fmt, ap);
+    va_end(ap);
+    return g_msg;
+}
+
+constexpr uint32_t NEVER = 0xFFFFFFFFu;
+
+struct FpVar {
+    bool ext = false;
+    uint32_t degree = 0, slot = 0, last_use = 0;  // last_use: the step that reads it last (its own step if none does)
+};
+struct MixVar {
+    uint32_t exp = 0, degree = 0, slot = 0, last_use = 0;
+};
+
+// a bounded slot file: the lowest free slot first, so that a program's footprint is its peak of live values
+struct SlotFile {
+    std::set<uint32_t> free_;
+    uint32_t top = 0, live = 0, peak = 0;
+    uint32_t take() {
+        ++live;
+        peak = std::max(peak, live);
+        if (!free_.empty()) {
+            const uint32_t s = *free_.begin();
+            free_.erase(free_.begin());
+            return s;
+        }
+        return top++;
+    }
+    void give(uint32_t s) {
+        --live;
+        free_.insert(s);
+    }
+};
+
+const char* compile(const bx_cons_program_desc* d, bx_cons_program* p) {
+    if (d->n_steps > BX_CONS_MAX_STEPS) return refuse("cons_program: %zu steps, more than BX_CONS_MAX_STEPS = %d", d->n_steps, BX_CONS_MAX_STEPS);
+    if (d->n_taps > BX_CONS_MAX_TAPS) return refuse("cons_program: %zu taps, more than BX_CONS_MAX_TAPS = %d", d->n_taps, BX_CONS_MAX_TAPS);
+    if (d->n_globals > BX_MAX_GLOBALS) return refuse("cons_program: n_globals %u is above BX_MAX_GLOBALS = %d", d->n_globals, BX_MAX_GLOBALS);
+    if ((d->n_steps && !d->steps) || (d->n_taps && !d->taps)) return refuse("cons_program: null step or tap list");
+
+    // ---- the tap list: ranges, and the tap set of every named column ----
+    std::map<std::pair<uint32_t, uint32_t>, std::set<uint32_t>> sets;
+    for (size_t t = 0; t < d->n_taps; ++t) {
+        const bx_cons_tap& tp = d->taps[t];
+        if (tp.group > 2) return refuse("cons_program: tap %zu: tap group %u out of range (0 code, 1 data, 2 accum)", t, tp.group);
+        if (tp.col > BX_CONS_MAX_COL) return refuse("cons_program: tap %zu: tap column %u out of range (at most %d)", t, tp.col, BX_CONS_MAX_COL);
+        if (tp.back > BX_CONS_MAX_BACK) return refuse("cons_program: tap %zu: tap back %u out of range (at most %d)", t, tp.back, BX_CONS_MAX_BACK);
+        std::set<uint32_t>& s = sets[{tp.group, tp.col}];
+        s.insert(0u);
+        s.insert(tp.back);
+        if (s.size() > BX_MAX_TAPS)
+            return refuse("cons_program: tap %zu: more than BX_MAX_TAPS = %d distinct backs on column %u of group %u", t, BX_MAX_TAPS, tp.col, tp.group);
+        p->max_col[tp.group] = std::max(p->max_col[tp.group], tp.col + 1);
+    }
+    p->taps.assign(d->taps, d->taps + d->n_taps);
+
+    // ---- pass 1: validation, types, mix exponents, degrees, last uses ----
+    std::vector<FpVar> fp;
+    std::vector<MixVar> mix;
+    std::vector<uint32_t> var_of(d->n_steps);  // step -> its var's index in its list
+    const auto use_fp = [&](size_t i, const char* what, uint32_t v) -> const char* {
+        if (v >= fp.size()) return refuse("cons_program: step %zu: operand %s = %u refers to a later or missing fp var (%zu so far)", i, what, v, fp.size());
+        fp[v].last_use = (uint32_t)i;
+        return nullptr;
+    };
+    const auto use_mix = [&](size_t i, const char* what, uint32_t v) -> const char* {
+        if (v >= mix.size()) return refuse("cons_program: step %zu: operand %s = %u refers to a later or missing mix var (%zu so far)", i, what, v, mix.size());
+        mix[v].last_use = (uint32_t)i;
+        return nullptr;
+    };
+#define CP_TRY(expr)                 \
+    do {                             \
+        const char* _m = (expr);     \
+        if (_m) return _m;           \
+    } while (0)
+    for (size_t i = 0; i < d->n_steps; ++i) {
+        const bx_cons_step& s = d->steps[i];
+        FpVar f;
+        MixVar m;
+        f.last_use = m.last_use = (uint32_t)i;
+        bool is_mix = false;
+        switch (s.op) {
+        case BX_CONS_CONST:
+            if (s.a >= P) return refuse("cons_program: step %zu: constant %u is not below P", i, s.a);
+            break;
+        case BX_CONS_CONST_EXT:
+            if (s.a >= P || s.b >= P || s.c >= P || s.d >= P) return refuse("cons_program: step %zu: ext constant (%u, %u, %u, %u) has a component not below P", i, s.a, s.b, s.c, s.d);
+            f.ext = true;
+            break;
+        case BX_CONS_GET:
+            if (s.a >= d->n_taps) return refuse("cons_program: step %zu: tap index %u out of range (%zu taps)", i, s.a, d->n_taps);
+            f.degree = 1;
+            break;
+        case BX_CONS_GET_GLOBAL:
+            if (s.a > 1) return refuse("cons_program: step %zu: GET_GLOBAL table %u out of range (0 globals, 1 mix)", i, s.a);
+            if (s.a == 0 && s.b >= d->n_globals) return refuse("cons_program: step %zu: global index %u out of range (%u globals)", i, s.b, d->n_globals);
+            if (s.a == 1 && s.b >= 4) return refuse("cons_program: step %zu: mix component %u out of range (an ext element has 4)", i, s.b);
+            break;
+        case BX_CONS_ADD:
+        case BX_CONS_SUB:
+        case BX_CONS_MUL:
+            CP_TRY(use_fp(i, "a", s.a));
+            CP_TRY(use_fp(i, "b", s.b));
+            f.ext = fp[s.a].ext || fp[s.b].ext;
+            f.degree = s.op == BX_CONS_MUL ? fp[s.a].degree + fp[s.b].degree : std::max(fp[s.a].degree, fp[s.b].degree);
+            break;
+        case BX_CONS_TRUE:
+            is_mix = true;
+            break;
+        case BX_CONS_AND_EQZ:
+            is_mix = true;
+            CP_TRY(use_mix(i, "a", s.a));
+            CP_TRY(use_fp(i, "b", s.b));
+            m.exp = mix[s.a].exp + 1;
+            m.degree = std::max(mix[s.a].degree, fp[s.b].degree);
+            break;
+        case BX_CONS_AND_COND:
+            is_mix = true;
+            CP_TRY(use_mix(i, "a", s.a));
+            CP_TRY(use_fp(i, "b", s.b));
+            CP_TRY(use_mix(i, "c", s.c));
+            m.exp = mix[s.a].exp + mix[s.c].exp;
+            m.degree = std::max(mix[s.a].degree, fp[s.b].degree + mix[s.c].degree);
+            break;
+        default:
+            return refuse("cons_program: step %zu: unknown op %u", i, s.op);
+        }
+        const uint32_t deg = is_mix ? m.degree : f.degree;
+        if (deg > BX_CONS_MAX_DEGREE)
+            return refuse("cons_program: step %zu: degree %u is above BX_CONS_MAX_DEGREE = %d (the quotient would not fit the 4N check evaluations)", i, deg, BX_CONS_MAX_DEGREE);
+        if (is_mix && m.exp > BX_CONS_MAX_STEPS) return refuse("cons_program: step %zu: %u constraints, more than BX_CONS_MAX_STEPS = %d", i, m.exp, BX_CONS_MAX_STEPS);
+        if (is_mix) {
+            var_of[i] = (uint32_t)mix.size();
+            mix.push_back(m);
+        } else {
+            var_of[i] = (uint32_t)fp.size();
+            fp.push_back(f);
+        }
+    }
+    if (d->ret >= mix.size()) return refuse("cons_program: ret = %u is not a mix var (%zu mix vars)", d->ret, mix.size());
+    mix[d->ret].last_use = NEVER;
+
+    // ---- pass 2: slots by last use, and the stream ----
+    SlotFile narrow, wide;
+    const uint32_t scal_consts = d->n_globals + 4;  // where the constants start in `scal`
+    uint32_t n_pows = 1;
+    const auto emit = [&](uint32_t op, uint32_t dst, uint32_t a, uint32_t b, uint32_t c, uint32_t imm) {
+        p->code.push_back(cp_w0(op, dst, a, b));
+        p->code.push_back(cp_w1(c, imm));
+    };
+    uint32_t fi = 0, mi = 0;
+    for (size_t i = 0; i < d->n_steps; ++i) {
+        const bx_cons_step& s = d->steps[i];
+        const uint32_t step = (uint32_t)i;
+        // operands that die here give their slots back BEFORE the result takes one (dst may alias a source: executors read first)
+        const auto drop_fp = [&](uint32_t v) {
+            if (fp[v].last_use == step) {
+                (fp[v].ext ? wide : narrow).give(fp[v].slot);
+                fp[v].last_use = NEVER - 1;  // an operand named twice is dropped once
+            }
+        };
+        const auto drop_mix = [&](uint32_t v) {
+            if (mix[v].last_use == step) {
+                wide.give(mix[v].slot);
+                mix[v].last_use = NEVER - 1;
+            }
+        };
+        const bool is_mix = s.op >= BX_CONS_TRUE;
+        uint32_t dst = 0;
+        if (!is_mix) {
+            FpVar& f = fp[fi];
+            const bool unused = f.last_use == step;
+            uint32_t sa = 0, sb = 0;
+            bool ea = false, eb = false;
+            if (s.op >= BX_CONS_ADD) {
+                sa = fp[s.a].slot, sb = fp[s.b].slot, ea = fp[s.a].ext, eb = fp[s.b].ext;
+                drop_fp(s.a);
+                drop_fp(s.b);
+            }
+            dst = f.slot = (f.ext ? wide : narrow).take();
+            switch (s.op) {
+            case BX_CONS_CONST:
+                emit(CP_LD_B, dst, 0, 0, 0, scal_consts + (uint32_t)p->consts.size());
+                p->consts.push_back(fp_encode(s.a));
+                break;
+            case BX_CONS_CONST_EXT:
+                emit(CP_LD_E, dst, 0, 0, 0, scal_consts + (uint32_t)p->consts.size());
+                for (uint32_t v : {s.a, s.b, s.c, s.d}) p->consts.push_back(fp_encode(v));
+                break;
+            case BX_CONS_GET:
+                emit(CP_TAP, dst, 0, 0, 0, s.a);
+                break;
+            case BX_CONS_GET_GLOBAL:
+                emit(CP_LD_B, dst, 0, 0, 0, s.a == 0 ? s.b : d->n_globals + s.b);
+                break;
+            case BX_CONS_ADD:
+            case BX_CONS_MUL:
+                if (!ea && !eb) emit(s.op == BX_CONS_ADD ? CP_ADD_BB : CP_MUL_BB, dst, sa, sb, 0, 0);
+                else if (ea && eb) emit(s.op == BX_CONS_ADD ? CP_ADD_EE : CP_MUL_EE, dst, sa, sb, 0, 0);
+                else emit(s.op == BX_CONS_ADD ? CP_ADD_EB : CP_MUL_EB, dst, ea ? sa : sb, ea ? sb : sa, 0, 0);  // commutative: ext first
+                break;
+            default:  // BX_CONS_SUB
+                emit(!ea && !eb ? CP_SUB_BB : (ea && eb ? CP_SUB_EE : (ea ? CP_SUB_EB : CP_SUB_BE)), dst, sa, sb, 0, 0);
+                break;
+            }
+            if (unused) (f.ext ? wide : narrow).give(dst);
+            ++fi;
+        } else {
+            MixVar& m = mix[mi];
+            const bool unused = m.last_use == step;
+            if (s.op == BX_CONS_TRUE) {
+                dst = m.slot = wide.take();
+                emit(CP_ZERO, dst, 0, 0, 0, 0);
+            } else {
+                const uint32_t sx = mix[s.a].slot, sy = fp[s.b].slot, e = mix[s.a].exp;
+                const bool ey = fp[s.b].ext;
+                const uint32_t sc = s.op == BX_CONS_AND_COND ? mix[s.c].slot : 0u;
+                drop_mix(s.a);
+                drop_fp(s.b);
+                if (s.op == BX_CONS_AND_COND) drop_mix(s.c);
+                dst = m.slot = wide.take();
+                if (s.op == BX_CONS_AND_EQZ) emit(ey ? CP_EQZ_E : CP_EQZ_B, dst, sx, sy, 0, e);
+                else emit(ey ? CP_COND_E : CP_COND_B, dst, sx, sy, sc, e);
+                n_pows = std::max(n_pows, e + 1);
+            }
+            if (unused) wide.give(dst);
+            ++mi;
+        }
+        if (narrow.peak > BX_CONS_MAX_NARROW || wide.peak > BX_CONS_MAX_WIDE) {
+            const bool nw = narrow.peak > BX_CONS_MAX_NARROW;
+            return refuse("cons_program: step %zu: the program needs %u live %s values, the limit is %d (BX_CONS_MAX_%s)", i, nw ? narrow.peak : wide.peak,
+                          nw ? "narrow (base)" : "wide (ext and mix)", nw ? BX_CONS_MAX_NARROW : BX_CONS_MAX_WIDE, nw ? "NARROW" : "WIDE");
+        }
+    }
+#undef CP_TRY
+    p->info.steps = (uint32_t)d->n_steps;
+    p->info.constraints = mix[d->ret].exp;
+    p->info.degree = mix[d->ret].degree;
+    p->info.narrow = narrow.top;
+    p->info.wide = wide.top;
+    p->info.instructions = (uint32_t)(p->code.size() / 2);
+    p->info.taps = (uint32_t)d->n_taps;
+    p->info.n_globals = d->n_globals;
+    p->n_pows = n_pows;
+    p->ret_slot = mix[d->ret].slot;
+    while ((p->code.size() / 2) % CP_FETCH) emit(CP_NOP, 0, 0, 0, 0, 0);
+    return nullptr;
+}
+
+}  // namespace
+}  // namespace bx
+
+extern "C" const char* bx_cons_program_create(const bx_cons_program_desc* desc, bx_cons_program** out) try {
+    if (!desc || !out) return "bx_cons_program_create: null argument";
+    *out = nullptr;
+    bx_cons_program* p = new bx_cons_program();
+    if (const char* e = bx::compile(desc, p)) {
+        delete p;
+        return e;
+    }
+    *out = p;
+    return nullptr;
+} catch (...) {
+    return "bx_cons_program_create: out of host memory";
+}
+
+extern "C" void bx_cons_program_destroy(bx_cons_program* prog) { delete prog; }
+
+extern "C" const char* bx_cons_program_info_get(const bx_cons_program* prog, bx_cons_program_info* out) {
+    if (!prog || !out) return "bx_cons_program_info_get: null argument";
+    *out = prog->info;
+    return nullptr;
+}
+
+extern "C" uint32_t bx_cons_program_taps(const bx_cons_program* prog, int group, uint32_t col, uint32_t backs_out[BX_MAX_TAPS]) {
+    uint32_t n = 0;
+    backs_out[n++] = 0;
+    if (!prog) return n;
+    // at most BX_MAX_TAPS distinct values by construction (create refuses a ninth); insertion keeps them sorted
+    for (const bx_cons_tap& t : prog->taps) {
+        if ((int)t.group != group || t.col != col) continue;
+        uint32_t k = 0;
+        while (k < n && backs_out[k] < t.back) ++k;
+        if (k < n && backs_out[k] == t.back) continue;
+        for (uint32_t j = n; j > k; --j) backs_out[j] = backs_out[j - 1];
+        backs_out[k] = t.back;
+        ++n;
+    }
+    return n;
+}
+
+extern "C" const char* bx_cons_program_constraints_at(const bx_cons_program* prog, const bx_tap_reader* taps, const uint32_t poly_mix[4], const uint32_t mix[4],
+                                                      const uint32_t* globals, uint32_t out[4]) try {
+    using namespace bx;
+    if (!prog || !taps || !taps->at || !poly_mix || !mix || !out) return "bx_cons_program_constraints_at: null argument";
+    if (prog->info.n_globals && !globals) return "bx_cons_program_constraints_at: the program names globals and none were given";
+    const uint32_t ng = prog->info.n_globals;
+    std::vector<uint32_t> scal(ng + 4 + prog->consts.size());
+    for (uint32_t i = 0; i < ng; ++i) scal[i] = globals[i];
+    for (uint32_t i = 0; i < 4; ++i) scal[ng + i] = mix[i];
+    std::copy(prog->consts.begin(), prog->consts.end(), scal.begin() + ng + 4);
+    std::vector<Fp4> pows(prog->n_pows);
+    const Fp4 pm{{poly_mix[0], poly_mix[1], poly_mix[2], poly_mix[3]}};
+    pows[0] = f4_one();
+    for (uint32_t e = 1; e < prog->n_pows; ++e) pows[e] = f4_mul(pows[e - 1], pm);
+    // on the verifier every value is ext: the narrow file holds Fp4 too
+    Fp4 nar[BX_CONS_MAX_NARROW], wid[BX_CONS_MAX_WIDE];
+    for (Fp4& v : nar) v = f4_zero();
+    for (Fp4& v : wid) v = f4_zero();
+    const char* err = nullptr;
+    const auto base = [](uint32_t w) { return Fp4{{w, 0u, 0u, 0u}}; };
+    for (size_t pc = 0; pc < prog->code.size(); pc += 2) {
+        const uint32_t w0 = prog->code[pc], w1 = prog->code[pc + 1];
+        const uint32_t op = w0 & 0xFFu, dst = (w0 >> 8) & 0xFFu, a = (w0 >> 16) & 0xFFu, b = w0 >> 24, c = w1 & 0xFFu, imm = w1 >> 8;
+        switch (op) {
+        case CP_NOP: break;
+        case CP_LD_B: nar[dst] = base(scal[imm]); break;
+        case CP_LD_E: wid[dst] = Fp4{{scal[imm], scal[imm + 1], scal[imm + 2], scal[imm + 3]}}; break;
+        case CP_TAP: {
+            const bx_cons_tap& t = prog->taps[imm];
+            Fp4 v = f4_zero();
+            if (const char* e = taps->at(taps->ctx, (int)t.group, t.col, (int)t.back, v.c)) {
+                err = e;
+                v = f4_zero();
+            }
+            nar[dst] = v;
+            break;
+        }
+        case CP_ADD_BB: nar[dst] = f4_add(nar[a], nar[b]); break;
+        case CP_SUB_BB: nar[dst] = f4_sub(nar[a], nar[b]); break;
+        case CP_MUL_BB: nar[dst] = f4_mul(nar[a], nar[b]); break;
+        case CP_ADD_EB: wid[dst] = f4_add(wid[a], nar[b]); break;
+        case CP_SUB_EB: wid[dst] = f4_sub(wid[a], nar[b]); break;
+        case CP_SUB_BE: wid[dst] = f4_sub(nar[a], wid[b]); break;
+        case CP_MUL_EB: wid[dst] = f4_mul(wid[a], nar[b]); break;
+        case CP_ADD_EE: wid[dst] = f4_add(wid[a], wid[b]); break;
+        case CP_SUB_EE: wid[dst] = f4_sub(wid[a], wid[b]); break;
+        case CP_MUL_EE: wid[dst] = f4_mul(wid[a], wid[b]); break;
+        case CP_ZERO: wid[dst] = f4_zero(); break;
+        case CP_EQZ_B: wid[dst] = f4_add(wid[a], f4_mul(pows[imm], nar[b])); break;
+        case CP_EQZ_E: wid[dst] = f4_add(wid[a], f4_mul(pows[imm], wid[b])); break;
+        case CP_COND_B: wid[dst] = f4_add(wid[a], f4_mul(f4_mul(pows[imm], wid[c]), nar[b])); break;
+        case CP_COND_E: wid[dst] = f4_add(wid[a], f4_mul(f4_mul(pows[imm], wid[c]), wid[b])); break;
+        default: return "bx_cons_program_constraints_at: corrupt instruction stream";
+        }
+    }
+    memcpy(out, wid[prog->ret_slot].c, 16);
+    return err;
+} catch (...) {
+    return "bx_cons_program_constraints_at: out of host memory";
+}

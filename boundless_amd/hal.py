@@ -320,6 +320,15 @@ class HipHal:
         _, m = _words(mix)
         self._check(self.lib.bx_mix_poly_coeffs(self.ctx, output.raw, ms, m, inp.raw, combos.raw, input_size, count))
 
+    def cons_program_eval_check(self, loaded, po2, check, code_eval, data_eval, accum_eval, widths, poly_mix, mix, globals_=()):
+        """A constraint program's eval_check (include/bx_program.h: bx_cons_program_eval_check): `loaded` = a program loaded on this
+        hal (boundless_amd.circuit.CompiledConsProgram.load); widths = (w_code, w_data, w_accum) of the three 4N x width evaluations."""
+        _, pm = _words(poly_mix)
+        _, m = _words(mix)
+        g, gp = _words(list(globals_) or [0])
+        self._check(loaded.program.lib.bx_cons_program_eval_check(self.ctx, loaded.dev, po2, check.raw, code_eval.raw, widths[0], data_eval.raw, widths[1],
+                                                                  accum_eval.raw, widths[2], pm, m, gp, len(globals_)))
+
     def batch_evaluate_any(self, coeffs, poly_count, which, xs, out):
         self._check(self.lib.bx_batch_evaluate_any(self.ctx, coeffs.raw, poly_count, which.raw, xs.raw, out.raw))
 

@@ -1,0 +1,167 @@
+/*
+ * bx_program.h — constraint programs: a circuit's constraints as DATA.  One description gives both halves a bx_circuit_ops
+ * table needs of them: `eval_check` (a gfx950 kernel that interprets the program over the 4N domain) and `constraints_at` (a
+ * host interpreter for the verifier), plus the tap sets.  No device code is written per circuit.
+ *
+ * Where this comes from
+ * ---------------------
+ * Upstream's circuits (rv32im, recursion, keccak) ship their constraints as a `PolyExtStepDef`: a flat list of steps (`Const`,
+ * `ConstExt`, `Get`, `GetGlobal`, `Add`, `Sub`, `Mul`, `True`, `AndEqz`, `AndCond`) and a return index, interpreted by the
+ * verifier's `poly_ext` [EXT: risc0-zkp, recalled; not in the reference tree].  RECALLED AND UNVERIFIED: the step names, the two
+ * separately numbered var lists, the operand order of AndEqz / AndCond and their (tot, mul) update rules, and GetGlobal's split
+ * into a "global" and a "mix" table.  THE TEXT BELOW, not upstream's, is normative here; an upstream table is translated to
+ * it, and any difference found on re-verification is a change to the translator, not to this header.
+ *
+ * Values (normative)
+ * ------------------
+ * A program is evaluated over a value field K: on the prover K = Fp at a domain point x = w_4N^row, on the verifier K = Fp4 at Z.
+ * There are two separately numbered lists.  fp vars hold values of K (or Fp4 on the prover once an ext constant flowed in); mix
+ * vars hold pairs (tot, mul) of Fp4.  Each step appends exactly one entry to exactly one list; operands name EARLIER entries.
+ *
+ *   step                appends  meaning
+ *   CONST a             fp       the field element a (canonical integer < P)
+ *   CONST_EXT a b c d   fp       the ext element a + b X + c X^2 + d X^3 (canonical integers < P)
+ *   GET a               fp       tap a of the program's tap list: (group 0 code / 1 data / 2 accum, col, back) = that column at
+ *                                x * w_N^-back; on the 4N domain this is row - 4 * back mod 4N
+ *   GET_GLOBAL a b      fp       a = 0: the public word globals[b];  a = 1: component b < 4 of accumulate's `mix`, as a BASE-field
+ *                                element (an ext challenge alpha is rebuilt as sum_k X^k * mix_k through CONST_EXT)
+ *   ADD a b, SUB a b, MUL a b    fp       fp[a] + fp[b], fp[a] - fp[b], fp[a] * fp[b]
+ *   TRUE                mix      (0, 1)
+ *   AND_EQZ a b         mix      x = mix[a], y = fp[b]:                   (x.tot + x.mul * y,  x.mul * poly_mix)
+ *   AND_COND a b c      mix      x = mix[a], cond = fp[b], inner = mix[c]: (x.tot + cond * inner.tot * x.mul,  x.mul * inner.mul)
+ *
+ * The result is mix[ret].tot.  A chain of AND_EQZ from TRUE is exactly sum_i poly_mix^i C_i.
+ *
+ * Compilation (bx_cons_program_create; host only, no ctx, no GPU)
+ * ---------------------------------------------------------------
+ *   validation   refused by name: an operand that names a later or missing var or the wrong list; a tap index, tap group, tap
+ *                back, global index or mix component out of range; a constant >= P; `ret` not a mix var; more than BX_MAX_TAPS
+ *                distinct backs on one column (0 always counts: every column is opened at Z); more than BX_CONS_MAX_STEPS steps.
+ *   types        on the prover an fp var is BASE unless a CONST_EXT flows into it; on the verifier everything is ext.  Every
+ *                arithmetic step is resolved to a base x base, ext x base or ext x ext opcode; the y of AND_EQZ and the cond of
+ *                AND_COND may be either.
+ *   mix powers   `mul` is always a statically known power of poly_mix: TRUE 0, AND_EQZ + 1, AND_COND + the inner's.  The
+ *                compiler resolves every x.mul to an index into a table of powers; no executor computes a mul.  The exponent
+ *                of `ret` is the program's constraint count.
+ *   degree       const and global 0, tap 1, add / sub max, mul sum, AND_EQZ max(x, y), AND_COND max(x, cond + inner).  The check
+ *                polynomial sum / ((3x)^N - 1) is committed as 4N evaluations: with columns of degree < N a sum of degree d has a
+ *                quotient of degree <= d (N - 1) - N, which is below 4N exactly for d <= BX_CONS_MAX_DEGREE = 5 — the bound
+ *                bx_prover.h already states for cons_degree.  A program above it is refused.
+ *   slots        values live in two bounded files, allocated by last use and reused when freed: NARROW slots (one word; base
+ *                values) and WIDE slots (four words; ext values and the tot of a mix var).  A program that needs more live values
+ *                than BX_CONS_MAX_NARROW / BX_CONS_MAX_WIDE is refused with the number it needs and the limit.  On the device a
+ *                narrow slot is 1 KiB and a wide slot 4 KiB of a workgroup's LDS: 32 + 4 * 24 = 128 KiB of the CU's 160.
+ *   output       ONE instruction stream, read by the host executor and by the device kernel alike.
+ */
+#ifndef BX_PROGRAM_H
+#define BX_PROGRAM_H
+#include "bx_circuit.h"
+#ifdef __cplusplus
+extern "C" {
+#endif
+#if defined(__GNUC__)
+#pragma GCC visibility push(default)
+#endif
+
+#define BX_CONS_MAX_STEPS 65536 /* steps of one program */
+#define BX_CONS_MAX_TAPS 4096   /* entries of a program's tap list */
+#define BX_CONS_MAX_BACK 65535  /* largest `back` of a tap */
+#define BX_CONS_MAX_COL 65535   /* largest column of a tap (group widths are below 65536) */
+#define BX_CONS_MAX_DEGREE 5    /* see "degree" above */
+#define BX_CONS_MAX_NARROW 32   /* live base values */
+#define BX_CONS_MAX_WIDE 24     /* live ext values and mix tots */
+
+enum bx_cons_op {
+    BX_CONS_CONST = 0,
+    BX_CONS_CONST_EXT = 1,
+    BX_CONS_GET = 2,
+    BX_CONS_GET_GLOBAL = 3,
+    BX_CONS_ADD = 4,
+    BX_CONS_SUB = 5,
+    BX_CONS_MUL = 6,
+    BX_CONS_TRUE = 7,
+    BX_CONS_AND_EQZ = 8,
+    BX_CONS_AND_COND = 9
+};
+
+/* one step: `op` and its operands in the order of the table above (unused operands are ignored) */
+typedef struct bx_cons_step {
+    uint32_t op;
+    uint32_t a, b, c, d;
+} bx_cons_step;
+
+typedef struct bx_cons_tap {
+    uint32_t group; /* 0 code, 1 data, 2 accum */
+    uint32_t col;
+    uint32_t back;
+} bx_cons_tap;
+
+typedef struct bx_cons_program_desc {
+    const bx_cons_step* steps;
+    size_t n_steps;
+    const bx_cons_tap* taps;
+    size_t n_taps;
+    uint32_t n_globals; /* public words the program may name: GET_GLOBAL 0 b needs b < n_globals <= BX_MAX_GLOBALS */
+    uint32_t ret;       /* the mix var whose tot is the result */
+} bx_cons_program_desc;
+
+typedef struct bx_cons_program_info {
+    uint32_t steps;
+    uint32_t constraints; /* the exponent of poly_mix at `ret` */
+    uint32_t degree;
+    uint32_t narrow; /* slots used */
+    uint32_t wide;
+    uint32_t instructions; /* of the compiled stream */
+    uint32_t taps;
+    uint32_t n_globals;
+} bx_cons_program_info;
+
+typedef struct bx_cons_program bx_cons_program;         /* a compiled program (host) */
+typedef struct bx_cons_program_dev bx_cons_program_dev; /* ... loaded on a ctx */
+typedef struct bx_cons_circuit bx_cons_circuit;         /* a bx_circuit_ops made of a program and a base table */
+
+/* Validates and compiles `desc` (nothing of it is referenced afterwards).  NULL = ok; the message of a refusal lives in a
+ * thread-local buffer until the calling thread's next refusal. */
+const char* bx_cons_program_create(const bx_cons_program_desc* desc, bx_cons_program** out);
+void bx_cons_program_destroy(bx_cons_program* prog);
+const char* bx_cons_program_info_get(const bx_cons_program* prog, bx_cons_program_info* out);
+/* The tap set of a column in the form bx_circuit_ops::taps wants: strictly increasing, backs_out[0] == 0, {0} for a column the
+ * program never names.  Returns the count, 1..BX_MAX_TAPS. */
+uint32_t bx_cons_program_taps(const bx_cons_program* prog, int group, uint32_t col, uint32_t backs_out[BX_MAX_TAPS]);
+
+/* Host executor (the verifier's side): the compiled stream over Fp4, tap values from `taps`.  `globals` holds the program's
+ * n_globals Montgomery words (may be NULL when that is 0).  A tap the reader refuses reads as zero, evaluation goes on and the
+ * reader's message is returned with the result.  No mutable global state: callable from several threads at once. */
+const char* bx_cons_program_constraints_at(const bx_cons_program* prog, const bx_tap_reader* taps, const uint32_t poly_mix[4], const uint32_t mix[4],
+                                           const uint32_t* globals, uint32_t out[4]);
+
+/* Uploads the stream, the constant table and the tap descriptors once.  bx_free releases what is still loaded on its ctx. */
+const char* bx_cons_program_load(bx_ctx* ctx, const bx_cons_program* prog, bx_cons_program_dev** out);
+const char* bx_cons_program_unload(bx_cons_program_dev* dev);
+/* The contract of bx_circuit_ops::eval_check: the four check planes (check.len = 16N) of result(x) / ((3x)^N - 1) over
+ * x = w_4N^row, N = 2^po2, po2 in [1, 24].  The three evaluation buffers are 4N x width column-major.  Refused: lengths that do not
+ * match, a tap column that is not below its group's width, n_globals below the program's.  `n_globals` is the length of `globals`
+ * (the table's eval_check has no such argument; it is here so that a short array is refused, not read past its end).
+ * Each call writes `globals`, `mix` and the powers of `poly_mix` into tables that belong to `dev`, on the ctx's stream: a loaded
+ * program serves one stream, its calls in order (a ctx has one stream, so that holds for every caller today).  To run one program
+ * from two ctxs, load it on each. */
+const char* bx_cons_program_eval_check(bx_ctx* ctx, bx_cons_program_dev* dev, uint32_t po2, bx_buf check, bx_buf code_eval, uint32_t w_code,
+                                       bx_buf data_eval, uint32_t w_data, bx_buf accum_eval, uint32_t w_accum, const uint32_t poly_mix[4],
+                                       const uint32_t mix[4], const uint32_t* globals, uint32_t n_globals);
+
+/* A bx_circuit_ops whose taps, eval_check and constraints_at come from `prog` and whose normalize, n_globals, create / destroy,
+ * code_group, witgen, accumulate, set_noise_seed and check_code are forwarded to `base` with base->user (base's own taps,
+ * eval_check and constraints_at may be NULL).  Its create loads the program on the ctx and checks it against the shape: tap
+ * columns within the widths, the program's n_globals equal to the base's.  `base` and `prog` must outlive the table, the table
+ * its provers.  It is a plug-in table: its code group is committed for every proof. */
+const char* bx_cons_circuit_create(const bx_circuit_ops* base, const bx_cons_program* prog, bx_cons_circuit** out);
+const bx_circuit_ops* bx_cons_circuit_ops(bx_cons_circuit* cc);
+void bx_cons_circuit_destroy(bx_cons_circuit* cc);
+
+#if defined(__GNUC__)
+#pragma GCC visibility pop
+#endif
+#ifdef __cplusplus
+}
+#endif
+#endif
