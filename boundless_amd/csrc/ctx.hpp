@@ -11,10 +11,9 @@
 
 #include "../../include/bx_hal.h"
 #include "fp.hpp"
+#include "ntt_plan.hpp"
 
 namespace bx {
-
-constexpr int TW_LOG = 13;  // stage-twiddle tables cover sub-transform sizes up to 2^13
 
 struct ProfRec {
     const char* name;
@@ -112,14 +111,7 @@ struct bx_ctx {
     size_t scratch_words = 0;
 
     // tunables
-    long ntt_block_log = 12;   // log2 of the contiguous-pass sub-transform (13 when the size needs it)
-    long ntt_tile_log = 14;    // log2 of the strided-pass LDS tile (elements)
-    long ntt_fast = 1;         // 1 = register-radix-16 passes (ntt_r16.hpp), 0 = one-stage-per-barrier v1 kernels
-    long ntt_tile_a_log = 12;  // log2 elements per pass-A workgroup (fast path)
-    long ntt_tile_b_log = 13;  // log2 elements per pass-B workgroup (fast path)
-    long ntt_cols_per_wg = 8;  // forward pass A (2^12 tiles): columns sharing one load of the tile's twist + twiddles
-    long ntt_group_cols = 0;   // forward transform: columns per pass-A + pass-B group (0 = all columns per pass)
-    long ntt_tile_b_wide = 1;  // grow the pass-B tile (up to 2^14) so that rows are at least 16 words wide
+    bx::NttTunables ntt;  // the ntt_* settings: what ntt_plan() reads (ntt_plan.hpp)
     long hash_rows_block = 256;
     long fold_deep = 2;              // large Merkle layers: up to this many levels per launch, depth first per lane (1 = one launch per layer)
     long dev_draws = 0;  // 1 = the prover draws the FRI challenges (which depend only on a Merkle root) on the device (bx_transcript_step): three blocking

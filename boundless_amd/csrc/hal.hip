@@ -684,29 +684,29 @@ extern "C" const char* bx_set_tunable(bx_ctx* c, const char* name, long value) t
     BX_REQUIRE(c, name != nullptr, "bx_set_tunable: null name");
     if (!strcmp(name, "ntt_block_log")) {
         BX_REQUIRE(c, value >= 1 && value <= TW_LOG, "ntt_block_log out of range [1,13]");
-        c->ntt_block_log = value;
+        c->ntt.block_log = value;
     } else if (!strcmp(name, "ntt_tile_log")) {
         BX_REQUIRE(c, value >= 6 && value <= 15, "ntt_tile_log out of range [6,15]");
-        c->ntt_tile_log = value;
+        c->ntt.tile_log = value;
     } else if (!strcmp(name, "hash_rows_block")) {
         BX_REQUIRE(c, value == 64 || value == 128 || value == 256, "hash_rows_block must be 64, 128 or 256");
         c->hash_rows_block = value;
     } else if (!strcmp(name, "ntt_fast")) {
-        c->ntt_fast = value != 0;
+        c->ntt.fast = value != 0;
     } else if (!strcmp(name, "ntt_tile_a_log")) {
         BX_REQUIRE(c, value >= 10 && value <= 13, "ntt_tile_a_log out of range [10,13]");
-        c->ntt_tile_a_log = value;
+        c->ntt.tile_a_log = value;
     } else if (!strcmp(name, "ntt_tile_b_log")) {
         BX_REQUIRE(c, value >= 10 && value <= 14, "ntt_tile_b_log out of range [10,14]");
-        c->ntt_tile_b_log = value;
+        c->ntt.tile_b_log = value;
     } else if (!strcmp(name, "ntt_cols_per_wg")) {
         BX_REQUIRE(c, value >= 1 && value <= 16, "ntt_cols_per_wg out of range [1,16]");
-        c->ntt_cols_per_wg = value;
+        c->ntt.cols_per_wg = value;
     } else if (!strcmp(name, "ntt_group_cols")) {
         BX_REQUIRE(c, value >= 0 && value <= 4096, "ntt_group_cols out of range [0,4096]");
-        c->ntt_group_cols = value;
+        c->ntt.group_cols = value;
     } else if (!strcmp(name, "ntt_tile_b_wide")) {
-        c->ntt_tile_b_wide = value != 0;
+        c->ntt.tile_b_wide = value != 0;
     } else if (!strcmp(name, "wait_spin_us")) {
         BX_REQUIRE(c, value >= 0 && value <= 10000, "wait_spin_us out of range [0, 10000]");
         c->wait_spin_us = value;

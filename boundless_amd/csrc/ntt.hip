@@ -19,6 +19,10 @@
 //   ntt_r16.hpp  (default) register-resident radix-16 steps, LDS only for regrouping — the fast path for tiles >= 2^10;
 //   this file    ntt_block_kernel / ntt_strided_kernel: one radix-2 stage per LDS round trip — the general fallback for
 //                small or unaligned shapes and unusual expand_bits (tunable ntt_fast = 0 forces it; both are tested).
+// Which family, compiled geometry and launch shape a pass takes is decided by ntt_plan() (ntt_plan.hpp, host-only) before the
+// first launch; the host half of this file executes plans.
+#include <utility>
+
 #include "ctx.hpp"
 #include "ntt_r16.hpp"
 
@@ -268,240 +272,124 @@ static const char* get_twist(bx_ctx* c, int m, int m_hi, bool inverse, uint32_t*
     return nullptr;
 }
 
-struct Split {
-    int m_hi, m_lo, lt;
-};
-static Split choose_split(bx_ctx* c, int m) {
-    Split sp;
-    int blk = (int)c->ntt_block_log;
-    if (blk > TW_LOG) blk = TW_LOG;
-    // sizes beyond 2^24 (segments of po2 23 / 24): a taller contiguous pass keeps the strided pass at <= 2^12 rows where it can,
-    // i.e. its LDS tile (<= 2^14 elements) at least four positions wide (measured: po2 23 proof 0.44 -> 0.38 s)
-    if (m - blk > 12 && blk < TW_LOG) blk = m - 12 < TW_LOG ? m - 12 : TW_LOG;
-    if (m <= blk) {
-        sp.m_hi = m;
-        sp.m_lo = 0;
-        sp.lt = 0;
-        return sp;
-    }
-    sp.m_hi = blk;
-    sp.m_lo = m - blk;
-    if (sp.m_lo > TW_LOG) {  // > 2^26: not reachable for BabyBear segment sizes, guarded by the callers
-        sp.m_lo = TW_LOG;
-        sp.m_hi = m - TW_LOG;
-    }
-    int tile = (int)c->ntt_tile_log;
-    if (tile < sp.m_lo) tile = sp.m_lo;
-    sp.lt = tile - sp.m_lo;
-    if (sp.lt > sp.m_hi) sp.lt = sp.m_hi;
-    return sp;
-}
-
 template <typename K>
 static const char* allow_lds(bx_ctx* c, K kernel, size_t bytes) {
     if (bytes > 64 * 1024) BX_HIP(c, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return nullptr;
 }
 
-// forward transform of `count` columns: in (size M >> expand_bits per column) -> out (size M per column).
-// ---- register-radix-16 fast path (ntt_r16.hpp) -------------------------------------------------------------
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-template <bool INV, bool PASS_A, int SKIP, int LR, int LT, int MAXT = 512>
-static const char* launch_r16_geom(bx_ctx* c, R16Args a, size_t count) {
-    uint32_t tile_elems = 1u << (a.lrows + a.lt);
-    size_t lds = ((size_t)tile_elems + (tile_elems >> 4)) * 4;
-    a.cols = (uint32_t)count;
-    BX_REQUIRE(c, (size_t)a.tiles * count < ((size_t)1 << 31), "ntt: too many workgroups in one launch");
-    BX_REQUIRE(c, tile_elems / 16 <= (uint32_t)MAXT, "ntt: tile larger than the kernel's launch bound");
-    BX_TRY(allow_lds(c, (ntt_r16_kernel<INV, PASS_A, SKIP, LR, LT, MAXT>), lds));
-    hipLaunchKernelGGL((ntt_r16_kernel<INV, PASS_A, SKIP, LR, LT, MAXT>), dim3(a.tiles * (unsigned)count), dim3(tile_elems / 16), lds,
-                       c->stream, a);
-    BX_LAUNCH_CHECK(c);
-    return nullptr;
+// ---- executing a plan (ntt_plan.hpp): which kernel runs, and in what shape, was decided before the first launch ----------
+using R16Kernel = void (*)(R16Args);
+
+// ntt_r16_kernel<INV, PASS_A, SKIP, ..> of every row of NTT_GEOMS: the one place a row index becomes an instantiation
+template <bool INV, bool PASS_A, int SKIP, size_t... I>
+static R16Kernel r16_row(int geom, std::index_sequence<I...>) {
+    static const R16Kernel rows[] = {ntt_r16_kernel<INV, PASS_A, SKIP, NTT_GEOMS[I].lr, NTT_GEOMS[I].lt, NTT_GEOMS[I].maxt>...};
+    return rows[geom];
 }
-template <int SKIP>
-static const char* launch_passA_multi(bx_ctx* c, R16Args a, size_t count, uint32_t cpw) {
-    a.cols = (uint32_t)count;
-    a.cpw = cpw;
-    size_t lds = ((size_t)4096 + 256) * 4 * 2;  // two tiles, alternating by column
-    unsigned groups = (unsigned)((count + cpw - 1) / cpw);
-    hipLaunchKernelGGL((ntt_passA_fwd12_multi_kernel<SKIP>), dim3(a.tiles * groups), dim3(256), lds, c->stream, a);
-    BX_LAUNCH_CHECK(c);
-    return nullptr;
+static R16Kernel r16_geom_kernel(bool inv, bool pass_a, int skip, int geom) {
+    constexpr auto rows = std::make_index_sequence<NTT_GEOM_COUNT>();
+    if (!pass_a) return inv ? r16_row<true, false, 0>(geom, rows) : r16_row<false, false, 0>(geom, rows);
+    if (inv) return r16_row<true, true, 0>(geom, rows);
+    return skip == 2 ? r16_row<false, true, 2>(geom, rows) : r16_row<false, true, 0>(geom, rows);
 }
-// hot geometries (BASELINE sizes 2^20 / 2^22, default tunables) get a compile-time specialisation
-template <bool INV, bool PASS_A, int SKIP>
-static const char* launch_r16(bx_ctx* c, const R16Args& a, size_t count) {
-    if (PASS_A && !INV && a.lr == 12 && a.lrows == 12 && a.lt == 0 && c->ntt_cols_per_wg > 1 && count > 1 &&
-        (a.expand == 0 || a.expand == 2)) {
-        if (SKIP == 2) return launch_passA_multi<2>(c, a, count, (uint32_t)c->ntt_cols_per_wg);
-        if (SKIP == 0) return launch_passA_multi<0>(c, a, count, (uint32_t)c->ntt_cols_per_wg);
+
+// a planned radix-16 pass: `a` holds the buffers, strides and factors, the plan everything else
+static const char* launch_r16_pass(bx_ctx* c, const NttPass& p, bool inv, bool pass_a, int skip, size_t count, R16Args a) {
+    a.tw = inv ? c->d_tw_inv : c->d_tw_fwd;
+    a.lr = p.lr; a.lrows = p.lrows; a.lt = p.lt; a.row_shift = p.row_shift;
+    a.tiles = p.tiles; a.cols = (uint32_t)count; a.cpw = p.cpw;
+    if (p.family == NTT_MULTI_A) {
+        const R16Kernel multi_kernel = skip == 2 ? ntt_passA_fwd12_multi_kernel<2> : ntt_passA_fwd12_multi_kernel<0>;
+        hipLaunchKernelGGL(multi_kernel, dim3(p.grid_x), dim3(p.threads), p.lds, c->stream, a);
+    } else {
+        const R16Kernel r16_kernel = r16_geom_kernel(inv, pass_a, skip, p.geom);
+        BX_TRY(allow_lds(c, r16_kernel, p.lds));
+        hipLaunchKernelGGL(r16_kernel, dim3(p.grid_x), dim3(p.threads), p.lds, c->stream, a);
     }
-    if (PASS_A && a.lr == 12 && a.lt == 0) return launch_r16_geom<INV, PASS_A, SKIP, 12, 0>(c, a, count);
-    if (!PASS_A && a.lr == 10 && a.lt == 3) return launch_r16_geom<INV, PASS_A, SKIP, 10, 3>(c, a, count);
-    if (!PASS_A && a.lr == 10 && a.lt == 4) return launch_r16_geom<INV, PASS_A, SKIP, 10, 4, 1024>(c, a, count);  // 64-byte rows
-    // po2 21 .. 24 segments (compose.yml:67 runs 21): strided passes of 2^11 .. 2^13 rows on the 2^14-element tile, 2^13 contiguous pass
-    if (!PASS_A && a.lr == 11 && a.lt == 3) return launch_r16_geom<INV, PASS_A, SKIP, 11, 3, 1024>(c, a, count);
-    if (!PASS_A && a.lr == 12 && a.lt == 2) return launch_r16_geom<INV, PASS_A, SKIP, 12, 2, 1024>(c, a, count);
-    if (!PASS_A && a.lr == 13 && a.lt == 1) return launch_r16_geom<INV, PASS_A, SKIP, 13, 1, 1024>(c, a, count);
-    if (PASS_A && a.lr == 13 && a.lt == 0 && a.lrows == 13) return launch_r16_geom<INV, PASS_A, SKIP, 13, 0>(c, a, count);
-    if (!PASS_A && a.lrows + a.lt > 13) return launch_r16_geom<INV, PASS_A, SKIP, 0, 0, 1024>(c, a, count);
-    if (!PASS_A && a.lr == 8 && a.lt == 5) return launch_r16_geom<INV, PASS_A, SKIP, 8, 5>(c, a, count);
-    return launch_r16_geom<INV, PASS_A, SKIP, 0, 0>(c, a, count);
+    BX_LAUNCH_CHECK(c);
+    return nullptr;
 }
 
-// pass A over `count` columns of size 2^m made of 2^(m - m_hi) blocks; returns false in *ok if the shape is not covered
-static const char* fast_pass_a(bx_ctx* c, bool inv, uint32_t* out, const uint32_t* in, const uint32_t* twist, uint32_t scale,
-                               size_t count, int m, int m_hi, int expand, int skip, bool* ok, const uint32_t* post = nullptr,
-                               bool* post_applied = nullptr) {
-    *ok = false;
-    int lrows = (int)c->ntt_tile_a_log;
-    if (lrows < m_hi) lrows = m_hi;
-    if (lrows > m) lrows = m;
-    if (lrows < 10 || m_hi < 1 || m_hi > TW_LOG) return nullptr;  // tile must fill at least one wave (16 elements/lane)
-    if (!aligned16(out) || !aligned16(in) || (((size_t)1 << m) >> expand) % 4 != 0) return nullptr;
-    if (!(skip == 0 || (skip == 2 && !inv))) return nullptr;
+// Pass A of plan `p` over its columns.  Forward: in (2^m >> expand words per column) -> out, `skip` leading stages skipped, times the
+// twist.  Inverse: in place, times the twist (or `scale` = 1/M where there is no pass B), and times `post` on the final store where
+// the plan says so.
+static const char* launch_pass_a(bx_ctx* c, const NttPlan& p, bool inv, uint32_t* out, const uint32_t* in, const uint32_t* twist,
+                                 uint32_t scale, const uint32_t* post, int m, int expand, int skip) {
+    const size_t M = (size_t)1 << m;
+    if (p.a.family == NTT_V1) {
+        const auto block_kernel = inv ? ntt_block_kernel<true> : ntt_block_kernel<false>;
+        BX_TRY(allow_lds(c, block_kernel, p.a.lds));
+        hipLaunchKernelGGL(block_kernel, dim3(p.a.grid_x, p.a.grid_y), dim3(p.a.threads), p.a.lds, c->stream, out, in,
+                           inv ? c->d_tw_inv : c->d_tw_fwd, twist, scale, p.a.lr, expand, skip + 1, M >> expand, M);
+        BX_LAUNCH_CHECK(c);
+        return nullptr;
+    }
     R16Args a;
-    a.out = out; a.in = in; a.tw = inv ? c->d_tw_inv : c->d_tw_fwd; a.twist = twist; a.scale = scale;
-    // the final store of the inverse pass A applies `post` only in its 16-words-per-thread form (the last step is K = 4 at s0 = 0 whenever m_hi >= 4)
-    const bool can_post = inv && post && m_hi >= 4;
-    a.post = can_post ? post : nullptr;
-    if (post_applied) *post_applied = can_post;
-    a.lr = m_hi; a.lrows = lrows; a.lt = 0; a.expand = expand; a.row_shift = 0;
-    a.tile_stride = 1u << lrows;
-    a.in_col_stride = ((size_t)1 << m) >> expand; a.out_col_stride = (size_t)1 << m;
-    a.tiles = 1u << (m - lrows);
-    *ok = true;
-    if (inv) return launch_r16<true, true, 0>(c, a, count);
-    if (skip == 2) return launch_r16<false, true, 2>(c, a, count);
-    return launch_r16<false, true, 0>(c, a, count);
-}
-// tile width (log2 positions) of pass B for a 2^m transform split at m_hi; -1 when the fast path does not cover the shape
-static int pass_b_lt(bx_ctx* c, int m, int m_hi) {
-    int m_lo = m - m_hi;
-    int tile = (int)c->ntt_tile_b_log;
-    // keep every row access at least 64 bytes wide: tall passes (>= 2^10 rows) take the 2^14-element tile (1024 threads);
-    // measured on the 2^22 LDE: -6 % time and 1.5x fewer HBM write bytes than 32-byte rows
-    // ... and the tallest ones (2^11 .. 2^13 rows) the same 2^14-element tile, as wide as it still allows (po2 24 proof 1.22 -> 0.86 s)
-    if (c->ntt_tile_b_wide && m_lo + 4 > tile) tile = m_lo + 4 <= 14 ? m_lo + 4 : 14;
-    if (tile < m_lo) tile = m_lo;
-    int lt = tile - m_lo;
-    if (lt > m_hi) lt = m_hi;
-    if (m_lo + lt < 10 || m_lo < 1 || m_lo > TW_LOG || m_lo + lt > 14) return -1;
-    return lt;
-}
-static const char* fast_pass_b(bx_ctx* c, bool inv, uint32_t* io, size_t count, int m, int m_hi, bool* ok) {
-    *ok = false;
-    int m_lo = m - m_hi;
-    const int lt = pass_b_lt(c, m, m_hi);
-    if (lt < 0) return nullptr;
-    // pass B addresses a column through a buffer descriptor with 32-bit byte offsets and a 32-bit num_records (ntt_r16.hpp glb_get /
-    // glb_put): a column must stay below 4 GiB, or loads past the wrap would return 0 and stores be dropped silently
-    BX_REQUIRE(c, (((size_t)1 << m) * 4) >> 32 == 0, "ntt: a column of 2^30 words or more does not fit pass B's 32-bit buffer offsets");
-    R16Args a;
-    a.out = io; a.in = io; a.tw = inv ? c->d_tw_inv : c->d_tw_fwd; a.twist = nullptr; a.scale = MONT_ONE;
-    a.lr = m_lo; a.lrows = m_lo; a.lt = lt; a.expand = 0; a.row_shift = m_hi;
-    a.tile_stride = 1u << lt;
-    a.in_col_stride = a.out_col_stride = (size_t)1 << m;
-    a.tiles = 1u << (m_hi - lt);
-    *ok = true;
-    if (inv) return launch_r16<true, false, 0>(c, a, count);
-    return launch_r16<false, false, 0>(c, a, count);
+    a.out = out; a.in = in; a.twist = twist; a.scale = scale;
+    a.post = p.post_on_a ? post : nullptr;
+    a.expand = expand;
+    a.tile_stride = 1u << p.a.lrows;
+    a.in_col_stride = M >> expand; a.out_col_stride = M;
+    return launch_r16_pass(c, p.a, inv, true, skip, p.count, a);
 }
 
+// Pass B of plan `p` over its columns, in place.
+static const char* launch_pass_b(bx_ctx* c, const NttPlan& p, bool inv, uint32_t* io, int m) {
+    const size_t M = (size_t)1 << m;
+    if (p.b.family == NTT_V1) {
+        const auto strided_kernel = inv ? ntt_strided_kernel<true> : ntt_strided_kernel<false>;
+        BX_TRY(allow_lds(c, strided_kernel, p.b.lds));
+        hipLaunchKernelGGL(strided_kernel, dim3(p.b.grid_x, p.b.grid_y), dim3(p.b.threads), p.b.lds, c->stream, io,
+                           inv ? c->d_tw_inv : c->d_tw_fwd, p.b.lr, p.b.lt, p.m_hi, M, p.b.tiles);
+        BX_LAUNCH_CHECK(c);
+        return nullptr;
+    }
+    R16Args a;
+    a.out = io; a.in = io; a.twist = nullptr; a.scale = MONT_ONE;
+    a.expand = 0;
+    a.tile_stride = 1u << p.b.lt;
+    a.in_col_stride = a.out_col_stride = M;
+    return launch_r16_pass(c, p.b, inv, false, 0, p.count, a);
+}
+
+// forward transform of `count` columns: in (size M >> expand_bits per column) -> out (size M per column), A then B.
 // `expand_bits` = load shift (out[i] = in[i >> bits]); `skip_bits` = leading stages skipped (== expand_bits for the
 // expanding form, and for the in-place Hal::batch_evaluate_ntt(io, count, expand_bits) with no load shift).
+// With ntt_group_cols the two passes run on a group of columns at a time (ntt_forward_group); the plan of a full group and the plan
+// of the ragged last one are both made before the first launch.
 static const char* forward(bx_ctx* c, uint32_t* out, const uint32_t* in, size_t count, int m, int expand_bits,
                            int skip_bits) {
     if (m == 0 || count == 0) {
         if (out != in) BX_HIP(c, hipMemcpyAsync(out, in, count * 4, hipMemcpyDeviceToDevice, c->stream));
         return nullptr;
     }
-    Split sp = choose_split(c, m);
-    BX_REQUIRE(c, sp.m_hi <= TW_LOG && sp.m_lo <= TW_LOG, "ntt: size too large");
-    BX_REQUIRE(c, expand_bits <= sp.m_hi && skip_bits <= sp.m_hi, "ntt: expand_bits larger than the block pass");
-    size_t M = (size_t)1 << m;
+    const bool al = aligned16(out) && aligned16(in);
+    const size_t g = ntt_forward_group(c->ntt, m, expand_bits, skip_bits, count, al);
+    const NttPlan full = ntt_plan(c->ntt, false, m, expand_bits, skip_bits, g, al, false);
+    const NttPlan last = count % g ? ntt_plan(c->ntt, false, m, expand_bits, skip_bits, count % g, al, false) : full;
+    BX_REQUIRE(c, !full.error, full.error);
+    BX_REQUIRE(c, !last.error, last.error);
+    const size_t M = (size_t)1 << m;
     uint32_t* twist = nullptr;
-    if (sp.m_lo) BX_TRY(get_twist(c, m, sp.m_hi, false, &twist));
-    bool done_a = false, done_b = false;
-    // Column groups (SURVEY hard part 5): run pass A and pass B back to back on `ntt_group_cols` columns at a time so that
-    // pass B finds what pass A just wrote in the 256 MB Infinity Cache instead of HBM (0 = one pass A and one pass B over all
-    // columns).  Measured on the 2^22 LDE, see DESIGN.md §4 "NTT traffic".
-    if (c->ntt_fast && c->ntt_group_cols > 0 && sp.m_lo && (size_t)c->ntt_group_cols < count) {
-        const size_t g = (size_t)c->ntt_group_cols;
-        bool all = true;
-        for (size_t c0 = 0; c0 < count && all; c0 += g) {
-            const size_t n = count - c0 < g ? count - c0 : g;
-            bool oa = false, ob = false;
-            BX_TRY(fast_pass_a(c, false, out + c0 * M, in + c0 * (M >> expand_bits), twist, MONT_ONE, n, m, sp.m_hi, expand_bits, skip_bits, &oa));
-            if (oa) BX_TRY(fast_pass_b(c, false, out + c0 * M, n, m, sp.m_hi, &ob));
-            all = oa && ob;
-            if (!all && c0 != 0) return set_msg(c, "ntt: column-group path became unavailable mid-way");
-        }
-        if (all) return nullptr;
-    }
-    if (c->ntt_fast) BX_TRY(fast_pass_a(c, false, out, in, twist, MONT_ONE, count, m, sp.m_hi, expand_bits, skip_bits, &done_a));
-    if (!done_a) {
-        unsigned R = 1u << sp.m_hi;
-        unsigned threads = R / 2 < 64 ? 64 : (R / 2 > 256 ? 256 : R / 2);
-        size_t lds = (size_t)R * 8;
-        BX_TRY(allow_lds(c, ntt_block_kernel<false>, lds));
-        hipLaunchKernelGGL(ntt_block_kernel<false>, dim3(1u << sp.m_lo, (unsigned)count), dim3(threads), lds, c->stream, out,
-                           in, c->d_tw_fwd, twist, MONT_ONE, sp.m_hi, expand_bits, skip_bits + 1, M >> expand_bits, M);
-        BX_LAUNCH_CHECK(c);
-    }
-    if (sp.m_lo && c->ntt_fast) BX_TRY(fast_pass_b(c, false, out, count, m, sp.m_hi, &done_b));
-    if (sp.m_lo && !done_b) {
-        unsigned rows = 1u << sp.m_lo;
-        unsigned total = rows << sp.lt;
-        unsigned threads = total / 2 > 1024 ? 1024 : (total / 2 < 64 ? 64 : total / 2);
-        if (threads > 512 && total <= 8192) threads = 512;
-        size_t lds = (size_t)total * 4 + (size_t)rows * 4;
-        BX_TRY(allow_lds(c, ntt_strided_kernel<false>, lds));
-        unsigned tiles = 1u << (sp.m_hi - sp.lt);
-        hipLaunchKernelGGL(ntt_strided_kernel<false>, dim3(tiles, (unsigned)count), dim3(threads), lds, c->stream, out,
-                           c->d_tw_fwd, sp.m_lo, sp.lt, sp.m_hi, M, tiles);
-        BX_LAUNCH_CHECK(c);
+    if (full.twist) BX_TRY(get_twist(c, m, full.m_hi, false, &twist));
+    for (size_t c0 = 0; c0 < count; c0 += g) {
+        const NttPlan& p = count - c0 < g ? last : full;
+        BX_TRY(launch_pass_a(c, p, false, out + c0 * M, in + c0 * (M >> expand_bits), twist, MONT_ONE, nullptr, m, expand_bits, skip_bits));
+        if (p.m_lo) BX_TRY(launch_pass_b(c, p, false, out + c0 * M, m));
     }
     return nullptr;
 }
 
-static const char* inverse(bx_ctx* c, uint32_t* io, size_t count, int m, const uint32_t* post = nullptr, bool* post_applied = nullptr) {
-    if (post_applied) *post_applied = false;
-    if (m == 0 || count == 0) return nullptr;
-    Split sp = choose_split(c, m);
-    BX_REQUIRE(c, sp.m_hi <= TW_LOG && sp.m_lo <= TW_LOG, "ntt: size too large");
-    size_t M = (size_t)1 << m;
+// inverse transform in place by plan `p` (m >= 1): B then A.  `post`: the factor table of a plan with post_on_a.
+static const char* inverse(bx_ctx* c, const NttPlan& p, uint32_t* io, int m, const uint32_t* post) {
     uint32_t* twist = nullptr;
-    bool done_a = false, done_b = false;
-    if (sp.m_lo) BX_TRY(get_twist(c, m, sp.m_hi, true, &twist));
-    if (sp.m_lo && c->ntt_fast) BX_TRY(fast_pass_b(c, true, io, count, m, sp.m_hi, &done_b));
-    if (sp.m_lo && !done_b) {
-        unsigned rows = 1u << sp.m_lo;
-        unsigned total = rows << sp.lt;
-        unsigned threads = total / 2 > 1024 ? 1024 : (total / 2 < 64 ? 64 : total / 2);
-        if (threads > 512 && total <= 8192) threads = 512;
-        size_t lds = (size_t)total * 4 + (size_t)rows * 4;
-        BX_TRY(allow_lds(c, ntt_strided_kernel<true>, lds));
-        unsigned tiles = 1u << (sp.m_hi - sp.lt);
-        hipLaunchKernelGGL(ntt_strided_kernel<true>, dim3(tiles, (unsigned)count), dim3(threads), lds, c->stream, io,
-                           c->d_tw_inv, sp.m_lo, sp.lt, sp.m_hi, M, tiles);
-        BX_LAUNCH_CHECK(c);
-    }
-    uint32_t scale = fp_inv(fp_encode((uint32_t)M));
-    if (c->ntt_fast) BX_TRY(fast_pass_a(c, true, io, io, twist, scale, count, m, sp.m_hi, 0, 0, &done_a, post, post_applied));
-    if (!done_a && post_applied) *post_applied = false;
-    if (!done_a) {
-        unsigned R = 1u << sp.m_hi;
-        unsigned threads = R / 2 < 64 ? 64 : (R / 2 > 256 ? 256 : R / 2);
-        size_t lds = (size_t)R * 8;
-        BX_TRY(allow_lds(c, ntt_block_kernel<true>, lds));
-        hipLaunchKernelGGL(ntt_block_kernel<true>, dim3(1u << sp.m_lo, (unsigned)count), dim3(threads), lds, c->stream, io,
-                           io, c->d_tw_inv, twist, scale, sp.m_hi, 0, 1, M, M);
-        BX_LAUNCH_CHECK(c);
-    }
-    return nullptr;
+    if (p.twist) BX_TRY(get_twist(c, m, p.m_hi, true, &twist));
+    if (p.m_lo) BX_TRY(launch_pass_b(c, p, true, io, m));
+    const uint32_t scale = fp_inv(fp_encode((uint32_t)((size_t)1 << m)));
+    return launch_pass_a(c, p, true, io, io, twist, scale, post, m, 0, 0);
 }
 
 static const char* get_zk(bx_ctx* c, int n, ZkTab* out) {
@@ -560,14 +448,19 @@ extern "C" const char* bx_batch_interpolate_zk(bx_ctx* c, bx_buf io, size_t coun
     BX_REQUIRE(c, count > 0 && io.len % count == 0 && is_pow2(io.len / count), "batch_interpolate_zk: io.len/count must be a power of two");
     BX_ENTER(c);
     const int m = ilog2(io.len / count);
-    bool fused = false;
+    NttPlan p;
     {
         OpScope op(c, "batch_interpolate_ntt", 8.0 * (double)io.len);
-        const uint32_t* post = nullptr;
-        if (m >= 12 && c->ntt_fast) BX_TRY(get_zk_full(c, m, &post));
-        BX_TRY(inverse(c, (uint32_t*)io.dptr, count, m, post, &fused));
+        if (m > 0) {
+            // the 2^m-word table of factors is worth building from 2^12 on, and is built only where the plan uses it
+            p = ntt_plan(c->ntt, true, m, 0, 0, count, aligned16(io.dptr), m >= 12);
+            BX_REQUIRE(c, !p.error, p.error);
+            const uint32_t* post = nullptr;
+            if (p.post_on_a) BX_TRY(get_zk_full(c, m, &post));
+            BX_TRY(inverse(c, p, (uint32_t*)io.dptr, m, post));
+        }
     }
-    if (fused) return nullptr;
+    if (p.post_on_a) return nullptr;
     return zk_shift_impl(c, io, count);
 } BX_ABI_CATCH(c, "bx_batch_interpolate_zk")
 
@@ -576,7 +469,11 @@ extern "C" const char* bx_batch_interpolate_ntt(bx_ctx* c, bx_buf io, size_t cou
     BX_REQUIRE(c, count > 0 && io.len % count == 0 && is_pow2(io.len / count), "batch_interpolate_ntt: io.len/count must be a power of two");
     BX_ENTER(c);
     OpScope op(c, "batch_interpolate_ntt", 8.0 * (double)io.len);
-    return inverse(c, (uint32_t*)io.dptr, count, ilog2(io.len / count));
+    const int m = ilog2(io.len / count);
+    if (m == 0) return nullptr;
+    const NttPlan p = ntt_plan(c->ntt, true, m, 0, 0, count, aligned16(io.dptr), false);
+    BX_REQUIRE(c, !p.error, p.error);
+    return inverse(c, p, (uint32_t*)io.dptr, m, nullptr);
 } BX_ABI_CATCH(c, "bx_batch_interpolate_ntt")
 
 extern "C" const char* bx_batch_evaluate_ntt(bx_ctx* c, bx_buf io, size_t count, size_t expand_bits) try {

@@ -1,7 +1,7 @@
 """GPU parity of the kernel paths that only a tunable (bx_set_tunable / BX_TUNABLES), a pointer alignment or a size
 selects — the paths the default settings and the power-of-two sizes of tests/test_hal_gpu.py never take.  Every comparison is
 bit-exact: against the C oracle, and for the `sha-256` suite against tests/sha256_ref.py.  A test that sets a tunable puts the
-default (csrc/ctx.hpp) back in a `finally` block, so no test sees a setting left over from another."""
+default (csrc/ctx.hpp, csrc/ntt_plan.hpp) back in a `finally` block, so no test sees a setting left over from another."""
 import contextlib
 import os
 import sys
@@ -205,7 +205,8 @@ def test_ntt_column_groups(hal, oracle, bits, g, count, cpw):
     """ntt_group_cols = g runs pass A and pass B of a two-pass forward transform on g columns at a time: input and output offsets per
     group, a ragged last group (5 = 2 + 2 + 1, 7 = 3 + 3 + 1, 7 = 5 + 2), one column per group; g >= count takes the ungrouped path.
     With ntt_cols_per_wg = 4 a group of three is narrower than the multi-column pass A and one of five is no multiple of it.
-    2^12 and 2^14 rows expand to 2^14 and 2^16: a contiguous pass of 2^12 and a strided pass of 4 and of 16 rows."""
+    2^12 and 2^14 rows expand to 2^14 and 2^16: a contiguous pass of 2^12 and a strided pass of 4 and of 16 rows.  Which kernel each
+    group launches (the ragged one included) is in tests/golden/ntt_launches.json, replayed by tests/test_ntt_plan_check_cpu.py."""
     n = 1 << bits
     x = ntt_columns(bits * 100 + count, n, count)
     y = ntt_columns(bits * 100 + count + 1, 4 * n, count)
@@ -229,8 +230,10 @@ def test_ntt_column_groups(hal, oracle, bits, g, count, cpw):
 def test_ntt_pass_b_without_the_widened_tile(hal, oracle, m, tile_b_log):
     """With ntt_tile_b_wide = 1 every strided pass of 2^10 or more rows is widened to the 2^14-element tile.  Switched off, a 2^22
     transform runs its 2^10-row pass B on the 2^13 tile — the compiled geometry ntt_r16_kernel<.., 10, 3> — or, with
-    ntt_tile_b_log = 12, on the generic one, and a 2^23 transform its 2^11-row pass on the generic geometry.  Both directions
-    (pass B serves the inverse too), two columns: random, and alternating 0 / P - 1."""
+    ntt_tile_b_log = 12, on the generic one, and a 2^23 transform its 2^11-row pass on the generic geometry.  That these settings
+    plan these kernels is checked without a GPU: the three tuples are cases of tests/golden/ntt_launches.json, which
+    tests/test_ntt_plan_check_cpu.py replays through the planner.  Both directions (pass B serves the inverse too), two columns:
+    random, and alternating 0 / P - 1."""
     size, n = 1 << m, 1 << (m - 2)
 
     def two_columns(seed, rows):
@@ -252,6 +255,47 @@ def test_ntt_pass_b_without_the_widened_tile(hal, oracle, m, tile_b_log):
         assert np.array_equal(io.view(), ref_out), "batch_expand_into_evaluate_ntt"
         assert np.array_equal(d_in.view(), small), "the input of the expanding call"
         io.free(), d_in.free()
+
+
+# ------------------------------------------------------------------ c'. NTT on a slice that is only word-aligned
+@pytest.mark.parametrize("off", [1, 3])
+@pytest.mark.parametrize("bits", [13, 14])
+def test_ntt_on_a_slice_that_is_only_word_aligned(hal, oracle, bits, off):
+    """Default tunables: a buffer that does not start on a 16-byte boundary cannot take the radix-16 pass A (16-byte accesses) and runs
+    the v1 contiguous pass beside the radix-16 strided pass, in both directions — the plan tests/test_ntt_plan_check_cpu.py replays
+    for the `offset` cases of tests/golden/ntt_launches.json.  2^13 and 2^14 are the smallest two-pass sizes.  Every entry point,
+    bit-exact against the oracle, and the words around the slice stay."""
+    n, count, pad = 1 << bits, 2, 8
+    rng = np.random.default_rng(bits * 10 + off)
+    x = rnd(bits * 10 + off, n * count)
+
+    def on_slice(call, data):
+        host = rng.integers(0, 1 << 32, off + data.size + pad, dtype=np.uint32)
+        host[off:off + data.size] = data
+        whole = hal.copy_from(host)
+        d = whole.slice(off, data.size)
+        assert d.raw.dptr % 16 != 0
+        call(d)
+        got = whole.view()
+        assert np.array_equal(got[:off], host[:off]) and np.array_equal(got[off + data.size:], host[off + data.size:]), "around the slice"
+        return got[off:off + data.size]
+
+    ref = x.copy()
+    oracle.bxo_batch_interpolate_ntt(ref, count, n)
+    assert np.array_equal(on_slice(lambda d: hal.batch_interpolate_ntt(d, count), x), ref), "batch_interpolate_ntt"
+    oracle.bxo_zk_shift(ref, count, n)
+    assert np.array_equal(on_slice(lambda d: hal.batch_interpolate_zk(d, count), x), ref), "batch_interpolate_zk"
+    for eb in (0, 2):
+        ref = x.copy()
+        oracle.bxo_batch_evaluate_ntt(ref, count, n, eb)
+        assert np.array_equal(on_slice(lambda d: hal.batch_evaluate_ntt(d, count, eb), x), ref), ("batch_evaluate_ntt", eb)
+    small = c(x[:n // 4 * count])  # n / 4 rows expand to the same two-pass size n
+    ref_out = np.zeros(n * count, np.uint32)
+    oracle.bxo_batch_expand_into_evaluate_ntt(ref_out, small, count, n // 4, 2)
+    out = hal.alloc(n * count)
+    assert out.raw.dptr % 16 == 0
+    assert np.array_equal(on_slice(lambda d: hal.batch_expand_into_evaluate_ntt(out, d, count, 2), small), small), "the input of the expanding call"
+    assert np.array_equal(out.view(), ref_out), "batch_expand_into_evaluate_ntt"
 
 
 # ------------------------------------------------------------------ d. hash_rows_block
