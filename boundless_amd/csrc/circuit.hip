@@ -7,12 +7,16 @@
 // All three stages are VALU-bound (no HBM or MFMA roofline applies): a derived cell / a constraint costs T*(G-2) reduced
 // products and T multiply-adds for the terms, then one reduction and one multiply-add per group of terms that share their
 // first factor (circuit_dev.hpp, the factored form: 32 groups at (64, 4), 16 at (48, 3)); for G <= 2, T*(G-1) products term by
-// term.  The loads around it are one coalesced dword per lane and column.
+// term.  At G = 4 the terms are instead products of two shared pair products (circuit_dev.hpp, the pair form): at T = 64, 44
+// reduced pair products, 64 multiply-adds, and one reduction and one multiply-add per group of three terms (23 groups).
+// The loads around it are one coalesced dword per lane and column.
 // The signed multiply-adds are left to the compiler in this translation unit (poseidon2.hip pins them as single asm
 // statements because its loop-carried cells get widened): here the terms of a cell share their inner products (7 pool entries
 // give at most 28 distinct pairs), and only un-pinned code lets hipcc find them, with none of the s_nops it places between
-// adjacent asm statements.  Per cell, compiled: 486 VALU instructions (368 multiply-class) at (T, G) = (64, 4) and 265 (127)
-// at (48, 3); term by term they were 630 (474) and 389 (218).  DESIGN.md §4 has the table.
+// adjacent asm statements.  Per cell, compiled, the factored form: 486 VALU instructions (368 multiply-class) at (T, G) = (64, 4)
+// and 265 (127) at (48, 3); term by term they were 630 (474) and 389 (218).  The pair form takes (64, 4) down by another 75
+// instructions per cell, 117 of them fewer multiply-class: witness_derive_kernel<64,4> 568 (368) -> 493 (251), eval_check_kernel<64,4>
+// 1340 (657) -> 1265 (540).  DESIGN.md §4 has the tables.
 #define BX_PLAIN_MAD 1
 #include <memory>
 #include <new>

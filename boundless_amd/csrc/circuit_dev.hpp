@@ -7,8 +7,27 @@
 // |result| <= ub(|t|) = |t|/2^32 + P/2 + 1, valid for |t| <= SREDC_MAX = 1.209 P^2; P^2/2^32 = 0.469 P) so that no product is
 // followed by a conditional subtraction and the sums stay unreduced in 64 bits.  Pool entries are centred once per cell, |c| <= P/2.
 //
-// G >= 3, the factored form.  pool_idx(t, 0) runs through all 16 pool entries on every block of 16 terms, so entry a is the first
-// factor of T/16 terms and   sum_{t: idx(t,0)=a} pool[a] * (rest of t)  =  pool[a] * sum_t (rest of t):  the product with pool[a]
+// G = 4, the pair form.  A term is a product of four pool entries and can be written as (pair) * (pair) in three ways; PairPlan picks
+// one split per term so that pairs recur (44 distinct pairs serve the 128 pair slots of T = 64, where the first-factor form below
+// computes 59 reduced products and 64 + 32 multiply-adds), and a term is then ONE multiply-add of two shared, reduced pair products.
+// The plan: each term's most popular split, four sweeps that re-choose a term's split where that frees a pair (51 pairs), then two
+// passes that drop a little-used pair outright by moving all its users to other splits (44).
+//   a pair                p = sredc(c_a * c_b), computed at its first use:   |p| <= ub(P^2/4) = 0.617 P
+//   a group               acc = sum of <= GRP = 3 terms p1 * p2:             |acc| <= 3 * 0.381 P^2 = 1.143 P^2 <= SREDC_MAX (four: 1.52)
+//                         no two terms of a group share a pair: hipcc would rewrite p*q1 + p*q2 as p*(q1 + q2) with a 64-bit sum
+//                         and emulate a 64 x 32-bit product
+//   its reduction         r = sredc(acc):                                    |r| <= 1.036 P, still an int32
+//   second level          acc2 = sum of r * R over <= 7 consecutive groups:  |acc2| <= 0.967 P^2 <= FINAL_MAX (eight: 1.105 P^2)
+//   third level           the same over the <= 4 second-level results:       |acc3| <= 4 * (P - 1) * R = 0.53 P^2
+// The terms are ordered so that a pair's uses lie in neighbouring groups (at most 7 pairs are computed and still awaited at any
+// point of T = 64), which keeps the pair products from costing registers: eval_check_kernel<64,4> compiles to 87 VGPRs, no scratch.
+// Every path from a term to the result is again a congruence mod P through three reductions against two factors R, so the
+// canonical result is the same word as the first-factor form's and the plain loop's.  PairPlan carries the bounds; cons_sum's
+// static_asserts hold them, and the host build (BX_CHECK_BOUNDS) asserts every pair, every sredc operand and every level's sum.
+//
+// G = 3 and G >= 5, the factored form (ConsPlan; built for G = 4 too, where tests read it, but no longer executed there).
+// pool_idx(t, 0) runs through all 16 pool entries on every block of 16 terms, so entry a is the first factor of T/16 terms
+// and   sum_{t: idx(t,0)=a} pool[a] * (rest of t)  =  pool[a] * sum_t (rest of t):  the product with pool[a]
 // is taken once per group of terms instead of once per term (one reduced product, 3 multiply-class instructions, less per term;
 // one reduction and one multiply-add more per group).  Every step is a congruence mod P and every path from a term to the result
 // passes G - 1 + 2 reductions against two factors R, as in the term-by-term form, so the canonical result is the same word.
@@ -129,9 +148,208 @@ struct ConsPlan {
 template <int TT, int GG>
 inline constexpr ConsPlan<TT, GG> cons_plan{};
 
+// The plan of the pair form (G = 4) for one T: which of its three splits into two pairs each term takes, the distinct pairs in
+// the order of their first use, and the terms in the order they are summed, cut into groups, with the bound of every accumulator.
+template <int TT>
+struct PairPlan {
+    static constexpr int NPOOL = (int)Circuit::POOL, NID = NPOOL * NPOOL;
+    static constexpr i64 BC = (i64)(P / 2);                   // a centred pool entry
+    static constexpr i64 PAIR = ub(BC * BC);                  // a reduced pair product
+    static constexpr i64 TERM = PAIR * PAIR;                  // one term of a group
+    static constexpr int GRP = (int)(SREDC_MAX / TERM);       // terms per group, at most
+    static_assert(GRP == 3 && GRP * TERM <= SREDC_MAX, "cons_sum: pair group beyond sredc's range");
+    static constexpr int pair_id(unsigned a, unsigned b) { return a < b ? (int)(a * NPOOL + b) : (int)(b * NPOOL + a); }
+
+    int np = 0, ng = 0, n2 = 0;            // distinct pairs, groups, second-level groups
+    int pa[2 * TT]{}, pb[2 * TT]{};        // pair p = pool[pa[p]] * pool[pb[p]], numbered by first use
+    int seq[TT]{}, s1[TT]{}, s2[TT]{};     // slot s sums term seq[s] = pair s1[s] * pair s2[s]
+    int pbeg[TT + 1]{};                    // pairs [pbeg[s], pbeg[s+1]) are computed at slot s, their first use
+    int gbeg[TT + 1]{}, lbeg[TT + 1]{};    // group g = slots [gbeg[g], gbeg[g+1]), second-level group l = groups [lbeg[l], lbeg[l+1])
+    int max_live = 0;                      // most pairs computed and still to be used at any slot
+    i64 max_group = 0, max_l2 = 0, max_l3 = 0;
+
+    constexpr PairPlan() {
+        // the three splits of every term: factor 0 with factor s+1, and the other two
+        int sp[TT][3][2]{}, pop[NID]{}, ref[NID]{}, ch[TT]{};
+        for (int t = 0; t < TT; ++t) {
+            unsigned x[4]{};
+            for (unsigned f = 0; f < 4; ++f) x[f] = Circuit::pool_idx((unsigned)t, f);
+            for (int s = 0; s < 3; ++s) {
+                sp[t][s][0] = pair_id(x[0], x[s + 1]);
+                sp[t][s][1] = pair_id(x[s == 0 ? 2 : 1], x[s == 2 ? 2 : 3]);
+                ++pop[sp[t][s][0]];
+                ++pop[sp[t][s][1]];
+            }
+        }
+        // start from each term's most popular split, then re-choose a term's split where that frees a pair; ref[] counts the
+        // uses of every pair under the current choice and is kept up to date, so a trial costs three look-ups
+        for (int t = 0; t < TT; ++t) {
+            for (int s = 1; s < 3; ++s)
+                if (pop[sp[t][s][0]] + pop[sp[t][s][1]] > pop[sp[t][ch[t]][0]] + pop[sp[t][ch[t]][1]]) ch[t] = s;
+            ++ref[sp[t][ch[t]][0]];
+            ++ref[sp[t][ch[t]][1]];
+        }
+        for (int sweep = 0; sweep < 4; ++sweep)
+            for (int t = 0; t < TT; ++t) {
+                --ref[sp[t][ch[t]][0]];
+                --ref[sp[t][ch[t]][1]];
+                int best = 0, best_new = 3, best_ref = 0;
+                for (int s = 0; s < 3; ++s) {
+                    const int a = sp[t][s][0], b = sp[t][s][1];
+                    const int fresh = (ref[a] == 0) + (ref[b] == 0 && b != a), shared = ref[a] + ref[b];
+                    if (fresh < best_new || (fresh == best_new && shared > best_ref)) best = s, best_new = fresh, best_ref = shared;
+                }
+                ch[t] = best;
+                ++ref[sp[t][best][0]];
+                ++ref[sp[t][best][1]];
+            }
+        // then pairs with few uses are dropped outright: all users of pair p move to splits without it, and the move stays if fewer
+        // distinct pairs remain — in the second pass also if as many, a sideways step after which further pairs can go.  Pairs are
+        // tried by rising use count; `delta` follows the distinct count through ref[], so a trial never rescans the terms' pairs.
+        for (int pass = 0; pass < 2; ++pass) {
+            int snap[NID]{};
+            for (int i = 0; i < NID; ++i) snap[i] = ref[i];
+            for (int r = 1; r <= 4; ++r)
+                for (int p = 0; p < NID; ++p) {
+                    if (snap[p] != r || ref[p] == 0 || ref[p] > 4) continue;
+                    int users[4]{}, was[4]{}, nu = 0, moved = 0, delta = 0;
+                    for (int t = 0; t < TT; ++t)
+                        if (sp[t][ch[t]][0] == p || sp[t][ch[t]][1] == p) users[nu++] = t;
+                    for (int u = 0; u < nu; ++u) {
+                        was[u] = ch[users[u]];
+                        for (int k = 0; k < 2; ++k) delta -= (--ref[sp[users[u]][was[u]][k]] == 0);
+                    }
+                    for (; moved < nu; ++moved) {
+                        const int t = users[moved];
+                        int best = -1, best_new = 3, best_ref = 0;
+                        for (int s = 0; s < 3; ++s) {
+                            const int a = sp[t][s][0], b = sp[t][s][1];
+                            if (a == p || b == p) continue;
+                            const int fresh = (ref[a] == 0) + (ref[b] == 0 && b != a), shared = ref[a] + ref[b];
+                            if (best < 0 || fresh < best_new || (fresh == best_new && shared > best_ref)) best = s, best_new = fresh, best_ref = shared;
+                        }
+                        if (best < 0) break;   // every split of this term holds p
+                        ch[t] = best;
+                        for (int k = 0; k < 2; ++k) delta += (ref[sp[t][best][k]]++ == 0);
+                    }
+                    if (moved < nu || delta > 0 || (delta == 0 && pass == 0)) {   // not better: put everything back
+                        for (int u = 0; u < moved; ++u)
+                            for (int k = 0; k < 2; ++k) --ref[sp[users[u]][ch[users[u]]][k]];
+                        for (int u = 0; u < nu; ++u) {
+                            ch[users[u]] = was[u];
+                            for (int k = 0; k < 2; ++k) ++ref[sp[users[u]][was[u]][k]];
+                        }
+                    }
+                }
+        }
+        // the order: the next term is the one that needs the fewest pairs not yet computed, then the one that uses the most pairs
+        // for the last time, so that a pair's uses lie close together.  No two terms of a group share a pair (hipcc would rewrite
+        // p*q1 + p*q2 as p*(q1 + q2) with a 64-bit sum and emulate a 64 x 32-bit product), so such terms go to neighbouring groups.
+        int num[NID]{}, live = 0, glen = 0, gp[2 * GRP]{};
+        bool placed[TT]{};
+        for (int i = 0; i < NID; ++i) num[i] = -1;
+        for (int slot = 0; slot < TT;) {
+            int best = -1, best_new = 3, best_last = -1;
+            if (glen < GRP)
+                for (int t = 0; t < TT; ++t) {
+                    if (placed[t]) continue;
+                    const int a = sp[t][ch[t]][0], b = sp[t][ch[t]][1];
+                    bool clash = false;
+                    for (int k = 0; k < 2 * glen; ++k) clash = clash || gp[k] == a || gp[k] == b;
+                    if (clash) continue;
+                    const int fresh = (num[a] < 0) + (num[b] < 0 && b != a);
+                    const int last = a == b ? (ref[a] == 2) : (ref[a] == 1) + (ref[b] == 1);
+                    if (fresh < best_new || (fresh == best_new && last > best_last)) best = t, best_new = fresh, best_last = last;
+                }
+            if (best < 0) {                // the group is full, or every term left shares a pair with it
+                gbeg[++ng] = slot;
+                glen = 0;
+                continue;
+            }
+            const int a = sp[best][ch[best]][0], b = sp[best][ch[best]][1];
+            for (int k = 0; k < 2; ++k) {
+                const int id = k ? b : a;
+                if (num[id] < 0) {
+                    num[id] = np;
+                    pa[np] = id / NPOOL;
+                    pb[np] = id % NPOOL;
+                    ++np;
+                    ++live;
+                }
+            }
+            if (live > max_live) max_live = live;
+            live -= (--ref[a] == 0);
+            live -= (--ref[b] == 0);
+            placed[best] = true;
+            seq[slot] = best;
+            s1[slot] = num[a];
+            s2[slot] = num[b];
+            gp[2 * glen] = a;
+            gp[2 * glen + 1] = b;
+            ++glen;
+            pbeg[++slot] = np;
+        }
+        gbeg[++ng] = TT;
+        i64 cur = 0;
+        for (int g = 0; g < ng; ++g) {     // second level: consecutive groups while the reduction stays below P
+            const i64 sum = (gbeg[g + 1] - gbeg[g]) * TERM, add = ub(sum) * (i64)MONT_ONE;
+            if (sum > max_group) max_group = sum;
+            if (g > 0 && cur + add > FINAL_MAX) {
+                max_l3 += ub(cur) * (i64)MONT_ONE;
+                lbeg[++n2] = g;
+                cur = 0;
+            }
+            cur += add;
+            if (cur > max_l2) max_l2 = cur;
+        }
+        max_l3 += ub(cur) * (i64)MONT_ONE;
+        lbeg[++n2] = ng;
+    }
+};
+template <int TT>
+inline constexpr PairPlan<TT> pair_plan{};
+
 template <int TT, int GG>
 BX_HD uint32_t cons_sum(const uint32_t (&pool_u)[Circuit::POOL], uint32_t T, uint32_t G) {
-    if constexpr (TT > 0 && GG >= 3) {
+    if constexpr (TT > 0 && GG == 4) {
+        constexpr int N2 = pair_plan<TT>.n2;
+        static_assert(pair_plan<TT>.max_group <= SREDC_MAX, "cons_sum: a group sum beyond sredc's range");
+        static_assert(pair_plan<TT>.max_l2 <= FINAL_MAX && pair_plan<TT>.max_l3 <= FINAL_MAX, "cons_sum: term count beyond the three reduction levels");
+        i32 pool[Circuit::POOL];
+#pragma unroll
+        for (unsigned i = 0; i < Circuit::POOL; ++i) pool[i] = fp_centre(pool_u[i]);
+        // every index below is a constant expression, so each pool entry and each pair product is a fixed register
+        i32 pr[pair_plan<TT>.np];
+        i64 acc3 = 0;
+        i32 result = 0;
+        static_for<0, N2>([&](auto lc) {
+            constexpr int l = decltype(lc)::value;
+            i64 acc2 = 0;
+            static_for<pair_plan<TT>.lbeg[l], pair_plan<TT>.lbeg[l + 1]>([&](auto gc) {
+                constexpr int g = decltype(gc)::value;
+                i64 acc = 0;
+                static_for<pair_plan<TT>.gbeg[g], pair_plan<TT>.gbeg[g + 1]>([&](auto sc) {
+                    constexpr int s = decltype(sc)::value;
+                    static_for<pair_plan<TT>.pbeg[s], pair_plan<TT>.pbeg[s + 1]>([&](auto pc) {
+                        constexpr int p = decltype(pc)::value;
+                        pr[p] = sredc(smul(pool[pair_plan<TT>.pa[p]], pool[pair_plan<TT>.pb[p]], p), p);
+                        BX_ASSERT_BOUND(pr[p] <= PairPlan<TT>::PAIR && pr[p] >= -PairPlan<TT>::PAIR, "cons_sum pair");
+                    });
+                    acc = smad(pr[pair_plan<TT>.s1[s]], pr[pair_plan<TT>.s2[s]], acc, s);
+                });
+                acc2 = smad_k(sredc(acc, 3), MONT_ONE, acc2, g);
+            });
+            BX_ASSERT_BOUND(acc2 <= FINAL_MAX && acc2 >= -FINAL_MAX, "cons_sum second level");
+            const i32 r2 = sredc(acc2, 2);
+            if constexpr (N2 == 1) result = r2;
+            else acc3 = smad_k(r2, MONT_ONE, acc3, l);
+        });
+        if constexpr (N2 > 1) {
+            BX_ASSERT_BOUND(acc3 <= FINAL_MAX && acc3 >= -FINAL_MAX, "cons_sum third level");
+            result = sredc(acc3, 0);
+        }
+        return (uint32_t)(result + (result < 0 ? (i32)P : 0));
+    } else if constexpr (TT > 0 && GG >= 3) {
         constexpr int N2 = cons_plan<TT, GG>.n2;
         static_assert(cons_plan<TT, GG>.max_inner <= SREDC_MAX && cons_plan<TT, GG>.max_outer <= SREDC_MAX, "cons_sum: a group sum beyond sredc's range");
         static_assert(cons_plan<TT, GG>.max_l2 <= FINAL_MAX && cons_plan<TT, GG>.max_l3 <= FINAL_MAX, "cons_sum: term count beyond the three reduction levels");
