@@ -1,8 +1,8 @@
 // hash_suite.hpp — the hash suites a ctx / a prover / a verification runs under (bx_set_hash_suite), host side.
 //
 // One place for what depends on the suite outside the kernels: its number and name, its host hashes, RNG and Merkle fold
-// (HostSuite), and the top-layer rule that fixes a seal's layout.  The device half is the launcher table of ctx.hpp
-// (HashLaunchers).  Header-only and free of HIP: verify.cpp / control_id.cpp / image_host.cpp also build with plain g++.  A further
+// (HostSuite).  (The top-layer rule of the Merkle trees belongs to the seal's layout: seal_layout.hpp.)  The device half is the
+// launcher table of ctx.hpp (HashLaunchers).  Header-only and free of HIP: verify.cpp / control_id.cpp / image_host.cpp also build with plain g++.  A further
 // suite is an entry in the enum and the name table, a case in each function of HostSuite, and a launcher table beside its kernels.
 #pragma once
 #include <stdint.h>
@@ -25,14 +25,6 @@ inline int parse_hash_suite(const char* name) {  // -1: not a suite this library
     return -1;
 }
 inline const char* hash_suite_name(int s) { return HASH_SUITE_NAMES[s]; }
-
-// MerkleTreeProver / MerkleTreeVerifier: the layer a seal carries in full, the deepest one with at most BX_QUERIES nodes.  Prover
-// and verifier lay the seal out by this one rule.
-inline unsigned top_layer_of(unsigned layers) {
-    unsigned top = 0;
-    while (top + 1 < layers && (2u << top) <= BX_QUERIES) ++top;
-    return top;
-}
 
 // The host half of a hash suite: the element hash of Merkle leaves and of what the transcript absorbs, and the pair hash of Merkle
 // interior nodes.  Poseidon2's pair hash is its 16-word sponge; SHA-256's is one compression (sha256_suite.hpp, convention 3).

@@ -13,6 +13,7 @@
 
 #include "circuit.hpp"
 #include "ctx.hpp"
+#include "seal_layout.hpp"
 #include "transcript.hpp"
 #include "../../include/bx_lookup.h"
 
@@ -34,22 +35,15 @@ __global__ void merkle_query_gather_kernel(uint32_t* __restrict__ out, const uin
     }
 }
 
-struct Tree {
-    size_t rows = 0, cols = 0;
-    unsigned layers = 0, top_layer = 0;
+struct Tree : TreeGeom {
     DevBuf nodes;
     uint32_t root[8];
-    size_t top_size() const { return (size_t)1 << top_layer; }
-    unsigned depth() const { return layers - top_layer; }
-    size_t query_words() const { return cols + 8u * depth(); }
 };
 
 struct Group {
     uint32_t width = 0;
     DevBuf coeffs, evaluated, combo_ids;
     Tree tree;
-    std::vector<std::vector<uint32_t>> backs;  // tap set per column: the rows back it is opened at (backs[c][0] == 0)
-    std::vector<uint32_t> combo;               // combo of each column (columns with the same tap set share one)
 };
 
 // One of the prover's two staging slots for a segment's bytes (bx_prover_submit_segment): pinned host copy -> HBM copy on the
@@ -64,7 +58,6 @@ struct SegSlot {
 };
 
 struct FriRound {
-    size_t size = 0;  // ext coefficients entering the round
     DevBuf evaluated, out_coeffs;
     Tree tree;
 };
@@ -75,10 +68,9 @@ using namespace bx;
 
 struct bx_prover {
     bx_ctx* c = nullptr;
-    bx_segment_params shape{};  // normalised by the circuit (defaults filled in)
+    SealLayout lay;  // the normalised shape and every integer that follows from it and the circuit's tap sets (seal_layout.hpp)
     const bx_circuit_ops* circ = nullptr;  // the circuit half: witgen / accumulate / eval_check / tap set (bx_circuit.h)
     void* circ_state = nullptr;
-    size_t N = 0;
     bool coeffs_bitrev = false;  // trace coefficients stay in bit-reversed order (N >= 2^15), see commit_group
     HostPoseidon2 h2;
     HostSuite hs;  // the ctx's hash suite at create time (bx_set_hash_suite is refused while the prover lives): h2 or SHA-256
@@ -93,11 +85,6 @@ struct bx_prover {
     bool code_committed = false;     // groups[0].{coeffs,evaluated,tree.nodes}, code_w and code_top are this shape's; dropped by any error
     std::vector<uint32_t> code_top;  // root + top layer of groups[0].tree as fetched: 8 * (2 * top_size - 1) words
     DevBuf tap_ptrs, tap_flags;  // per tap evaluation: the device address of its coefficient column and its storage order (N >= 2^15)
-    std::vector<std::vector<uint32_t>> combo_backs;  // trace combos in order of first appearance; the check combo comes after them
-    std::vector<uint32_t> tap_which;                 // polynomial index of every tap evaluation (fixed per shape)
-    size_t tap_first[5] = {0, 0, 0, 0, 0};           // first tap evaluation of each group
-    size_t n_div = 0;                                // DEEP divisions per proof
-    uint32_t n_globals = 0;                          // public words of the statement (bx_circuit_ops::n_globals)
     ~bx_prover() {
         if (circ && circ_state && circ->destroy) circ->destroy(circ->user, circ_state);
         if (copy_stream) (void)hipStreamSynchronize(copy_stream);  // a segment submitted and never proved may still be on its way up
@@ -113,7 +100,6 @@ struct bx_prover {
     DevBuf final_coeffs;
     DevBuf tstate, dev_chal;  // device half of the transcript: 24 cells + pool counter; the challenges it drew (4 words per step)
     uint32_t last_roots[32];
-    size_t seal_bound = 0;
     char err[512];
     bool prologue_done = false;  // prove_prologue was already enqueued for the next bx_prove_submitted
     char seg_err[256];  // bx_prover_submit_segment may run on another thread than the proof: its own message buffer
@@ -138,12 +124,9 @@ const char* perr(bx_prover* p, const char* m) {
         if (_m) return perr(p, _m);               \
     } while (0)
 
-const char* tree_init(bx_ctx* c, Tree& t, size_t rows, size_t cols) {
-    t.rows = rows;
-    t.cols = cols;
-    t.layers = (unsigned)ilog2(rows);
-    t.top_layer = top_layer_of(t.layers);
-    return t.nodes.alloc(c, 16 * rows);
+const char* tree_init(bx_ctx* c, Tree& t, const TreeGeom& geom) {
+    static_cast<TreeGeom&>(t) = geom;
+    return t.nodes.alloc(c, 16 * t.rows);
 }
 
 // MerkleTreeProver::new: leaves + every layer, enqueued; nothing is read back
@@ -208,8 +191,6 @@ const char* commit_group(bx_prover* p, Group& g, Transcript& T) {
     return nullptr;
 }
 
-Fp4 host_pow(Fp4 a, uint64_t e) { return f4_pow(a, e); }
-
 }  // namespace
 
 extern "C" const char* bx_merkle_query_gather(bx_ctx* c, bx_buf out, bx_buf matrix, bx_buf nodes, size_t rows, size_t cols,
@@ -246,11 +227,17 @@ extern "C" const char* bx_prover_create_with_circuit(bx_ctx* c, const bx_segment
     std::unique_ptr<bx_prover> p(new (std::nothrow) bx_prover());
     BX_REQUIRE(c, p != nullptr, "bx_prover_create: out of host memory");
     p->c = c;
-    p->shape = *shape;
     p->circ = circuit;
+    bx_segment_params norm = *shape;
     if (circuit->normalize)
-        if (const char* e = circuit->normalize(circuit->user, &p->shape)) return set_msg(c, e);
-    p->N = (size_t)1 << shape->po2;
+        if (const char* e = circuit->normalize(circuit->user, &norm)) return set_msg(c, e);
+    // every integer of the proof, before anything is allocated: a circuit table that is refused has cost nothing
+    p->lay = seal_layout(norm, circuit);
+    const SealLayout& L = p->lay;
+    if (L.error) {
+        snprintf(c->err, sizeof c->err, "bx_prover_create: %s", L.error);
+        return c->err;
+    }
     p->coeffs_bitrev = shape->po2 >= 15 && c->deep_bitrev;
     // only the built-in circuits are known to the library to be shape-only (synth_code_cell / lookup_code_cell with a constant seed); a
     // plug-in's code_group is opaque and is called for every proof
@@ -258,70 +245,36 @@ extern "C" const char* bx_prover_create_with_circuit(bx_ctx* c, const bx_segment
     p->err[0] = 0;
     p->h2.load(c->h_rc, c->h_diag);
     p->hs = HostSuite{c->hash_suite, &p->h2};
-    const size_t N = p->N, D = 4 * N;
-    const uint32_t widths[4] = {shape->w_code, shape->w_data, shape->w_accum, BX_CHECK_SIZE};
-    size_t total_taps = 0, max_w = 0;
+    const size_t N = L.N, total_taps = L.total_taps;
     for (int g = 0; g < 4; ++g) {
         Group& G = p->groups[g];
-        G.width = widths[g];
-        max_w = std::max<size_t>(max_w, G.width);
+        G.width = L.widths[g];
         BX_TRY(G.coeffs.alloc(c, (size_t)G.width * N));
-        BX_TRY(G.evaluated.alloc(c, (size_t)G.width * D));
-        BX_TRY(tree_init(c, G.tree, D, G.width));
-        // the circuit's tap set (bx_circuit.h): every column is opened at Z and at the rows back its set lists; columns with
-        // the same set share a combo, combos are numbered in order of first appearance, the check group's comes last
-        G.backs.resize(G.width);
-        G.combo.resize(G.width);
-        for (uint32_t col = 0; col < G.width; ++col) {
-            if (g == 3) {
-                G.backs[col] = {0};
-                continue;
-            }
-            uint32_t bk[BX_MAX_TAPS];
-            const uint32_t k = circuit->taps(circuit->user, &p->shape, g, col, bk);
-            BX_REQUIRE(c, k >= 1 && k <= BX_MAX_TAPS && bk[0] == 0, "bx_prover_create: a tap set has 1..8 entries and starts with 0");
-            for (uint32_t t = 1; t < k; ++t) BX_REQUIRE(c, bk[t] > bk[t - 1] && bk[t] < N, "bx_prover_create: tap sets are strictly increasing");
-            G.backs[col].assign(bk, bk + k);
-            size_t id = 0;
-            while (id < p->combo_backs.size() && p->combo_backs[id] != G.backs[col]) ++id;
-            if (id == p->combo_backs.size()) p->combo_backs.push_back(G.backs[col]);
-            G.combo[col] = (uint32_t)id;
-        }
+        BX_TRY(G.evaluated.alloc(c, (size_t)G.width * 4 * N));
+        BX_TRY(tree_init(c, G.tree, L.trees[g]));
     }
-    BX_REQUIRE(c, p->combo_backs.size() + 1 <= BX_MAX_COMBOS, "bx_prover_create: too many distinct tap sets");
-    const size_t n_combos = p->combo_backs.size() + 1;
     for (int g = 0; g < 4; ++g) {
         Group& G = p->groups[g];
-        if (g == 3) G.combo.assign(G.width, (uint32_t)(n_combos - 1));
         BX_TRY(G.combo_ids.alloc(c, G.width));
-        BX_TRY(bx_h2d(c, G.combo_ids.b, G.combo.data(), G.width));
-        for (uint32_t col = 0; col < G.width; ++col) {
-            for (size_t t = 0; t < G.backs[col].size(); ++t) p->tap_which.push_back(col);
-            total_taps += G.backs[col].size();
-        }
-        p->tap_first[g + 1] = p->tap_which.size();
+        BX_TRY(bx_h2d(c, G.combo_ids.b, L.combo[g].data(), G.width));
     }
-    p->n_div = 1;
-    for (auto& cb : p->combo_backs) p->n_div += cb.size();
     if (circuit->create)
-        if (const char* e = circuit->create(circuit->user, c, &p->shape, &p->circ_state)) return e == c->err ? e : set_msg(c, e);
-    p->n_globals = circuit->n_globals ? circuit->n_globals(circuit->user, &p->shape) : 0;
-    BX_REQUIRE(c, p->n_globals <= BX_MAX_GLOBALS, "bx_prover_create: too many public words");
+        if (const char* e = circuit->create(circuit->user, c, &p->lay.shape, &p->circ_state)) return e == c->err ? e : set_msg(c, e);
     BX_TRY(p->code_w.alloc(c, (size_t)shape->w_code * N));
-    BX_TRY(p->combos.alloc(c, n_combos * 4 * N));
+    BX_TRY(p->combos.alloc(c, L.n_combos * 4 * N));
     BX_TRY(p->final_poly.alloc(c, 4 * N));
     // tap evaluations of all four groups go up, run and come back as one batch (one host round trip instead of twelve)
     BX_TRY(p->which.alloc(c, total_taps));
     BX_TRY(p->xs.alloc(c, 4 * total_taps));
     BX_TRY(p->evals.alloc(c, 4 * total_taps));
-    BX_TRY(p->rems.alloc(c, 4 * p->n_div));
-    BX_TRY(bx_h2d(c, p->which.slice(0, total_taps), p->tap_which.data(), total_taps));  // fixed per shape
+    BX_TRY(p->rems.alloc(c, 4 * L.n_div));
+    BX_TRY(bx_h2d(c, p->which.slice(0, total_taps), L.tap_which.data(), total_taps));  // fixed per shape
     if (N >= ((size_t)1 << 15)) {  // all four groups' taps in one launch set (bx_batch_evaluate_ptrs)
         std::vector<uint32_t> ptrs(2 * total_taps), flags(total_taps);
         size_t e = 0;
         for (int g = 0; g < 4; ++g)
-            for (size_t t = p->tap_first[g]; t < p->tap_first[g + 1]; ++t, ++e) {
-                const unsigned long long a = (unsigned long long)(uintptr_t)((uint32_t*)p->groups[g].coeffs.b.dptr + (size_t)p->tap_which[t] * N);
+            for (size_t t = L.tap_first[g]; t < L.tap_first[g + 1]; ++t, ++e) {
+                const unsigned long long a = (unsigned long long)(uintptr_t)((uint32_t*)p->groups[g].coeffs.b.dptr + (size_t)L.tap_which[t] * N);
                 ptrs[2 * e] = (uint32_t)a;
                 ptrs[2 * e + 1] = (uint32_t)(a >> 32);
                 flags[e] = (p->coeffs_bitrev && g < 3) ? 1u : 0u;
@@ -331,38 +284,19 @@ extern "C" const char* bx_prover_create_with_circuit(bx_ctx* c, const bx_segment
         BX_TRY(bx_h2d(c, p->tap_ptrs.b, ptrs.data(), ptrs.size()));
         BX_TRY(bx_h2d(c, p->tap_flags.b, flags.data(), flags.size()));
     }
-    // FRI rounds
-    size_t size = N;
-    size_t fri_query_words = 0;
-    p->rounds.reserve(8);
-    while (size > BX_FRI_MIN_DEGREE) {
-        p->rounds.emplace_back();
-        FriRound& r = p->rounds.back();
-        r.size = size;
-        BX_TRY(r.evaluated.alloc(c, 4 * 4 * size));
-        BX_TRY(r.out_coeffs.alloc(c, 4 * size / BX_FRI_FOLD));
-        BX_TRY(tree_init(c, r.tree, 4 * size / BX_FRI_FOLD, 4 * BX_FRI_FOLD));
-        fri_query_words += r.tree.query_words();
-        size /= BX_FRI_FOLD;
+    p->rounds.resize(L.rounds.size());
+    for (size_t i = 0; i < L.rounds.size(); ++i) {
+        FriRound& r = p->rounds[i];
+        BX_TRY(r.evaluated.alloc(c, 4 * 4 * L.rounds[i].size));
+        BX_TRY(r.out_coeffs.alloc(c, 4 * L.rounds[i].size / BX_FRI_FOLD));
+        BX_TRY(tree_init(c, r.tree, L.rounds[i].tree));
     }
-    BX_TRY(p->final_coeffs.alloc(c, 4 * size));
+    BX_TRY(p->final_coeffs.alloc(c, 4 * L.final_size));
     BX_TRY(p->tstate.alloc(c, 32));
     BX_TRY(p->dev_chal.alloc(c, 4 * (p->rounds.size() + 4)));
-    size_t max_q = 0, trace_query_words = 0;
-    for (int g = 0; g < 4; ++g) {
-        max_q = std::max(max_q, p->groups[g].tree.query_words());
-        trace_query_words += p->groups[g].tree.query_words();
-    }
-    for (auto& r : p->rounds) max_q = std::max(max_q, r.tree.query_words());
     // the 50 openings of every tree are gathered into one buffer and copied back together
-    BX_TRY(p->positions.alloc(c, BX_QUERIES * (4 + p->rounds.size())));
-    BX_TRY(p->qout.alloc(c, (trace_query_words + fri_query_words) * BX_QUERIES));
-    // seal bound: header + tops + coeff_u + final coeffs + queries
-    size_t bound = BX_SEAL_HEADER_WORDS + p->n_globals;
-    for (int g = 0; g < 4; ++g) bound += 8 * p->groups[g].tree.top_size();
-    for (auto& r : p->rounds) bound += 8 * r.tree.top_size();
-    bound += 4 * total_taps + 4 * size + BX_QUERIES * (trace_query_words + fri_query_words);
-    p->seal_bound = bound;
+    BX_TRY(p->positions.alloc(c, BX_QUERIES * L.n_trees()));
+    BX_TRY(p->qout.alloc(c, L.per_query * BX_QUERIES));
     memset(p->last_roots, 0, sizeof p->last_roots);
     BX_HIP(c, hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking));
     for (SegSlot& sl : p->seg) {
@@ -383,7 +317,7 @@ extern "C" const char* bx_prover_destroy(bx_prover* p) try {
     delete p;
     return nullptr;
 } BX_ABI_CATCH(nullptr, "bx_prover_destroy")  // p may be gone by then
-extern "C" size_t bx_prover_seal_words(const bx_prover* p) { return p ? p->seal_bound : 0; }
+extern "C" size_t bx_prover_seal_words(const bx_prover* p) { return p ? p->lay.seal_words : 0; }
 extern "C" const char* bx_prover_last_roots(const bx_prover* p, uint32_t roots_out[32]) try {
     if (!p) return "bx_prover_last_roots: null prover";
     memcpy(roots_out, p->last_roots, sizeof p->last_roots);
@@ -517,7 +451,7 @@ extern "C" const char* bx_prover_set_noise_seed(bx_prover* p, uint64_t noise_see
 extern "C" const char* bx_prove_segment(bx_prover* p, uint64_t seed, uint32_t* seal_out, size_t seal_cap, size_t* seal_words) try {
     if (!p) return "bx_prove_segment: null prover";
     uint8_t wire[BX_SEGMENT_WIRE_BYTES];
-    bx_segment_encode(0, p->shape.po2, seed, wire);  // the circuit derives the noise seed from the seed
+    bx_segment_encode(0, p->lay.shape.po2, seed, wire);  // the circuit derives the noise seed from the seed
     return bx_prove_segment_bytes(p, wire, sizeof wire, seal_out, seal_cap, seal_words);
 } BX_ABI_CATCH((p ? p->c : nullptr), "bx_prove_segment")
 extern "C" const char* bx_prove_segment_zk(bx_prover* p, uint64_t seed, uint64_t noise_seed, uint32_t* seal_out, size_t seal_cap, size_t* seal_words) try {
@@ -556,107 +490,129 @@ extern "C" const char* bx_prover_control_id(bx_prover* p, uint32_t id_out[8]) tr
     return r;
 } BX_ABI_CATCH((p ? p->c : nullptr), "bx_prover_control_id")
 
-static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t* seal_out, size_t seal_cap, size_t* seal_words) {
-    bx_ctx* c = p->c;
-    if (hipSetDevice(c->device) != hipSuccess) return perr(p, "bx_prove_segment: hipSetDevice failed");
-    const size_t N = p->N, D = 4 * N;
-    const uint32_t po2 = p->shape.po2;
-    Transcript T(p->hs);
-    T.seal.reserve(p->seal_bound);
-    TraceRange whole(c, "bx:prove_segment");
+// ---- one proof: the stages of DESIGN.md section 1, in transcript order.  Every length, count and offset they use is the layout's
+//      (p->lay); what one stage leaves for the next is in Proof. ----
+namespace {
 
-    // ---- header ----
-    {
-        uint32_t hdr[BX_SEAL_HEADER_WORDS] = {po2, p->shape.w_code, p->shape.w_data, p->shape.w_accum, p->shape.cons_terms, p->shape.cons_degree};
-        uint32_t enc[BX_SEAL_HEADER_WORDS], dg[8];
-        for (int i = 0; i < BX_SEAL_HEADER_WORDS; ++i) enc[i] = fp_encode(hdr[i]);
-        T.write(hdr, BX_SEAL_HEADER_WORDS);
-        p->hs.hash_elems(dg, enc, BX_SEAL_HEADER_WORDS);
-        T.commit(dg);
-    }
-    // ---- witness generation (code + data), then the commits in transcript order; the accumulate step needs the
-    //      challenge drawn after the data commit, like upstream's accum mix ----
+struct Proof {
+    Transcript T;
+    Fp4 beta = f4_zero();              // the accumulators' mix, drawn after the data commit
+    uint32_t globals[BX_MAX_GLOBALS];  // the statement's public words as witgen produced them
+    Fp4 Z = f4_zero(), Z4 = f4_zero();  // the DEEP point, and the check columns' point Z^4 / 3
+    std::vector<std::vector<Fp4>> pts;  // per trace combo: the points Z * w_N^-b of its tap set
+    std::vector<uint32_t> coeff_u;      // flattened ext elems, column by column, group by group
+    explicit Proof(const HostSuite& hs) : T(hs) { memset(globals, 0, sizeof globals); }
+};
+
+void write_header(bx_prover* p, Proof& pf) {
+    const bx_segment_params& sh = p->lay.shape;
+    uint32_t hdr[BX_SEAL_HEADER_WORDS] = {sh.po2, sh.w_code, sh.w_data, sh.w_accum, sh.cons_terms, sh.cons_degree};
+    uint32_t enc[BX_SEAL_HEADER_WORDS], dg[8];
+    for (int i = 0; i < BX_SEAL_HEADER_WORDS; ++i) enc[i] = fp_encode(hdr[i]);
+    pf.T.write(hdr, BX_SEAL_HEADER_WORDS);
+    p->hs.hash_elems(dg, enc, BX_SEAL_HEADER_WORDS);
+    pf.T.commit(dg);
+}
+
+// witness generation (code + data), the public words, then the commits in transcript order
+const char* witgen_and_commit(bx_prover* p, Proof& pf, const SegSlot& seg) {
+    bx_ctx* c = p->c;
     const bx_circuit_ops* circ = p->circ;
-    Fp4 beta = f4_zero();
-    uint32_t globals[BX_MAX_GLOBALS];
-    memset(globals, 0, sizeof globals);
+    Transcript& T = pf.T;
+    const uint32_t n_globals = p->lay.n_globals;
     {
         TraceRange tr(c, "bx:witgen");  // the code group and its commitment are kept from an earlier proof or already enqueued (prove_prologue)
         PV(circ->witgen(circ->user, p->circ_state, c, p->code_w.b, p->groups[1].coeffs.b, seg.host, seg.len,
-                        bx_buf{seg.dev, (seg.len + 3) / 4}, globals));
+                        bx_buf{seg.dev, (seg.len + 3) / 4}, pf.globals));
     }
-    if (p->n_globals) {  // the statement's public words: in the seal and in the transcript before any commitment
+    if (n_globals) {  // the statement's public words: in the seal and in the transcript before any commitment
         uint32_t dg[8];
-        for (uint32_t i = 0; i < p->n_globals; ++i)
-            if (globals[i] >= P) return perr(p, "bx_prove_segment: the circuit produced a non-canonical public word");
-        T.write(globals, p->n_globals);
-        p->hs.hash_elems(dg, globals, p->n_globals);
+        for (uint32_t i = 0; i < n_globals; ++i)
+            if (pf.globals[i] >= P) return perr(p, "bx_prove_segment: the circuit produced a non-canonical public word");
+        T.write(pf.globals, n_globals);
+        p->hs.hash_elems(dg, pf.globals, n_globals);
         T.commit(dg);
     }
-    {   // code and data: neither commit needs anything from the transcript, so both are enqueued and ONE round trip brings back both
-        // roots and top layers; the transcript absorbs them in order (code, then data) and only then is beta drawn
-        size_t used = 0;
-        const uint32_t* host[2] = {nullptr, nullptr};
-        TraceRange tr(c, "bx:commit_data");
-        PV(commit_group_work(p, p->groups[1]));
-        if (!p->code_committed) PV(tree_fetch(p, p->groups[0].tree, &used, &host[0]));
-        PV(tree_fetch(p, p->groups[1].tree, &used, &host[1]));
-        PV(d2h_batch_wait(c));
-        if (p->code_committed) {
-            host[0] = p->code_top.data();  // the code tree's root and top layer as the first proof fetched them
-        } else if (p->code_once) {
-            p->code_top.assign(host[0], host[0] + 8 * (2 * p->groups[0].tree.top_size() - 1));
-            p->code_committed = true;
-        }
-        for (int g = 0; g < 2; ++g) {
-            tree_absorb(p->groups[g].tree, host[g], T);
-            memcpy(p->last_roots + 8 * g, p->groups[g].tree.root, 32);
-        }
+    // code and data: neither commit needs anything from the transcript, so both are enqueued and ONE round trip brings back both
+    // roots and top layers; the transcript absorbs them in order (code, then data) and only then is beta drawn
+    size_t used = 0;
+    const uint32_t* host[2] = {nullptr, nullptr};
+    TraceRange tr(c, "bx:commit_data");
+    PV(commit_group_work(p, p->groups[1]));
+    if (!p->code_committed) PV(tree_fetch(p, p->groups[0].tree, &used, &host[0]));
+    PV(tree_fetch(p, p->groups[1].tree, &used, &host[1]));
+    PV(d2h_batch_wait(c));
+    if (p->code_committed) {
+        host[0] = p->code_top.data();  // the code tree's root and top layer as the first proof fetched them
+    } else if (p->code_once) {
+        p->code_top.assign(host[0], host[0] + 8 * (2 * p->groups[0].tree.top_size() - 1));
+        p->code_committed = true;
     }
+    for (int g = 0; g < 2; ++g) {
+        tree_absorb(p->groups[g].tree, host[g], T);
+        memcpy(p->last_roots + 8 * g, p->groups[g].tree.root, 32);
+    }
+    return nullptr;
+}
+
+// the accumulate step needs the challenge drawn after the data commit, like upstream's accum mix
+const char* accumulate_and_commit(bx_prover* p, Proof& pf) {
+    bx_ctx* c = p->c;
+    const bx_circuit_ops* circ = p->circ;
+    Group& G = p->groups[2];
+    pf.beta = pf.T.random_ext();
     {
-        Group& G = p->groups[2];
-        beta = T.random_ext();
-        {
-            TraceRange tr(c, "bx:accumulate");
-            PV(circ->accumulate(circ->user, p->circ_state, c, G.coeffs.b, beta.c));  // CircuitHal::accumulate
-        }
-        TraceRange tr(c, "bx:commit_accum");
-        PV(commit_group(p, G, T));
-        memcpy(p->last_roots + 16, G.tree.root, 32);
+        TraceRange tr(c, "bx:accumulate");
+        PV(circ->accumulate(circ->user, p->circ_state, c, G.coeffs.b, pf.beta.c));  // CircuitHal::accumulate
     }
-    // ---- eval_check: the constraint polynomial over the 4N domain, divided by the vanishing polynomial ----
+    TraceRange tr(c, "bx:commit_accum");
+    PV(commit_group(p, G, pf.T));
+    memcpy(p->last_roots + 16, G.tree.root, 32);
+    return nullptr;
+}
+
+// eval_check: the constraint polynomial over the 4N domain, divided by the vanishing polynomial
+const char* eval_check_and_commit(bx_prover* p, Proof& pf) {
+    bx_ctx* c = p->c;
+    const bx_circuit_ops* circ = p->circ;
     Group& CK = p->groups[3];
+    Fp4 poly_mix = pf.T.random_ext();
+    // the 16N-word check buffer holds the 4 ext planes over the 4N domain                       (CircuitHal::eval_check)
     {
-        Fp4 poly_mix = T.random_ext();
-        // the 16N-word check buffer holds the 4 ext planes over the 4N domain                       (CircuitHal::eval_check)
-        {
-            TraceRange tr(c, "bx:eval_check");
-            PV(circ->eval_check(circ->user, p->circ_state, c, CK.coeffs.b, p->groups[0].evaluated.b, p->groups[1].evaluated.b,
-                                p->groups[2].evaluated.b, poly_mix.c, beta.c, globals));
-        }
-        TraceRange tr(c, "bx:commit_check");
-        PV(bx_batch_interpolate_ntt(c, CK.coeffs.b, 4));        // 4 polynomials of size 4N
-        PV(bx_zk_shift(c, CK.coeffs.b, BX_CHECK_SIZE));         // viewed as 16 polynomials of size N
-        PV(bx_batch_expand_into_evaluate_ntt(c, CK.evaluated.b, CK.coeffs.b, BX_CHECK_SIZE, 2));
-        PV(bx_batch_bit_reverse(c, CK.coeffs.b, BX_CHECK_SIZE));
-        PV(tree_commit(p, CK.tree, CK.evaluated.b, T));
-        memcpy(p->last_roots + 24, CK.tree.root, 32);
+        TraceRange tr(c, "bx:eval_check");
+        PV(circ->eval_check(circ->user, p->circ_state, c, CK.coeffs.b, p->groups[0].evaluated.b, p->groups[1].evaluated.b,
+                            p->groups[2].evaluated.b, poly_mix.c, pf.beta.c, pf.globals));
     }
-    // ---- DEEP: evaluate every tap at Z * back_one^back, write/commit coeff_u ----
-    TraceStages stage(c);
-    stage.next("bx:deep_taps");
-    const Fp4 Z = T.random_ext();
-    const uint32_t back_one = fp_inv(fp_pow(fp_encode(137u), (uint64_t)1 << (27 - po2)));  // ROU_REV[po2] = w_N^-1
+    TraceRange tr(c, "bx:commit_check");
+    PV(bx_batch_interpolate_ntt(c, CK.coeffs.b, 4));        // 4 polynomials of size 4N
+    PV(bx_zk_shift(c, CK.coeffs.b, BX_CHECK_SIZE));         // viewed as 16 polynomials of size N
+    PV(bx_batch_expand_into_evaluate_ntt(c, CK.evaluated.b, CK.coeffs.b, BX_CHECK_SIZE, 2));
+    PV(bx_batch_bit_reverse(c, CK.coeffs.b, BX_CHECK_SIZE));
+    PV(tree_commit(p, CK.tree, CK.evaluated.b, pf.T));
+    memcpy(p->last_roots + 24, CK.tree.root, 32);
+    return nullptr;
+}
+
+// DEEP: evaluate every tap at Z * back_one^back, write/commit coeff_u
+const char* deep_taps(bx_prover* p, Proof& pf) {
+    bx_ctx* c = p->c;
+    const SealLayout& L = p->lay;
+    const size_t N = L.N;
+    pf.Z = pf.T.random_ext();
+    const Fp4 Z = pf.Z;
+    const uint32_t back_one = fp_inv(fp_pow(fp_encode(137u), (uint64_t)1 << (27 - L.shape.po2)));  // ROU_REV[po2] = w_N^-1
     // check columns hold g(3z) of the split check(y) = sum_q y^q g_q(y^4), so their tap is z = Z^4 / 3: the verifier can
     // then test check(Z) against the trace taps (verify.cpp)
-    const Fp4 Z4 = f4_scale(host_pow(Z, 4), fp_inv(MONT_THREE));
-    const size_t n_trace_combos = p->combo_backs.size(), n_combos = n_trace_combos + 1;
+    pf.Z4 = f4_scale(f4_pow(Z, 4), fp_inv(MONT_THREE));
+    const size_t n_trace_combos = L.n_trace_combos;
     // per combo: the points Z * w_N^-b of its tap set and the matrix that turns the values there into the coefficients of the
     // interpolating polynomial (PolyGroup / Prover::finalize: `poly_interpolate` per register; the points are shared by all
     // registers of a combo, so the Lagrange basis is expanded once per combo)
-    std::vector<std::vector<Fp4>> pts(n_trace_combos), interp(n_trace_combos);
+    std::vector<std::vector<Fp4>>& pts = pf.pts;
+    std::vector<std::vector<Fp4>> interp(n_trace_combos);
+    pts.assign(n_trace_combos, {});
     for (size_t id = 0; id < n_trace_combos; ++id) {
-        const auto& B = p->combo_backs[id];
+        const auto& B = L.combo_backs[id];
         const size_t k = B.size();
         for (uint32_t b : B) pts[id].push_back(f4_scale(Z, fp_pow(back_one, b)));
         interp[id].assign(k * k, f4_zero());  // interp[t * k + i] = coefficient t of the basis polynomial L_i
@@ -677,25 +633,23 @@ static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t
             for (size_t t = 0; t < k; ++t) interp[id][t * k + i] = f4_mul(poly[t], inv);
         }
     }
-    std::vector<uint32_t> coeff_u;  // flattened ext elems, column by column, group by group
+    std::vector<uint32_t>& coeff_u = pf.coeff_u;
     {
         std::vector<uint32_t> xs;
-        for (int g = 0; g < 4; ++g) {
-            Group& G = p->groups[g];
-            for (uint32_t col = 0; col < G.width; ++col)
-                for (size_t t = 0; t < G.backs[col].size(); ++t) {
-                    const Fp4& x = g == 3 ? Z4 : pts[G.combo[col]][t];
+        for (int g = 0; g < 4; ++g)
+            for (uint32_t col = 0; col < L.widths[g]; ++col)
+                for (size_t t = 0; t < L.backs(g, col).size(); ++t) {
+                    const Fp4& x = g == 3 ? pf.Z4 : pts[L.combo[g][col]][t];
                     xs.insert(xs.end(), x.c, x.c + 4);
                 }
-        }
-        const size_t ne_all = p->tap_which.size();
+        const size_t ne_all = L.total_taps;
         PV(h2d_staged(c, p->xs.slice(0, 4 * ne_all), xs.data(), 4 * ne_all));  // no wait: the evaluations' read-back below is the round trip
         if (p->tap_ptrs.b.dptr) {
             PV(bx_batch_evaluate_ptrs(c, p->tap_ptrs.b, p->tap_flags.b, N, p->xs.slice(0, 4 * ne_all), p->evals.slice(0, 4 * ne_all)));
         } else {
             for (int g = 0; g < 4; ++g) {
                 Group& G = p->groups[g];
-                const size_t o = p->tap_first[g], ne = p->tap_first[g + 1] - p->tap_first[g];
+                const size_t o = L.tap_first[g], ne = L.tap_first[g + 1] - L.tap_first[g];
                 if (p->coeffs_bitrev && g < 3)
                     PV(bx_batch_evaluate_any_bitrev(c, G.coeffs.b, G.width, p->which.slice(o, ne), p->xs.slice(4 * o, 4 * ne), p->evals.slice(4 * o, 4 * ne)));
                 else
@@ -705,14 +659,13 @@ static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t
         std::vector<uint32_t> ev(4 * ne_all);
         PV(bx_d2h(c, ev.data(), p->evals.slice(0, 4 * ne_all), 4 * ne_all));
         size_t e = 0;
-        for (int g = 0; g < 4; ++g) {
-            Group& G = p->groups[g];
-            for (uint32_t col = 0; col < G.width; ++col) {
-                const size_t k = G.backs[col].size();
+        for (int g = 0; g < 4; ++g)
+            for (uint32_t col = 0; col < L.widths[g]; ++col) {
+                const size_t k = L.backs(g, col).size();
                 if (k == 1) {  // a single tap: the "polynomial" is the value itself
                     coeff_u.insert(coeff_u.end(), ev.begin() + 4 * e, ev.begin() + 4 * e + 4);
                 } else {
-                    const auto& M = interp[G.combo[col]];
+                    const auto& M = interp[L.combo[g][col]];
                     for (size_t t = 0; t < k; ++t) {
                         Fp4 ct = f4_zero();
                         for (size_t i = 0; i < k; ++i) {
@@ -724,17 +677,22 @@ static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t
                 }
                 e += k;
             }
-        }
     }
-    {
-        uint32_t dg[8];
-        T.write(coeff_u.data(), coeff_u.size());
-        p->hs.hash_elems(dg, coeff_u.data(), coeff_u.size());
-        T.commit(dg);
-    }
-    // ---- DEEP: mix every column into its combo, subtract the mixed u polynomials, divide by every tap point ----
-    stage.next("bx:deep_combos");
-    const Fp4 mix = T.random_ext();
+    uint32_t dg[8];
+    pf.T.write(coeff_u.data(), coeff_u.size());
+    p->hs.hash_elems(dg, coeff_u.data(), coeff_u.size());
+    pf.T.commit(dg);
+    return nullptr;
+}
+
+// DEEP: mix every column into its combo, subtract the mixed u polynomials, divide by every tap point
+const char* deep_combos(bx_prover* p, Proof& pf) {
+    bx_ctx* c = p->c;
+    const SealLayout& L = p->lay;
+    const size_t N = L.N, n_trace_combos = L.n_trace_combos, n_combos = L.n_combos;
+    const std::vector<std::vector<Fp4>>& pts = pf.pts;
+    const std::vector<uint32_t>& coeff_u = pf.coeff_u;
+    const Fp4 mix = pf.T.random_ext();
     if (hipMemsetAsync(p->combos.b.dptr, 0, p->combos.b.len * 4, c->stream) != hipSuccess) return perr(p, "bx_prove_segment: memset failed");
     {
         Fp4 cur = f4_one();
@@ -744,8 +702,8 @@ static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t
             Group& G = p->groups[g];
             PV(bx_mix_poly_coeffs(c, p->combos.b, cur.c, mix.c, G.coeffs.b, G.combo_ids.b, G.width, N));
             for (uint32_t col = 0; col < G.width; ++col) {
-                const uint32_t id = G.combo[col];
-                for (size_t t = 0; t < G.backs[col].size(); ++t, u += 4) {
+                const uint32_t id = L.combo[g][col];
+                for (size_t t = 0; t < L.combo_backs[id].size(); ++t, u += 4) {
                     Fp4 cu{{coeff_u[u], coeff_u[u + 1], coeff_u[u + 2], coeff_u[u + 3]}};
                     combo_u[id * BX_MAX_TAPS + t] = f4_add(combo_u[id * BX_MAX_TAPS + t], f4_mul(cur, cu));
                 }
@@ -778,7 +736,7 @@ static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t
                 }
             if (r == 0) {
                 which[cnt] = (uint32_t)n_trace_combos;
-                memcpy(zs + 4 * cnt++, Z4.c, 16);
+                memcpy(zs + 4 * cnt++, pf.Z4.c, 16);
             }
             if (!cnt) break;
             PV(bx_poly_divide_batch_indexed(c, p->combos.b, n_combos, cnt, which, zs, p->rems.slice(4 * d, 4 * cnt)));
@@ -789,113 +747,138 @@ static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t
     }
     PV(bx_eltwise_sum_extelem(c, p->final_poly.b, p->combos.b));
     PV(bx_batch_bit_reverse(c, p->final_poly.b, 4));
+    return nullptr;
+}
 
-    // ---- fri_prove ----
-    stage.next("bx:fri_prove");
-    {
-        bx_buf coeffs = p->final_poly.b;
-        // (Poseidon2 only: there is no device-side SHA-256 RNG, so a sha-256 prover draws on the host whatever dev_draws says)
-        const bool dev = c->dev_draws != 0 && !p->rounds.empty() && p->hs.suite == SUITE_POSEIDON2;
+const char* fri_prove(bx_prover* p, Proof& pf) {
+    bx_ctx* c = p->c;
+    Transcript& T = pf.T;
+    bx_buf coeffs = p->final_poly.b;
+    // (Poseidon2 only: there is no device-side SHA-256 RNG, so a sha-256 prover draws on the host whatever dev_draws says)
+    const bool dev = c->dev_draws != 0 && !p->rounds.empty() && p->hs.suite == SUITE_POSEIDON2;
+    if (dev) {
+        // A round's challenge depends on nothing but the round's root, so the device half of the transcript draws it
+        // (bx_transcript_step: 1-2 permutations on one quad, ~20 us) and the fold reads it from device memory: no host round trip
+        // inside the loop.  Roots, top layers, the drawn challenges and the final coefficients come back in ONE copy after the
+        // loop; the host transcript then replays the same commits (it writes the seal) and must draw the same words.
+        uint32_t st[25];
+        memcpy(st, T.cells(), 24 * sizeof(uint32_t));
+        st[24] = T.pool_used();
+        PV(h2d_staged(c, p->tstate.slice(0, 25), st, 25));
+    }
+    size_t ri = 0;
+    for (FriRound& r : p->rounds) {
+        PV(bx_batch_expand_into_evaluate_ntt(c, r.evaluated.b, coeffs, 4, 2));
         if (dev) {
-            // A round's challenge depends on nothing but the round's root, so the device half of the transcript draws it
-            // (bx_transcript_step: 1-2 permutations on one quad, ~20 us) and the fold reads it from device memory: no host round trip
-            // inside the loop.  Roots, top layers, the drawn challenges and the final coefficients come back in ONE copy after the
-            // loop; the host transcript then replays the same commits (it writes the seal) and must draw the same words.
-            uint32_t st[25];
-            memcpy(st, T.cells(), 24 * sizeof(uint32_t));
-            st[24] = T.pool_used();
-            PV(h2d_staged(c, p->tstate.slice(0, 25), st, 25));
-        }
-        size_t ri = 0;
-        for (FriRound& r : p->rounds) {
-            PV(bx_batch_expand_into_evaluate_ntt(c, r.evaluated.b, coeffs, 4, 2));
-            if (dev) {
-                PV(tree_build(p, r.tree, r.evaluated.b));
-                PV(bx_transcript_step(c, p->tstate.b, r.tree.nodes.slice(8, 8), 1, p->dev_chal.slice(4 * ri, 4), 1));
-                PV(bx_fri_fold_dev(c, r.out_coeffs.b, coeffs, p->dev_chal.slice(4 * ri, 4)));
-            } else {
-                PV(tree_commit(p, r.tree, r.evaluated.b, T));
-                Fp4 fold_mix = T.random_ext();
-                PV(bx_fri_fold(c, r.out_coeffs.b, coeffs, fold_mix.c));
-            }
-            coeffs = r.out_coeffs.b;
-            ++ri;
-        }
-        PV(bx_eltwise_copy_elem(c, p->final_coeffs.b, coeffs));
-        PV(bx_batch_bit_reverse(c, p->final_coeffs.b, 4));
-        const size_t nfc = p->final_coeffs.b.len;
-        std::vector<uint32_t> fc(nfc);
-        uint32_t dg[8];
-        if (dev) {
-            size_t used = 0;
-            std::vector<const uint32_t*> host(p->rounds.size(), nullptr);
-            const uint32_t *fc_host = nullptr, *chal = nullptr;
-            for (size_t i = 0; i < p->rounds.size(); ++i) PV(tree_fetch(p, p->rounds[i].tree, &used, &host[i]));
-            PV(d2h_batch_add(c, &used, p->dev_chal.slice(0, 4 * p->rounds.size()), 4 * p->rounds.size(), &chal));
-            PV(d2h_batch_add(c, &used, p->final_coeffs.b, nfc, &fc_host));
-            PV(d2h_batch_wait(c));
-            for (size_t i = 0; i < p->rounds.size(); ++i) {
-                tree_absorb(p->rounds[i].tree, host[i], T);
-                const Fp4 fold_mix = T.random_ext();
-                if (memcmp(fold_mix.c, chal + 4 * i, 16) != 0) return perr(p, "bx_prove_segment: the device transcript drew a different FRI challenge than the host transcript");
-            }
-            memcpy(fc.data(), fc_host, nfc * 4);
+            PV(tree_build(p, r.tree, r.evaluated.b));
+            PV(bx_transcript_step(c, p->tstate.b, r.tree.nodes.slice(8, 8), 1, p->dev_chal.slice(4 * ri, 4), 1));
+            PV(bx_fri_fold_dev(c, r.out_coeffs.b, coeffs, p->dev_chal.slice(4 * ri, 4)));
         } else {
-            PV(bx_d2h(c, fc.data(), p->final_coeffs.b, fc.size()));
+            PV(tree_commit(p, r.tree, r.evaluated.b, T));
+            Fp4 fold_mix = T.random_ext();
+            PV(bx_fri_fold(c, r.out_coeffs.b, coeffs, fold_mix.c));
         }
-        T.write(fc.data(), fc.size());
-        p->hs.hash_elems(dg, fc.data(), fc.size());
-        T.commit(dg);
+        coeffs = r.out_coeffs.b;
+        ++ri;
     }
-    // ---- queries: positions come only from the RNG (writes do not feed it), so draw all 50 first, gather each tree
-    //      for the whole batch on the device, then lay the seal out in upstream's query-major order ----
-    stage.next("bx:queries");
-    {
-        const unsigned bits = (unsigned)ilog2(D);
-        uint32_t pos0[BX_QUERIES];
-        for (int q = 0; q < BX_QUERIES; ++q) pos0[q] = T.random_bits(bits) % (uint32_t)D;
-        size_t n_trees = 4 + p->rounds.size();
-        std::vector<size_t> qw(n_trees), off(n_trees + 1, 0);
-        std::vector<uint32_t> all_pos(n_trees * BX_QUERIES);
-        uint32_t pos[BX_QUERIES];
-        memcpy(pos, pos0, sizeof pos);
-        for (size_t t = 0; t < n_trees; ++t) {
-            Tree& tr = t < 4 ? p->groups[t].tree : p->rounds[t - 4].tree;
-            if (t >= 4)
-                for (int q = 0; q < BX_QUERIES; ++q) pos[q] %= (uint32_t)tr.rows;  // group = pos % (domain / FRI_FOLD)
-            memcpy(all_pos.data() + t * BX_QUERIES, pos, sizeof pos);
-            qw[t] = tr.query_words();
-            off[t + 1] = off[t] + qw[t] * BX_QUERIES;
-        }
-        PV(h2d_staged(c, p->positions.b, all_pos.data(), all_pos.size()));
-        for (size_t t = 0; t < n_trees; ++t) {
-            Tree& tr = t < 4 ? p->groups[t].tree : p->rounds[t - 4].tree;
-            bx_buf matrix = t < 4 ? p->groups[t].evaluated.b : p->rounds[t - 4].evaluated.b;
-            PV(bx_merkle_query_gather(c, p->qout.slice(off[t], qw[t] * BX_QUERIES), matrix, tr.nodes.b, tr.rows, tr.cols,
-                                      p->positions.slice(t * BX_QUERIES, BX_QUERIES), BX_QUERIES, tr.top_size()));
-        }
+    PV(bx_eltwise_copy_elem(c, p->final_coeffs.b, coeffs));
+    PV(bx_batch_bit_reverse(c, p->final_coeffs.b, 4));
+    const size_t nfc = p->final_coeffs.b.len;
+    std::vector<uint32_t> fc(nfc);
+    uint32_t dg[8];
+    if (dev) {
         size_t used = 0;
-        const uint32_t *host_all = nullptr, *rems = nullptr;
-        std::vector<uint32_t> big;
-        if (off[n_trees] + 4 * p->n_div + 8 <= bx_ctx::STAGE_WORDS) {
-            PV(d2h_batch_add(c, &used, p->qout.slice(0, off[n_trees]), off[n_trees], &host_all));
-            PV(d2h_batch_add(c, &used, p->rems.b, 4 * p->n_div, &rems));
-            PV(d2h_batch_wait(c));
-        } else {  // seals of the largest shapes do not fit the pinned landing area: two plain copies
-            big.resize(off[n_trees] + 4 * p->n_div);
-            PV(bx_d2h(c, big.data(), p->qout.slice(0, off[n_trees]), off[n_trees]));
-            PV(bx_d2h(c, big.data() + off[n_trees], p->rems.b, 4 * p->n_div));
-            host_all = big.data();
-            rems = big.data() + off[n_trees];
+        std::vector<const uint32_t*> host(p->rounds.size(), nullptr);
+        const uint32_t *fc_host = nullptr, *chal = nullptr;
+        for (size_t i = 0; i < p->rounds.size(); ++i) PV(tree_fetch(p, p->rounds[i].tree, &used, &host[i]));
+        PV(d2h_batch_add(c, &used, p->dev_chal.slice(0, 4 * p->rounds.size()), 4 * p->rounds.size(), &chal));
+        PV(d2h_batch_add(c, &used, p->final_coeffs.b, nfc, &fc_host));
+        PV(d2h_batch_wait(c));
+        for (size_t i = 0; i < p->rounds.size(); ++i) {
+            tree_absorb(p->rounds[i].tree, host[i], T);
+            const Fp4 fold_mix = T.random_ext();
+            if (memcmp(fold_mix.c, chal + 4 * i, 16) != 0) return perr(p, "bx_prove_segment: the device transcript drew a different FRI challenge than the host transcript");
         }
-        for (size_t i = 0; i < 4 * p->n_div; ++i)
-            if (rems[i] != 0) return perr(p, "bx_prove_segment: DEEP quotient has a non-zero remainder");
-        for (int q = 0; q < BX_QUERIES; ++q)
-            for (size_t t = 0; t < n_trees; ++t) T.write(host_all + off[t] + (size_t)q * qw[t], qw[t]);
+        memcpy(fc.data(), fc_host, nfc * 4);
+    } else {
+        PV(bx_d2h(c, fc.data(), p->final_coeffs.b, fc.size()));
     }
+    T.write(fc.data(), fc.size());
+    p->hs.hash_elems(dg, fc.data(), fc.size());
+    T.commit(dg);
+    return nullptr;
+}
+
+// queries: positions come only from the RNG (writes do not feed it), so draw all 50 first, gather each tree for the whole batch on
+// the device, then lay the seal out in upstream's query-major order
+const char* queries(bx_prover* p, Proof& pf) {
+    bx_ctx* c = p->c;
+    const SealLayout& L = p->lay;
+    Transcript& T = pf.T;
+    const size_t D = 4 * L.N, n_trees = L.n_trees(), n_div = L.n_div;
+    const size_t all_words = BX_QUERIES * L.per_query;  // the gather buffer holds tree after tree, each with its 50 openings
+    const unsigned bits = L.trees[0].layers;            // log2 of D
+    uint32_t pos[BX_QUERIES];
+    for (int q = 0; q < BX_QUERIES; ++q) pos[q] = T.random_bits(bits) % (uint32_t)D;
+    std::vector<uint32_t> all_pos(n_trees * BX_QUERIES);
+    for (size_t t = 0; t < n_trees; ++t) {
+        if (t >= 4)
+            for (int q = 0; q < BX_QUERIES; ++q) pos[q] %= (uint32_t)L.tree(t).rows;  // group = pos % (domain / FRI_FOLD)
+        memcpy(all_pos.data() + t * BX_QUERIES, pos, sizeof pos);
+    }
+    PV(h2d_staged(c, p->positions.b, all_pos.data(), all_pos.size()));
+    for (size_t t = 0; t < n_trees; ++t) {
+        Tree& tr = t < 4 ? p->groups[t].tree : p->rounds[t - 4].tree;
+        bx_buf matrix = t < 4 ? p->groups[t].evaluated.b : p->rounds[t - 4].evaluated.b;
+        PV(bx_merkle_query_gather(c, p->qout.slice(BX_QUERIES * L.query_off[t], BX_QUERIES * L.query_words[t]), matrix, tr.nodes.b, tr.rows, tr.cols,
+                                  p->positions.slice(t * BX_QUERIES, BX_QUERIES), BX_QUERIES, tr.top_size()));
+    }
+    size_t used = 0;
+    const uint32_t *host_all = nullptr, *rems = nullptr;
+    std::vector<uint32_t> big;
+    if (all_words + 4 * n_div + 8 <= bx_ctx::STAGE_WORDS) {
+        PV(d2h_batch_add(c, &used, p->qout.slice(0, all_words), all_words, &host_all));
+        PV(d2h_batch_add(c, &used, p->rems.b, 4 * n_div, &rems));
+        PV(d2h_batch_wait(c));
+    } else {  // seals of the largest shapes do not fit the pinned landing area: two plain copies
+        big.resize(all_words + 4 * n_div);
+        PV(bx_d2h(c, big.data(), p->qout.slice(0, all_words), all_words));
+        PV(bx_d2h(c, big.data() + all_words, p->rems.b, 4 * n_div));
+        host_all = big.data();
+        rems = big.data() + all_words;
+    }
+    for (size_t i = 0; i < 4 * n_div; ++i)
+        if (rems[i] != 0) return perr(p, "bx_prove_segment: DEEP quotient has a non-zero remainder");
+    for (int q = 0; q < BX_QUERIES; ++q)
+        for (size_t t = 0; t < n_trees; ++t) T.write(host_all + BX_QUERIES * L.query_off[t] + (size_t)q * L.query_words[t], L.query_words[t]);
+    return nullptr;
+}
+
+}  // namespace
+
+static const char* prove_segment_impl(bx_prover* p, const SegSlot& seg, uint32_t* seal_out, size_t seal_cap, size_t* seal_words) {
+    bx_ctx* c = p->c;
+    if (hipSetDevice(c->device) != hipSuccess) return perr(p, "bx_prove_segment: hipSetDevice failed");
+    Proof pf(p->hs);
+    pf.T.seal.reserve(p->lay.seal_words);
+    TraceRange whole(c, "bx:prove_segment");
+    write_header(p, pf);
+    BX_TRY(witgen_and_commit(p, pf, seg));
+    BX_TRY(accumulate_and_commit(p, pf));
+    BX_TRY(eval_check_and_commit(p, pf));
+    TraceStages stage(c);
+    stage.next("bx:deep_taps");
+    BX_TRY(deep_taps(p, pf));
+    stage.next("bx:deep_combos");
+    BX_TRY(deep_combos(p, pf));
+    stage.next("bx:fri_prove");
+    BX_TRY(fri_prove(p, pf));
+    stage.next("bx:queries");
+    BX_TRY(queries(p, pf));
     stage.close();
-    if (seal_words) *seal_words = T.seal.size();
-    if (T.seal.size() > seal_cap) return perr(p, "bx_prove_segment: seal buffer too small");
-    memcpy(seal_out, T.seal.data(), T.seal.size() * 4);
+    const std::vector<uint32_t>& seal = pf.T.seal;
+    if (seal_words) *seal_words = seal.size();
+    if (seal.size() > seal_cap) return perr(p, "bx_prove_segment: seal buffer too small");
+    memcpy(seal_out, seal.data(), seal.size() * 4);
     return nullptr;
 }

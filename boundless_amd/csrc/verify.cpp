@@ -5,7 +5,9 @@
 // merkle::MerkleTreeVerifier} (risc0-zkp 3.0.3, reference Cargo.lock:9155): replay the transcript, check the constraint
 // identity at the random point Z (here: of the synthetic circuit specified in bx_prover.h), then for each query verify the
 // Merkle openings, recompute the DEEP quotient from the opened trace rows and follow the FRI folds to the final polynomial.
-// Pure CPU code (the reference verifies on the CPU as well); it shares only fp.hpp, hash_suite.hpp and transcript.hpp with the prover.
+// Pure CPU code (the reference verifies on the CPU as well).  With the prover it shares the field and the hashes (fp.hpp,
+// hash_suite.hpp, transcript.hpp) and the integers that say where a seal's words stand (seal_layout.hpp); every check below — the
+// constraint identity, the mixed u polynomials, the DEEP quotient, the FRI chain — is its own arithmetic.
 #include <stdio.h>
 #include <string.h>
 
@@ -22,6 +24,7 @@
 #include "lookup.hpp"
 #include "fp.hpp"
 #include "poseidon2_params.hpp"
+#include "seal_layout.hpp"
 #include "transcript.hpp"
 
 namespace {
@@ -68,17 +71,11 @@ uint32_t rou(unsigned k) { return fp_pow(fp_encode(137u), (uint64_t)1 << (27 - k
 const uint32_t* digest_words(Reader& rd, const HostSuite& h, size_t k) { return h.digests_are_elems() ? rd.take_elems(k) : rd.take(k); }
 
 // MerkleTreeVerifier: top layer read from the seal, root recomputed and committed
-struct TreeV {
-    size_t rows, cols;
-    unsigned layers, top_layer;
+struct TreeV : TreeGeom {
     std::vector<uint32_t> top;  // nodes [top_size, 2*top_size) as in the prover, indexable by node id - top_size
     uint32_t root[8];           // recomputed from the top layer
-    size_t top_size() const { return (size_t)1 << top_layer; }
-    void read_and_commit(Reader& rd, Transcript& T, const HostSuite& h, size_t rows_, size_t cols_) {
-        rows = rows_;
-        cols = cols_;
-        layers = ilog2u(rows);
-        top_layer = top_layer_of(layers);
+    void read_and_commit(Reader& rd, Transcript& T, const HostSuite& h, const TreeGeom& geom) {
+        TreeGeom::operator=(geom);
         size_t ts = top_size();
         const uint32_t* t = digest_words(rd, h, 8 * ts);
         top.assign(t, t + 8 * ts);
@@ -140,7 +137,7 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
     Reader rd{seal, words};
 
     // ---- header ----
-    const uint32_t* hdr = rd.take(6);
+    const uint32_t* hdr = rd.take(BX_SEAL_HEADER_WORDS);
     const uint32_t po2 = hdr[0];
     const uint32_t widths[4] = {hdr[1], hdr[2], hdr[3], BX_CHECK_SIZE};
     VCHECK(po2 >= 9 && po2 <= 24, "header: po2 out of range");
@@ -158,13 +155,13 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
         VCHECK(norm.cons_terms == shape.cons_terms && norm.cons_degree == shape.cons_degree, "header: bad circuit knobs");
     }
     {
-        uint32_t enc[6], dg[8];
-        for (int i = 0; i < 6; ++i) enc[i] = fp_encode(hdr[i]);
-        h.hash_elems(dg, enc, 6);
+        uint32_t enc[BX_SEAL_HEADER_WORDS], dg[8];
+        for (int i = 0; i < BX_SEAL_HEADER_WORDS; ++i) enc[i] = fp_encode(hdr[i]);
+        h.hash_elems(dg, enc, BX_SEAL_HEADER_WORDS);
         T.commit(dg);
     }
     const size_t N = (size_t)1 << po2, D = 4 * N;
-    // ---- the statement's public words ----
+    // ---- the statement's public words (they stand in front of the commitments; the layout, built below, counts them again) ----
     const uint32_t n_globals = circ->n_globals ? circ->n_globals(circ->user, &shape) : 0;
     VCHECK(n_globals <= BX_MAX_GLOBALS, "circuit: too many public words");
     const uint32_t* globals = rd.take_elems(n_globals);
@@ -175,7 +172,7 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
     }
     // ---- trace commitments ----
     TreeV trees[4];
-    trees[0].read_and_commit(rd, T, h, D, widths[0]);
+    trees[0].read_and_commit(rd, T, h, TreeGeom(D, widths[0]));
     // ---- the code group is the circuit's, not the prover's: its root must be a control ID (upstream: check_code(po2, root)).
     //      An explicit context is a lookup and is asked at once; the circuit's own check may have to compute the ID (seconds for
     //      a shape outside its table), so it runs last: only a seal that is otherwise a valid proof can make the verifier pay ----
@@ -183,45 +180,21 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
     else if (suite == SUITE_SHA256)  // a table's check_code knows one suite (it has no suite parameter): only the built-in circuits' IDs follow it
         VCHECK(circ == bx_synthetic_circuit() || builtin_sha256_ids(circ), "no control IDs to check the code root against (sha-256: a plug-in circuit needs a verifier context)");
     else VCHECK(circ->check_code != nullptr, "no control IDs to check the code root against (the circuit table has no check_code: pass a verifier context)");
-    trees[1].read_and_commit(rd, T, h, D, widths[1]);
+    trees[1].read_and_commit(rd, T, h, TreeGeom(D, widths[1]));
     const Fp4 beta = T.random_ext();  // the accumulators' mix
-    trees[2].read_and_commit(rd, T, h, D, widths[2]);
+    trees[2].read_and_commit(rd, T, h, TreeGeom(D, widths[2]));
     const Fp4 poly_mix = T.random_ext();
-    trees[3].read_and_commit(rd, T, h, D, widths[3]);
+    trees[3].read_and_commit(rd, T, h, TreeGeom(D, widths[3]));
     const Fp4 Z = T.random_ext();
     // ---- taps ----
     // every column contributes at least one ext tap value to coeff_u: refuse a header whose widths the seal cannot back before
     // spending any per-column work on it (an 8 KB seal claiming three 65535-column groups used to cost seconds here)
     VCHECK(rd.n - rd.pos >= 4 * ((size_t)widths[0] + widths[1] + widths[2] + widths[3]), "seal truncated");
-    // tap set of every column (the rows back it is opened at) and the combo it belongs to: columns with the same set share
-    // a DEEP combination polynomial, combos in order of first appearance, the check group's last (as in prover.hip)
-    std::vector<std::vector<std::vector<uint32_t>>> backs(4);
-    std::vector<std::vector<uint32_t>> combo(4);
-    std::vector<std::vector<uint32_t>> combo_backs;
-    size_t total_taps = 0;
-    for (int g = 0; g < 4; ++g) {
-        backs[g].resize(widths[g]);
-        combo[g].resize(widths[g]);
-        for (uint32_t c = 0; c < widths[g]; ++c) {
-            if (g == 3) {
-                backs[g][c] = {0};
-            } else {
-                uint32_t bk[BX_MAX_TAPS];
-                const uint32_t k = circ->taps(circ->user, &shape, g, c, bk);
-                VCHECK(k >= 1 && k <= BX_MAX_TAPS && bk[0] == 0, "circuit: a tap set has 1..8 entries and starts with 0");
-                for (uint32_t t = 1; t < k; ++t) VCHECK(bk[t] > bk[t - 1] && bk[t] < N, "circuit: tap sets are strictly increasing");
-                backs[g][c].assign(bk, bk + k);
-                size_t id = 0;
-                while (id < combo_backs.size() && combo_backs[id] != backs[g][c]) ++id;
-                if (id == combo_backs.size()) combo_backs.push_back(backs[g][c]);
-                combo[g][c] = (uint32_t)id;
-            }
-            total_taps += backs[g][c].size();
-        }
-    }
-    VCHECK(combo_backs.size() + 1 <= BX_MAX_COMBOS, "circuit: too many distinct tap sets");
-    const size_t n_trace_combos = combo_backs.size(), n_combos = n_trace_combos + 1;
-    for (uint32_t c = 0; c < widths[3]; ++c) combo[3][c] = (uint32_t)n_trace_combos;
+    // tap set of every column (the rows back it is opened at), the combo it belongs to and every length from here on: the layout
+    // the prover proved by (seal_layout.hpp)
+    const SealLayout L = seal_layout(shape, circ);
+    VCHECK(L.error == nullptr, std::string("circuit: ") + (L.error ? L.error : ""));
+    const size_t total_taps = L.total_taps, n_trace_combos = L.n_trace_combos, n_combos = L.n_combos;
     const uint32_t* coeff_u = rd.take_elems(4 * total_taps);
     {
         uint32_t dg[8];
@@ -236,17 +209,17 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
     {
         // tap values: where[g][c] = offset of column c's first ext element in coeff_u
         std::vector<std::vector<size_t>> where(4);
-        size_t u = 0;
         for (int g = 0; g < 4; ++g) {
             where[g].resize(widths[g]);
+            size_t u = 4 * L.tap_first[g];
             for (uint32_t c = 0; c < widths[g]; ++c) {
                 where[g][c] = u;
-                u += 4 * backs[g][c].size();
+                u += 4 * L.backs(g, c).size();
             }
         }
         auto at = [&](int g, uint32_t c, int back) -> Fp4 {  // the column's polynomial at Z (back 0) or Z * w_N^-1 (back 1)
             VCHECK(g >= 0 && g < 4 && c < widths[g] && back >= 0, "internal: tap out of range");
-            const auto& B = backs[g][c];
+            const auto& B = L.backs(g, c);
             bool member = false;
             for (uint32_t b : B) member |= b == (uint32_t)back;
             VCHECK(member, "circuit: reads a tap that is not in the column's tap set");
@@ -294,8 +267,8 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
         size_t u = 0;
         for (int g = 0; g < 4; ++g)
             for (uint32_t c = 0; c < widths[g]; ++c) {
-                const uint32_t id = combo[g][c];
-                for (size_t t = 0; t < backs[g][c].size(); ++t, u += 4)
+                const uint32_t id = L.combo[g][c];
+                for (size_t t = 0; t < L.backs(g, c).size(); ++t, u += 4)
                     combo_u[id * BX_MAX_TAPS + t] = f4_add(combo_u[id * BX_MAX_TAPS + t], f4_mul(cur, ld(coeff_u + u)));
                 mixpow.push_back(cur);
                 cur = f4_mul(cur, mix);
@@ -303,21 +276,15 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
     }
     // ---- FRI commitments ----
     struct Round {
-        size_t size;
         TreeV tree;
         Fp4 fold_mix;
     };
-    std::vector<Round> rounds;
-    size_t size = N;
-    while (size > BX_FRI_MIN_DEGREE) {
-        rounds.emplace_back();
-        Round& r = rounds.back();
-        r.size = size;
-        r.tree.read_and_commit(rd, T, h, 4 * size / BX_FRI_FOLD, 4 * BX_FRI_FOLD);
-        r.fold_mix = T.random_ext();
-        size /= BX_FRI_FOLD;
+    std::vector<Round> rounds(L.rounds.size());
+    for (size_t i = 0; i < rounds.size(); ++i) {
+        rounds[i].tree.read_and_commit(rd, T, h, L.rounds[i].tree);
+        rounds[i].fold_mix = T.random_ext();
     }
-    const size_t final_size = size;
+    const size_t final_size = L.final_size;
     const uint32_t* fin = rd.take_elems(4 * final_size);  // SoA planes, natural coefficient order
     {
         uint32_t dg[8];
@@ -332,10 +299,7 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
     // order, exactly what reading the seal front to back reports.
     size_t positions[BX_QUERIES];
     for (int q = 0; q < BX_QUERIES; ++q) positions[q] = T.random_bits(ilog2u(D)) % D;
-    size_t per_query = 0;
-    for (int g = 0; g < 4; ++g) per_query += trees[g].cols + 8 * (size_t)(trees[g].layers - trees[g].top_layer);
-    for (const Round& r : rounds) per_query += r.tree.cols + 8 * (size_t)(r.tree.layers - r.tree.top_layer);
-    const size_t queries_at = rd.pos;
+    const size_t per_query = L.per_query, queries_at = L.queries_at;  // where rd stands: all in front of it was taken by the layout's counts
     auto check_query = [&](int q) {
         Reader rd{seal, words};  // this query's own cursor (shadows the stream's)
         rd.pos = queries_at + (size_t)q * per_query;
@@ -348,18 +312,18 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
         for (int g = 0; g < 4; ++g) {
             const uint32_t* vals = trees[g].verify_open(rd, h, pos);
             for (uint32_t c = 0; c < widths[g]; ++c, ++col_global) {
-                const uint32_t id = combo[g][c];
+                const uint32_t id = L.combo[g][c];
                 num[id] = f4_add(num[id], f4_scale(mixpow[col_global], vals[c]));
             }
         }
         // goal = sum over combos of (combo(y) - u_combo(y)) / prod_{b in its tap set} (y - Z w_N^-b); the check combo's point is Z^4/3
         Fp4 goal = f4_zero();
         for (size_t id = 0; id < n_combos; ++id) {
-            const size_t k = id < n_trace_combos ? combo_backs[id].size() : 1;
+            const size_t k = L.combo_backs[id].size();
             Fp4 uy = f4_zero();
             for (size_t t = k; t-- > 0;) uy = f4_add(f4_mul(uy, y), combo_u[id * BX_MAX_TAPS + t]);
             Fp4 den = f4_one();
-            for (size_t t = 0; t < k; ++t) den = f4_mul(den, f4_sub(y, id < n_trace_combos ? zback(combo_backs[id][t]) : Z4));
+            for (size_t t = 0; t < k; ++t) den = f4_mul(den, f4_sub(y, id < n_trace_combos ? zback(L.combo_backs[id][t]) : Z4));
             goal = f4_add(goal, f4_mul(f4_sub(num[id], uy), f4_inv(den)));
         }
         // FRI chain
@@ -443,7 +407,7 @@ void verify(const uint32_t* seal, size_t words, const bx_circuit_ops* circ, cons
         for (int q = 0; q < BX_QUERIES; ++q)
             if (failed[q]) throw Fail{errs[q].empty() ? "query check failed" : errs[q]};
     }
-    rd.pos = queries_at + (size_t)BX_QUERIES * per_query;
+    rd.pos = L.seal_words;  // behind the last query
     if (rd.pos > rd.n) throw Fail{"seal truncated"};
     VCHECK(rd.pos == rd.n, "trailing words after the last query");
     if (!vctx) {  // (the same detour as above: a table's check_code has no suite parameter)

@@ -284,6 +284,41 @@ def test_a_dishonest_code_group_is_refused_by_the_control_id_and_by_nothing_else
         verify_seal(forged.seal, circuit=ops2)
 
 
+def test_a_refused_tap_set_costs_nothing_and_the_next_prover_states_its_seals_size():
+    """A table whose tap sets are not strictly increasing is refused by name at create — by the layout (csrc/seal_layout.hpp), before
+    anything is allocated — and the ctx it was tried on stays good: a valid prover of the same circuit created on it afterwards proves,
+    its seal verifies and has exactly bx_prover_seal_words words."""
+    from boundless_amd.circuit import CircuitOps
+    from boundless_amd.hal import HalError, HipHal, load_library
+    from boundless_amd.prover import HipProverServer, Segment, verify_seal
+
+    class Unordered(SquareCircuit):
+        def taps(self, shape, group, col):
+            return [0, 3, 1] if (group == 1 and col == 0) else [0]
+
+    lib = load_library()
+    po2, widths = 10, (2, 3, 2)
+    hal = HipHal(0)
+    try:
+        bad = Unordered(lib)
+        bad.bind(po2, widths)
+        with pytest.raises(HalError, match="^bx_prover_create: tap sets are strictly increasing$"):
+            HipProverServer(0, po2=po2, widths=widths, hal=hal, circuit=CircuitOps.from_object(bad))
+        assert bad.calls == []
+        circ = SquareCircuit(lib)
+        circ.bind(po2, widths)
+        ops = CircuitOps.from_object(circ, b"square-plus-back")
+        srv = HipProverServer(0, po2=po2, widths=widths, hal=hal, circuit=ops)
+        try:
+            receipt = srv.prove_segment(Segment(index=0, po2=po2, seed=77))
+            assert receipt.seal.size == srv.lib.bx_prover_seal_words(srv.handle)
+            verify_seal(receipt.seal, circuit=ops, ctx=srv.verifier_context())
+        finally:
+            srv.close()
+    finally:
+        hal.close()
+
+
 def test_errors_of_a_plugged_circuit_surface_as_error_strings():
     from boundless_amd.circuit import CircuitOps
     from boundless_amd.hal import HalError, load_library

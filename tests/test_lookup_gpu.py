@@ -214,6 +214,7 @@ def test_a_lookup_seal_is_accepted_by_its_circuit_and_by_no_other(po2, widths):
     try:
         r = srv.prove_segment(Segment(index=0, po2=po2, seed=31 + po2))
         assert r.seal[:6].tolist() == [po2, *widths, 0, 0]
+        assert r.seal.size == srv.lib.bx_prover_seal_words(srv.handle)
         verify_seal(r.seal, circuit="lookup")
         with pytest.raises(HalError):
             verify_seal(r.seal, circuit="synthetic")

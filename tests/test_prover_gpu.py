@@ -202,6 +202,21 @@ def test_seal_is_deterministic_and_shape_errors():
         HipProverServer(0, po2=5)
 
 
+@pytest.mark.parametrize("po2,widths", [(9, (1, 1, 1)), (10, (2, 5, 8))])
+def test_seal_words_is_the_size_of_the_seal_at_small_shapes(po2, widths):
+    """bx_prover_seal_words is the layout's exact length (csrc/seal_layout.hpp), not a bound: the narrowest shape, and one whose data
+    group has a column with three tap rows."""
+    from boundless_amd.prover import HipProverServer, Segment
+
+    srv = HipProverServer(0, po2=po2, widths=widths)
+    try:
+        r = srv.prove_segment(Segment(index=0, po2=po2, seed=11))
+        assert r.seal.size == srv.lib.bx_prover_seal_words(srv.handle)
+        assert r.seal.size == ol.prove_segment(po2, *widths, 11)[0].size
+    finally:
+        srv.close()
+
+
 @pytest.mark.parametrize("po2", [18, 20])
 def test_full_size_properties(po2):
     """BASELINE shape (2^20 cycles, widths 16/256/64): the DEEP quotients divide exactly (checked inside the prover),
