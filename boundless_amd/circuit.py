@@ -195,8 +195,16 @@ def _cons_lib():
         lib.bx_cons_circuit_ops.restype = C.POINTER(CircuitOps)
         lib.bx_cons_circuit_destroy.argtypes = [vp]
         lib.bx_cons_circuit_destroy.restype = None
+        lib.bx_cons_program_digest.argtypes = [vp, u32p]
+        lib.bx_cons_program_emit_hip.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        lib.bx_cons_program_attach_kernel.argtypes = [vp, C.c_char_p, C.c_size_t]
+        lib.bx_cons_program_detach_kernel.argtypes = [vp]
+        lib.bx_cons_program_kernel_attached.argtypes = [vp]
+        lib.bx_cons_program_kernel_attached.restype = C.c_int
+        lib.bx_cons_circuit_set_kernel.argtypes = [vp, C.c_char_p, C.c_size_t]
         for name in ("bx_cons_program_create", "bx_cons_program_info_get", "bx_cons_program_constraints_at", "bx_cons_program_load", "bx_cons_program_unload",
-                     "bx_cons_program_eval_check", "bx_cons_circuit_create"):
+                     "bx_cons_program_eval_check", "bx_cons_circuit_create", "bx_cons_program_digest", "bx_cons_program_emit_hip",
+                     "bx_cons_program_attach_kernel", "bx_cons_program_detach_kernel", "bx_cons_circuit_set_kernel"):
             getattr(lib, name).restype = C.c_char_p
         lib._cons_bound = True
     return lib
@@ -252,6 +260,30 @@ class CompiledConsProgram:
             raise HalError(msg.decode())
         return list(out)
 
+    def digest(self):
+        """bx_cons_program_digest as 64 hex digits (the 32 bytes in order): what a generated kernel carries and attach compares"""
+        from .hal import HalError
+
+        out = (C.c_uint32 * 8)()
+        msg = self.lib.bx_cons_program_digest(self.handle, out)
+        if msg:
+            raise HalError(msg.decode())
+        return b"".join(int(w).to_bytes(4, "little") for w in out).hex()
+
+    def emit_hip(self):
+        """bx_cons_program_emit_hip: the generated translation unit as text (boundless_amd.consgen compiles it)"""
+        from .hal import HalError
+
+        need = C.c_size_t(0)
+        msg = self.lib.bx_cons_program_emit_hip(self.handle, None, 0, C.byref(need))
+        if msg:
+            raise HalError(msg.decode())
+        buf = C.create_string_buffer(need.value)
+        msg = self.lib.bx_cons_program_emit_hip(self.handle, buf, need.value, C.byref(need))
+        if msg:
+            raise HalError(msg.decode())
+        return buf.value.decode()
+
     def load(self, hal):
         dev = C.c_void_p()
         hal._check(self.lib.bx_cons_program_load(hal.ctx, self.handle, C.byref(dev)))
@@ -279,6 +311,26 @@ class LoadedConsProgram:
         if self.dev:
             dev, self.dev = self.dev, None
             self.hal._check(self.program.lib.bx_cons_program_unload(dev))
+
+    def attach_kernel(self, path_or_bytes):
+        """bx_cons_program_attach_kernel: a code object built by boundless_amd.consgen for THIS program (a path, or its bytes);
+        hal.cons_program_eval_check then launches it instead of the interpreter.  A refusal raises HalError."""
+        image = _kernel_image(path_or_bytes)
+        self.hal._check(self.program.lib.bx_cons_program_attach_kernel(self.dev, image, len(image)))
+
+    def detach_kernel(self):
+        self.hal._check(self.program.lib.bx_cons_program_detach_kernel(self.dev))
+
+    @property
+    def kernel_attached(self):
+        return bool(self.dev) and bool(self.program.lib.bx_cons_program_kernel_attached(self.dev))
+
+
+def _kernel_image(path_or_bytes):
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        return bytes(path_or_bytes)
+    with open(path_or_bytes, "rb") as f:
+        return f.read()
 
 
 class ConsProgram:
@@ -366,10 +418,11 @@ class ConsProgram:
         return CompiledConsProgram(lib, handle, self.n_globals)
 
 
-def _from_program(program, base):
-    """CircuitOps.from_program(program, base): the table whose taps, eval_check and constraints_at come from `program` (a
-    CompiledConsProgram) and everything else from `base` (a CircuitOps: from_object, lookup_circuit() or synthetic_circuit()).
-    The result is used like any other table (HipProverServer(circuit=...), verify_seal(circuit=...)); it keeps program and base alive."""
+def _from_program(program, base, kernel=None):
+    """CircuitOps.from_program(program, base, kernel=None): the table whose taps, eval_check and constraints_at come from `program`
+    (a CompiledConsProgram) and everything else from `base` (a CircuitOps: from_object, lookup_circuit() or synthetic_circuit()).
+    kernel: a code object generated from `program` (boundless_amd.consgen; a path or its bytes) that eval_check launches instead of
+    the interpreter; a prover's creation fails with attach_kernel's message if it is not this program's.  The result is used like any other table (HipProverServer(circuit=...), verify_seal(circuit=...)); it keeps program and base alive."""
     import weakref
 
     from .hal import HalError
@@ -380,6 +433,12 @@ def _from_program(program, base):
     msg = lib.bx_cons_circuit_create(base_ptr, program.handle, C.byref(cc))
     if msg:
         raise HalError(msg.decode())
+    if kernel is not None:
+        image = _kernel_image(kernel)
+        msg = lib.bx_cons_circuit_set_kernel(cc, image, len(image))
+        if msg:
+            lib.bx_cons_circuit_destroy(cc)
+            raise HalError(msg.decode())
     ops = lib.bx_cons_circuit_ops(cc).contents
     ops._keepalive = (program, base)
     weakref.finalize(ops, lib.bx_cons_circuit_destroy, cc)

@@ -1,0 +1,109 @@
+"""Off-line compile step of generated constraint-program kernels (include/bx_program.h, "Generated kernels").
+
+    python -m boundless_amd.consgen DESC.json -o OUT.hsaco [--emit-only]
+
+A description is JSON: {"n_globals": g, "ret": r, "taps": [[group, col, back], ...], "steps": [[op, a, b, c, d], ...]} with the op
+numbers of enum bx_cons_op.  It is compiled by bx_cons_program_create, written as text by bx_cons_program_emit_hip and built with
+hipcc, device code only, with the flags the library's own kernels are built with (build.FLAGS: gfx950, -fno-gpu-rdc,
+-ffp-contract=off, -I csrc).  Beside OUT.hsaco goes OUT.meta.json: the program's digest, the compiler's resource report for
+bx_cp_eval (-Rpass-analysis=kernel-resource-usage: VGPRs, SGPRs, scratch, occupancy), the program's steps and instructions, and the
+seconds hipcc took.  --emit-only writes the text to OUT instead and runs no compiler.
+
+This runs where hipcc is, before the code object is needed: the library loads what was built (bx_cons_program_attach_kernel) and
+compiles nothing at run time.
+"""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+import time
+
+from . import build as b
+from .circuit import ConsProgram
+
+
+def program_of(desc):
+    """-> CompiledConsProgram of a description (a dict as in the JSON above)"""
+    p = ConsProgram(int(desc["n_globals"]))
+    p.steps = [tuple(int(v) for v in s) for s in desc["steps"]]
+    p.tap_list = [tuple(int(v) for v in t) for t in desc["taps"]]
+    p.n_fp = sum(1 for s in p.steps if s[0] < 7)
+    p.n_mix = len(p.steps) - p.n_fp
+    return p.compile(ret=int(desc["ret"]))
+
+
+def _resource_usage(stderr, kernel="bx_cp_eval"):
+    out, on = {}, False
+    for line in stderr.splitlines():
+        m = re.search(r"remark:\s+(.*?):\s+(.*?) \[-Rpass-analysis", line)
+        if not m:
+            continue
+        key, val = m.group(1).strip(), m.group(2).strip()
+        if key == "Function Name":
+            on = kernel in val
+        elif on:
+            out[key] = int(val) if val.isdigit() else val
+    return out
+
+
+def compile_text(text, out_path, extra_flags=()):
+    """hipcc over one generated translation unit -> (resource report of bx_cp_eval, seconds)"""
+    with tempfile.TemporaryDirectory() as tmp:
+        src = os.path.join(tmp, "bx_cp_generated.hip")
+        with open(src, "w") as f:
+            f.write(text)
+        cmd = ["hipcc", "-x", "hip", "--cuda-device-only"] + b.FLAGS + ["-cuid=bxcpgenerated", "-Rpass-analysis=kernel-resource-usage"] + list(extra_flags) + [
+            "-c", src, "-o", out_path]
+        t0 = time.time()
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        secs = time.time() - t0
+    if r.returncode != 0:
+        raise RuntimeError("hipcc failed for the generated kernel:\n" + r.stdout + r.stderr[-4000:])
+    return _resource_usage(r.stderr), secs
+
+
+def compile_program(desc, out_path, emit_only=False):
+    """Compiles the description `desc` (a dict, or the path of a JSON file) into the code object `out_path` and writes
+    `<out_path minus .hsaco>.meta.json` beside it; -> the meta dict.  emit_only: writes the generated text to out_path, nothing else."""
+    if not isinstance(desc, dict):
+        with open(desc) as f:
+            desc = json.load(f)
+    prog = program_of(desc)
+    try:
+        text = prog.emit_hip()
+        if emit_only:
+            with open(out_path, "w") as f:
+                f.write(text)
+            return {"digest": prog.digest()}
+        usage, secs = compile_text(text, out_path)
+        info = prog.info
+        meta = {"digest": prog.digest(), "vgprs": usage.get("VGPRs"), "agprs": usage.get("AGPRs"), "sgprs": usage.get("TotalSGPRs"),
+                "scratch_bytes": usage.get("ScratchSize [bytes/lane]"), "occupancy_waves_per_simd": usage.get("Occupancy [waves/SIMD]"),
+                "lds_bytes": usage.get("LDS Size [bytes/block]"), "steps": info["steps"], "instructions": info["instructions"],
+                "narrow": info["narrow"], "wide": info["wide"], "text_bytes": len(text), "hipcc_seconds": round(secs, 2)}
+        with open(meta_path(out_path), "w") as f:
+            json.dump(meta, f, indent=1)
+            f.write("\n")
+        return meta
+    finally:
+        prog.close()
+
+
+def meta_path(out_path):
+    return (out_path[:-6] if out_path.endswith(".hsaco") else out_path) + ".meta.json"
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("desc")
+    ap.add_argument("-o", "--out", required=True)
+    ap.add_argument("--emit-only", action="store_true")
+    a = ap.parse_args(argv)
+    print(json.dumps(compile_program(a.desc, a.out, a.emit_only)))
+
+
+if __name__ == "__main__":
+    sys.exit(main())

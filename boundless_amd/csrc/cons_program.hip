@@ -22,6 +22,7 @@
 
 #include "circuit_common.hpp"
 #include "cons_program.hpp"
+#include "cons_program_dev.hpp"
 
 namespace bx {
 
@@ -132,14 +133,7 @@ __global__ __launch_bounds__(256) void cons_program_kernel(uint32_t* __restrict_
 
 }  // namespace bx
 
-// a program loaded on a ctx
-struct bx_cons_program_dev {
-    bx_ctx* ctx = nullptr;
-    bx_cons_program_info info{};
-    uint32_t n_pows = 1, ret_slot = 0, n_fetch = 0, max_col[3] = {0, 0, 0};
-    size_t lds = 0;
-    bx::DevBuf code, taps, scal, mixpows;
-};
+// a program loaded on a ctx: bx_cons_program_dev (cons_program_dev.hpp)
 
 namespace bx {
 namespace {
@@ -156,7 +150,10 @@ void cons_programs_release(bx_ctx* c) {
         ds.swap(it->second);
         g_loaded.erase(it);
     }
-    for (bx_cons_program_dev* d : ds) delete d;  // the caller has drained the stream
+    for (bx_cons_program_dev* d : ds) {  // the caller has drained the stream
+        cons_gen_release(d);
+        delete d;
+    }
 }
 }  // namespace bx
 
@@ -173,6 +170,7 @@ extern "C" const char* bx_cons_program_load(bx_ctx* c, const bx_cons_program* pr
     d->ret_slot = prog->ret_slot;
     d->n_fetch = (uint32_t)(prog->code.size() / (2 * CP_FETCH));
     for (int g = 0; g < 3; ++g) d->max_col[g] = prog->max_col[g];
+    BX_TRY(bx_cons_program_digest(prog, d->digest));  // what a generated kernel must have been built from (attach_kernel)
     // the compiler refuses what does not fit; a stream from anywhere else must not reach the kernel
     BX_REQUIRE(c, prog->info.narrow <= BX_CONS_MAX_NARROW && prog->info.wide >= 1 && prog->info.wide <= BX_CONS_MAX_WIDE && prog->ret_slot < prog->info.wide &&
                       prog->code.size() % (2 * CP_FETCH) == 0,
@@ -222,6 +220,7 @@ extern "C" const char* bx_cons_program_unload(bx_cons_program_dev* dev) try {
     if (!c) return "bx_cons_program_unload: not a loaded program (unloaded twice, or its ctx was freed)";
     (void)hipSetDevice(c->device);
     (void)stream_wait(c);  // a launch may still read the tables
+    cons_gen_release(dev);
     delete dev;
     return nullptr;
 } BX_ABI_CATCH(nullptr, "bx_cons_program_unload")
@@ -256,6 +255,7 @@ extern "C" const char* bx_cons_program_eval_check(bx_ctx* c, bx_cons_program_dev
     BX_TRY(mix_power_table(c, dev->mixpows.b, poly_mix, dev->n_pows));
     ConsLaunch L;
     vanishing_inverses(po2, L.zinv);
+    if (dev->gen_fn) return cons_gen_launch(c, dev, po2, L.zinv, check, code_eval, data_eval, accum_eval);  // the generated kernel, when one is attached
     L.dom = (uint32_t)dom;
     L.n_fetch = dev->n_fetch;
     L.n_narrow = dev->info.narrow;
@@ -276,6 +276,7 @@ struct bx_cons_circuit {
     bx_circuit_ops ops{};
     const bx_circuit_ops* base = nullptr;
     const bx_cons_program* prog = nullptr;
+    std::vector<uint8_t> kernel;  // bx_cons_circuit_set_kernel: the code object create attaches (empty = the interpreter)
 };
 
 namespace bx {
@@ -324,6 +325,12 @@ const char* cc_create(void* u, bx_ctx* c, const bx_segment_params* shape, void**
     st->shape = *shape;
     st->n_globals = ng;
     BX_TRY(bx_cons_program_load(c, cc->prog, &st->dev));
+    if (!cc->kernel.empty())
+        if (const char* e = bx_cons_program_attach_kernel(st->dev, cc->kernel.data(), cc->kernel.size())) {
+            const char* kept = e == c->err ? e : set_msg(c, e);
+            (void)bx_cons_program_unload(st->dev);
+            return kept;
+        }
     if (b->create)
         if (const char* e = b->create(b->user, c, shape, &st->base_state)) {
             const char* kept = e == c->err ? e : set_msg(c, e);
@@ -394,6 +401,13 @@ extern "C" const char* bx_cons_circuit_create(const bx_circuit_ops* base, const 
     return nullptr;
 } catch (...) {
     return "bx_cons_circuit_create: out of host memory";
+}
+extern "C" const char* bx_cons_circuit_set_kernel(bx_cons_circuit* cc, const void* image, size_t len) try {
+    if (!cc || (len && !image)) return "bx_cons_circuit_set_kernel: null argument";
+    cc->kernel.assign((const uint8_t*)image, (const uint8_t*)image + len);
+    return nullptr;
+} catch (...) {
+    return "bx_cons_circuit_set_kernel: out of host memory";
 }
 extern "C" const bx_circuit_ops* bx_cons_circuit_ops(bx_cons_circuit* cc) { return cc ? &cc->ops : nullptr; }
 extern "C" void bx_cons_circuit_destroy(bx_cons_circuit* cc) { delete cc; }

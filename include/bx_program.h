@@ -1,7 +1,8 @@
 /*
  * bx_program.h — constraint programs: a circuit's constraints as DATA.  One description gives both halves a bx_circuit_ops
- * table needs of them: `eval_check` (a gfx950 kernel that interprets the program over the 4N domain) and `constraints_at` (a
- * host interpreter for the verifier), plus the tap sets.  No device code is written per circuit.
+ * table needs of them: `eval_check` (a gfx950 kernel that interprets the program over the 4N domain, or one generated from the
+ * program off line: "Generated kernels" below) and `constraints_at` (a host interpreter for the verifier), plus the tap sets.
+ * No device code is written per circuit by hand.
  *
  * Where this comes from
  * ---------------------
@@ -52,6 +53,43 @@
  *                than BX_CONS_MAX_NARROW / BX_CONS_MAX_WIDE is refused with the number it needs and the limit.  On the device a
  *                narrow slot is 1 KiB and a wide slot 4 KiB of a workgroup's LDS: 32 + 4 * 24 = 128 KiB of the CU's 160.
  *   output       ONE instruction stream, read by the host executor and by the device kernel alike.
+ *
+ * Generated kernels (normative)
+ * -----------------------------
+ * The interpreter pays for every value with an LDS round trip and for every step with a fetch and a dispatch.  A program may
+ * instead be given a kernel GENERATED from its compiled stream, built off line and attached to the loaded program; without one
+ * the interpreter runs, exactly as before.  Nothing is compiled at run time.
+ *
+ *   digest       bx_cons_program_digest: SHA-256 over the bytes "bx-cons-program" and then, each as a little-endian 32-bit word,
+ *                the ABI number (1), n_globals, the number of mix powers, the result's slot, the length of the stream in words
+ *                and the stream, the number of constants and the constants (Montgomery words), the number of taps and
+ *                (group, col, back) of every tap.  The 32 bytes are returned as eight little-endian words.  It depends on the
+ *                description alone: the same on every machine, different after a change to one constant, tap, step or `ret`.
+ *   text         bx_cons_program_emit_hip: one translation unit, a pure function of the compiled program (no time, no path, no
+ *                address).  Straight-line code, one statement per instruction of the stream, in stream order: a narrow slot
+ *                is a uint32_t local, a wide slot an Fp4 local, so the allocator's 32 + 4 * 24 = 128 live words bound the
+ *                kernel's registers.  The arithmetic is the interpreter's (fp_add / fp_sub / fp_mul / fp_neg, f4_add / f4_sub /
+ *                f4_scale / f4_mul_lz / f4_zero, same operand order): every value is canonical, canonical words are unique, so
+ *                the two executors agree word for word.  Constants are Montgomery-word literals; globals and `mix` are read
+ *                from a table of n_globals + 4 words written per call; mix powers from the canonical power table by literal
+ *                index.  A tap is one load at group_base + (col << (po2 + 2)) + r_back with r_back = (i - 4 back) & (4N - 1)
+ *                computed once per distinct back.  A program of more than 1024 instructions is written as segments of that many,
+ *                each a device function of its own that is not inlined (the compiler's time on one function grows faster than
+ *                linearly); between two segments the slots go through a struct in memory at fixed offsets.  Such a kernel is
+ *                given the whole register file and runs at the lowest occupancy; shorter programs are one function and keep
+ *                every slot in a register.  The text includes csrc/cons_program_gen.hpp, the frame: the argument
+ *                struct, the accessors, the division by (3x)^N - 1, and two wrappers.  Under hipcc:
+ *                    extern "C" __global__ __launch_bounds__(256) void bx_cp_eval(bx_cp_gen_args)
+ *                one lane per domain point, lanes past 4N return, no LDS, with the device symbols bx_cp_abi (one word) and
+ *                bx_cp_digest (eight).  Under a host compiler: a function that fills the four planes from host arrays.
+ *   build        python -m boundless_amd.consgen DESC.json -o OUT.hsaco: hipcc, device only, the library's own flags.
+ *   attach       bx_cons_program_attach_kernel.  Refused by name before anything reaches HIP: an image that starts with neither
+ *                the ELF magic nor "__CLANG_OFFLOAD_BUNDLE__".  Refused by name with the module unloaded again: a code object
+ *                without bx_cp_eval, bx_cp_abi or bx_cp_digest; another ABI number; a digest that is not the loaded program's; a
+ *                second attach without a detach.  bx_cons_program_unload and bx_free detach what is still attached.
+ *   launch       bx_cons_program_eval_check with a kernel attached: the same argument checks and the same table updates, then
+ *                the attached kernel on the ctx's stream, ceil(4N / 256) workgroups of 256 lanes, no dynamic LDS, profiled as
+ *                "cons_program_eval_check_gen".
  */
 #ifndef BX_PROGRAM_H
 #define BX_PROGRAM_H
@@ -149,12 +187,27 @@ const char* bx_cons_program_eval_check(bx_ctx* ctx, bx_cons_program_dev* dev, ui
                                        bx_buf data_eval, uint32_t w_data, bx_buf accum_eval, uint32_t w_accum, const uint32_t poly_mix[4],
                                        const uint32_t mix[4], const uint32_t* globals, uint32_t n_globals);
 
+/* Generated kernels (see the section of that name above).  The digest of the compiled form, eight words. */
+const char* bx_cons_program_digest(const bx_cons_program* prog, uint32_t out[8]);
+/* The generated translation unit as NUL-terminated text.  *need receives its size with the NUL.  buf == NULL only asks for
+ * that size.  A cap below *need is refused and nothing is written; nothing is ever written past cap. */
+const char* bx_cons_program_emit_hip(const bx_cons_program* prog, char* buf, size_t cap, size_t* need);
+/* Attaches the code object `image` (len bytes: an ELF code object or a clang offload bundle; not referenced afterwards) to a
+ * loaded program, whose eval_check then launches it; detach drains the stream and unloads it, and is refused when nothing is
+ * attached.  kernel_attached: 1 or 0. */
+const char* bx_cons_program_attach_kernel(bx_cons_program_dev* dev, const void* image, size_t len);
+const char* bx_cons_program_detach_kernel(bx_cons_program_dev* dev);
+int bx_cons_program_kernel_attached(const bx_cons_program_dev* dev);
+
 /* A bx_circuit_ops whose taps, eval_check and constraints_at come from `prog` and whose normalize, n_globals, create / destroy,
  * code_group, witgen, accumulate, set_noise_seed and check_code are forwarded to `base` with base->user (base's own taps,
  * eval_check and constraints_at may be NULL).  Its create loads the program on the ctx and checks it against the shape: tap
  * columns within the widths, the program's n_globals equal to the base's.  `base` and `prog` must outlive the table, the table
  * its provers.  It is a plug-in table: its code group is committed for every proof. */
 const char* bx_cons_circuit_create(const bx_circuit_ops* base, const bx_cons_program* prog, bx_cons_circuit** out);
+/* Copies a generated kernel's code object into the table: its create attaches it right after loading the program, and fails
+ * with attach_kernel's message if it is refused.  len == 0 goes back to the interpreter.  Set before a prover is created. */
+const char* bx_cons_circuit_set_kernel(bx_cons_circuit* cc, const void* image, size_t len);
 const bx_circuit_ops* bx_cons_circuit_ops(bx_cons_circuit* cc);
 void bx_cons_circuit_destroy(bx_cons_circuit* cc);
 

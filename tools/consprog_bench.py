@@ -1,4 +1,5 @@
-"""What interpreting a circuit's constraints costs against a hand-written kernel for the same constraints.
+"""What interpreting a circuit's constraints costs against a hand-written kernel for the same constraints, and what a kernel
+generated from the same program costs.
 
     python tools/consprog_bench.py [--po2 20] [--widths 16 256 64] [--calls 26] [--warmup 5] [--out profiles/r13_cons_program.json]
 
@@ -7,7 +8,10 @@ One process, the lookup circuit at the given shape, random evaluation matrices (
                constraints costs
   interpreter  cons_program_kernel (bx_cons_program_eval_check) on the lookup circuit written as a constraint program
                (tests/cons_program_ref.py: lookup_program) over the same evaluations
-Median ms of `calls` calls after `warmup`, each bracketed by HIP events on the ctx's stream, two interleaved rounds; the two outputs
+  generated    the kernel generated from that program (boundless_amd.consgen), attached to a second load of it — a row only when the
+               shape has a description under tests/golden/consgen/ (po2 20, widths 16 256 64 has); the description and the code object
+               are read from tests/consgen_cases.py's directories, nothing is generated or compiled here
+Median ms of `calls` calls after `warmup`, each bracketed by HIP events on the ctx's stream, two interleaved rounds; the outputs
 are compared word for word first.  Recorded with the times: their ratio, the program's info, the kernel's registers / scratch /
 occupancy (hipcc -Rpass-analysis=kernel-resource-usage), its dynamic LDS for this program, and the static instruction mix of its text
 (tools/isa_mix.py; the text holds CP_FETCH = 4 copies of the dispatcher, one per instruction of a fetch).  Stamped with the library's
@@ -92,7 +96,7 @@ def main():
         for c in range(w):
             buf.slice(c * dom, dom).copy_from(rng.integers(0, P, dom, dtype=np.uint32))
         evals.append(buf)
-    checks = [hal.alloc(4 * dom), hal.alloc(4 * dom)]
+    checks = [hal.alloc(4 * dom), hal.alloc(4 * dom), hal.alloc(4 * dom)]
     pm = (C.c_uint32 * 4)(*[int(v) for v in rng.integers(0, P, 4)])
     mix = (C.c_uint32 * 4)(*[int(v) for v in rng.integers(0, P, 4)])
     g = (C.c_uint32 * 2)(*[int(v) for v in rng.integers(0, P, 2)])
@@ -113,13 +117,28 @@ def main():
     def interpreter():
         hal.cons_program_eval_check(loaded, po2, checks[1], evals[0], evals[1], evals[2], widths, list(pm), list(mix), list(g))
 
-    builtin()
-    interpreter()
-    same = bool(np.array_equal(checks[0].view(), checks[1].view()))
-    samples = {"builtin": [], "interpreter": []}
+    import consgen_cases
+
+    gen_name = "lookup_%d_%d_%d_%d" % ((po2,) + widths)
+    gen_loaded = gen_compiled = gen_meta = None
+    if gen_name in consgen_cases.NAMES:
+        gen_compiled = consgen_cases.compiled(gen_name)
+        assert gen_compiled.digest() == compiled.digest(), "the committed description is not the program this tool builds"
+        gen_loaded = gen_compiled.load(hal)
+        gen_loaded.attach_kernel(consgen_cases.kernel_path(gen_name))
+        gen_meta = consgen_cases.meta(gen_name)
+
+    def generated():
+        hal.cons_program_eval_check(gen_loaded, po2, checks[2], evals[0], evals[1], evals[2], widths, list(pm), list(mix), list(g))
+
+    rows = [("builtin", builtin), ("interpreter", interpreter)] + ([("generated", generated)] if gen_loaded else [])
+    for _, fn in rows:
+        fn()
+    same = all(bool(np.array_equal(checks[0].view(), checks[k].view())) for k in range(1, len(rows)))
+    samples = {k: [] for k, _ in rows}
     for _ in range(2):  # interleaved, so that a drifting clock does not favour whichever ran first
-        samples["builtin"] += timed(hal, builtin, a.calls // 2, a.warmup)
-        samples["interpreter"] += timed(hal, interpreter, a.calls // 2, a.warmup)
+        for k, fn in rows:
+            samples[k] += timed(hal, fn, a.calls // 2, a.warmup)
     res = {k: {"ms": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4), "calls": len(v)} for k, v in samples.items()}
     info = compiled.info
     import isa_mix
@@ -132,15 +151,25 @@ def main():
            "ns_per_point_and_instruction": round(res["interpreter"]["ms"] * 1e6 / dom / info["instructions"], 5),
            "program_info": info, "lds_bytes_per_workgroup": (info["narrow"] + 4 * info["wide"]) * 1024,
            "kernel_resources": resource_usage(), "isa_mix": isa_mix.analyse(SRC, ["cons_program_kernel"])}
-    print(json.dumps({k: doc[k] for k in ("same_words", "timing", "interpreter_over_builtin", "program_info", "kernel_resources")}), flush=True)
+    keys = ("same_words", "timing", "interpreter_over_builtin", "program_info", "kernel_resources")
+    if gen_loaded:
+        doc["generated_over_builtin"] = round(res["generated"]["ms"] / res["builtin"]["ms"], 3)
+        doc["interpreter_over_generated"] = round(res["interpreter"]["ms"] / res["generated"]["ms"], 3)
+        doc["generated_below_interpreter"] = res["generated"]["ms_max"] < res["interpreter"]["ms_min"]  # the whole range, in this run
+        doc["generated_kernel"] = gen_meta
+        doc["note"] += "; generated = bx_cp_eval built off line from the same program (boundless_amd.consgen) and attached to a second load of it"
+        keys += ("generated_over_builtin", "interpreter_over_generated", "generated_below_interpreter", "generated_kernel")
+    print(json.dumps({k: doc[k] for k in keys}), flush=True)
     with open(a.out, "w") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")
     loaded.unload()
+    if gen_loaded:
+        gen_loaded.unload()
     hal.sync()
     ops.destroy(None, state)
     hal.close()
-    assert same, "the interpreter and the built-in kernel disagree"
+    assert same, "the executors disagree with the built-in kernel"
 
 
 if __name__ == "__main__":
