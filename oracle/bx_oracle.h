@@ -118,6 +118,33 @@ void bxo_set_witness_fault(int group, uint32_t col, uint32_t row);
 /* test hook: a dishonest prover that commits its own code group (1: `last` == 0 and a false g_1; 2: `first` == 0, zero
  * accumulators and a false g_0; 0: honest).  Only a control-ID check of the code root can refuse such a seal. */
 void bxo_set_cheat(int mode);
+/* test hook: a prover of a TRUE statement that lies in exactly one place behind the constraint identity and is otherwise
+ * self-consistent (it commits, draws challenges and opens honestly from whatever it committed).  Process-global like the two
+ * hooks above; BXO_FAULT_NONE switches it off and leaves every seal byte-identical.
+ *   TAP_PAIR(k, compensate)  a false evaluation claim: with d = ext one, the tap value of check column 4k gets + Z^2 d and, if
+ *                            `compensate`, that of check column 4k+1 gets - d.  The verifier weights column 4k+q by Z^(rev2 q),
+ *                            so 1 * g_4k + Z^2 * g_4k+1 — and with it the constraint identity — is unchanged; uncompensated,
+ *                            the identity fails.  The DEEP step subtracts the lied values, its division leaves a remainder,
+ *                            and the prover goes on with the quotient.
+ *   LAYER0_SHIFT             ext one is added to coefficient 0 of the DEEP sum before FRI round 0: all of FRI is consistent and
+ *                            of low degree, but it is not the quotient of the committed trace.
+ *   FOLD_MIX(r)              round r folds with fold_mix + 1 instead of the challenge it drew.
+ *   FINAL(j)                 one is added to natural-order coefficient j (component 0) of the final polynomial before it is
+ *                            written and committed.
+ *   ROWS(r, m)               one is added to every word of the rows with index % m == 0 of round r's evaluation matrix before
+ *                            its tree is built: a committed function that is not a polynomial's evaluations.
+ *   OPEN_NEIGHBOUR(q, t)     query q opens tree t (0..3 the trace groups, 4 + r FRI round r) at index ^ 1: an authentic row and
+ *                            path of the committed tree, for another position than the one the transcript drew. */
+enum {
+    BXO_FAULT_NONE = 0,
+    BXO_FAULT_TAP_PAIR = 1,
+    BXO_FAULT_LAYER0_SHIFT = 2,
+    BXO_FAULT_FOLD_MIX = 3,
+    BXO_FAULT_FINAL = 4,
+    BXO_FAULT_ROWS = 5,
+    BXO_FAULT_OPEN_NEIGHBOUR = 6
+};
+void bxo_set_prover_fault(int kind, uint32_t a, uint32_t b);
 void bxo_free(void* p);
 
 /* ---- program image (bx_oracle_image.c): risc0_zkvm::compute_image_id of an "R0BF" program binary.  PINNED by the

@@ -258,6 +258,20 @@ void bxo_set_witness_fault(int group, uint32_t col, uint32_t row) {
 static int cheat_mode = 0;
 void bxo_set_cheat(int mode) { cheat_mode = mode; }
 
+/* Test hook: a DISHONEST prover that proves a true statement but lies in exactly ONE place behind the constraint identity
+ * (kind 0 = honest; the kinds and their parameters: bx_oracle.h, BXO_FAULT_*).  Everywhere else it stays self-consistent: it
+ * commits what it computed from the lie, draws its challenges from that transcript and opens honestly from what it committed.
+ * So header, public words, trace commitments and control ID are an honest prover's, every hash compare in front of the lie sees
+ * honest data, and only the checks that tie the committed trace to one low-degree polynomial — the DEEP quotient against FRI's
+ * first layer, the fold chain, the final polynomial, and the position a Merkle path is hashed at — can refuse the seal. */
+static int pf_kind = BXO_FAULT_NONE;
+static uint32_t pf_a, pf_b;
+void bxo_set_prover_fault(int kind, uint32_t a, uint32_t b) {
+    pf_kind = kind;
+    pf_a = a;
+    pf_b = b;
+}
+
 /* Returns a malloc'ed seal (caller frees with bxo_free) or NULL on an internal consistency failure. */
 uint32_t* bxo_prove_segment_ex(uint32_t po2, uint32_t w_code, uint32_t w_data, uint32_t w_accum, uint32_t terms, uint32_t degree,
                                uint64_t seed, size_t* seal_words, uint32_t roots_out[32]) {
@@ -561,6 +575,13 @@ uint32_t* bxo_prove_segment_zk(uint32_t po2, uint32_t w_code, uint32_t w_data, u
                     memcpy(xs + 4 * e, x.c, 16);
                 }
             bxo_batch_evaluate_any(grp[g].coeffs, n, which, xs, ev, ne);
+            if (pf_kind == BXO_FAULT_TAP_PAIR && g == 3 && 4 * pf_a + 1 < CHECK_SIZE) {
+                /* the check columns have one tap each: evaluation e is column e */
+                const e4 z2 = e4mul(Z, Z);
+                uint32_t* v = ev + 4 * (size_t)(4 * pf_a);
+                for (int k = 0; k < 4; k++) v[k] = bxo_fp_add(v[k], z2.c[k]);
+                if (pf_b) v[4] = bxo_fp_sub(v[4], bxo_fp_encode(1));
+            }
             e = 0;
             for (uint32_t c = 0; c < grp[g].width; c++) {
                 /* [EXT] poly_interpolate: the polynomial of degree < k through the k tap points, by Newton's divided
@@ -635,6 +656,7 @@ uint32_t* bxo_prove_segment_zk(uint32_t po2, uint32_t w_code, uint32_t w_data, u
     uint32_t* fin = (uint32_t*)malloc(4 * n * 4);
     bxo_eltwise_sum_extelem(fin, combos, n, n_combos);
     bxo_batch_bit_reverse(fin, 4, n);
+    if (pf_kind == BXO_FAULT_LAYER0_SHIFT) fin[0] = bxo_fp_add(fin[0], bxo_fp_encode(1)); /* coefficient 0 stands first in either order */
     free(combos);
     free(coeff_u);
 
@@ -649,9 +671,15 @@ uint32_t* bxo_prove_segment_zk(uint32_t po2, uint32_t w_code, uint32_t w_data, u
         size_t domain = size * INV_RATE;
         revals[r] = (uint32_t*)malloc(4 * domain * 4);
         bxo_batch_expand_into_evaluate_ntt(revals[r], coeffs, 4, size, 2);
+        if (pf_kind == BXO_FAULT_ROWS && pf_a == r && pf_b >= 1) {
+            const size_t rows = domain / FRI_FOLD; /* the matrix is rows x 64, column-major */
+            for (size_t row = 0; row < rows; row += pf_b)
+                for (size_t col = 0; col < FRI_FOLD * 4; col++) revals[r][col * rows + row] = bxo_fp_add(revals[r][col * rows + row], bxo_fp_encode(1));
+        }
         tree_build(&rt[r], revals[r], domain / FRI_FOLD, FRI_FOLD * 4);
         tree_commit(&rt[r], &io);
         e4 fold_mix = iop_random_ext(&io);
+        if (pf_kind == BXO_FAULT_FOLD_MIX && pf_a == r) fold_mix.c[0] = bxo_fp_add(fold_mix.c[0], bxo_fp_encode(1));
         uint32_t* out = (uint32_t*)malloc(4 * (size / FRI_FOLD) * 4);
         bxo_fri_fold(out, coeffs, fold_mix.c, size / FRI_FOLD);
         free(coeffs);
@@ -660,6 +688,7 @@ uint32_t* bxo_prove_segment_zk(uint32_t po2, uint32_t w_code, uint32_t w_data, u
     }
     {
         bxo_batch_bit_reverse(coeffs, 4, size);
+        if (pf_kind == BXO_FAULT_FINAL && pf_a < size) coeffs[pf_a] = bxo_fp_add(coeffs[pf_a], bxo_fp_encode(1));
         uint32_t dg[8];
         iop_write(&io, coeffs, 4 * size);
         bxo_hash_elem_slice(dg, coeffs, 4 * size, 1);
@@ -669,10 +698,12 @@ uint32_t* bxo_prove_segment_zk(uint32_t po2, uint32_t w_code, uint32_t w_data, u
     for (int q = 0; q < QUERIES; q++) {
         uint32_t rng = iop_random_bits(&io, ilog2sz(dom));
         size_t pos = rng % dom;
-        for (int g = 0; g < 4; g++) tree_prove(&grp[g].tree, &io, pos);
+        /* the tree this query opens one leaf beside the drawn position (none for an honest prover) */
+        const size_t beside = pf_kind == BXO_FAULT_OPEN_NEIGHBOUR && pf_a == (uint32_t)q ? pf_b : (size_t)-1;
+        for (int g = 0; g < 4; g++) tree_prove(&grp[g].tree, &io, pos ^ (size_t)(beside == (size_t)g));
         for (size_t r = 0; r < n_rounds; r++) {
             size_t group = pos % rt[r].rows;
-            tree_prove(&rt[r], &io, group);
+            tree_prove(&rt[r], &io, group ^ (size_t)(beside == 4 + r));
             pos = group;
         }
     }
@@ -683,7 +714,7 @@ uint32_t* bxo_prove_segment_zk(uint32_t po2, uint32_t w_code, uint32_t w_data, u
     free(rt);
     free(revals);
     for (int g = 0; g < 4; g++) group_free(&grp[g]);
-    if (!ok) {
+    if (!ok && pf_kind != BXO_FAULT_TAP_PAIR) { /* a false tap value leaves a remainder by design: that prover goes on regardless */
         free(io.seal);
         return NULL;
     }

@@ -78,6 +78,7 @@ def lib(path=None):
         "bxo_rng_random_bits": ([u32p, C.c_uint], C.c_uint32),
         "bxo_set_witness_fault": ([C.c_int, C.c_uint32, C.c_uint32], None),
         "bxo_set_cheat": ([C.c_int], None),
+        "bxo_set_prover_fault": ([C.c_int, C.c_uint32, C.c_uint32], None),
         "bxo_control_id": ([C.c_uint32, C.c_uint32, u32p], None),
         "bxo_free": ([C.c_void_p], None),
         "bxo_compute_image_id": ([C.c_char_p, sz, C.c_char_p, u32p], C.c_int),
@@ -133,6 +134,21 @@ def prove_segment(po2, w_code, w_data, w_accum, seed, L=None, terms=0, degree=0,
     seal = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint32)), shape=(n.value,)).copy()
     L.bxo_free(ptr)
     return seal, roots.reshape(4, 8)
+
+
+# bxo_set_prover_fault kinds (bx_oracle.h: BXO_FAULT_*)
+FAULT_NONE, FAULT_TAP_PAIR, FAULT_LAYER0_SHIFT, FAULT_FOLD_MIX, FAULT_FINAL, FAULT_ROWS, FAULT_OPEN_NEIGHBOUR = range(7)
+
+
+def prove_segment_with_fault(kind, a, b, po2, w_code, w_data, w_accum, seed, L=None):
+    """The seal of a prover that lies in one place (bx_oracle.h: bxo_set_prover_fault) and is otherwise self-consistent.  The
+    hook is process-global: it is switched off again whatever happens."""
+    L = L or lib()
+    L.bxo_set_prover_fault(kind, a, b)
+    try:
+        return prove_segment(po2, w_code, w_data, w_accum, seed, L=L)
+    finally:
+        L.bxo_set_prover_fault(FAULT_NONE, 0, 0)
 
 
 def control_id(po2, w_code, L=None):
