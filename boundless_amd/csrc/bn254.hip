@@ -510,6 +510,21 @@ const char* ntt_coset(bx_ctx* c, bx_groth16_key* k, uint32_t* x) {
     return nullptr;
 }
 
+// Every coordinate of `count` points (`coords` 32-byte Fq limbs each) is below q.  Host only, over the zkey's bytes: the field code
+// assumes reduced inputs (its equality and zero tests are limb compares), so an encoding x + q of a coordinate can pass on_curve and
+// then miss the doubling branch of an addition — a wrong sum that comes back fully reduced.
+const char* coords_below_q(bx_ctx* c, const uint8_t* p, size_t count, size_t coords, const char* what) {
+    for (size_t i = 0; i < count * coords; i++) {
+        uint32_t w[8];
+        memcpy(w, p + 32 * i, 32);
+        if (ge_mod<FqP>(w)) {
+            snprintf(c->err, sizeof c->err, "bx_groth16_key_load: %s: point %zu has a coordinate not below q", what, i / coords);
+            return c->err;
+        }
+    }
+    return nullptr;
+}
+
 const char* key_load(bx_ctx* c, const uint8_t* p, size_t len, bx_groth16_key* k) {
     bx::ZkeyView z;
     char msg[256];
@@ -520,6 +535,19 @@ const char* key_load(bx_ctx* c, const uint8_t* p, size_t len, bx_groth16_key* k)
     const size_t n = I.n_vars, N = I.domain_size, nc = I.n_vars - I.n_public - 1, half = std::max<size_t>(1, N / 2);
     BX_REQUIRE(c, n + 2 <= BX_BN254_MSM_MAX_N && nc + N + 3 <= BX_BN254_MSM_MAX_N,
                "bx_groth16_key_load: the key's MSMs (n_vars + 2, n_vars - n_public - 1 + domain_size + 3 points) exceed BX_BN254_MSM_MAX_N");
+    // coordinates below q, over the bytes about to be staged (and IC / gamma2, which stay on the host)
+    {
+        const uint8_t* h = z.sec[2];
+        const struct {
+            const uint8_t* at;
+            size_t count, coords;
+            const char* what;
+        } lists[] = {{h + 84, 1, 2, "section 2 (alpha1)"}, {h + 148, 1, 2, "section 2 (beta1)"},  {h + 212, 1, 4, "section 2 (beta2)"},
+                     {h + 340, 1, 4, "section 2 (gamma2)"}, {h + 468, 1, 2, "section 2 (delta1)"}, {h + 532, 1, 4, "section 2 (delta2)"},
+                     {z.sec[3], (size_t)I.n_public + 1, 2, "section 3 (IC)"}, {z.sec[5], n, 2, "section 5 (A)"}, {z.sec[6], n, 2, "section 6 (B1)"},
+                     {z.sec[7], n, 4, "section 7 (B2)"}, {z.sec[8], nc, 2, "section 8 (C)"}, {z.sec[9], N, 2, "section 9 (H)"}};
+        for (auto& l : lists) BX_TRY(coords_below_q(c, l.at, l.count, l.coords, l.what));
+    }
     // IC and gamma2 take no part in proving (they are uploaded nowhere): checked here, on the host
     for (uint32_t i = 0; i <= I.n_public; i++) {
         Aff<Fq> p;

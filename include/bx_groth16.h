@@ -56,7 +56,8 @@ const char* bx_groth16_zkey_inspect(const char* path, bx_groth16_info* out);
 const char* bx_groth16_zkey_inspect_mem(const void* bytes, size_t len, bx_groth16_info* out);
 
 /* Parse, upload (chunked through pinned staging) and prepare a key on ctx: twiddles, the coefficient lists sorted by constraint
- * (CSR), every G1 / G2 point checked to lie on its curve (those the prover uses on the device; IC and gamma2 on the host; no
+ * (CSR), every G1 / G2 point checked to have its coordinates below q (on the host, over the file's bytes: "... has a coordinate
+ * not below q", naming the section) and to lie on its curve (those the prover uses on the device; IC and gamma2 on the host; no
  * subgroup check).  Refuses a key whose MSMs would exceed BX_BN254_MSM_MAX_N points.  Blocks. */
 const char* bx_groth16_key_load(bx_ctx* ctx, const char* path, bx_groth16_key** out);
 const char* bx_groth16_key_load_mem(bx_ctx* ctx, const void* bytes, size_t len, bx_groth16_key** out);
@@ -73,8 +74,11 @@ const char* bx_groth16_proof_json(const bx_groth16_proof* proof, char* buf, size
 const char* bx_groth16_public_json(const bx_groth16_proof* proof, char* buf, size_t cap);
 
 /* sum scalars[i] * points[i] on device buffers (the prover's hot path).  points: affine, Montgomery form, little-endian, 16 words
- * per G1 point (x, y), 32 per G2 point (x.c0, x.c1, y.c0, y.c1), infinity as zeros; scalars: 8 words each, canonical.  out (host):
- * the affine result in canonical coordinates (16 / 32 words), infinity as zeros.  n <= BX_BN254_MSM_MAX_N.  Blocks. */
+ * per G1 point (x, y), 32 per G2 point (x.c0, x.c1, y.c0, y.c1), infinity as zeros.  Every coordinate must be below q and every
+ * point on its curve: the hot path checks neither (bx_groth16_key_load does, for a key's points), and a coordinate stored as x + q
+ * can give a wrong, fully reduced sum.  scalars: 8 words each; all 256 bits are read, so a scalar k that is not below r gives
+ * (k mod r) * P, as the group law says — canonical scalars are not required (bx_groth16_prove checks its witness itself).  out
+ * (host): the affine result in canonical coordinates (16 / 32 words), infinity as zeros.  n <= BX_BN254_MSM_MAX_N.  Blocks. */
 const char* bx_bn254_msm_g1(bx_ctx* ctx, bx_buf points, bx_buf scalars, size_t n, uint32_t* out);
 const char* bx_bn254_msm_g2(bx_ctx* ctx, bx_buf points, bx_buf scalars, size_t n, uint32_t* out);
 
