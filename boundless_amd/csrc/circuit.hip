@@ -16,7 +16,12 @@
 // adjacent asm statements.  Per cell, compiled, the factored form: 486 VALU instructions (368 multiply-class) at (T, G) = (64, 4)
 // and 265 (127) at (48, 3); term by term they were 630 (474) and 389 (218).  The pair form takes (64, 4) down by another 75
 // instructions per cell, 117 of them fewer multiply-class: witness_derive_kernel<64,4> 568 (368) -> 493 (251), eval_check_kernel<64,4>
-// 1340 (657) -> 1265 (540).  DESIGN.md §4 has the tables.
+// 1340 (657) -> 1265 (540).  One thing the un-pinned code must be kept from: with the constant R in sight hipcc turns a level's
+// sum of r_i * R into (sum of r_i) * R with a 64-bit sum and an emulated product, so the second and third level multiply by an
+// opaque copy of R (circuit_dev.hpp, smad_r); and the walk keeps its pool centred in registers (DerivedRegs<true>) instead of
+// centring all 16 entries per cell.  Together, the walk's loop body per cell, VALU instructions (multiplies): witness_derive_kernel<64,4>
+// 412 (251) -> 312 (274), eval_check_kernel<64,4> 467 (275) -> 367 (298); whole kernels 493 -> 438 and 1265 -> 1210; 65 -> 54 and
+// 87 -> 78 VGPRs.  DESIGN.md §4 has the tables.
 #define BX_PLAIN_MAD 1
 #include <memory>
 #include <new>
@@ -64,24 +69,27 @@ __global__ __launch_bounds__(256) void witness_derive_kernel(uint32_t* __restric
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     const uint32_t rb1 = (r + n - 1) & (n - 1), rb2 = (r + n - 2) & (n - 1);
-    const auto code_at = [&](unsigned i) -> uint32_t {
+    // the compiled constraint sums walk over centred registers (a word is centred where it enters them), <0, 0> over canonical ones
+    using Regs = DerivedRegs<(TT > 0)>;
+    using word = typename Regs::word;
+    const auto code_at = [&](unsigned i) -> word {
         const int col = cc.csel_col(i);
-        return col < 0 ? MONT_ONE : code[(size_t)col * n + r];
+        return Regs::enter(col < 0 ? MONT_ONE : code[(size_t)col * n + r]);
     };
-    DerivedRegs w;
+    Regs w;
 #pragma unroll
     for (int q = 0; q < 8; ++q) w.ring[q] = code_at((unsigned)q);
 #pragma unroll
-    for (int q = 0; q < 3; ++q) w.u[q] = data[(size_t)((uint32_t)q % cc.F) * n + r];
+    for (int q = 0; q < 3; ++q) w.u[q] = Regs::enter(data[(size_t)((uint32_t)q % cc.F) * n + r]);
 #pragma unroll
     for (int q = 0; q < 4; ++q) w.k[q] = code_at((unsigned)q);
     for (uint32_t j = 0; j < cc.J; ++j) {
-        uint32_t pool[Circuit::POOL];
+        word pool[Circuit::POOL];
         const int sb = Circuit::slot1_back(j);
-        w.fill(pool, sb == 0 ? w.u[0] : data[(size_t)j * n + (sb == 1 ? rb1 : rb2)]);
+        w.fill(pool, sb == 0 ? w.u[0] : Regs::enter(data[(size_t)j * n + (sb == 1 ? rb1 : rb2)]));
         const uint32_t d = cons_sum<TT, GG>(pool, cc.T, cc.G);
-        data[(size_t)(cc.F + j) * n + r] = d;
-        w.shift(d, data[(size_t)((j + 3) % cc.F) * n + r], code_at(j + 4));
+        data[(size_t)(cc.F + j) * n + r] = d;  // canonical, as every word in memory
+        w.shift(Regs::enter(d), Regs::enter(data[(size_t)((j + 3) % cc.F) * n + r]), code_at(j + 4));
     }
 }
 
@@ -118,24 +126,26 @@ __global__ __launch_bounds__(256) void eval_check_kernel(uint32_t* __restrict__ 
     const uint32_t ib2 = (i + dom - 8u) & (dom - 1u);  // two rows back
     LazyExtAcc mixacc;  // sum_j poly_mix^j * C_j over the derived-column constraints (ext weight x base value)
     mixacc.reset();
-    const auto code_at = [&](unsigned q) -> uint32_t {
+    using Regs = DerivedRegs<(TT > 0)>;  // centred registers for the compiled constraint sums, as in witness_derive_kernel
+    using word = typename Regs::word;
+    const auto code_at = [&](unsigned q) -> word {
         const int col = cc.csel_col(q);
-        return col < 0 ? MONT_ONE : ecode[(size_t)col * dom + i];
+        return Regs::enter(col < 0 ? MONT_ONE : ecode[(size_t)col * dom + i]);
     };
-    DerivedRegs w;
+    Regs w;
 #pragma unroll
     for (int q = 0; q < 8; ++q) w.ring[q] = code_at((unsigned)q);
 #pragma unroll
-    for (int q = 0; q < 3; ++q) w.u[q] = edata[(size_t)((uint32_t)q % cc.F) * dom + i];
+    for (int q = 0; q < 3; ++q) w.u[q] = Regs::enter(edata[(size_t)((uint32_t)q % cc.F) * dom + i]);
 #pragma unroll
     for (int q = 0; q < 4; ++q) w.k[q] = code_at((unsigned)q);
     for (uint32_t j = 0; j < cc.J; ++j) {
-        uint32_t pool[Circuit::POOL];
+        word pool[Circuit::POOL];
         const int sb = Circuit::slot1_back(j);
-        w.fill(pool, sb == 0 ? w.u[0] : edata[(size_t)j * dom + (sb == 1 ? ib : ib2)]);
-        const uint32_t d = edata[(size_t)(cc.F + j) * dom + i];
+        w.fill(pool, sb == 0 ? w.u[0] : Regs::enter(edata[(size_t)j * dom + (sb == 1 ? ib : ib2)]));
+        const uint32_t d = edata[(size_t)(cc.F + j) * dom + i];  // the committed word: canonical where the constraint subtracts from it
         mix_add(mixacc, mixpows_c, j, fp_sub(d, cons_sum<TT, GG>(pool, cc.T, cc.G)));
-        w.shift(d, edata[(size_t)((j + 3) % cc.F) * dom + i], code_at(j + 4));
+        w.shift(Regs::enter(d), Regs::enter(edata[(size_t)((j + 3) % cc.F) * dom + i]), code_at(j + 4));
     }
     Fp4 tot = mixacc.finish();
     const uint32_t first = ecode[i];

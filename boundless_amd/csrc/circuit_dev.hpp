@@ -5,7 +5,14 @@
 //
 // The compile-time paths run on the signed, bounded Montgomery arithmetic of poseidon2_arith.hpp (sredc(t) = (t + mP)/2^32,
 // |result| <= ub(|t|) = |t|/2^32 + P/2 + 1, valid for |t| <= SREDC_MAX = 1.209 P^2; P^2/2^32 = 0.469 P) so that no product is
-// followed by a conditional subtraction and the sums stay unreduced in 64 bits.  Pool entries are centred once per cell, |c| <= P/2.
+// followed by a conditional subtraction and the sums stay unreduced in 64 bits.  Pool entries are centred, |c| <= P/2: by the walk of
+// circuit.hip once per word, where it enters the registers (DerivedRegs<true> and the centred entry of cons_sum, 4 of the 16 entries
+// are new per cell), by the canonical-pool signature once per call.  The second and third level multiply by an opaque copy of R
+// (smad_r) so that each addend stays one v_mad_i64_i32.  Compiled, the walk's loop body per cell, VALU instructions / multiplies
+// (v_mad_i64_i32 + v_mul_lo_u32 + v_mad_u64_u32): witness_derive_kernel<64,4> 412 / 251 -> 312 / 274 (54 VGPRs, it was 65),
+// eval_check_kernel<64,4> 467 / 275 -> 367 / 298 (78 VGPRs, it was 87: six waves per SIMD again).  The multiplies that came are the
+// level steps that had been folded into emulated 64 x 32-bit products; the 123 other instructions that went are that emulation's sign
+// extensions, 64-bit adds and copies, and the centring of twelve entries that had been centred a cell before.
 //
 // G = 4, the pair form.  A term is a product of four pool entries and can be written as (pair) * (pair) in three ways; PairPlan picks
 // one split per term so that pairs recur (44 distinct pairs serve the 128 pair slots of T = 64, where the first-factor form below
@@ -20,7 +27,7 @@
 //   second level          acc2 = sum of r * R over <= 7 consecutive groups:  |acc2| <= 0.967 P^2 <= FINAL_MAX (eight: 1.105 P^2)
 //   third level           the same over the <= 4 second-level results:       |acc3| <= 4 * (P - 1) * R = 0.53 P^2
 // The terms are ordered so that a pair's uses lie in neighbouring groups (at most 7 pairs are computed and still awaited at any
-// point of T = 64), which keeps the pair products from costing registers: eval_check_kernel<64,4> compiles to 87 VGPRs, no scratch.
+// point of T = 64), which keeps the pair products from costing registers: eval_check_kernel<64,4> compiles to 78 VGPRs, no scratch.
 // Every path from a term to the result is again a congruence mod P through three reductions against two factors R, so the
 // canonical result is the same word as the first-factor form's and the plain loop's.  PairPlan carries the bounds; cons_sum's
 // static_asserts hold them, and the host build (BX_CHECK_BOUNDS) asserts every pair, every sredc operand and every level's sum.
@@ -55,6 +62,8 @@
 // In both forms the last reduction is < P in magnitude, so one conditional add of P makes it canonical, and the result is
 // bit-identical to the plain form; tests compare both paths with the oracle.
 #pragma once
+#include <type_traits>
+
 #include "circuit.hpp"
 #include "fp.hpp"
 #include "poseidon2_arith.hpp"
@@ -309,15 +318,35 @@ struct PairPlan {
 template <int TT>
 inline constexpr PairPlan<TT> pair_plan{};
 
+// r * R + c, the step of the second and third reduction level.  In a translation unit that leaves its multiply-adds to the compiler
+// (BX_PLAIN_MAD) the device build multiplies by an opaque copy of R, one per use: with the constant in sight hipcc rewrites a level's
+// sum of r_i * R as (sum of r_i) * R, sign-extends every r_i, adds them in 64 bits and emulates a 64 x 32-bit product (about 28
+// instructions for a level of seven, where this is 7 v_mad_i64_i32).  The copy lives in an SGPR (an s_mov per use, no VALU work), is
+// signed so that the product stays a v_mad_i64_i32 (an opaque unsigned word gets an emulated v_mad_u64_u32 product), and comes out of a
+// volatile asm (CSE merges the copies of a plain one and the rewrite is back).  Same 64-bit integer either way.
+BX_HD i64 smad_r(i32 r, i64 c, int alt = 0) {
+#if defined(__HIP_DEVICE_COMPILE__) && defined(BX_PLAIN_MAD)
+    (void)alt;
+    i32 k = (i32)MONT_ONE;
+    asm volatile("" : "+s"(k));
+    return (i64)r * (i64)k + c;
+#else
+    return smad_k(r, MONT_ONE, c, alt);
+#endif
+}
+
+// The compile-time paths, on a pool that is already centred: |pool[i]| <= P/2 is what every bound of the plans rests on, and the
+// host build (BX_CHECK_BOUNDS) asserts it for every entry.  The walk of circuit.hip calls this with the pool its DerivedRegs<true>
+// keep centred from cell to cell; the canonical-pool signature below centres and forwards.
 template <int TT, int GG>
-BX_HD uint32_t cons_sum(const uint32_t (&pool_u)[Circuit::POOL], uint32_t T, uint32_t G) {
-    if constexpr (TT > 0 && GG == 4) {
+BX_HD uint32_t cons_sum(const i32 (&pool)[Circuit::POOL], uint32_t /*T*/, uint32_t /*G*/) {
+    static_assert(TT > 0 && GG > 0, "cons_sum: the run-time form takes a canonical pool");
+#pragma unroll
+    for (unsigned i = 0; i < Circuit::POOL; ++i) BX_ASSERT_BOUND(pool[i] <= (i32)(P / 2) && pool[i] >= -(i32)(P / 2), "cons_sum: a pool entry that is not centred");
+    if constexpr (GG == 4) {
         constexpr int N2 = pair_plan<TT>.n2;
         static_assert(pair_plan<TT>.max_group <= SREDC_MAX, "cons_sum: a group sum beyond sredc's range");
         static_assert(pair_plan<TT>.max_l2 <= FINAL_MAX && pair_plan<TT>.max_l3 <= FINAL_MAX, "cons_sum: term count beyond the three reduction levels");
-        i32 pool[Circuit::POOL];
-#pragma unroll
-        for (unsigned i = 0; i < Circuit::POOL; ++i) pool[i] = fp_centre(pool_u[i]);
         // every index below is a constant expression, so each pool entry and each pair product is a fixed register
         i32 pr[pair_plan<TT>.np];
         i64 acc3 = 0;
@@ -337,25 +366,22 @@ BX_HD uint32_t cons_sum(const uint32_t (&pool_u)[Circuit::POOL], uint32_t T, uin
                     });
                     acc = smad(pr[pair_plan<TT>.s1[s]], pr[pair_plan<TT>.s2[s]], acc, s);
                 });
-                acc2 = smad_k(sredc(acc, 3), MONT_ONE, acc2, g);
+                acc2 = smad_r(sredc(acc, 3), acc2, g);
             });
             BX_ASSERT_BOUND(acc2 <= FINAL_MAX && acc2 >= -FINAL_MAX, "cons_sum second level");
             const i32 r2 = sredc(acc2, 2);
             if constexpr (N2 == 1) result = r2;
-            else acc3 = smad_k(r2, MONT_ONE, acc3, l);
+            else acc3 = smad_r(r2, acc3, l);
         });
         if constexpr (N2 > 1) {
             BX_ASSERT_BOUND(acc3 <= FINAL_MAX && acc3 >= -FINAL_MAX, "cons_sum third level");
             result = sredc(acc3, 0);
         }
         return (uint32_t)(result + (result < 0 ? (i32)P : 0));
-    } else if constexpr (TT > 0 && GG >= 3) {
+    } else if constexpr (GG >= 3) {
         constexpr int N2 = cons_plan<TT, GG>.n2;
         static_assert(cons_plan<TT, GG>.max_inner <= SREDC_MAX && cons_plan<TT, GG>.max_outer <= SREDC_MAX, "cons_sum: a group sum beyond sredc's range");
         static_assert(cons_plan<TT, GG>.max_l2 <= FINAL_MAX && cons_plan<TT, GG>.max_l3 <= FINAL_MAX, "cons_sum: term count beyond the three reduction levels");
-        i32 pool[Circuit::POOL];
-#pragma unroll
-        for (unsigned i = 0; i < Circuit::POOL; ++i) pool[i] = fp_centre(pool_u[i]);
         // every index below is a constant expression (static_for hands its counter over as a type), so each pool reference is a
         // fixed register and each accumulator a fresh value of its group
         i64 acc3 = 0;
@@ -379,19 +405,16 @@ BX_HD uint32_t cons_sum(const uint32_t (&pool_u)[Circuit::POOL], uint32_t T, uin
                     });
                     outer = smad(sredc(inner, 3), pool[cons_plan<TT, GG>.first[q]], outer, q);
                 });
-                acc2 = smad_k(sredc(outer, 1), MONT_ONE, acc2, o);
+                acc2 = smad_r(sredc(outer, 1), acc2, o);
             });
             const i32 r2 = sredc(acc2, 2);
             if constexpr (N2 == 1) result = r2;
-            else acc3 = smad_k(r2, MONT_ONE, acc3, l);
+            else acc3 = smad_r(r2, acc3, l);
         });
         if constexpr (N2 > 1) result = sredc(acc3, 0);
         return (uint32_t)(result + (result < 0 ? (i32)P : 0));
-    } else if constexpr (TT > 0) {
+    } else {
         static_assert(TT <= 3 * 8 * 7 && GG >= 1, "cons_sum: term count beyond the three reduction levels");
-        i32 pool[Circuit::POOL];
-#pragma unroll
-        for (unsigned i = 0; i < Circuit::POOL; ++i) pool[i] = fp_centre(pool_u[i]);
         constexpr int GRP = 3, NG = (TT + GRP - 1) / GRP;
         i64 acc2 = 0, acc3 = 0;
         i32 result = 0;
@@ -408,16 +431,28 @@ BX_HD uint32_t cons_sum(const uint32_t (&pool_u)[Circuit::POOL], uint32_t T, uin
                 }
             }
             const i32 r = sredc(acc, 3);
-            acc2 = smad_k(r, MONT_ONE, acc2, g);
+            acc2 = smad_r(r, acc2, g);
             if ((g & 7) == 7 || g == NG - 1) {
                 const i32 r2 = sredc(acc2, 1);
                 acc2 = 0;
                 if constexpr (NG <= 8) result = r2;
-                else acc3 = smad_k(r2, MONT_ONE, acc3, 2);
+                else acc3 = smad_r(r2, acc3, 2);
             }
         }
         if constexpr (NG > 8) result = sredc(acc3, 0);
         return (uint32_t)(result + (result < 0 ? (i32)P : 0));
+    }
+}
+
+// The canonical-pool signature: the compile-time paths centre the pool and take the entry above; <0, 0> is the run-time form on
+// canonical words.
+template <int TT, int GG>
+BX_HD uint32_t cons_sum(const uint32_t (&pool_u)[Circuit::POOL], uint32_t T, uint32_t G) {
+    if constexpr (TT > 0) {
+        i32 pool[Circuit::POOL];
+#pragma unroll
+        for (unsigned i = 0; i < Circuit::POOL; ++i) pool[i] = fp_centre(pool_u[i]);
+        return cons_sum<TT, GG>(pool, T, G);
     } else {
         uint32_t sum = 0;
         for (uint32_t t = 0; t < T; ++t) {
@@ -433,10 +468,20 @@ BX_HD uint32_t cons_sum(const uint32_t (&pool_u)[Circuit::POOL], uint32_t T, uin
 // point) share keeps the pool of column F+j in registers from one column to the next: the eight previous derived columns in `ring`
 // (csel(0..7) before the first), free columns j, j+1, j+2 in `u`, code csel(j..j+3) in `k`.  Slot 1 alone is loaded per column,
 // where Circuit::slot1_back asks for a row back (else it repeats slot 0).  Circuit::pool_src states the same rule for the host.
+// CENTRED (the compile-time paths of cons_sum): the registers hold centred words, |c| <= P/2.  A word is centred once, by enter(),
+// where it is loaded or produced — the 8 + 3 + 4 initial loads, slot 1's back-tap, and per column the derived value, the next free
+// column and the next code selector — where centring the whole pool per cell redid twelve of sixteen entries.  Only the registers
+// are centred: every word that is stored or compared stays canonical.  DerivedRegs<false> keeps canonical words for the run-time form.
+template <bool CENTRED>
 struct DerivedRegs {
-    uint32_t ring[8], u[3], k[4];
+    using word = std::conditional_t<CENTRED, i32, uint32_t>;
+    BX_HD static word enter(uint32_t v) {
+        if constexpr (CENTRED) return fp_centre(v);
+        else return v;
+    }
+    word ring[8], u[3], k[4];
     // the pool of the column the walk stands at
-    BX_HD void fill(uint32_t (&pool)[Circuit::POOL], uint32_t slot1) const {
+    BX_HD void fill(word (&pool)[Circuit::POOL], word slot1) const {
         pool[0] = u[0]; pool[1] = slot1; pool[2] = u[1]; pool[3] = u[2];
 #pragma unroll
         for (int q = 0; q < 8; ++q) pool[4 + q] = ring[q];
@@ -444,7 +489,7 @@ struct DerivedRegs {
         for (int q = 0; q < 4; ++q) pool[12 + q] = k[q];
     }
     // on to column j+1: d = the value of column F+j, next_u = free column (j+3) mod F, next_k = code csel(j+4)
-    BX_HD void shift(uint32_t d, uint32_t next_u, uint32_t next_k) {
+    BX_HD void shift(word d, word next_u, word next_k) {
 #pragma unroll
         for (int q = 7; q > 0; --q) ring[q] = ring[q - 1];
         ring[0] = d;
