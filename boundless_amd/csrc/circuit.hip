@@ -6,9 +6,10 @@
 //
 // All three stages are VALU-bound (no HBM or MFMA roofline applies): a derived cell / a constraint costs T*(G-2) reduced
 // products and T multiply-adds for the terms, then one reduction and one multiply-add per group of terms that share their
-// first factor (circuit_dev.hpp, the factored form: 32 groups at (64, 4), 16 at (48, 3)); for G <= 2, T*(G-1) products term by
-// term.  At G = 4 the terms are instead products of two shared pair products (circuit_dev.hpp, the pair form): at T = 64, 44
-// reduced pair products, 64 multiply-adds, and one reduction and one multiply-add per group of three terms (23 groups).
+// first factor (circuit_dev.hpp, the factored form: 16 groups at (48, 3)); for G <= 2, T*(G-1) products term by term.  At G = 4 the
+// terms are instead products of two shared pair products (circuit_dev.hpp, the pair form): at T = 64, 44 reduced pair products and 64
+// multiply-adds.  In every form the sum is one 64-bit chain that is folded (hi * R + lo, one multiply-add) where it would leave 64
+// bits — 13 times at (64, 4) — and reduced once at the end (circuit_dev.hpp, fold_r).
 // The loads around it are one coalesced dword per lane and column.
 // The signed multiply-adds are left to the compiler in this translation unit (poseidon2.hip pins them as single asm
 // statements because its loop-carried cells get widened): here the terms of a cell share their inner products (7 pool entries
@@ -16,12 +17,14 @@
 // adjacent asm statements.  Per cell, compiled, the factored form: 486 VALU instructions (368 multiply-class) at (T, G) = (64, 4)
 // and 265 (127) at (48, 3); term by term they were 630 (474) and 389 (218).  The pair form takes (64, 4) down by another 75
 // instructions per cell, 117 of them fewer multiply-class: witness_derive_kernel<64,4> 568 (368) -> 493 (251), eval_check_kernel<64,4>
-// 1340 (657) -> 1265 (540).  One thing the un-pinned code must be kept from: with the constant R in sight hipcc turns a level's
-// sum of r_i * R into (sum of r_i) * R with a 64-bit sum and an emulated product, so the second and third level multiply by an
-// opaque copy of R (circuit_dev.hpp, smad_r); and the walk keeps its pool centred in registers (DerivedRegs<true>) instead of
-// centring all 16 entries per cell.  Together, the walk's loop body per cell, VALU instructions (multiplies): witness_derive_kernel<64,4>
-// 412 (251) -> 312 (274), eval_check_kernel<64,4> 467 (275) -> 367 (298); whole kernels 493 -> 438 and 1265 -> 1210; 65 -> 54 and
-// 87 -> 78 VGPRs.  DESIGN.md §4 has the tables.
+// 1340 (657) -> 1265 (540).  Two things the un-pinned code must be kept from.  With a constant factor in sight hipcc turns a sum of
+// r_i * R into (sum of r_i) * R, and two terms with a common factor into one product of a 64-bit sum, each with an emulated
+// 64 x 32-bit product; and it reassociates a chain's sum so that the fold comes in through a 64-bit add.  So the fold multiplies by
+// an opaque copy of R and every step of a chain hides its result from the optimiser (circuit_dev.hpp: fold_r, smad_chain, smad_r);
+// and the walk keeps its pool centred in registers (DerivedRegs<true>) instead of centring all 16 entries per cell.  The walk's loop
+// body per cell, VALU instructions (multiplies), with the levels as multiply-adds and the centred walk: witness_derive_kernel<64,4>
+// 412 (251) -> 312 (274), eval_check_kernel<64,4> 467 (275) -> 367 (298); with the chain folded instead of reduced and rescaled:
+// -> 262 (211) and 317 (235), 54 -> 46 and 78 -> 70 VGPRs (seven waves per SIMD in eval_check).  DESIGN.md §4 has the tables.
 #define BX_PLAIN_MAD 1
 #include <memory>
 #include <new>

@@ -7,12 +7,23 @@
 // |result| <= ub(|t|) = |t|/2^32 + P/2 + 1, valid for |t| <= SREDC_MAX = 1.209 P^2; P^2/2^32 = 0.469 P) so that no product is
 // followed by a conditional subtraction and the sums stay unreduced in 64 bits.  Pool entries are centred, |c| <= P/2: by the walk of
 // circuit.hip once per word, where it enters the registers (DerivedRegs<true> and the centred entry of cons_sum, 4 of the 16 entries
-// are new per cell), by the canonical-pool signature once per call.  The second and third level multiply by an opaque copy of R
-// (smad_r) so that each addend stays one v_mad_i64_i32.  Compiled, the walk's loop body per cell, VALU instructions / multiplies
-// (v_mad_i64_i32 + v_mul_lo_u32 + v_mad_u64_u32): witness_derive_kernel<64,4> 412 / 251 -> 312 / 274 (54 VGPRs, it was 65),
-// eval_check_kernel<64,4> 467 / 275 -> 367 / 298 (78 VGPRs, it was 87: six waves per SIMD again).  The multiplies that came are the
-// level steps that had been folded into emulated 64 x 32-bit products; the 123 other instructions that went are that emulation's sign
-// extensions, 64-bit adds and copies, and the centring of twelve entries that had been centred a cell before.
+// are new per cell), by the canonical-pool signature once per call.
+//
+// The sum of a cell's terms is carried in a CHAIN: one signed 64-bit accumulator that is never reduced on the way.  Where it would
+// leave 64 bits it is FOLDED instead, a = hi * 2^32 + lo  ->  hi * R + lo (fold_r; R = 2^32 mod P = 2^28 - 2, so the value is congruent
+// mod P and |result| <= |a|/16 + 2^32 + R): one v_mad_i64_i32 and the copy that puts lo beside a zero register, where the earlier form
+// reduced every group of three terms and multiplied it by R again (sredc + smad_r, three multiply-class instructions per group, and a
+// second and third level of the same on top).  The terms carry one factor R more than the result; the one sredc at the end, of the
+// folded chain, takes it away, so the canonical result is the same word as the earlier forms' and the plain loop's.
+//   a chain               A <= fold_ub(A) + (the terms of a segment), with the segment cut so that A < 2^63 = 2.2755 P^2
+//   the end               result = sredc(fold_r(A)):  fold_ub(A) <= 0.14 P^2 + 2^32 <= FINAL_MAX, so |result| < P and one conditional
+//                         add of P makes it canonical
+// Each step of a chain hides its result from the optimiser (smad_chain: an empty asm, no instruction).  In sight, hipcc reassociates
+// fold + t1 + ... + tn into fold + (t1 + ... + tn) and pays a 64-bit add per segment, and it rewrites two terms with a common factor,
+// p*q1 + p*q2, as p*(q1 + q2) with a 64-bit sum and an emulated 64 x 32-bit product.  Compiled, the walk's loop body per cell, VALU
+// instructions / multiplies (v_mad_i64_i32 + v_mul_lo_u32 + v_mad_u64_u32): witness_derive_kernel<64,4> 312 / 274 -> 262 / 211 (46
+// VGPRs, it was 54), eval_check_kernel<64,4> 367 / 298 -> 317 / 235 (70 VGPRs, it was 78: seven waves per SIMD); (48, 3) 211 / 134 ->
+// 144 / 102, (16, 3) 122 / 84 -> 110 / 69, (8, 2) 56 / 19 -> 49 / 11; no scratch, no v_mad_u64_u32 in any of them.
 //
 // G = 4, the pair form.  A term is a product of four pool entries and can be written as (pair) * (pair) in three ways; PairPlan picks
 // one split per term so that pairs recur (44 distinct pairs serve the 128 pair slots of T = 64, where the first-factor form below
@@ -20,24 +31,20 @@
 // The plan: each term's most popular split, four sweeps that re-choose a term's split where that frees a pair (51 pairs), then two
 // passes that drop a little-used pair outright by moving all its users to other splits (44).
 //   a pair                p = sredc(c_a * c_b), computed at its first use:   |p| <= ub(P^2/4) = 0.617 P
-//   a group               acc = sum of <= GRP = 3 terms p1 * p2:             |acc| <= 3 * 0.381 P^2 = 1.143 P^2 <= SREDC_MAX (four: 1.52)
-//                         no two terms of a group share a pair: hipcc would rewrite p*q1 + p*q2 as p*(q1 + q2) with a 64-bit sum
-//                         and emulate a 64 x 32-bit product
-//   its reduction         r = sredc(acc):                                    |r| <= 1.036 P, still an int32
-//   second level          acc2 = sum of r * R over <= 7 consecutive groups:  |acc2| <= 0.967 P^2 <= FINAL_MAX (eight: 1.105 P^2)
-//   third level           the same over the <= 4 second-level results:       |acc3| <= 4 * (P - 1) * R = 0.53 P^2
-// The terms are ordered so that a pair's uses lie in neighbouring groups (at most 7 pairs are computed and still awaited at any
-// point of T = 64), which keeps the pair products from costing registers: eval_check_kernel<64,4> compiles to 78 VGPRs, no scratch.
-// Every path from a term to the result is again a congruence mod P through three reductions against two factors R, so the
-// canonical result is the same word as the first-factor form's and the plain loop's.  PairPlan carries the bounds; cons_sum's
-// static_asserts hold them, and the host build (BX_CHECK_BOUNDS) asserts every pair, every sredc operand and every level's sum.
+//   a term                p1 * p2:                                           |t| <= 0.381 P^2
+//   a segment             <= SEG = 5 terms added to the chain after its fold: A <= A/16 + 5 * 0.381 P^2, A <= 2.033 P^2 (six: 2.44 P^2)
+//                         no two terms of a segment share a pair (the rewrite above, should a step ever be left in sight)
+// FoldPlan orders PairPlan's terms into the segments (13 at T = 64) so that a pair's uses lie close together (at most 11 pairs are
+// computed and still awaited at any point of T = 64) and deals them over its chains; cons_sum runs one chain (FOLD_CHAINS), two or
+// three compile to two and four instructions more per cell.  PairPlan's own groups of GRP = 3 and its levels are still built (tests read
+// them) but no longer executed.  FoldPlan carries the bounds; cons_sum's static_asserts hold them, and the host build
+// (BX_CHECK_BOUNDS) asserts every pair, every fold's operand and result, every chain after every segment and the sredc operand.
 //
-// G = 3 and G >= 5, the factored form (ConsPlan; built for G = 4 too, where tests read it, but no longer executed there).
+// G = 3 and G >= 5, the factored form (ConsPlan; built for G = 4 too, where tests read it, but not executed there).
 // pool_idx(t, 0) runs through all 16 pool entries on every block of 16 terms, so entry a is the first factor of T/16 terms
 // and   sum_{t: idx(t,0)=a} pool[a] * (rest of t)  =  pool[a] * sum_t (rest of t):  the product with pool[a]
 // is taken once per group of terms instead of once per term (one reduced product, 3 multiply-class instructions, less per term;
-// one reduction and one multiply-add more per group).  Every step is a congruence mod P and every path from a term to the result
-// passes G - 1 + 2 reductions against two factors R, as in the term-by-term form, so the canonical result is the same word.
+// one reduction and one multiply-add more per group).
 //   the rest of a term    y = pool[idx(t,1)],  y <- sredc(y * pool[idx(t,f)]) for f = 2 .. G-2,  then  y * pool[idx(t,G-1)]:
 //                         G = 3: |y| <= 0.5 P, term <= 0.25 P^2;   G = 4: |y| <= 0.617 P, term <= 0.309 P^2;
 //                         G >= 5: |y| <= 0.65 P for any chain length, term <= 0.325 P^2
@@ -45,21 +52,17 @@
 //                         G >= 4: ISZ = 3 (four terms would be 1.234 P^2 > SREDC_MAX).  An entry with more terms than ISZ gets
 //                         several inner groups of balanced size (four terms at G = 4: 2 + 2, |inner| <= 0.617 P^2)
 //   its reduction         s = sredc(inner):   G = 3: |s| <= 0.97 P (4 terms), 0.85 P (3);   G = 4: 0.79 P (2 terms), 0.93 P (3)
-//   outer group           outer = sum of s * pool[a] over consecutive inner groups, as many as keep it <= SREDC_MAX:
-//                         G = 3: 2 groups of 4 terms (0.97 P^2);   G = 4: 3 groups of 2 terms (1.18 P^2), 2 groups of 3 (0.93 P^2)
-//   its reduction         r = sredc(outer):   |r| <= 1.06 P at most (G = 4, T = 64), still an int32
-//   second level          acc2 = sum of r * R over consecutive outer groups  (R = 2^32 mod P = 0.1334 P, so sredc(acc2) == sum r),
-//                         as many as keep |acc2| <= FINAL_MAX = 1.0667 P^2, the largest operand whose reduction is < P in magnitude
-//   third level           the same over the second-level results (one group; more is refused at compile time)
+//   the chain             A = sum of s * pool[a] over the inner groups, folded in front of each of ConsPlan's fold segments: as few
+//                         segments as keep A < 2^63, the groups spread evenly over them, no pool entry twice in a segment
+//                         ((48, 3): 16 groups in 4 segments of 4, A <= 1.82 P^2)
 // ConsPlan builds the groups at compile time from pool_idx and carries the bound of every accumulator with them; cons_sum's
-// static_asserts hold the plan to SREDC_MAX / FINAL_MAX, and the host build (BX_CHECK_BOUNDS) asserts every sredc operand it meets.
+// static_asserts hold the plan to SREDC_MAX / FINAL_MAX, and the host build (BX_CHECK_BOUNDS) asserts every sredc operand, fold and
+// chain it meets.  Its outer groups and levels (obeg, lbeg, n2, max_outer, max_l2, max_l3) describe the earlier form and are kept for
+// the tests that read them.
 //
-// G <= 2 has no shared product to factor out and keeps the term-by-term form:
-//   a group of 3 terms        acc = sum x * c_last:         |acc| <= 3 * 0.5 P * 0.5 P = 0.75 P^2
-//   its reduction             r = sredc(acc):               |r| <= 0.85 P
-//   second level, 8 groups    acc2 = sum r * R:             |acc2| <= 8 * 0.85 * 0.1334 P^2 = 0.91 P^2,  |r2| <= 0.93 P
-//   third level, <= 7 second-level results, same form:      |acc3| <= 7 * 0.93 * 0.1334 P^2 = 0.87 P^2,  |r3| <= 0.91 P
-// In both forms the last reduction is < P in magnitude, so one conditional add of P makes it canonical, and the result is
+// G <= 2 has no shared product to factor out: one chain of the terms x * c_last (<= 0.25 P^2 each) in their order, folded in front of
+// every eighth: A <= A/16 + 8 * 0.25 P^2, A <= 2.134 P^2.
+// In every form the last reduction is < P in magnitude, so one conditional add of P makes it canonical, and the result is
 // bit-identical to the plain form; tests compare both paths with the oracle.
 #pragma once
 #include <type_traits>
@@ -106,6 +109,9 @@ struct ConsPlan {
     int first[TT]{}, len[TT]{}, term[TT][ISZ]{};  // inner group q: its shared first factor, its terms
     int obeg[TT + 1]{}, lbeg[TT + 1]{};    // outer group o = inner groups [obeg[o], obeg[o+1]), second-level group l likewise
     i64 max_inner = 0, max_outer = 0, max_l2 = 0, max_l3 = 0;
+    // the fold form (fold_r below): ONE chain over all inner groups' s * pool[a], folded at the head of every segment but the first
+    int nf = 0, fbeg[TT + 1]{};            // segment f = inner groups [fbeg[f], fbeg[f+1])
+    i64 max_fchain = 0, max_ftotal = 0;    // the largest chain value, the folded chain that is reduced at the end
 
     constexpr ConsPlan() {
         // inner groups in the order (g, a): the g-th group of every pool entry before any (g+1)-th, so that an outer group never
@@ -152,6 +158,31 @@ struct ConsPlan {
         }
         max_l3 += ub(cur) * (i64)MONT_ONE;
         lbeg[++n2] = no;
+        // segments of the fold form: as few as the bound allows (a cut wherever the next group would take the chain beyond 64 bits),
+        // then the same number of segments with the groups spread evenly, which leaves the chain the most room
+        const int fewest = cut_segments(nq);
+        if (cut_segments((nq + fewest - 1) / fewest) > fewest) cut_segments(nq);
+    }
+    // fills nf, fbeg and the fold form's bounds: at most `cap` consecutive inner groups to a segment, fewer where the chain would leave
+    // 64 bits or a pool entry would come twice (hipcc would add the two reductions first and emulate a 64 x 32-bit product for the sum)
+    constexpr int cut_segments(int cap) {
+        i64 cur = 0;
+        nf = 0;
+        max_fchain = 0;
+        for (int q = 0; q < nq; ++q) {
+            const i64 add = ub(len[q] * TERM) * BC;
+            bool again = false;
+            for (int r = fbeg[nf]; r < q; ++r) again = again || first[r] == first[q];
+            if (q > 0 && (again || q - fbeg[nf] >= cap || cur > INT64_MAX - add)) {
+                fbeg[++nf] = q;
+                cur = fold_ub(cur);
+            }
+            cur += add;
+            if (cur > max_fchain) max_fchain = cur;
+        }
+        fbeg[++nf] = nq;
+        max_ftotal = fold_ub(cur);
+        return nf;
     }
 };
 template <int TT, int GG>
@@ -318,10 +349,110 @@ struct PairPlan {
 template <int TT>
 inline constexpr PairPlan<TT> pair_plan{};
 
-// r * R + c, the step of the second and third reduction level.  In a translation unit that leaves its multiply-adds to the compiler
-// (BX_PLAIN_MAD) the device build multiplies by an opaque copy of R, one per use: with the constant in sight hipcc rewrites a level's
-// sum of r_i * R as (sum of r_i) * R, sign-extends every r_i, adds them in 64 bits and emulates a 64 x 32-bit product (about 28
-// instructions for a level of seven, where this is 7 v_mad_i64_i32).  The copy lives in an SGPR (an s_mov per use, no VALU work), is
+// The order in which the pair form (G = 4) is executed: PairPlan's pairs and splits, its terms put into SEGMENTS of at most SEG and
+// the segments dealt round-robin over NCH chains.  A chain is one 64-bit accumulator that is never reduced on the way: before a
+// segment adds its terms the chain is folded, a -> hi(a) * R + lo(a) (fold_r), which is congruent mod P and sixteen times smaller.
+//   a term                |p1 * p2| <= TERM = 0.381 P^2                                    (2^63 = 2.2755 P^2)
+//   a chain               A <= fold_ub(A) + SEG * TERM = A/16 + 5 * 0.381 P^2:  A <= 2.033 P^2 < 2^63  (six terms: 2.44 P^2)
+//   the total             sum of the NCH folded chains <= NCH * (0.127 P^2 + 2^32 + R) <= FINAL_MAX, so its reduction is < P
+// The order is PairPlan's greedy one with SEG in the place of GRP: the next term is the one that needs the fewest pairs not yet
+// computed, then the one that uses the most pairs for the last time; no two terms of a segment share a pair (hipcc would rewrite
+// p*q1 + p*q2 as p*(q1 + q2) with a 64-bit sum and an emulated product).  One rule comes first: a pair with as many uses left as
+// segments left goes into the current segment, or its last users end up in short segments of their own (T = 64: 17 segments
+// without the rule, the last four of one term; 13 with it).  Pairs are numbered again, by first use in this order.
+template <int TT, int NCH_ = 1>
+struct FoldPlan {
+    static constexpr int SEG = 5, NCH = NCH_;
+    static constexpr i64 TERM = PairPlan<TT>::TERM;
+    // the chain bound with every segment full, however many segments: fold_ub(A) <= A/16 + R + 2^32, so 16/15 of the rest holds
+    static constexpr i64 STEADY = (SEG * TERM + (i64)MONT_ONE + ((i64)1 << 32)) / 15 * 16 + 16;
+    static_assert(NCH >= 1 && STEADY < INT64_MAX && fold_ub(STEADY) + SEG * TERM <= STEADY, "cons_sum: the chain bound is not invariant below 2^63");
+
+    int np = 0, ns = 0;                    // distinct pairs, segments
+    int pa[2 * TT]{}, pb[2 * TT]{};        // pair p = pool[pa[p]] * pool[pb[p]], numbered by first use
+    int seq[TT]{}, s1[TT]{}, s2[TT]{};     // slot s sums term seq[s] = pair s1[s] * pair s2[s]
+    int pbeg[TT + 1]{};                    // pairs [pbeg[s], pbeg[s+1]) are computed at slot s, their first use
+    int sbeg[TT + 1]{};                    // segment g = slots [sbeg[g], sbeg[g+1]), on chain g % NCH
+    int max_live = 0;                      // most pairs computed and still to be used at any slot
+    i64 max_chain = 0, max_total = 0;      // the largest chain value, the sum of the folded chains
+
+    constexpr FoldPlan() {
+        const PairPlan<TT>& pp = pair_plan<TT>;
+        int ta[TT]{}, tb[TT]{}, ref[2 * TT]{}, num[2 * TT]{};   // a term's two pairs in PairPlan's numbering, uses left, new number
+        for (int s = 0; s < TT; ++s) {
+            ta[pp.seq[s]] = pp.s1[s];
+            tb[pp.seq[s]] = pp.s2[s];
+            ++ref[pp.s1[s]];
+            ++ref[pp.s2[s]];
+        }
+        for (int i = 0; i < 2 * TT; ++i) num[i] = -1;
+        int live = 0, glen = 0, gp[2 * SEG]{};
+        bool placed[TT]{};
+        for (int slot = 0; slot < TT;) {
+            int best = -1, best_new = 3, best_last = -1, best_due = 0;
+            const int segs_left = (TT - slot + glen + SEG - 1) / SEG;   // this segment and the full ones the other terms would fill
+            if (glen < SEG)
+                for (int t = 0; t < TT; ++t) {
+                    if (placed[t]) continue;
+                    const int a = ta[t], b = tb[t];
+                    bool clash = false;
+                    for (int k = 0; k < 2 * glen; ++k) clash = clash || gp[k] == a || gp[k] == b;
+                    if (clash) continue;
+                    // a pair with as many uses left as segments left must be used in every one of them, or segments get added at the end
+                    const int most = ref[a] > ref[b] ? ref[a] : ref[b], due = most >= segs_left ? most : 0;
+                    const int fresh = (num[a] < 0) + (num[b] < 0 && b != a);
+                    const int last = a == b ? (ref[a] == 2) : (ref[a] == 1) + (ref[b] == 1);
+                    if (due > best_due || (due == best_due && (fresh < best_new || (fresh == best_new && last > best_last))))
+                        best = t, best_new = fresh, best_last = last, best_due = due;
+                }
+            if (best < 0) {                // the segment is full, or every term left shares a pair with it
+                sbeg[++ns] = slot;
+                glen = 0;
+                continue;
+            }
+            const int a = ta[best], b = tb[best];
+            for (int k = 0; k < 2; ++k) {
+                const int id = k ? b : a;
+                if (num[id] < 0) {
+                    num[id] = np;
+                    pa[np] = pp.pa[id];
+                    pb[np] = pp.pb[id];
+                    ++np;
+                    ++live;
+                }
+            }
+            if (live > max_live) max_live = live;
+            live -= (--ref[a] == 0);
+            live -= (--ref[b] == 0);
+            placed[best] = true;
+            seq[slot] = best;
+            s1[slot] = num[a];
+            s2[slot] = num[b];
+            gp[2 * glen] = a;
+            gp[2 * glen + 1] = b;
+            ++glen;
+            pbeg[++slot] = np;
+        }
+        sbeg[++ns] = TT;
+        i64 chain[NCH]{};
+        for (int g = 0; g < ns; ++g) {     // chain g % NCH: folded (but for its first segment), then this segment's terms on top
+            i64& a = chain[g % NCH];
+            a = (g < NCH ? 0 : fold_ub(a)) + (sbeg[g + 1] - sbeg[g]) * TERM;
+            if (a > max_chain) max_chain = a;
+        }
+        for (int c = 0; c < NCH && c < ns; ++c) max_total += fold_ub(chain[c]);
+    }
+};
+template <int TT, int NCH = 1>
+inline constexpr FoldPlan<TT, NCH> fold_plan{};
+constexpr int FOLD_CHAINS = 1;   // one chain: two compile to two instructions more per cell and measured slower, three lose a wave
+template <int TT>
+inline constexpr FoldPlan<TT, FOLD_CHAINS> cons_fold{};   // the plan cons_sum<TT, 4> executes
+
+// r * R + c: the product inside fold_r, and a term of a G = 1 sum (the lone factor times the Montgomery one).  In a translation unit
+// that leaves its multiply-adds to the compiler (BX_PLAIN_MAD) the device build multiplies by an opaque copy of R, one per use: with the
+// constant in sight hipcc rewrites a sum of r_i * R as (sum of r_i) * R, sign-extends every r_i, adds them in 64 bits and emulates a
+// 64 x 32-bit product, and it takes a single r * R apart into shifts.  The copy lives in an SGPR (an s_mov per use, no VALU work), is
 // signed so that the product stays a v_mad_i64_i32 (an opaque unsigned word gets an emulated v_mad_u64_u32 product), and comes out of a
 // volatile asm (CSE merges the copies of a plain one and the rewrite is back).  Same 64-bit integer either way.
 BX_HD i64 smad_r(i32 r, i64 c, int alt = 0) {
@@ -335,6 +466,28 @@ BX_HD i64 smad_r(i32 r, i64 c, int alt = 0) {
 #endif
 }
 
+// a -> hi(a) * R + lo(a) with lo unsigned: congruent to a mod P since 2^32 == R, and |result| <= |a|/16 + 2^32 + R.  One multiply-add,
+// by smad_r's opaque signed copy of R where the multiply-adds are the compiler's: one v_mad_i64_i32 whose addend is (lo, 0).
+BX_HD i64 fold_r(i64 a, int alt = 0) {
+    BX_ASSERT_BOUND(a >= -INT64_MAX, "fold_r operand");
+    const i64 r = smad_r((i32)(a >> 32), (i64)(uint32_t)a, alt);
+    BX_ASSERT_BOUND(iabs64(r) <= iabs64(a) / 16 + ((i64)1 << 32) + (i64)MONT_ONE, "fold_r result");
+    return r;
+}
+// a * b + c, a step of a chain.  The device build of a BX_PLAIN_MAD translation unit hides the result from the optimiser (an empty asm, no
+// instruction): left in sight, hipcc reassociates fold + t1 + ... + t5 into fold + (t1 + ... + t5), sums the terms in a chain of their own
+// and pays a 64-bit add per segment to bring the fold in; hidden, every step is the one v_mad_i64_i32 whose addend is the chain.
+BX_HD i64 smad_chain(i32 a, i32 b, i64 c, int alt = 0) {
+#if defined(__HIP_DEVICE_COMPILE__) && defined(BX_PLAIN_MAD)
+    (void)alt;
+    i64 r = (i64)a * (i64)b + c;
+    asm("" : "+v"(r));
+    return r;
+#else
+    return smad(a, b, c, alt);
+#endif
+}
+
 // The compile-time paths, on a pool that is already centred: |pool[i]| <= P/2 is what every bound of the plans rests on, and the
 // host build (BX_CHECK_BOUNDS) asserts it for every entry.  The walk of circuit.hip calls this with the pool its DerivedRegs<true>
 // keep centred from cell to cell; the canonical-pool signature below centres and forwards.
@@ -344,102 +497,79 @@ BX_HD uint32_t cons_sum(const i32 (&pool)[Circuit::POOL], uint32_t /*T*/, uint32
 #pragma unroll
     for (unsigned i = 0; i < Circuit::POOL; ++i) BX_ASSERT_BOUND(pool[i] <= (i32)(P / 2) && pool[i] >= -(i32)(P / 2), "cons_sum: a pool entry that is not centred");
     if constexpr (GG == 4) {
-        constexpr int N2 = pair_plan<TT>.n2;
-        static_assert(pair_plan<TT>.max_group <= SREDC_MAX, "cons_sum: a group sum beyond sredc's range");
-        static_assert(pair_plan<TT>.max_l2 <= FINAL_MAX && pair_plan<TT>.max_l3 <= FINAL_MAX, "cons_sum: term count beyond the three reduction levels");
+        using Plan = FoldPlan<TT, FOLD_CHAINS>;
+        constexpr int NCH = Plan::NCH < cons_fold<TT>.ns ? Plan::NCH : cons_fold<TT>.ns;
+        static_assert(cons_fold<TT>.max_chain <= Plan::STEADY, "cons_sum: a chain beyond its steady-state bound");
+        static_assert(cons_fold<TT>.max_total <= FINAL_MAX, "cons_sum: the folded chains beyond the last reduction's range");
         // every index below is a constant expression, so each pool entry and each pair product is a fixed register
-        i32 pr[pair_plan<TT>.np];
-        i64 acc3 = 0;
-        i32 result = 0;
-        static_for<0, N2>([&](auto lc) {
-            constexpr int l = decltype(lc)::value;
-            i64 acc2 = 0;
-            static_for<pair_plan<TT>.lbeg[l], pair_plan<TT>.lbeg[l + 1]>([&](auto gc) {
-                constexpr int g = decltype(gc)::value;
-                i64 acc = 0;
-                static_for<pair_plan<TT>.gbeg[g], pair_plan<TT>.gbeg[g + 1]>([&](auto sc) {
-                    constexpr int s = decltype(sc)::value;
-                    static_for<pair_plan<TT>.pbeg[s], pair_plan<TT>.pbeg[s + 1]>([&](auto pc) {
-                        constexpr int p = decltype(pc)::value;
-                        pr[p] = sredc(smul(pool[pair_plan<TT>.pa[p]], pool[pair_plan<TT>.pb[p]], p), p);
-                        BX_ASSERT_BOUND(pr[p] <= PairPlan<TT>::PAIR && pr[p] >= -PairPlan<TT>::PAIR, "cons_sum pair");
-                    });
-                    acc = smad(pr[pair_plan<TT>.s1[s]], pr[pair_plan<TT>.s2[s]], acc, s);
+        i32 pr[cons_fold<TT>.np];
+        i64 chain[NCH];
+        static_for<0, cons_fold<TT>.ns>([&](auto gc) {
+            constexpr int g = decltype(gc)::value, c = g % Plan::NCH;
+            static_for<cons_fold<TT>.sbeg[g], cons_fold<TT>.sbeg[g + 1]>([&](auto sc) {
+                constexpr int s = decltype(sc)::value;
+                static_for<cons_fold<TT>.pbeg[s], cons_fold<TT>.pbeg[s + 1]>([&](auto pc) {
+                    constexpr int p = decltype(pc)::value;
+                    pr[p] = sredc(smul(pool[cons_fold<TT>.pa[p]], pool[cons_fold<TT>.pb[p]], p), p);
+                    BX_ASSERT_BOUND(pr[p] <= PairPlan<TT>::PAIR && pr[p] >= -PairPlan<TT>::PAIR, "cons_sum pair");
                 });
-                acc2 = smad_r(sredc(acc, 3), acc2, g);
+                // a segment's first term goes on top of the folded chain (the chain's first segment: on nothing), the others follow
+                if constexpr (s > cons_fold<TT>.sbeg[g]) chain[c] = smad_chain(pr[cons_fold<TT>.s1[s]], pr[cons_fold<TT>.s2[s]], chain[c], s);
+                else if constexpr (g >= Plan::NCH) chain[c] = smad_chain(pr[cons_fold<TT>.s1[s]], pr[cons_fold<TT>.s2[s]], fold_r(chain[c], g), s);
+                else chain[c] = smul(pr[cons_fold<TT>.s1[s]], pr[cons_fold<TT>.s2[s]], s);
             });
-            BX_ASSERT_BOUND(acc2 <= FINAL_MAX && acc2 >= -FINAL_MAX, "cons_sum second level");
-            const i32 r2 = sredc(acc2, 2);
-            if constexpr (N2 == 1) result = r2;
-            else acc3 = smad_r(r2, acc3, l);
+            BX_ASSERT_BOUND(chain[c] <= cons_fold<TT>.max_chain && chain[c] >= -cons_fold<TT>.max_chain, "cons_sum chain");
         });
-        if constexpr (N2 > 1) {
-            BX_ASSERT_BOUND(acc3 <= FINAL_MAX && acc3 >= -FINAL_MAX, "cons_sum third level");
-            result = sredc(acc3, 0);
-        }
+        i64 total = fold_r(chain[0], 0);
+        static_for<1, NCH>([&](auto cc) { total += fold_r(chain[decltype(cc)::value], decltype(cc)::value); });
+        BX_ASSERT_BOUND(total <= cons_fold<TT>.max_total && total >= -cons_fold<TT>.max_total, "cons_sum folded chains");
+        const i32 result = sredc(total, 0);   // takes away the terms' surplus factor R
         return (uint32_t)(result + (result < 0 ? (i32)P : 0));
     } else if constexpr (GG >= 3) {
-        constexpr int N2 = cons_plan<TT, GG>.n2;
-        static_assert(cons_plan<TT, GG>.max_inner <= SREDC_MAX && cons_plan<TT, GG>.max_outer <= SREDC_MAX, "cons_sum: a group sum beyond sredc's range");
-        static_assert(cons_plan<TT, GG>.max_l2 <= FINAL_MAX && cons_plan<TT, GG>.max_l3 <= FINAL_MAX, "cons_sum: term count beyond the three reduction levels");
+        static_assert(cons_plan<TT, GG>.max_inner <= SREDC_MAX, "cons_sum: a group sum beyond sredc's range");
+        static_assert(cons_plan<TT, GG>.max_ftotal <= FINAL_MAX, "cons_sum: the folded chain beyond the last reduction's range");
         // every index below is a constant expression (static_for hands its counter over as a type), so each pool reference is a
-        // fixed register and each accumulator a fresh value of its group
-        i64 acc3 = 0;
-        i32 result = 0;
-        static_for<0, N2>([&](auto lc) {
-            constexpr int l = decltype(lc)::value;
-            i64 acc2 = 0;
-            static_for<cons_plan<TT, GG>.lbeg[l], cons_plan<TT, GG>.lbeg[l + 1]>([&](auto oc) {
-                constexpr int o = decltype(oc)::value;
-                i64 outer = 0;
-                static_for<cons_plan<TT, GG>.obeg[o], cons_plan<TT, GG>.obeg[o + 1]>([&](auto qc) {
-                    constexpr int q = decltype(qc)::value;
-                    i64 inner = 0;
-                    static_for<0, cons_plan<TT, GG>.len[q]>([&](auto kc) {
-                        constexpr int k = decltype(kc)::value;
-                        constexpr unsigned t = (unsigned)cons_plan<TT, GG>.term[q][k];
-                        i32 y = pool[Circuit::pool_idx(t, 1u)];
+        // fixed register; the chain is the one value that lives from group to group
+        i64 chain = 0;
+        static_for<0, cons_plan<TT, GG>.nf>([&](auto fc) {
+            constexpr int f = decltype(fc)::value;
+            static_for<cons_plan<TT, GG>.fbeg[f], cons_plan<TT, GG>.fbeg[f + 1]>([&](auto qc) {
+                constexpr int q = decltype(qc)::value;
+                i64 inner = 0;
+                static_for<0, cons_plan<TT, GG>.len[q]>([&](auto kc) {
+                    constexpr int k = decltype(kc)::value;
+                    constexpr unsigned t = (unsigned)cons_plan<TT, GG>.term[q][k];
+                    i32 y = pool[Circuit::pool_idx(t, 1u)];
 #pragma unroll
-                        for (int f = 2; f + 1 < GG; ++f) y = sredc(smul(y, pool[Circuit::pool_idx(t, (unsigned)f)], f), f);
-                        inner = smad(y, pool[Circuit::pool_idx(t, (unsigned)(GG - 1))], inner, k);
-                    });
-                    outer = smad(sredc(inner, 3), pool[cons_plan<TT, GG>.first[q]], outer, q);
+                    for (int g = 2; g + 1 < GG; ++g) y = sredc(smul(y, pool[Circuit::pool_idx(t, (unsigned)g)], g), g);
+                    inner = smad_chain(y, pool[Circuit::pool_idx(t, (unsigned)(GG - 1))], inner, k);
                 });
-                acc2 = smad_r(sredc(outer, 1), acc2, o);
+                const i32 s = sredc(inner, 3);
+                if constexpr (q > cons_plan<TT, GG>.fbeg[f]) chain = smad_chain(s, pool[cons_plan<TT, GG>.first[q]], chain, q);
+                else if constexpr (f > 0) chain = smad_chain(s, pool[cons_plan<TT, GG>.first[q]], fold_r(chain, f), q);
+                else chain = smul(s, pool[cons_plan<TT, GG>.first[q]], q);
             });
-            const i32 r2 = sredc(acc2, 2);
-            if constexpr (N2 == 1) result = r2;
-            else acc3 = smad_r(r2, acc3, l);
+            BX_ASSERT_BOUND(iabs64(chain) <= (cons_plan<TT, GG>.max_fchain), "cons_sum chain");
         });
-        if constexpr (N2 > 1) result = sredc(acc3, 0);
+        const i32 result = sredc(fold_r(chain, 0), 0);
         return (uint32_t)(result + (result < 0 ? (i32)P : 0));
     } else {
-        static_assert(TT <= 3 * 8 * 7 && GG >= 1, "cons_sum: term count beyond the three reduction levels");
-        constexpr int GRP = 3, NG = (TT + GRP - 1) / GRP;
-        i64 acc2 = 0, acc3 = 0;
-        i32 result = 0;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const int nk = (g + 1) * GRP <= TT ? GRP : TT - g * GRP;
-            i64 acc = 0;
-#pragma unroll
-            for (int k = 0; k < GRP; ++k) {
-                if (k < nk) {
-                    const i32 x = pool[Circuit::pool_idx((unsigned)(g * GRP + k), 0u)];
-                    if constexpr (GG == 1) acc = smad_k(x, MONT_ONE, acc, k);
-                    else acc = smad(x, pool[Circuit::pool_idx((unsigned)(g * GRP + k), 1u)], acc, k);
-                }
-            }
-            const i32 r = sredc(acc, 3);
-            acc2 = smad_r(r, acc2, g);
-            if ((g & 7) == 7 || g == NG - 1) {
-                const i32 r2 = sredc(acc2, 1);
-                acc2 = 0;
-                if constexpr (NG <= 8) result = r2;
-                else acc3 = smad_r(r2, acc3, 2);
-            }
-        }
-        if constexpr (NG > 8) result = sredc(acc3, 0);
+        // one chain of the terms in their order, folded in front of every SEG2 of them: A <= A/16 + 8 * 0.25 P^2, A <= 2.134 P^2 < 2^63
+        constexpr int SEG2 = 8;
+        constexpr i64 TERM = (i64)(P / 2) * (GG == 1 ? (i64)MONT_ONE : (i64)(P / 2));
+        constexpr i64 STEADY = (SEG2 * TERM + (i64)MONT_ONE + ((i64)1 << 32)) / 15 * 16 + 16;
+        static_assert(GG >= 1 && STEADY < INT64_MAX && fold_ub(STEADY) + SEG2 * TERM <= STEADY && fold_ub(STEADY) <= FINAL_MAX, "cons_sum: the chain bound is not invariant below 2^63");
+        i64 chain = 0;
+        static_for<0, TT>([&](auto tc) {
+            constexpr unsigned t = (unsigned)decltype(tc)::value;
+            const i32 x = pool[Circuit::pool_idx(t, 0u)];
+            if constexpr (t > 0 && t % SEG2 == 0) chain = fold_r(chain, (int)t);
+            if constexpr (GG == 1) chain = smad_r(x, chain, (int)t);
+            else if constexpr (t == 0) chain = smul(x, pool[Circuit::pool_idx(t, 1u)], 0);
+            else chain = smad_chain(x, pool[Circuit::pool_idx(t, 1u)], chain, (int)t);
+            BX_ASSERT_BOUND(chain <= STEADY && chain >= -STEADY, "cons_sum chain");
+        });
+        const i32 result = sredc(fold_r(chain, 0), 0);
         return (uint32_t)(result + (result < 0 ? (i32)P : 0));
     }
 }
