@@ -53,13 +53,14 @@ __global__ void witness_free_kernel(uint32_t* __restrict__ data, Circuit cc, uin
         data[i] = synth_word(r < act ? gseed : nseed, c, r);
     }
 }
-// offsets of pair p's scatter: entry r of column 4p+2 goes to column 4p+3, row perm_p(r)   (built once per prover)
+// offsets of pair p's scatter: entry r of column 4p+2 goes to column 4p+3, row perm_p(r) — relative to that column, which is the
+// scatter's `into` (the whole group buffer would contain `values`, column 4p+2: bx_hal.h, "Operand overlap")   (built once per prover)
 __global__ void perm_offsets_kernel(uint32_t* __restrict__ offsets, uint32_t* __restrict__ index, Circuit cc) {
     const uint32_t n = 1u << cc.po2, act = cc.active_rows();
     const size_t total = (size_t)n * cc.pairs, stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         const uint32_t p = (uint32_t)(i >> cc.po2), r = (uint32_t)(i & (n - 1));
-        offsets[i] = r < act ? (4 * p + 3) * n + cc.perm_row(p, r) : 0u;
+        offsets[i] = r < act ? cc.perm_row(p, r) : 0u;
     }
     // one entry per active cycle, none for the noise cycles
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += stride) index[i] = (uint32_t)(i < act ? i : act);
@@ -270,8 +271,8 @@ const char* synth_witgen(void*, void* state, bx_ctx* c, bx_buf code, bx_buf data
         BX_LAUNCH_CHECK(c);
     }
     for (uint32_t p = 0; p < cc.pairs; ++p) {
-        bx_buf values{(uint32_t*)data.dptr + (size_t)(4 * p + 2) * n, n};
-        BX_TRY(bx_scatter(c, data, st->perm_index.slice(0, n + 1), st->perm_offsets.slice((size_t)p * n, n), values));
+        bx_buf values{(uint32_t*)data.dptr + (size_t)(4 * p + 2) * n, n}, into{(uint32_t*)data.dptr + (size_t)(4 * p + 3) * n, n};
+        BX_TRY(bx_scatter(c, into, st->perm_index.slice(0, n + 1), st->perm_offsets.slice((size_t)p * n, n), values));
     }
     if (cc.J) {
         OpScope op(c, "witgen_derive", 4.0 * (double)(n * (cc.J + cc.J + cc.J / 4)));

@@ -12,6 +12,7 @@
 #include "../../include/bx_hal.h"
 #include "fp.hpp"
 #include "ntt_plan.hpp"
+#include "operands.hpp"
 
 namespace bx {
 
@@ -201,6 +202,8 @@ inline bool mul_le(size_t a, size_t b, size_t limit) {
     size_t p;
     return !__builtin_mul_overflow(a, b, &p) && p <= limit;
 }
+// bufs_overlap / bufs_same, the operand rule of every entry point with two or more buffers: operands.hpp (host-only, so that it is
+// also checked as a stand-alone program)
 inline int ilog2(size_t n) {
     int k = 0;
     while (((size_t)1 << k) < n) k++;

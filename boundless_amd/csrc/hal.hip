@@ -384,6 +384,7 @@ const char* hash_rows_suite(bx_ctx* c, bx_buf out, bx_buf matrix, int suite) {
     size_t rows = out.len / 8;
     BX_REQUIRE(c, rows > 0 && matrix.len % rows == 0, "hash_rows: matrix.len not a multiple of rows");
     BX_REQUIRE(c, rows <= 0xffffffffu, "hash_rows: too many rows");
+    BX_REQUIRE(c, !bufs_overlap(out, matrix), "hash_rows: out and matrix overlap");
     BX_ENTER(c);
     return hash_rows_op(c, suite, (uint32_t*)out.dptr, matrix, rows);
 }
@@ -431,6 +432,7 @@ extern "C" const char* bx_merkle_build(bx_ctx* c, bx_buf nodes, bx_buf matrix, s
     if (!c) return "bx_merkle_build: null ctx";
     BX_REQUIRE(c, holds_tree(nodes, rows), "merkle_build: nodes must hold 2*rows digests, rows a power of two");
     BX_REQUIRE(c, matrix.len % rows == 0, "merkle_build: matrix.len not a multiple of rows");
+    BX_REQUIRE(c, !bufs_overlap(nodes, matrix), "merkle_build: nodes and matrix overlap");
     BX_ENTER(c);
     BX_TRY(hash_rows_op(c, c->hash_suite, (uint32_t*)nodes.dptr + 8 * rows, matrix, rows));
     return merkle_fold_layers(c, c->hash_suite, nodes, rows);
@@ -594,7 +596,10 @@ extern "C" const char* bx_d2h(bx_ctx* c, uint32_t* dst, bx_buf src, size_t words
 extern "C" const char* bx_d2d(bx_ctx* c, bx_buf dst, bx_buf src, size_t words) try {
     if (!c) return "bx_d2d: null ctx";
     BX_REQUIRE(c, words <= src.len && words <= dst.len, "bx_d2d: copy larger than a buffer");
+    // the words actually copied, not the len fields: two views of one allocation may be copied between as long as the ranges moved are apart
+    BX_REQUIRE(c, dst.dptr == src.dptr || !bufs_overlap(bx_buf{dst.dptr, words}, bx_buf{src.dptr, words}), "bx_d2d: dst and src overlap");
     BX_ENTER(c);
+    if (dst.dptr == src.dptr || !words) return nullptr;  // a copy onto itself: nothing to move
     BX_HIP(c, hipMemcpyAsync(dst.dptr, src.dptr, words * 4, hipMemcpyDeviceToDevice, c->stream));
     return nullptr;
 } BX_ABI_CATCH(c, "bx_d2d")

@@ -61,8 +61,9 @@ extern "C" const char* bx_image_page_cells(bx_ctx* c, bx_buf out, bx_buf raw, si
 } BX_ABI_CATCH(c, "bx_image_page_cells")
 
 // Digest of node `top` (canonical words) from the pages and the given digests below it.  Every digest lives in one device pool:
-// [0, n) page digests | [n] the zero page | per level its parents then its zero subtree | the given digests; a level's fold reads
-// any earlier entry of the pool through absolute indices, so given digests enter at whatever level they belong to.
+// [0, n) page digests | [n] the zero page | the given digests | per level its parents then its zero subtree; a level's fold reads
+// any earlier entry of the pool through absolute indices, so given digests enter at whatever level they belong to — and writes
+// behind everything it reads: `in` of its bx_hash_fold_indexed is the pool up to the level's first output, `out` starts there.
 static const char* image_node(bx_ctx* c, const bx_image* im, uint32_t top, uint32_t out[8]) {
     // node 0 does not exist (0 << k never reaches the leaf layer: the loop below would not end) and nothing lies beyond the leaves
     BX_REQUIRE(c, top >= 1 && top < (2u << BX_MERKLE_DEPTH), "image: node index outside the tree");
@@ -87,17 +88,16 @@ static const char* image_node(bx_ctx* c, const bx_image* im, uint32_t top, uint3
     for (auto it = im->pages.lower_bound(leaf_lo - (1u << BX_MERKLE_DEPTH)); it != im->pages.end() && it->first + (1u << BX_MERKLE_DEPTH) < leaf_hi; ++it)
         page_idx.push_back(it->first);
     const size_t n = page_idx.size();
-    // pool positions: pages [0,n), zero page n; level outputs appended; given digests at the end
+    // pool positions: pages [0,n), zero page n, the given digests; level outputs appended
     struct Node { uint32_t idx, pos; };
     std::vector<Node> cur;
     for (size_t i = 0; i < n; ++i) cur.push_back({page_idx[i] + (1u << BX_MERKLE_DEPTH), (uint32_t)i});
-    uint32_t zero_pos = (uint32_t)n, pool = (uint32_t)n + 1;
-    // given digests get their pool positions after all computed entries; count computed entries first (each level: parents + zero)
+    const uint32_t given_base = (uint32_t)n + 1;
+    uint32_t zero_pos = (uint32_t)n, pool = given_base + (uint32_t)n_given;
     std::vector<uint32_t> sel;
     std::vector<size_t> level_off, level_cnt, level_out;
     std::vector<std::pair<uint32_t, const uint32_t*>> given_order;  // pool order of the given digests
-    // two passes are avoided by reserving the given digests' positions relative to an offset fixed afterwards
-    const uint32_t GIVEN = 0x80000000u;  // position = GIVEN | ordinal, rewritten below
+    const uint32_t GIVEN = 0x80000000u;  // position = GIVEN | ordinal in the order the levels take them up, rewritten below
     auto merge_given = [&](int lvl, std::vector<Node>& nodes) -> const char* {
         for (auto& g : given[lvl]) {
             nodes.push_back({g.first, GIVEN | (uint32_t)given_order.size()});
@@ -133,12 +133,11 @@ static const char* image_node(bx_ctx* c, const bx_image* im, uint32_t top, uint3
         cur.swap(nxt);
     }
     BX_REQUIRE(c, given_order.size() == n_given, "image: internal error (given digests)");
-    const uint32_t given_base = pool;
     for (auto& v : sel)
         if (v & GIVEN) v = given_base + (v & ~GIVEN);
     uint32_t result_pos = cur.empty() ? zero_pos : cur[0].pos;
     if (result_pos & GIVEN) result_pos = given_base + (result_pos & ~GIVEN);
-    const size_t pool_digests = (size_t)given_base + n_given;
+    const size_t pool_digests = pool;
     // device layout, one allocation: raw pages | cell matrix | digest pool | sel
     const size_t n1 = n + 1, raw_w = n1 * BX_PAGE_WORDS, mat_w = n1 * 2 * BX_PAGE_WORDS, pool_w = pool_digests * 8;
     bx_buf all{nullptr, 0};
@@ -161,7 +160,7 @@ static const char* image_node(bx_ctx* c, const bx_image* im, uint32_t top, uint3
         // Poseidon2 whatever the ctx's suite: upstream's image ID does not depend on hashfn (bx_hash_fold_indexed is Poseidon2 only)
         if ((m = hash_rows_suite(c, bx_buf{dpool.dptr, 8 * n1}, mat, SUITE_POSEIDON2))) break;
         for (int d = 0; d < top_level && !m; ++d)
-            m = bx_hash_fold_indexed(c, bx_buf{(uint32_t*)dpool.dptr + 8 * level_out[d], 8 * level_cnt[d]}, dpool,
+            m = bx_hash_fold_indexed(c, bx_buf{(uint32_t*)dpool.dptr + 8 * level_out[d], 8 * level_cnt[d]}, bx_buf{dpool.dptr, 8 * level_out[d]},
                                      bx_buf{(uint32_t*)dsel.dptr + level_off[d], 2 * level_cnt[d]}, level_cnt[d]);
         if (m) break;
         uint32_t mont[8];

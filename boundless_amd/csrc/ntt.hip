@@ -490,7 +490,8 @@ extern "C" const char* bx_batch_expand_into_evaluate_ntt(bx_ctx* c, bx_buf out, 
     if (!c) return "bx_batch_expand_into_evaluate_ntt: null ctx";
     BX_REQUIRE(c, count > 0 && in.len % count == 0 && is_pow2(in.len / count), "batch_expand_into_evaluate_ntt: in.len/count must be a power of two");
     BX_REQUIRE(c, expand_bits < 32 && out.len >> expand_bits == in.len && out.len == (in.len << expand_bits), "batch_expand_into_evaluate_ntt: out.len != in.len << expand_bits");
-    BX_REQUIRE(c, out.dptr != in.dptr || expand_bits == 0, "batch_expand_into_evaluate_ntt: in-place expansion");
+    // the expansion reads in[i >> bits] while other lanes write out: only the transform in place (no expansion) may share memory
+    BX_REQUIRE(c, (expand_bits == 0 && bufs_same(out, in)) || !bufs_overlap(out, in), "batch_expand_into_evaluate_ntt: out and in overlap");
     BX_ENTER(c);
     OpScope op(c, "batch_expand_into_evaluate_ntt", 4.0 * (double)in.len + 4.0 * (double)out.len);
     int m = ilog2(out.len / count);

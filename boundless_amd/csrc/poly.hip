@@ -442,6 +442,7 @@ static inline unsigned grid1d(size_t n, unsigned bs = 256, size_t cap = 65536) {
 extern "C" const char* bx_fri_fold(bx_ctx* c, bx_buf out, bx_buf in, const uint32_t mix[4]) try {
     if (!c) return "bx_fri_fold: null ctx";
     BX_REQUIRE(c, out.len % 4 == 0 && in.len == out.len * BX_FRI_FOLD, "fri_fold: input.len must be 16 * output.len");
+    BX_REQUIRE(c, !bufs_overlap(out, in), "fri_fold: out and in overlap");
     BX_ENTER(c);
     size_t count = out.len / 4;
     OpScope op(c, "fri_fold", 4.0 * (double)(in.len + out.len));
@@ -455,6 +456,8 @@ extern "C" const char* bx_fri_fold_dev(bx_ctx* c, bx_buf out, bx_buf in, bx_buf 
     if (!c) return "bx_fri_fold_dev: null ctx";
     BX_REQUIRE(c, out.len % 4 == 0 && in.len == out.len * BX_FRI_FOLD, "fri_fold_dev: input.len must be 16 * output.len");
     BX_REQUIRE(c, mix_ext.dptr != nullptr && mix_ext.len >= 4, "fri_fold_dev: mix is one ext element in device memory");
+    BX_REQUIRE(c, !bufs_overlap(out, in), "fri_fold_dev: out and in overlap");
+    BX_REQUIRE(c, !bufs_overlap(out, bx_buf{mix_ext.dptr, 4}), "fri_fold_dev: out and mix_ext overlap");
     BX_ENTER(c);
     size_t count = out.len / 4;
     OpScope op(c, "fri_fold", 4.0 * (double)(in.len + out.len));
@@ -470,6 +473,8 @@ extern "C" const char* bx_mix_poly_coeffs(bx_ctx* c, bx_buf out, const uint32_t 
     if (!c) return "bx_mix_poly_coeffs: null ctx";
     BX_REQUIRE(c, mul_le(input_size, count, in.len) && combos.len >= input_size, "mix_poly_coeffs: input/combos too small");
     BX_REQUIRE(c, count > 0 && mul_le(4, count, out.len) && out.len % (4 * count) == 0, "mix_poly_coeffs: out.len not a multiple of 4*count");
+    BX_REQUIRE(c, !bufs_overlap(out, in), "mix_poly_coeffs: out and in overlap");
+    BX_REQUIRE(c, !bufs_overlap(out, combos), "mix_poly_coeffs: out and combos overlap");
     BX_ENTER(c);
     if (!input_size) return nullptr;
     size_t n_combos = out.len / (4 * count);
@@ -496,6 +501,9 @@ static const char* evaluate_any_impl(bx_ctx* c, bx_buf coeffs, size_t poly_count
     BX_REQUIRE(c, poly_count > 0 && coeffs.len % poly_count == 0, "batch_evaluate_any: coeffs.len not a multiple of poly_count");
     size_t evals = which.len;
     BX_REQUIRE(c, xs.len == 4 * evals && out.len == 4 * evals, "batch_evaluate_any: xs/out must hold one ext elem per eval");
+    BX_REQUIRE(c, !bufs_overlap(out, coeffs), "batch_evaluate_any: out and coeffs overlap");
+    BX_REQUIRE(c, !bufs_overlap(out, which), "batch_evaluate_any: out and which overlap");
+    BX_REQUIRE(c, !bufs_overlap(out, xs), "batch_evaluate_any: out and xs overlap");
     BX_ENTER(c);
     size_t poly_size = coeffs.len / poly_count;
     size_t seg_elems = (size_t)EV_T * EV_K;
@@ -546,6 +554,9 @@ extern "C" const char* bx_batch_evaluate_ptrs(bx_ctx* c, bx_buf poly_ptrs, bx_bu
     if (!c) return "bx_batch_evaluate_ptrs: null ctx";
     const size_t evals = flags.len, seg_elems = (size_t)EV_T * EV_K;
     BX_REQUIRE(c, poly_ptrs.len == 2 * evals && xs.len == 4 * evals && out.len == 4 * evals, "batch_evaluate_ptrs: one pointer (two words), one flag, one point and one result per evaluation");
+    BX_REQUIRE(c, !bufs_overlap(out, poly_ptrs), "batch_evaluate_ptrs: out and poly_ptrs overlap");
+    BX_REQUIRE(c, !bufs_overlap(out, flags), "batch_evaluate_ptrs: out and flags overlap");
+    BX_REQUIRE(c, !bufs_overlap(out, xs), "batch_evaluate_ptrs: out and xs overlap");
     BX_REQUIRE(c, is_pow2(poly_size) && poly_size >= seg_elems && poly_size / seg_elems <= 512, "batch_evaluate_ptrs: polynomial size must be a power of two in [2^15, 2^24]");
     BX_REQUIRE(c, evals <= 65535 && ((uintptr_t)poly_ptrs.dptr & 7u) == 0, "batch_evaluate_ptrs: at most 65535 evaluations, pointers 8-byte aligned");
     BX_ENTER(c);
@@ -571,6 +582,9 @@ extern "C" const char* bx_batch_evaluate_ptrs(bx_ctx* c, bx_buf poly_ptrs, bx_bu
 extern "C" const char* bx_eltwise_add_elem(bx_ctx* c, bx_buf out, bx_buf a, bx_buf b) try {
     if (!c) return "bx_eltwise_add_elem: null ctx";
     BX_REQUIRE(c, out.len == a.len && a.len == b.len, "eltwise_add_elem: length mismatch");
+    // element-wise: out may BE a or b (same start, same length: every lane reads its own words before it writes); a and b are inputs
+    BX_REQUIRE(c, bufs_same(out, a) || !bufs_overlap(out, a), "eltwise_add_elem: out and a overlap");
+    BX_REQUIRE(c, bufs_same(out, b) || !bufs_overlap(out, b), "eltwise_add_elem: out and b overlap");
     BX_ENTER(c);
     OpScope op(c, "eltwise_add_elem", 12.0 * (double)out.len);
     hipLaunchKernelGGL(eltwise_add_kernel, dim3(grid1d(out.len)), dim3(256), 0, c->stream, (uint32_t*)out.dptr,
@@ -591,7 +605,9 @@ extern "C" const char* bx_eltwise_mul_factor(bx_ctx* c, bx_buf io, uint32_t fact
 extern "C" const char* bx_eltwise_copy_elem(bx_ctx* c, bx_buf out, bx_buf in) try {
     if (!c) return "bx_eltwise_copy_elem: null ctx";
     BX_REQUIRE(c, out.len == in.len, "eltwise_copy_elem: length mismatch");
+    BX_REQUIRE(c, bufs_same(out, in) || !bufs_overlap(out, in), "eltwise_copy_elem: out and in overlap");
     BX_ENTER(c);
+    if (out.dptr == in.dptr || !out.len) return nullptr;  // a copy onto itself: nothing to move
     OpScope op(c, "eltwise_copy_elem", 8.0 * (double)out.len);
     BX_HIP(c, hipMemcpyAsync(out.dptr, in.dptr, out.len * 4, hipMemcpyDeviceToDevice, c->stream));
     return nullptr;
@@ -607,6 +623,7 @@ extern "C" const char* bx_eltwise_zeroize_elem(bx_ctx* c, bx_buf io) try {
 extern "C" const char* bx_eltwise_sum_extelem(bx_ctx* c, bx_buf out, bx_buf in) try {
     if (!c) return "bx_eltwise_sum_extelem: null ctx";
     BX_REQUIRE(c, out.len % 4 == 0 && out.len > 0 && in.len % out.len == 0, "eltwise_sum_extelem: in.len not a multiple of out.len");
+    BX_REQUIRE(c, !bufs_overlap(out, in), "eltwise_sum_extelem: out and in overlap");
     BX_ENTER(c);
     size_t count = out.len / 4, to_add = in.len / out.len;
     OpScope op(c, "eltwise_sum_extelem", 4.0 * (double)(in.len + out.len));
@@ -619,6 +636,9 @@ extern "C" const char* bx_gather_sample(bx_ctx* c, bx_buf dst, bx_buf src, size_
     if (!c) return "bx_gather_sample: null ctx";
     BX_REQUIRE(c, dst.len >= size, "gather_sample: dst too small");
     BX_REQUIRE(c, size == 0 || (idx < src.len && mul_le(size - 1, stride, src.len - 1 - idx)), "gather_sample: source index out of range");
+    // before the queue decision, so that the queued and the direct path refuse alike (the queue's hazard intervals only relate a
+    // gather to EARLIER ones): the words written against the whole of src
+    BX_REQUIRE(c, !bufs_overlap(bx_buf{dst.dptr, size}, src), "gather_sample: dst and src overlap");
     if (!size) return nullptr;
     // Small gathers are queued and launched together by the next call that touches the ctx (ctx.hpp, "Deferred ... gather_sample"):
     // the openings of a proof are ~5 000 of them.  Stream order as the caller sees it is kept: anything that could observe the
@@ -669,6 +689,9 @@ const char* gather_flush(bx_ctx* c) {
 extern "C" const char* bx_scatter(bx_ctx* c, bx_buf into, bx_buf index, bx_buf offsets, bx_buf values) try {
     if (!c) return "bx_scatter: null ctx";
     BX_REQUIRE(c, offsets.len == values.len, "scatter: offsets and values must have the same length");
+    BX_REQUIRE(c, !bufs_overlap(into, index), "scatter: into and index overlap");
+    BX_REQUIRE(c, !bufs_overlap(into, offsets), "scatter: into and offsets overlap");
+    BX_REQUIRE(c, !bufs_overlap(into, values), "scatter: into and values overlap");
     BX_ENTER(c);
     if (index.len < 2 || offsets.len == 0) return nullptr;
     // asynchronous like every other entry point: range errors are raised on the device and reported by the next

@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // hash_fold with an indirection: out[j] = H(in[sel[2j]] || in[sel[2j+1]]).  The levels of a SPARSE Merkle tree (the zkVM
 // memory image, bx_image.h: 2^22 leaves of which a few hundred exist) are folded with it: the host lists, per level, which
 // two digests of the level below (or that level's all-zero digest) feed each surviving parent.
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void hash_fold_indexed_kernel(uint32_t* out, const uint32_t* in,  // out may be a range of the pool `in` names (no sel entry inside it): not __restrict__
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void hash_fold_indexed_kernel(uint32_t* out, const uint32_t* in,  // (bx_hash_fold_indexed refuses an out that overlaps in)
                                                                 const uint32_t* __restrict__ sel, const uint32_t* __restrict__ prm,
                                                                 uint32_t count, uint32_t n_in) {
     uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -579,6 +579,8 @@ extern "C" const char* bx_hash_fold_indexed(bx_ctx* c, bx_buf out, bx_buf in, bx
     BX_REQUIRE(c, count <= 0xffffffffu && in.len / 8 <= 0xffffffffu, "hash_fold_indexed: too many digests");
     if (count == 0) return nullptr;
     BX_REQUIRE(c, out.dptr && in.dptr && sel.dptr && in.len >= 8, "hash_fold_indexed: null or empty buffer");
+    BX_REQUIRE(c, !bufs_overlap(out, in), "hash_fold_indexed: out and in overlap");
+    BX_REQUIRE(c, !bufs_overlap(out, sel), "hash_fold_indexed: out and sel overlap");
     BX_ENTER(c);
     OpScope op(c, "hash_fold_indexed", 104.0 * (double)count);
     hipLaunchKernelGGL(hash_fold_indexed_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream, (uint32_t*)out.dptr,
@@ -594,6 +596,8 @@ extern "C" const char* bx_transcript_step(bx_ctx* c, bx_buf state, bx_buf digest
     BX_REQUIRE(c, state.dptr != nullptr && state.len >= 25, "transcript_step: the state is 24 cells and the pool counter");
     BX_REQUIRE(c, n_commit <= 64 && n_ext <= 64, "transcript_step: at most 64 commits and 64 challenges per step");
     BX_REQUIRE(c, digests.len >= 8 * n_commit && out_ext.len >= 4 * n_ext, "transcript_step: digests / out too small");
+    BX_REQUIRE(c, !bufs_overlap(out_ext, state), "transcript_step: out_ext and state overlap");
+    BX_REQUIRE(c, !bufs_overlap(out_ext, digests), "transcript_step: out_ext and digests overlap");
     BX_ENTER(c);
     if (!n_commit && !n_ext) return nullptr;
     OpScope op(c, "transcript_step", 4.0 * (double)(50 + 8 * n_commit + 4 * n_ext));

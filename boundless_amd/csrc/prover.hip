@@ -200,6 +200,9 @@ extern "C" const char* bx_merkle_query_gather(bx_ctx* c, bx_buf out, bx_buf matr
     BX_REQUIRE(c, matrix.len == rows * cols && nodes.len == 16 * rows, "merkle_query_gather: matrix/nodes size mismatch");
     unsigned depth = (unsigned)(ilog2(rows) - ilog2(top_size));
     BX_REQUIRE(c, out.len >= n_queries * (cols + 8 * depth) && positions.len >= n_queries, "merkle_query_gather: out/positions too small");
+    BX_REQUIRE(c, !bufs_overlap(out, matrix), "merkle_query_gather: out and matrix overlap");
+    BX_REQUIRE(c, !bufs_overlap(out, nodes), "merkle_query_gather: out and nodes overlap");
+    BX_REQUIRE(c, !bufs_overlap(out, positions), "merkle_query_gather: out and positions overlap");
     BX_ENTER(c);
     if (!n_queries) return nullptr;
     OpScope op(c, "merkle_query_gather", 4.0 * (double)(n_queries * (cols + 8 * depth)) * 2.0);

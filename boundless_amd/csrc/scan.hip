@@ -740,6 +740,7 @@ using namespace bx;
 extern "C" const char* bx_poly_divide(bx_ctx* c, bx_buf poly, const uint32_t z[4], bx_buf rem_out) try {
     if (!c) return "bx_poly_divide: null ctx";
     BX_REQUIRE(c, poly.len % 4 == 0 && rem_out.len >= 4, "poly_divide: poly must be AoS ext, remainder buffer >= 4 words");
+    BX_REQUIRE(c, !bufs_overlap(bx_buf{rem_out.dptr, 4}, poly), "poly_divide: rem_out and poly overlap");
     BX_ENTER(c);
     size_t size = poly.len / 4;
     if (!size) return nullptr;
@@ -753,6 +754,7 @@ extern "C" const char* bx_poly_divide_batch(bx_ctx* c, bx_buf polys, size_t coun
     if (!c) return "bx_poly_divide_batch: null ctx";
     BX_REQUIRE(c, count >= 1 && count <= 65535 && polys.len % (4 * count) == 0, "poly_divide_batch: the buffer does not split into `count` AoS ext polynomials");
     BX_REQUIRE(c, zs != nullptr && rems_out.len >= 4 * count, "poly_divide_batch: one point and one remainder slot per polynomial");
+    BX_REQUIRE(c, !bufs_overlap(bx_buf{rems_out.dptr, 4 * count}, polys), "poly_divide_batch: rems_out and polys overlap");
     BX_REQUIRE(c, ((uintptr_t)polys.dptr & 15u) == 0 && ((uintptr_t)rems_out.dptr & 15u) == 0, "poly_divide_batch: buffers must be 16-byte aligned");
     BX_ENTER(c);
     const size_t size = polys.len / 4 / count;
@@ -765,6 +767,7 @@ extern "C" const char* bx_poly_divide_batch_indexed(bx_ctx* c, bx_buf polys, siz
     if (!c) return "bx_poly_divide_batch_indexed: null ctx";
     BX_REQUIRE(c, n_polys >= 1 && n_polys <= polys.len / 4 && polys.len % (4 * n_polys) == 0, "poly_divide_batch_indexed: the buffer does not split into n_polys AoS ext polynomials");
     BX_REQUIRE(c, count <= 65535 && which != nullptr && zs != nullptr && rems_out.len >= 4 * count, "poly_divide_batch_indexed: one index, one point and one remainder slot per division");
+    BX_REQUIRE(c, !bufs_overlap(bx_buf{rems_out.dptr, 4 * count}, polys), "poly_divide_batch_indexed: rems_out and polys overlap");
     BX_REQUIRE(c, ((uintptr_t)polys.dptr & 15u) == 0 && ((uintptr_t)rems_out.dptr & 15u) == 0, "poly_divide_batch_indexed: buffers must be 16-byte aligned");
     for (size_t q = 0; q < count; ++q) BX_REQUIRE(c, which[q] < n_polys, "poly_divide_batch_indexed: polynomial index out of range");
     {
@@ -859,6 +862,8 @@ extern "C" const char* bx_logup_accumulate(bx_ctx* c, bx_buf out, bx_buf denoms,
     const size_t n = out.len / 4 / count;
     BX_REQUIRE(c, out.len / 4 <= SC_MAX_ELEMS, "logup_accumulate: too many elements");  // bounds n, and the one-launch inversion over all sequences
     BX_REQUIRE(c, mul_le(count, n, mults.len), "logup_accumulate: one multiplicity per denominator");
+    BX_REQUIRE(c, bufs_same(out, denoms) || !bufs_overlap(out, denoms), "logup_accumulate: out and denoms overlap");
+    BX_REQUIRE(c, !bufs_overlap(out, bx_buf{mults.dptr, count * n}), "logup_accumulate: out and mults overlap");
     BX_REQUIRE(c, ((uintptr_t)out.dptr & 15u) == 0 && ((uintptr_t)denoms.dptr & 15u) == 0 && ((uintptr_t)mults.dptr & 3u) == 0,
                "logup_accumulate: ext buffers must be 16-byte aligned");
     BX_ENTER(c);

@@ -30,6 +30,15 @@
  *     k*size).  Digests are 8 words.  Matrices are column-major (column c = [c*rows, (c+1)*rows)).
  *   - bx_buf is a plain (device pointer, length) pair, so memory owned by another allocator on the same
  *     device (e.g. a torch tensor's data_ptr) may be passed in.
+ *   - Operand overlap.  Two operands overlap when their byte ranges [dptr, dptr + 4 * len) share a byte; an empty buffer overlaps
+ *     nothing.  AN OUTPUT MUST NOT OVERLAP ANY OTHER OPERAND OF THE SAME CALL: the kernels write through __restrict__ pointers while
+ *     other lanes still read.  Such a call is refused on the host, before anything is enqueued, with "<entry point>: <a> and <b>
+ *     overlap"; nothing is written and the ctx stays usable.  Operands that touch (one ends where the other starts) do not overlap.
+ *     Inputs may overlap inputs freely.  Four element-wise exceptions accept an output that IS an input (same start, same length) and
+ *     still refuse every partial overlap: bx_eltwise_add_elem, bx_eltwise_copy_elem / bx_d2d, bx_logup_accumulate and
+ *     bx_batch_expand_into_evaluate_ntt with expand_bits = 0; each says so below.  The rule is about the operands' ADDRESSES: what an
+ *     index operand in device memory holds (which, combos, sel, positions, offsets, poly_ptrs) is not read by the host, and a value
+ *     out of range there stays the caller's responsibility.
  */
 #ifndef BX_HAL_H
 #define BX_HAL_H
@@ -89,6 +98,8 @@ const char* bx_alloc_init(bx_ctx* ctx, size_t words, uint32_t value, bx_buf* out
 const char* bx_release(bx_ctx* ctx, bx_buf buf);
 const char* bx_h2d(bx_ctx* ctx, bx_buf dst, const uint32_t* src, size_t words);
 const char* bx_d2h(bx_ctx* ctx, uint32_t* dst, bx_buf src, size_t words); /* blocks */
+/* dst[0 .. words) = src[0 .. words).  Overlap is judged on the `words` copied, not on the len fields: the two ranges must be apart, or
+ * start at the same address (a well-formed no-op). */
 const char* bx_d2d(bx_ctx* ctx, bx_buf dst, bx_buf src, size_t words);
 /* Hal::eltwise_copy_elem_slice(into, from: &[Elem], from_rows, from_cols, from_offset, from_stride, into_offset, into_stride)
  * ([EXT] risc0-zkp; the CUDA HAL uploads `from` and runs its `eltwise_copy_fp_region` kernel): a strided 2-D copy of a HOST slice
@@ -120,7 +131,9 @@ const char* bx_batch_interpolate_ntt(bx_ctx* ctx, bx_buf io, size_t count);
 /* Hal::batch_evaluate_ntt(io, count, expand_bits): bit-reversed coefficients -> natural-order evaluations,
  * in place, skipping the first expand_bits stages. */
 const char* bx_batch_evaluate_ntt(bx_ctx* ctx, bx_buf io, size_t count, size_t expand_bits);
-/* Hal::batch_expand_into_evaluate_ntt(out, in, count, expand_bits): out[i] = in[i >> bits] then evaluate. */
+/* Hal::batch_expand_into_evaluate_ntt(out, in, count, expand_bits): out[i] = in[i >> bits] then evaluate.  out and in must not overlap
+ * — `in` being a slice of `out` (its last quarter, say) included: the expansion is not in place — except out = in (same start, same
+ * length) with expand_bits = 0, which is bx_batch_evaluate_ntt. */
 const char* bx_batch_expand_into_evaluate_ntt(bx_ctx* ctx, bx_buf out, bx_buf in, size_t count,
                                               size_t expand_bits);
 /* Hal::batch_bit_reverse(io, count) */
@@ -140,21 +153,21 @@ const char* bx_poseidon2_get_params(bx_ctx* ctx, uint32_t* rc213, uint32_t* diag
  * tests/golden/MANIFEST.json. */
 const char* bx_poseidon2_default_params(uint32_t* rc213, uint32_t* diag24);
 /* Hal::hash_rows(output, matrix): out_digests.len/8 rows; cols = matrix.len/rows.  (This and the next three follow the ctx's
- * hash suite: Poseidon2, or SHA-256 after bx_set_hash_suite(ctx, "sha-256").) */
+ * hash suite: Poseidon2, or SHA-256 after bx_set_hash_suite(ctx, "sha-256").)  out_digests must not overlap matrix. */
 const char* bx_hash_rows(bx_ctx* ctx, bx_buf out_digests, bx_buf matrix);
 /* Hal::hash_fold(io, input_size, output_size): io[out+i] = H(io[in+2i] || io[in+2i+1]), digest indices. */
 const char* bx_hash_fold(bx_ctx* ctx, bx_buf io_digests, size_t input_size, size_t output_size);
 /* MerkleTreeProver::new's loop in one call: nodes has 2*rows digests; hashes the rows of `matrix` into
- * nodes[rows..2rows) and folds every layer down to nodes[1]. */
+ * nodes[rows..2rows) and folds every layer down to nodes[1].  nodes_digests must not overlap matrix. */
 const char* bx_merkle_build(bx_ctx* ctx, bx_buf nodes_digests, bx_buf matrix, size_t rows);
 /* Extension: the fold half alone — the leaf digests are already in nodes[rows .. 2 rows). */
 const char* bx_merkle_fold(bx_ctx* ctx, bx_buf nodes_digests, size_t rows);
 
 /* ---- Hal FRI / DEEP family ---- */
-/* Hal::fri_fold(output, input, mix): SoA planes; input.len = 16*output.len. `mix` = 4 host words. */
+/* Hal::fri_fold(output, input, mix): SoA planes; input.len = 16*output.len. `mix` = 4 host words.  out must not overlap in. */
 const char* bx_fri_fold(bx_ctx* ctx, bx_buf out, bx_buf in, const uint32_t mix[4]);
 /* Extension: the same with `mix` in device memory (4 words), so that a challenge drawn on the device (bx_transcript_step) feeds
- * the fold without a host round trip. */
+ * the fold without a host round trip.  out must overlap neither in nor mix_ext. */
 const char* bx_fri_fold_dev(bx_ctx* ctx, bx_buf out, bx_buf in, bx_buf mix_ext);
 /* Extension: one step of the Fiat-Shamir transcript on the device (risc0_zkp Poseidon2Rng: `mix(digest)` n_commit times, then
  * `random_elem` 4 * n_ext times).  state = 25 words: the 24 sponge cells (Montgomery) and the number of rate cells already handed
@@ -162,14 +175,16 @@ const char* bx_fri_fold_dev(bx_ctx* ctx, bx_buf out, bx_buf in, bx_buf mix_ext);
  * Enqueued like everything else: with the tunable `dev_draws` = 1 the prover uses it where a challenge depends on nothing but a root
  * (the FRI rounds; measured no faster than the host round trips on MI355X, hence off by default), reads roots,
  * top layers and the drawn challenges back later in ONE copy, and replays the same steps on the host transcript (which also
- * writes the seal), checking that both sides drew the same words. */
+ * writes the seal), checking that both sides drew the same words.  out_ext must overlap neither state25 nor digests. */
 const char* bx_transcript_step(bx_ctx* ctx, bx_buf state25, bx_buf digests, size_t n_commit, bx_buf out_ext, size_t n_ext);
 /* Hal::mix_poly_coeffs(output, mix_start, mix, input, combos, input_size, count):
- * out_ext[combos[i]*count + idx] += mix_start*mix^i * in[i*count + idx], i < input_size, idx < count. */
+ * out_ext[combos[i]*count + idx] += mix_start*mix^i * in[i*count + idx], i < input_size, idx < count.  out_ext must overlap neither in
+ * nor combos_u32; combos[i] < out_ext.len / (4 * count) is the caller's responsibility. */
 const char* bx_mix_poly_coeffs(bx_ctx* ctx, bx_buf out_ext, const uint32_t mix_start[4],
                                const uint32_t mix[4], bx_buf in, bx_buf combos_u32, size_t input_size,
                                size_t count);
-/* Hal::batch_evaluate_any(coeffs, poly_count, which, xs, out): out[i] = sum_j coeffs[which[i]*size+j]*xs[i]^j */
+/* Hal::batch_evaluate_any(coeffs, poly_count, which, xs, out): out[i] = sum_j coeffs[which[i]*size+j]*xs[i]^j.  out_ext must overlap
+ * none of coeffs, which_u32 and xs_ext (this and the _bitrev form); which[i] < poly_count is the caller's responsibility. */
 const char* bx_batch_evaluate_any(bx_ctx* ctx, bx_buf coeffs, size_t poly_count, bx_buf which_u32,
                                   bx_buf xs_ext, bx_buf out_ext);
 /* Extensions for provers that keep coefficient polynomials in bit-reversed order (what batch_interpolate_ntt leaves
@@ -181,12 +196,16 @@ const char* bx_batch_evaluate_any_bitrev(bx_ctx* ctx, bx_buf coeffs_bitrev, size
 const char* bx_batch_bit_reverse_ext(bx_ctx* ctx, bx_buf io_ext, size_t count);
 /* Extension: evaluations over several coefficient buffers in one launch set: evaluation i evaluates, at xs[i], the polynomial of
  * poly_size coefficients (a power of two in [2^15, 2^24]) at device address poly_ptrs[i] (a little-endian u64 in two words), stored
- * bit-reversed when flags[i] & 1.  The prover's DEEP step evaluates the taps of all four groups with one call. */
+ * bit-reversed when flags[i] & 1.  The prover's DEEP step evaluates the taps of all four groups with one call.  out_ext must overlap
+ * none of poly_ptrs_u64, flags_u32 and xs_ext.  The polynomials the pointers name are not operands the library can see: that they are
+ * valid, and that none of them overlaps out_ext, stays the caller's responsibility. */
 const char* bx_batch_evaluate_ptrs(bx_ctx* ctx, bx_buf poly_ptrs_u64, bx_buf flags_u32, size_t poly_size, bx_buf xs_ext, bx_buf out_ext);
 /* Extension: batch_interpolate_ntt(io, count) followed by zk_shift(io, count) as one call; on the register-radix path the
  * shift rides on the final store of the inverse transform.  Same result as the two calls. */
 const char* bx_batch_interpolate_zk(bx_ctx* ctx, bx_buf io, size_t count);
-/* Hal::eltwise_add_elem / eltwise_copy_elem / eltwise_zeroize_elem / eltwise_sum_extelem */
+/* Hal::eltwise_add_elem / eltwise_copy_elem / eltwise_zeroize_elem / eltwise_sum_extelem.
+ * add: out may BE a, b or both (same start, same length), and a may overlap b in any way (two inputs); a partial overlap of out with a
+ * or b is refused.  copy: out may BE in (a well-formed no-op); a partial overlap is refused.  sum: out must not overlap in_ext. */
 const char* bx_eltwise_add_elem(bx_ctx* ctx, bx_buf out, bx_buf a, bx_buf b);
 const char* bx_eltwise_copy_elem(bx_ctx* ctx, bx_buf out, bx_buf in);
 const char* bx_eltwise_zeroize_elem(bx_ctx* ctx, bx_buf io);
@@ -198,7 +217,8 @@ const char* bx_eltwise_mul_factor(bx_ctx* ctx, bx_buf io, uint32_t factor_mont);
  * next call of any kind on the ctx (or bx_get_stream): stream order as the caller observes it is unchanged, the ~3.7 us of launch
  * cost per gather is paid once per batch.  Tunable "gather_defer" = 0 launches each gather at once; so does a ctx that runs on
  * an adopted stream (bx_set_stream), whose owner enqueues work there that this library does not see.  Work a caller enqueues
- * directly on the ctx's OWN stream must fetch it with bx_get_stream each time (which flushes), not from an earlier call. */
+ * directly on the ctx's OWN stream must fetch it with bx_get_stream each time (which flushes), not from an earlier call.
+ * The `size` words written at dst must not overlap src; refused alike whether the gather would have been queued or launched. */
 const char* bx_gather_sample(bx_ctx* ctx, bx_buf dst, bx_buf src, size_t idx, size_t size, size_t stride);
 /* Hal::prefix_products(io): io[i] = io[i] * io[i-1] over AoS ext elements (inclusive running product; the circuit's
  * accumulate step uses it for its grand products). */
@@ -226,16 +246,17 @@ const char* bx_batch_prefix_sums(bx_ctx* ctx, bx_buf io_ext, size_t count);
 /* bx_logup_accumulate: out[s][i] = sum_{j <= i} mults[s][j] * denoms[s][j]^-1 for `count` sequences of n = out_ext.len/4/count
  * elements: denoms_ext (same length as out_ext) holds the ext denominators, mults (at least count * n words, sequence s at s * n) the
  * base-field multiplicities.  A zero denominator contributes zero.  Word for word what bx_batch_invert_ext, an element-wise
- * scale by mults and bx_batch_prefix_sums give, with one read of denoms and mults and one write of out; out may be denoms itself
- * (any other overlap of out with denoms or mults is the caller's error). */
+ * scale by mults and bx_batch_prefix_sums give, with one read of denoms and mults and one write of out; out may BE denoms (same start,
+ * same length); any other overlap of out with denoms, and any overlap of out with mults, is refused. */
 const char* bx_logup_accumulate(bx_ctx* ctx, bx_buf out_ext, bx_buf denoms_ext, bx_buf mults, size_t count);
 /* Hal::scatter(into, index, offsets, values): for cycle c < index.len - 1, every entry e in [index[c], index[c+1])
  * writes into[offsets[e]] = values[e].  All four are device buffers.  Asynchronous: an offset outside `into` or an index
  * range outside offsets/values is detected on the device and reported by the next blocking call on the ctx (bx_d2h,
- * bx_sync), which returns the error string. */
+ * bx_sync), which returns the error string.  `into` must overlap none of index, offsets and values. */
 const char* bx_scatter(bx_ctx* ctx, bx_buf into, bx_buf index_u32, bx_buf offsets_u32, bx_buf values);
 /* DEEP quotient (upstream: core/poly.rs poly_divide, run per combo): in-place synthetic division of the
- * natural-order AoS ext polynomial by (x - z); the remainder (4 words) is written to rem_out_dev. */
+ * natural-order AoS ext polynomial by (x - z); the remainder (4 words) is written to rem_out_dev, which must not overlap the
+ * polynomial (this and the two batch forms: the 4 words per division against the whole polynomial buffer). */
 const char* bx_poly_divide(bx_ctx* ctx, bx_buf poly_ext, const uint32_t z[4], bx_buf rem_out_dev);
 
 /* Extension: `count` AoS ext polynomials back to back, polynomial q divided in place by (x - zs[q]) (zs: 4 host words per

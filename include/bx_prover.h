@@ -145,7 +145,8 @@ const char* bx_prover_last_roots(const bx_prover* prover, uint32_t roots_out[32]
 
 /* MerkleTreeProver::prove for a batch of queries: for query q, out[q*(cols + 8*depth) ...] receives the `cols`
  * column values of row positions[q] followed by the `depth` sibling digests from the leaf layer up to (excluding)
- * the layer of `top_size` nodes. positions is a device u32 buffer. */
+ * the layer of `top_size` nodes. positions is a device u32 buffer.  out must overlap none of matrix, nodes_digests and positions
+ * (bx_hal.h, "Operand overlap"); positions[q] < rows is the caller's responsibility. */
 const char* bx_merkle_query_gather(bx_ctx* ctx, bx_buf out, bx_buf matrix, bx_buf nodes_digests, size_t rows,
                                    size_t cols, bx_buf positions_u32, size_t n_queries, size_t top_size);
 
