@@ -17,7 +17,7 @@
 namespace bx {
 
 constexpr int CELLS = 24, RATE = 16, RF_HALF = 4, RP = 21;
-constexpr int DIAG_OFF = 216;  // diagonal starts 16-byte aligned in the device parameter table
+constexpr int DIAG_OFF = 216;  // diagonal starts 32-byte aligned in the device parameter table (it and the tables behind it are read by 32-byte scalar loads)
 constexpr int PAIR_OFF = DIAG_OFF + 24, P2_TABLE = PAIR_OFF + 2 * CELLS;  // behind it: the paired rounds' E[24], A[24] (centred)
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -37,7 +37,7 @@ constexpr int PAIR_OFF = DIAG_OFF + 24, P2_TABLE = PAIR_OFF + 2 * CELLS;  // beh
 //     constants are stored pre-scaled, and only the two layers that must hand back Montgomery form (before the internal
 //     rounds, and at the end) multiply by a correction constant (poseidon2_arith.hpp: representation tracking).
 // Results are congruent mod P at every step and the words that leave the permutation are canonical, so the output is
-// bit-identical to the reduce-everywhere form (6.3 k VALU instructions per permutation by PMC, down from ~14.5 k).
+// bit-identical to the reduce-everywhere form (6.1 k VALU instructions per permutation by PMC, down from ~14.5 k).
 //
 // Magnitude bounds (rho = P / 2^32 = 0.46875; sredc(t) in [t/2^32 - P/2, t/2^32 + P/2); int32 holds 1.0667 P):
 //   redc64s output                     |x| <= 57 + P/2                           (external rounds' S-box input)
@@ -53,9 +53,17 @@ constexpr int PAIR_OFF = DIAG_OFF + 24, P2_TABLE = PAIR_OFF + 2 * CELLS;  // beh
 // ---------------------------------------------------------------------------------------------------------------
 // Device parameter table (round constants scaled by p2_rc_scale(i) so that they can ride in a REDC accumulator of the
 // round's representation): [0,96) external rounds 0-3 | [96,117) internal rounds | [117,213) external rounds 4-7 |
-// [216,240) internal diagonal (plain Montgomery form, used as a multiplier; 16-byte aligned) | [240,288) the constants of the
+// [216,240) internal diagonal (plain Montgomery form, used as a multiplier; 32-byte aligned) | [240,288) the constants of the
 // paired internal rounds derived from it (p2_pair_consts: E[24], A[24], centred, as two's-complement words).
 // Input: cells < P (canonical).  Output: canonical.
+// [LO, HI) is the LIVE RANGE: the output cells the caller reads.  A sponge that absorbs again reads the capacity, <16, 24> (the rate is
+// overwritten by the next 16 columns); its last permutation and every Merkle fold read the digest, <0, 8>.  The compiler drops what plain
+// C computes for a dead cell by itself, but not the pinned multiply-adds, so the last layer is split: all 24 S-boxes and the layer's blocks
+// and column sums are computed as ever (every output needs them), and the final add, the reduction that restores the Montgomery form,
+// canon and the store run for the live cells only.  io[] keeps its input words in the dead cells.
+typedef uint32_t sgpr8 __attribute__((ext_vector_type(8)));
+static_assert(DIAG_OFF % 8 == 0 && PAIR_OFF % 8 == 0 && CELLS % 8 == 0, "the tables are read as 32-byte octets");
+template <int LO = 0, int HI = CELLS>
 __device__ __forceinline__ void poseidon2_mix(uint32_t* io, const uint32_t* __restrict__ prm) {
     i32 s[CELLS];
     i64 y[CELLS];
@@ -80,24 +88,25 @@ __device__ __forceinline__ void poseidon2_mix(uint32_t* io, const uint32_t* __re
     // internal rounds: cells[i] = sum + diag[i]*cells[i].  Rounds 1..20 go two at a time (internal_round_pair: cells 1..23 return
     // to 32 bits once per pair); in the last one sum is accumulated in 64 bits, turned into sum_r = sum * 2^32 mod P by one
     // reduction, and rides in each cell's REDC accumulator together with external round 4's constants.
-    // The 24 diagonal words are wave-uniform.  Loaded as scalars the compiler re-issues the s_load (+ s_waitcnt stall) in every
-    // internal round; held in VGPRs they cost 24 registers.  So: six 16-byte vector loads through an offset the compiler cannot prove uniform (an opaque zero), issued once,
-    // then v_readfirstlane into SGPRs — values the compiler can neither rematerialise from memory nor widen, and that the
-    // multiply-adds read as their one scalar operand.
-    // The constants of the paired rounds (E, A: poseidon2_arith.hpp) are fetched the same way in front of the pairs, the diagonal
-    // itself only behind them, for the single last round: 48 + a few SGPRs are live in the loop, not 72.
-    uint32_t zero;
-    asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
+    // The 24 diagonal words are wave-uniform, and the multiply-adds read them as their one scalar operand.  Loaded as plain scalars
+    // the compiler re-issues the s_load (+ s_waitcnt stall) in every internal round; held in VGPRs they cost 24 registers.  So each table
+    // is fetched ONCE by 32-byte scalar loads from the wave-uniform table pointer straight into SGPR octets, and the octets then pass
+    // through an empty volatile statement as SGPR in/out operands: behind it they are values the compiler can neither rematerialise
+    // from memory nor widen, the wait is the compiler's own, in front of the statement, and no vector instruction is spent on
+    // them (the tables used to come through 18 vector loads and 72 v_readfirstlane).  The loads stay the compiler's, not text
+    // inside the statement: a statement that takes the table pointer makes the pointer escape, and every round constant of the
+    // kernel then comes through a vector load and a full wait (tools/experiments/README.md).
+    // The constants of the paired rounds (E, A: poseidon2_arith.hpp) are fetched in front of the pairs, the diagonal itself only
+    // behind them, for the single last round: 48 + a few SGPRs are live in the loop, not 72.
     {
+        const sgpr8* kp = reinterpret_cast<const sgpr8*>(prm + PAIR_OFF);
+        sgpr8 k0 = kp[0], k1 = kp[1], k2 = kp[2], k3 = kp[3], k4 = kp[4], k5 = kp[5];
+        asm volatile("" : "+s"(k0), "+s"(k1), "+s"(k2), "+s"(k3), "+s"(k4), "+s"(k5));
         i32 pk[2 * CELLS];
-        const uint4* kp = reinterpret_cast<const uint4*>(prm + PAIR_OFF + zero);
 #pragma unroll
-        for (int i = 0; i < 2 * CELLS / 4; ++i) {
-            const uint4 v = kp[i];
-            pk[4 * i] = (i32)__builtin_amdgcn_readfirstlane(v.x);
-            pk[4 * i + 1] = (i32)__builtin_amdgcn_readfirstlane(v.y);
-            pk[4 * i + 2] = (i32)__builtin_amdgcn_readfirstlane(v.z);
-            pk[4 * i + 3] = (i32)__builtin_amdgcn_readfirstlane(v.w);
+        for (int i = 0; i < 8; ++i) {
+            pk[i] = (i32)k0[i], pk[8 + i] = (i32)k1[i], pk[16 + i] = (i32)k2[i];
+            pk[24 + i] = (i32)k3[i], pk[32 + i] = (i32)k4[i], pk[40 + i] = (i32)k5[i];
         }
 #pragma unroll 1
         for (int r = 0; r < RP - 1; r += 2) {
@@ -106,35 +115,34 @@ __device__ __forceinline__ void poseidon2_mix(uint32_t* io, const uint32_t* __re
     }
     uint32_t diag[CELLS];
     {
-        const uint4* dp = reinterpret_cast<const uint4*>(prm + DIAG_OFF + zero);
+        const sgpr8* dp = reinterpret_cast<const sgpr8*>(prm + DIAG_OFF);
+        sgpr8 d0 = dp[0], d1 = dp[1], d2 = dp[2];
+        asm volatile("" : "+s"(d0), "+s"(d1), "+s"(d2));
 #pragma unroll
-        for (int i = 0; i < CELLS / 4; ++i) {
-            const uint4 v = dp[i];
-            diag[4 * i] = __builtin_amdgcn_readfirstlane(v.x);
-            diag[4 * i + 1] = __builtin_amdgcn_readfirstlane(v.y);
-            diag[4 * i + 2] = __builtin_amdgcn_readfirstlane(v.z);
-            diag[4 * i + 3] = __builtin_amdgcn_readfirstlane(v.w);
-        }
+        for (int i = 0; i < 8; ++i) diag[i] = d0[i], diag[8 + i] = d1[i], diag[16 + i] = d2[i];
     }
     internal_round<true>(s, diag, prm + 117);  // external round 4's constants ride in the last internal round
-    // external rounds 4..7
+    // external rounds 4..7: one copy of the S-boxes and of the layer's core for all four rounds; the loop is left from its middle in
+    // the last round, whose finish (live cells only) stands behind it
+    i64 t[4];
 #pragma unroll 1
-    for (int r = 0; r < RF_HALF; ++r) {
+    for (int r = 0;; ++r) {
         sbox7s_n<CELLS / 2>(s);  // two halves: 12 independent chains are enough ILP and halve the live 64-bit temporaries
         sbox7s_n<CELLS / 2>(s + CELLS / 2);
-        m_ext64s(s, y);
-        if (r < RF_HALF - 1) {
-            redc64s_all(y, prm + 117 + (r + 1) * CELLS, s);
-        } else {
-            red64ks_all<K1_END, K2_END, false>(y, 0u, s);
-#pragma unroll
-            for (int i = 0; i < CELLS; ++i) io[i] = canon(s[i]);  // canonical Montgomery words leave the permutation
-        }
+        m_ext64s_core(s, y, t);
+        asm volatile("" : "+s"(r));  // the counter stays a scalar: left alone it becomes a 64-bit byte offset in VGPRs, compared and read back per round
+        if (r == RF_HALF - 1) break;
+        m_ext64s_finish(y, t);
+        redc64s_all(y, prm + 117 + (r + 1) * CELLS, s);
     }
+    m_ext64s_finish<LO, HI>(y, t);
+    red64ks_all<K1_END, K2_END, false, LO, HI>(y, 0u, s);
+#pragma unroll
+    for (int i = LO; i < HI; ++i) io[i] = canon(s[i]);  // canonical Montgomery words leave the permutation
 }
 
 // Occupancy: the stage-wise order fixes the register pressure (the statements are volatile), so the stages are 12 cells wide
-// (3 four-cell groups in the linear layer): 108-120 VGPRs, four waves per SIMD without spills.  Five (96 VGPRs) spills.
+// (3 four-cell groups in the linear layer): 100-120 VGPRs, four waves per SIMD without spills.  Five (96 VGPRs) spills.
 // hash_rows: lane = row.  matrix is column-major rows x cols.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void hash_rows_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ matrix,
                                                         const uint32_t* __restrict__ prm, uint32_t rows, uint32_t cols) {
@@ -144,17 +152,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
     for (int i = 0; i < CELLS; ++i) s[i] = 0u;
     const uint32_t* p = matrix + r;
+    // Two inlined permutations: the loop takes every block of 16 columns but the last and hands on the capacity only (cells 16..23:
+    // the rate is overwritten by the next block); the peeled one is the last block, full (cols a multiple of 16), padded with zeros, or
+    // empty (cols == 0: the digest of the zero state), and hands on the digest only.
     uint32_t c = 0;
-    for (; c + RATE <= cols; c += RATE) {
+    for (; c + RATE < cols; c += RATE) {
 #pragma unroll
         for (int i = 0; i < RATE; ++i) s[i] = p[(size_t)(c + i) * rows];
-        poseidon2_mix(s, prm);
+        poseidon2_mix<RATE, CELLS>(s, prm);
     }
-    if (c < cols || cols == 0) {
 #pragma unroll
-        for (int i = 0; i < RATE; ++i) s[i] = (c + i < cols) ? p[(size_t)(c + i) * rows] : 0u;
-        poseidon2_mix(s, prm);
-    }
+    for (int i = 0; i < RATE; ++i) s[i] = (c + i < cols) ? p[(size_t)(c + i) * rows] : 0u;
+    poseidon2_mix<0, 8>(s, prm);
     uint4* o = reinterpret_cast<uint4*>(out + (size_t)r * 8);
     o[0] = make_uint4(s[0], s[1], s[2], s[3]);
     o[1] = make_uint4(s[4], s[5], s[6], s[7]);
@@ -174,7 +183,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     s[12] = v3.x; s[13] = v3.y; s[14] = v3.z; s[15] = v3.w;
 #pragma unroll
     for (int k = 16; k < CELLS; ++k) s[k] = 0u;
-    poseidon2_mix(s, prm);
+    poseidon2_mix<0, 8>(s, prm);
     uint4* o = reinterpret_cast<uint4*>(io + ((size_t)output_size + i) * 8);
     o[0] = make_uint4(s[0], s[1], s[2], s[3]);
     o[1] = make_uint4(s[4], s[5], s[6], s[7]);
@@ -201,7 +210,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     s[12] = v3.x; s[13] = v3.y; s[14] = v3.z; s[15] = v3.w;
 #pragma unroll
     for (int k = 16; k < CELLS; ++k) s[k] = 0u;
-    poseidon2_mix(s, prm);
+    poseidon2_mix<0, 8>(s, prm);
     uint4* o = reinterpret_cast<uint4*>(out + (size_t)j * 8);
     o[0] = make_uint4(s[0], s[1], s[2], s[3]);
     o[1] = make_uint4(s[4], s[5], s[6], s[7]);
@@ -223,7 +232,7 @@ __device__ __forceinline__ void fold_pair(uint32_t* out8, const uint32_t* a8, co
     // (a scalar zero the compiler cannot see through, added to the pointer: the loads stay scalar loads of the same table)
     uint32_t z;
     asm volatile("s_mov_b32 %0, 0" : "=s"(z));
-    poseidon2_mix(s, prm + z);
+    poseidon2_mix<0, 8>(s, prm + z);
 #pragma unroll
     for (int k = 0; k < 8; ++k) out8[k] = s[k];
 }
@@ -278,7 +287,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         s[12] = v3.x; s[13] = v3.y; s[14] = v3.z; s[15] = v3.w;
 #pragma unroll
         for (int k = 16; k < CELLS; ++k) s[k] = 0u;
-        poseidon2_mix(s, prm);
+        poseidon2_mix<0, 8>(s, prm);
         uint4* o = reinterpret_cast<uint4*>(io + ((size_t)out_size + i) * 8);
         o[0] = make_uint4(s[0], s[1], s[2], s[3]);
         o[1] = make_uint4(s[4], s[5], s[6], s[7]);
@@ -296,7 +305,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             for (int k = 0; k < 16; ++k) s[k] = sh[tid * 16 + k];
 #pragma unroll
             for (int k = 16; k < CELLS; ++k) s[k] = 0u;
-            poseidon2_mix(s, prm);
+            poseidon2_mix<0, 8>(s, prm);
             uint4* o = reinterpret_cast<uint4*>(io + ((size_t)out_size + blockIdx.x * width + tid) * 8);
             o[0] = make_uint4(s[0], s[1], s[2], s[3]);
             o[1] = make_uint4(s[4], s[5], s[6], s[7]);

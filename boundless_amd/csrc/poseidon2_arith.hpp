@@ -313,13 +313,16 @@ BX_HD i32 red64ks(i64 y, uint32_t add) {
     if (HAS_ADD) acc = add_u32(acc, add);
     return sredc(smad_k((i32)(y >> 32), K2, acc));
 }
-// the 24 representation-changing reductions of a layer, stage-wise; only cell 0 may carry an addend
-template <uint32_t K1, uint32_t K2, bool HAS_ADD0>
+// the representation-changing reductions of a layer's cells [LO, HI) (default: all 24), stage-wise, at most 12 chains at a time;
+// only cell 0 may carry an addend.  Cells outside the range are neither read nor written.
+template <uint32_t K1, uint32_t K2, bool HAS_ADD0, int LO = 0, int HI = P2_CELLS>
 BX_HD void red64ks_all(const i64* y, uint32_t add0, i32* s) {
     static_assert(K1 < (1u << 29) && K2 < P, "correction constant too large for the accumulator bound");
-    constexpr int H = P2_CELLS / 2;
+    static_assert(0 <= LO && LO < HI && HI <= P2_CELLS && (!HAS_ADD0 || LO == 0), "live range");
+    constexpr int H = HI - LO < P2_CELLS / 2 ? HI - LO : P2_CELLS / 2;
+    static_assert((HI - LO) % H == 0, "live range: a whole number of stages");
 #pragma unroll
-    for (int h = 0; h < P2_CELLS; h += H) {
+    for (int h = LO; h < HI; h += H) {
         i64 acc[H];
 #pragma unroll
         for (int i = 0; i < H; ++i) {
@@ -337,7 +340,10 @@ BX_HD void red64ks_all(const i64* y, uint32_t add0, i32* s) {
 //   w_k = M4 * x_k,  T = sum_k w_k,  y_k = w_k + T.   M4 by the Poseidon2 addition chain (appendix B):
 //   t0 = a+b, t1 = c+d, t2 = 2b + t1, t3 = 2d + t0, t4 = 4 t1 + t3, t5 = 4 t0 + t2, w = [t3+t5, t5, t2+t4, t4].
 // Rows of the whole layer sum to <= 112, so |y| <= 112 * 2^31 = B_Y for any int32 cells.
-BX_HD void m_ext64s(const i32* s, i64* y) {
+// Two parts: m_ext64s_core leaves the blocks w_k in y and the column sums T in t (every output needs all of it), and
+// m_ext64s_finish<LO, HI> adds T to the cells [LO, HI) only: the last layer of a permutation whose caller reads 8 cells finishes
+// 8 (poseidon2_mix<LO, HI>), and the pinned reductions behind it run on those 8.
+BX_HD void m_ext64s_core(const i32* s, i64* y, i64* t) {
     // The 4-cell groups advance three at a time (see sredc_n): enough independent chains to keep dependent multiply-adds
     // apart, and half the live 64-bit temporaries of advancing all six together (131 -> <= 128 VGPRs = a fourth wave per SIMD).
 #pragma unroll
@@ -371,15 +377,23 @@ BX_HD void m_ext64s(const i32* s, i64* y) {
             y[4 * g + 3] = t4;
         }
     }
-    i64 t[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         t[j] = y[j];
 #pragma unroll
         for (int k = 4; k < P2_CELLS; k += 4) t[j] += y[k + j];
     }
+}
+template <int LO = 0, int HI = P2_CELLS>
+BX_HD void m_ext64s_finish(i64* y, const i64* t) {
+    static_assert(0 <= LO && LO < HI && HI <= P2_CELLS, "live range");
 #pragma unroll
-    for (int i = 0; i < P2_CELLS; ++i) y[i] += t[i & 3];
+    for (int i = LO; i < HI; ++i) y[i] += t[i & 3];
+}
+BX_HD void m_ext64s(const i32* s, i64* y) {
+    i64 t[4];
+    m_ext64s_core(s, y, t);
+    m_ext64s_finish(y, t);
 }
 
 // internal rounds: sum of the 24 cells (|sum| < 2^37) -> sum * 2^32 mod P with |result| <= B_SUMR.  The low word is taken
@@ -486,6 +500,10 @@ static_assert(T_PAIRI <= SREDC_MAX && ub(T_PAIRI) <= B_INT, "paired rounds: cell
 constexpr i32 K23R3 = (i32)cx_mul(23u, R3) - (cx_mul(23u, R3) > P / 2 ? (i32)P : 0);             // 23 R^3, centred
 
 // g -> hi(g) * R + lo(g) with lo unsigned: congruent to g mod P, one multiply-add
+// On the device each fold is preceded by one v_mov_b32 (seven per paired step): the multiply-add takes its addend only as a 64-bit
+// register pair, so the zero-extended low word {lo, 0} has to be built beside a register that holds zero.  The move is needed:
+// adding the pair of g itself would need the multiplier R - 2^32 = -2P, which is not a 32-bit word, and adding lo through a
+// second multiply-add (lo * 1 + hi * R) replaces a 2-cycle move by a 4-cycle multiply-class instruction.
 BX_HD i64 fold64(i64 g, int alt = 0) { return smad_k((i32)(g >> 32), MONT_ONE, (i64)(uint32_t)g, alt); }
 // the constants of the paired rounds from the Montgomery diagonal: E[24] then A[24]
 BX_HD void p2_pair_consts(const uint32_t* diag, i32* E, i32* A) {
@@ -624,8 +642,9 @@ BX_HD uint32_t canon(i32 v) {
 // version differs only in pinning the internal-round sum to v_mad_i64_i32 and in reading the diagonal and the paired rounds'
 // constants from its parameter table (where poseidon2_upload_params put what p2_pair_consts derives) into SGPRs.
 // prm: [0,96) | [96,117) | [117,213) round constants * p2_rc_scale(i) (canonical), [DIAG..DIAG+24) diagonal (Montgomery).
-// Input and output: canonical Montgomery words.
-template <int DIAG>
+// Input and output: canonical Montgomery words.  [LO, HI): the live cells, as in the device's poseidon2_mix<LO, HI>: the last layer is
+// finished, reduced, made canonical and stored for those cells only, and io[] keeps its input words everywhere else.
+template <int DIAG, int LO = 0, int HI = P2_CELLS>
 BX_HD void poseidon2_mix_bounded(uint32_t* io, const uint32_t* prm) {
     i32 s[P2_CELLS];
     i64 y[P2_CELLS];
@@ -651,13 +670,16 @@ BX_HD void poseidon2_mix_bounded(uint32_t* io, const uint32_t* prm) {
     for (int r = 0; r < 20; r += 2) internal_round_pair(s, pair_e, pair_a, prm + 97 + r);
     internal_round<true>(s, diag, prm + 117);
     for (int r = 0; r < 4; ++r) {
+        i64 t[4];
         sbox7s_n<P2_CELLS>(s);
-        m_ext64s(s, y);
+        m_ext64s_core(s, y, t);
         if (r < 3) {
+            m_ext64s_finish(y, t);
             redc64s_all(y, prm + 117 + (r + 1) * P2_CELLS, s);
         } else {
-            red64ks_all<K1_END, K2_END, false>(y, 0u, s);
-            for (int i = 0; i < P2_CELLS; ++i) io[i] = canon(s[i]);
+            m_ext64s_finish<LO, HI>(y, t);
+            red64ks_all<K1_END, K2_END, false, LO, HI>(y, 0u, s);
+            for (int i = LO; i < HI; ++i) io[i] = canon(s[i]);
         }
     }
 }
