@@ -3,67 +3,58 @@
 // Both knobs are compile-time for the shapes the prover is tuned for (every pool reference is then a fixed register);
 // <0, 0> is the run-time fallback for any other (T, G) and uses plain canonical arithmetic.
 //
-// The compile-time paths run on the signed, bounded Montgomery arithmetic of poseidon2_arith.hpp (sredc(t) = (t + mP)/2^32,
-// |result| <= ub(|t|) = |t|/2^32 + P/2 + 1, valid for |t| <= SREDC_MAX = 1.209 P^2; P^2/2^32 = 0.469 P) so that no product is
-// followed by a conditional subtraction and the sums stay unreduced in 64 bits.  Pool entries are centred, |c| <= P/2: by the walk of
-// circuit.hip once per word, where it enters the registers (DerivedRegs<true> and the centred entry of cons_sum, 4 of the 16 entries
-// are new per cell), by the canonical-pool signature once per call.
+// The arithmetic.  The compile-time paths run on the signed, bounded Montgomery arithmetic of poseidon2_arith.hpp (sredc(t) =
+// (t + mP)/2^32, |result| <= ub(|t|) = |t|/2^32 + P/2 + 1, valid for |t| <= SREDC_MAX = 1.209 P^2; P^2/2^32 = 0.469 P), so that no
+// product is followed by a conditional subtraction and the sums stay unreduced in 64 bits.  Pool entries are centred, |c| <= P/2: by
+// the walk of circuit.hip once per word, where it enters the registers (DerivedRegs<true> and the centred entry of cons_sum; 4 of the
+// 16 entries are new per cell), by the canonical-pool signature once per call.
 //
-// The sum of a cell's terms is carried in a CHAIN: one signed 64-bit accumulator that is never reduced on the way.  Where it would
-// leave 64 bits it is FOLDED instead, a = hi * 2^32 + lo  ->  hi * R + lo (fold_r; R = 2^32 mod P = 2^28 - 2, so the value is congruent
-// mod P and |result| <= |a|/16 + 2^32 + R): one v_mad_i64_i32 and the copy that puts lo beside a zero register, where the earlier form
-// reduced every group of three terms and multiplied it by R again (sredc + smad_r, three multiply-class instructions per group, and a
-// second and third level of the same on top).  The terms carry one factor R more than the result; the one sredc at the end, of the
-// folded chain, takes it away, so the canonical result is the same word as the earlier forms' and the plain loop's.
-//   a chain               A <= fold_ub(A) + (the terms of a segment), with the segment cut so that A < 2^63 = 2.2755 P^2
-//   the end               result = sredc(fold_r(A)):  fold_ub(A) <= 0.14 P^2 + 2^32 <= FINAL_MAX, so |result| < P and one conditional
-//                         add of P makes it canonical
-// Each step of a chain hides its result from the optimiser (smad_chain: an empty asm, no instruction).  In sight, hipcc reassociates
-// fold + t1 + ... + tn into fold + (t1 + ... + tn) and pays a 64-bit add per segment, and it rewrites two terms with a common factor,
-// p*q1 + p*q2, as p*(q1 + q2) with a 64-bit sum and an emulated 64 x 32-bit product.  Compiled, the walk's loop body per cell, VALU
-// instructions / multiplies (v_mad_i64_i32 + v_mul_lo_u32 + v_mad_u64_u32): witness_derive_kernel<64,4> 312 / 274 -> 262 / 211 (46
-// VGPRs, it was 54), eval_check_kernel<64,4> 367 / 298 -> 317 / 235 (70 VGPRs, it was 78: seven waves per SIMD); (48, 3) 211 / 134 ->
-// 144 / 102, (16, 3) 122 / 84 -> 110 / 69, (8, 2) 56 / 19 -> 49 / 11; no scratch, no v_mad_u64_u32 in any of them.
+// The chain.  The sum of a cell's terms is one signed 64-bit accumulator that is never reduced on the way.  Where it would leave 64
+// bits it is FOLDED, a = hi * 2^32 + lo  ->  hi * R + lo (fold_r; R = 2^32 mod P = 2^28 - 2, so the value is congruent mod P and
+// |result| <= |a|/16 + 2^32 + R): one v_mad_i64_i32 and the copy that puts lo beside a zero register.  The terms carry one factor R
+// more than the result; the one sredc at the end, of the folded chain, takes it away.
+//   a chain               A <= fold_ub(A) + (the terms of a segment), with the segments cut so that A < 2^63 = 2.2755 P^2
+//   the end               result = sredc(fold_r(A)):  fold_ub(A) <= 0.14 P^2 + 2^32 <= FINAL_MAX, so |result| < P, one conditional
+//                         add of P makes it canonical, and the word is the one the run-time loop gives
+// Two fences keep hipcc from undoing this where the multiply-adds are the compiler's (BX_PLAIN_MAD, as in circuit.hip).  smad_chain
+// hides each step's result behind an empty asm (no instruction): in sight, hipcc reassociates fold + t1 + ... + tn into
+// fold + (t1 + ... + tn) and pays a 64-bit add per segment, and it rewrites two terms with a common factor, p*q1 + p*q2, as
+// p*(q1 + q2) with a 64-bit sum and an emulated 64 x 32-bit product.  smad_r multiplies by an opaque signed copy of R, one per use:
+// with the constant in sight hipcc rewrites a sum of r_i * R as (sum of r_i) * R, again with an emulated product, and takes a single
+// r * R apart into shifts.  Compiled, the walk's loop body per cell, VALU instructions / multiplies (v_mad_i64_i32 + v_mul_lo_u32 +
+// v_mad_u64_u32): witness_derive_kernel<64,4> 262 / 211 (46 VGPRs), eval_check_kernel<64,4> 317 / 235 (70 VGPRs: seven waves per
+// SIMD); (48, 3) 144 / 102, (16, 3) 110 / 69, (8, 2) 49 / 11; no scratch, no v_mad_u64_u32 in any of them.
 //
-// G = 4, the pair form.  A term is a product of four pool entries and can be written as (pair) * (pair) in three ways; PairPlan picks
-// one split per term so that pairs recur (44 distinct pairs serve the 128 pair slots of T = 64, where the first-factor form below
-// computes 59 reduced products and 64 + 32 multiply-adds), and a term is then ONE multiply-add of two shared, reduced pair products.
-// The plan: each term's most popular split, four sweeps that re-choose a term's split where that frees a pair (51 pairs), then two
-// passes that drop a little-used pair outright by moving all its users to other splits (44).
+// G = 4, the pair form.  A term is a product of four pool entries and can be written as (pair) * (pair) in three ways.  PairPlan
+// picks one split per term so that pairs recur (44 distinct pairs serve the 128 pair slots of T = 64), and a term is ONE multiply-add
+// of two shared, reduced pair products.  PairPlan carries that choice and nothing else: per term, the ids of its two pairs.
+// FoldPlan is what cons_sum executes: it numbers the pairs by first use, orders the terms into segments (13 at T = 64) so that a
+// pair's uses lie close together (at most 11 pairs are computed and still awaited at any point of T = 64), and carries the bounds.
 //   a pair                p = sredc(c_a * c_b), computed at its first use:   |p| <= ub(P^2/4) = 0.617 P
 //   a term                p1 * p2:                                           |t| <= 0.381 P^2
 //   a segment             <= SEG = 5 terms added to the chain after its fold: A <= A/16 + 5 * 0.381 P^2, A <= 2.033 P^2 (six: 2.44 P^2)
 //                         no two terms of a segment share a pair (the rewrite above, should a step ever be left in sight)
-// FoldPlan orders PairPlan's terms into the segments (13 at T = 64) so that a pair's uses lie close together (at most 11 pairs are
-// computed and still awaited at any point of T = 64) and deals them over its chains; cons_sum runs one chain (FOLD_CHAINS), two or
-// three compile to two and four instructions more per cell.  PairPlan's own groups of GRP = 3 and its levels are still built (tests read
-// them) but no longer executed.  FoldPlan carries the bounds; cons_sum's static_asserts hold them, and the host build
-// (BX_CHECK_BOUNDS) asserts every pair, every fold's operand and result, every chain after every segment and the sredc operand.
 //
-// G = 3 and G >= 5, the factored form (ConsPlan; built for G = 4 too, where tests read it, but not executed there).
-// pool_idx(t, 0) runs through all 16 pool entries on every block of 16 terms, so entry a is the first factor of T/16 terms
-// and   sum_{t: idx(t,0)=a} pool[a] * (rest of t)  =  pool[a] * sum_t (rest of t):  the product with pool[a]
-// is taken once per group of terms instead of once per term (one reduced product, 3 multiply-class instructions, less per term;
-// one reduction and one multiply-add more per group).
+// G = 3 and G >= 5, the factored form.  pool_idx(t, 0) runs through all 16 pool entries on every block of 16 terms, so entry a is the
+// first factor of T/16 terms and   sum_{t: idx(t,0)=a} pool[a] * (rest of t)  =  pool[a] * sum_t (rest of t):  the product with
+// pool[a] is taken once per group of terms instead of once per term.  ConsPlan carries the inner groups (their shared first factor,
+// their terms), the fold segments they are dealt into, and the bound of every accumulator.
 //   the rest of a term    y = pool[idx(t,1)],  y <- sredc(y * pool[idx(t,f)]) for f = 2 .. G-2,  then  y * pool[idx(t,G-1)]:
-//                         G = 3: |y| <= 0.5 P, term <= 0.25 P^2;   G = 4: |y| <= 0.617 P, term <= 0.309 P^2;
-//                         G >= 5: |y| <= 0.65 P for any chain length, term <= 0.325 P^2
+//                         G = 3: |y| <= 0.5 P, term <= 0.25 P^2;   G >= 5: |y| <= 0.65 P for any chain length, term <= 0.325 P^2
 //   inner group           inner = sum of <= ISZ terms with the same first factor:  G = 3: ISZ = 4, |inner| <= 1.0 P^2;
-//                         G >= 4: ISZ = 3 (four terms would be 1.234 P^2 > SREDC_MAX).  An entry with more terms than ISZ gets
-//                         several inner groups of balanced size (four terms at G = 4: 2 + 2, |inner| <= 0.617 P^2)
-//   its reduction         s = sredc(inner):   G = 3: |s| <= 0.97 P (4 terms), 0.85 P (3);   G = 4: 0.79 P (2 terms), 0.93 P (3)
-//   the chain             A = sum of s * pool[a] over the inner groups, folded in front of each of ConsPlan's fold segments: as few
-//                         segments as keep A < 2^63, the groups spread evenly over them, no pool entry twice in a segment
+//                         G >= 5: ISZ = 3 (four terms would leave SREDC_MAX).  An entry with more terms than ISZ gets several inner
+//                         groups of balanced size
+//   its reduction         s = sredc(inner):   G = 3: |s| <= 0.97 P (4 terms), 0.85 P (3)
+//   the chain             A = sum of s * pool[a] over the inner groups, folded in front of each fold segment: as few segments as
+//                         keep A < 2^63, the groups spread evenly over them, no pool entry twice in a segment
 //                         ((48, 3): 16 groups in 4 segments of 4, A <= 1.82 P^2)
-// ConsPlan builds the groups at compile time from pool_idx and carries the bound of every accumulator with them; cons_sum's
-// static_asserts hold the plan to SREDC_MAX / FINAL_MAX, and the host build (BX_CHECK_BOUNDS) asserts every sredc operand, fold and
-// chain it meets.  Its outer groups and levels (obeg, lbeg, n2, max_outer, max_l2, max_l3) describe the earlier form and are kept for
-// the tests that read them.
 //
 // G <= 2 has no shared product to factor out: one chain of the terms x * c_last (<= 0.25 P^2 each) in their order, folded in front of
 // every eighth: A <= A/16 + 8 * 0.25 P^2, A <= 2.134 P^2.
-// In every form the last reduction is < P in magnitude, so one conditional add of P makes it canonical, and the result is
-// bit-identical to the plain form; tests compare both paths with the oracle.
+//
+// cons_sum's static_asserts hold every plan to SREDC_MAX / FINAL_MAX and the chains to their steady-state bound; the host build
+// (BX_CHECK_BOUNDS) asserts every pool entry, pair, sredc operand, fold operand and result, and every chain after every segment
+// (tests/cons_sum_check.cpp).  Tests compare every form with the run-time loop and with the oracle.
 #pragma once
 #include <type_traits>
 
@@ -105,17 +96,16 @@ struct ConsPlan {
     static constexpr int ISZ = (int)(SREDC_MAX / TERM) < 4 ? (int)(SREDC_MAX / TERM) : 4;  // terms per inner group, at most
     static_assert(ISZ >= 1 && ISZ * TERM <= SREDC_MAX, "cons_sum: inner group beyond sredc's range");
 
-    int nq = 0, no = 0, n2 = 0;            // inner groups, outer groups, second-level groups
+    int nq = 0;                            // inner groups
     int first[TT]{}, len[TT]{}, term[TT][ISZ]{};  // inner group q: its shared first factor, its terms
-    int obeg[TT + 1]{}, lbeg[TT + 1]{};    // outer group o = inner groups [obeg[o], obeg[o+1]), second-level group l likewise
-    i64 max_inner = 0, max_outer = 0, max_l2 = 0, max_l3 = 0;
-    // the fold form (fold_r below): ONE chain over all inner groups' s * pool[a], folded at the head of every segment but the first
+    i64 max_inner = 0;                     // the largest inner sum
+    // ONE chain over all inner groups' s * pool[a], folded (fold_r below) at the head of every segment but the first
     int nf = 0, fbeg[TT + 1]{};            // segment f = inner groups [fbeg[f], fbeg[f+1])
     i64 max_fchain = 0, max_ftotal = 0;    // the largest chain value, the folded chain that is reduced at the end
 
     constexpr ConsPlan() {
-        // inner groups in the order (g, a): the g-th group of every pool entry before any (g+1)-th, so that an outer group never
-        // holds two groups of one entry (hipcc would add their reductions first and emulate a 64 x 32-bit product for the sum)
+        // inner groups in the order (g, a): the g-th group of every pool entry before any (g+1)-th, so that neighbours in the chain
+        // are groups of different entries (cut_segments)
         for (int g = 0; g < TT; ++g)
             for (int a = 0; a < NPOOL; ++a) {
                 int members[TT]{}, n = 0;
@@ -131,39 +121,12 @@ struct ConsPlan {
                 if (sz * TERM > max_inner) max_inner = sz * TERM;
                 ++nq;
             }
-        i64 rb[TT + 1]{};                  // bound of each outer group's reduction
-        i64 cur = 0;
-        for (int q = 0; q < nq; ++q) {     // outer groups: consecutive inner groups while the sum stays reducible
-            const i64 add = ub(len[q] * TERM) * BC;
-            if (q > 0 && cur + add > SREDC_MAX) {
-                rb[no++] = ub(cur);
-                obeg[no] = q;
-                cur = 0;
-            }
-            cur += add;
-            if (cur > max_outer) max_outer = cur;
-        }
-        rb[no++] = ub(cur);
-        obeg[no] = nq;
-        cur = 0;
-        for (int o = 0; o < no; ++o) {     // second level: consecutive outer groups while the reduction stays below P
-            const i64 add = rb[o] * (i64)MONT_ONE;
-            if (o > 0 && cur + add > FINAL_MAX) {
-                max_l3 += ub(cur) * (i64)MONT_ONE;
-                lbeg[++n2] = o;
-                cur = 0;
-            }
-            cur += add;
-            if (cur > max_l2) max_l2 = cur;
-        }
-        max_l3 += ub(cur) * (i64)MONT_ONE;
-        lbeg[++n2] = no;
-        // segments of the fold form: as few as the bound allows (a cut wherever the next group would take the chain beyond 64 bits),
+        // the fold segments: as few as the bound allows (a cut wherever the next group would take the chain beyond 64 bits),
         // then the same number of segments with the groups spread evenly, which leaves the chain the most room
         const int fewest = cut_segments(nq);
         if (cut_segments((nq + fewest - 1) / fewest) > fewest) cut_segments(nq);
     }
-    // fills nf, fbeg and the fold form's bounds: at most `cap` consecutive inner groups to a segment, fewer where the chain would leave
+    // fills nf, fbeg and the chain's bounds: at most `cap` consecutive inner groups to a segment, fewer where the chain would leave
     // 64 bits or a pool entry would come twice (hipcc would add the two reductions first and emulate a 64 x 32-bit product for the sum)
     constexpr int cut_segments(int cap) {
         i64 cur = 0;
@@ -188,25 +151,16 @@ struct ConsPlan {
 template <int TT, int GG>
 inline constexpr ConsPlan<TT, GG> cons_plan{};
 
-// The plan of the pair form (G = 4) for one T: which of its three splits into two pairs each term takes, the distinct pairs in
-// the order of their first use, and the terms in the order they are summed, cut into groups, with the bound of every accumulator.
+// The choice of the pair form (G = 4) for one T: which of its three splits into two pairs each term takes.
 template <int TT>
 struct PairPlan {
     static constexpr int NPOOL = (int)Circuit::POOL, NID = NPOOL * NPOOL;
     static constexpr i64 BC = (i64)(P / 2);                   // a centred pool entry
     static constexpr i64 PAIR = ub(BC * BC);                  // a reduced pair product
-    static constexpr i64 TERM = PAIR * PAIR;                  // one term of a group
-    static constexpr int GRP = (int)(SREDC_MAX / TERM);       // terms per group, at most
-    static_assert(GRP == 3 && GRP * TERM <= SREDC_MAX, "cons_sum: pair group beyond sredc's range");
+    static constexpr i64 TERM = PAIR * PAIR;                  // one term: a product of two pairs
     static constexpr int pair_id(unsigned a, unsigned b) { return a < b ? (int)(a * NPOOL + b) : (int)(b * NPOOL + a); }
 
-    int np = 0, ng = 0, n2 = 0;            // distinct pairs, groups, second-level groups
-    int pa[2 * TT]{}, pb[2 * TT]{};        // pair p = pool[pa[p]] * pool[pb[p]], numbered by first use
-    int seq[TT]{}, s1[TT]{}, s2[TT]{};     // slot s sums term seq[s] = pair s1[s] * pair s2[s]
-    int pbeg[TT + 1]{};                    // pairs [pbeg[s], pbeg[s+1]) are computed at slot s, their first use
-    int gbeg[TT + 1]{}, lbeg[TT + 1]{};    // group g = slots [gbeg[g], gbeg[g+1]), second-level group l = groups [lbeg[l], lbeg[l+1])
-    int max_live = 0;                      // most pairs computed and still to be used at any slot
-    i64 max_group = 0, max_l2 = 0, max_l3 = 0;
+    int pair[TT][2]{};                     // term t = pair pair[t][0] * pair pair[t][1], as pair_id; [0] holds the term's factor 0
 
     constexpr PairPlan() {
         // the three splits of every term: factor 0 with factor s+1, and the other two
@@ -282,32 +236,75 @@ struct PairPlan {
                     }
                 }
         }
-        // the order: the next term is the one that needs the fewest pairs not yet computed, then the one that uses the most pairs
-        // for the last time, so that a pair's uses lie close together.  No two terms of a group share a pair (hipcc would rewrite
-        // p*q1 + p*q2 as p*(q1 + q2) with a 64-bit sum and emulate a 64 x 32-bit product), so such terms go to neighbouring groups.
-        int num[NID]{}, live = 0, glen = 0, gp[2 * GRP]{};
-        bool placed[TT]{};
+        for (int t = 0; t < TT; ++t)
+            for (int k = 0; k < 2; ++k) pair[t][k] = sp[t][ch[t]][k];
+    }
+};
+template <int TT>
+inline constexpr PairPlan<TT> pair_plan{};
+
+// What cons_sum<TT, 4> executes: PairPlan's splits, the terms put into SEGMENTS of at most SEG on one chain, the pairs numbered by
+// first use.  The chain is a 64-bit accumulator that is never reduced on the way: before a segment adds its terms the chain is
+// folded, a -> hi(a) * R + lo(a) (fold_r), which is congruent mod P and sixteen times smaller.
+//   a term                |p1 * p2| <= TERM = 0.381 P^2                                    (2^63 = 2.2755 P^2)
+//   the chain             A <= fold_ub(A) + SEG * TERM = A/16 + 5 * 0.381 P^2:  A <= 2.033 P^2 < 2^63  (six terms: 2.44 P^2)
+//   the total             the folded chain <= 0.127 P^2 + 2^32 + R <= FINAL_MAX, so its reduction is < P
+// The order is greedy: the next term is the one that needs the fewest pairs not yet computed, then the one that uses the most pairs
+// for the last time, so that a pair's uses lie close together; candidates are taken by rising term index and only a strictly better
+// one replaces the choice.  No two terms of a segment share a pair (hipcc would rewrite p*q1 + p*q2 as p*(q1 + q2) with a 64-bit sum
+// and an emulated product).  One rule comes first: a pair with as many uses left as segments left goes into the current segment, or
+// its last users end up in short segments of their own (T = 64: 17 segments without the rule, the last four of one term; 13 with it).
+// One chain: segments dealt over two or three were tried and cost instructions, time or a wave (tools/experiments/README.md).
+template <int TT>
+struct FoldPlan {
+    static constexpr int SEG = 5, NPOOL = PairPlan<TT>::NPOOL, NID = PairPlan<TT>::NID;
+    static constexpr i64 TERM = PairPlan<TT>::TERM;
+    // the chain bound with every segment full, however many segments: fold_ub(A) <= A/16 + R + 2^32, so 16/15 of the rest holds
+    static constexpr i64 STEADY = (SEG * TERM + (i64)MONT_ONE + ((i64)1 << 32)) / 15 * 16 + 16;
+    static_assert(STEADY < INT64_MAX && fold_ub(STEADY) + SEG * TERM <= STEADY, "cons_sum: the chain bound is not invariant below 2^63");
+
+    int np = 0, ns = 0;                    // distinct pairs, segments
+    int pa[2 * TT]{}, pb[2 * TT]{};        // pair p = pool[pa[p]] * pool[pb[p]], numbered by first use
+    int seq[TT]{}, s1[TT]{}, s2[TT]{};     // slot s sums term seq[s] = pair s1[s] * pair s2[s]
+    int pbeg[TT + 1]{};                    // pairs [pbeg[s], pbeg[s+1]) are computed at slot s, their first use
+    int sbeg[TT + 1]{};                    // segment g = slots [sbeg[g], sbeg[g+1])
+    int max_live = 0;                      // most pairs computed and still to be used at any slot
+    i64 max_chain = 0, max_total = 0;      // the largest chain value, the folded chain that is reduced at the end
+
+    constexpr FoldPlan() {
+        const PairPlan<TT>& pp = pair_plan<TT>;
+        int ref[NID]{}, num[NID]{};        // by pair id: uses left, number (-1 until its first use)
+        for (int t = 0; t < TT; ++t) {
+            ++ref[pp.pair[t][0]];
+            ++ref[pp.pair[t][1]];
+        }
         for (int i = 0; i < NID; ++i) num[i] = -1;
+        int live = 0, glen = 0, gp[2 * SEG]{};
+        bool placed[TT]{};
         for (int slot = 0; slot < TT;) {
-            int best = -1, best_new = 3, best_last = -1;
-            if (glen < GRP)
+            int best = -1, best_new = 3, best_last = -1, best_due = 0;
+            const int segs_left = (TT - slot + glen + SEG - 1) / SEG;   // this segment and the full ones the other terms would fill
+            if (glen < SEG)
                 for (int t = 0; t < TT; ++t) {
                     if (placed[t]) continue;
-                    const int a = sp[t][ch[t]][0], b = sp[t][ch[t]][1];
+                    const int a = pp.pair[t][0], b = pp.pair[t][1];
                     bool clash = false;
                     for (int k = 0; k < 2 * glen; ++k) clash = clash || gp[k] == a || gp[k] == b;
                     if (clash) continue;
+                    // a pair with as many uses left as segments left must be used in every one of them, or segments get added at the end
+                    const int most = ref[a] > ref[b] ? ref[a] : ref[b], due = most >= segs_left ? most : 0;
                     const int fresh = (num[a] < 0) + (num[b] < 0 && b != a);
                     const int last = a == b ? (ref[a] == 2) : (ref[a] == 1) + (ref[b] == 1);
-                    if (fresh < best_new || (fresh == best_new && last > best_last)) best = t, best_new = fresh, best_last = last;
+                    if (due > best_due || (due == best_due && (fresh < best_new || (fresh == best_new && last > best_last))))
+                        best = t, best_new = fresh, best_last = last, best_due = due;
                 }
-            if (best < 0) {                // the group is full, or every term left shares a pair with it
-                gbeg[++ng] = slot;
+            if (best < 0) {                // the segment is full, or every term left shares a pair with it
+                sbeg[++ns] = slot;
                 glen = 0;
                 continue;
             }
-            const int a = sp[best][ch[best]][0], b = sp[best][ch[best]][1];
-            for (int k = 0; k < 2; ++k) {
+            const int a = pp.pair[best][0], b = pp.pair[best][1];
+            for (int k = 0; k < 2; ++k) {  // both new: the pair that holds the term's factor 0 gets the lower number
                 const int id = k ? b : a;
                 if (num[id] < 0) {
                     num[id] = np;
@@ -329,125 +326,17 @@ struct PairPlan {
             ++glen;
             pbeg[++slot] = np;
         }
-        gbeg[++ng] = TT;
-        i64 cur = 0;
-        for (int g = 0; g < ng; ++g) {     // second level: consecutive groups while the reduction stays below P
-            const i64 sum = (gbeg[g + 1] - gbeg[g]) * TERM, add = ub(sum) * (i64)MONT_ONE;
-            if (sum > max_group) max_group = sum;
-            if (g > 0 && cur + add > FINAL_MAX) {
-                max_l3 += ub(cur) * (i64)MONT_ONE;
-                lbeg[++n2] = g;
-                cur = 0;
-            }
-            cur += add;
-            if (cur > max_l2) max_l2 = cur;
-        }
-        max_l3 += ub(cur) * (i64)MONT_ONE;
-        lbeg[++n2] = ng;
-    }
-};
-template <int TT>
-inline constexpr PairPlan<TT> pair_plan{};
-
-// The order in which the pair form (G = 4) is executed: PairPlan's pairs and splits, its terms put into SEGMENTS of at most SEG and
-// the segments dealt round-robin over NCH chains.  A chain is one 64-bit accumulator that is never reduced on the way: before a
-// segment adds its terms the chain is folded, a -> hi(a) * R + lo(a) (fold_r), which is congruent mod P and sixteen times smaller.
-//   a term                |p1 * p2| <= TERM = 0.381 P^2                                    (2^63 = 2.2755 P^2)
-//   a chain               A <= fold_ub(A) + SEG * TERM = A/16 + 5 * 0.381 P^2:  A <= 2.033 P^2 < 2^63  (six terms: 2.44 P^2)
-//   the total             sum of the NCH folded chains <= NCH * (0.127 P^2 + 2^32 + R) <= FINAL_MAX, so its reduction is < P
-// The order is PairPlan's greedy one with SEG in the place of GRP: the next term is the one that needs the fewest pairs not yet
-// computed, then the one that uses the most pairs for the last time; no two terms of a segment share a pair (hipcc would rewrite
-// p*q1 + p*q2 as p*(q1 + q2) with a 64-bit sum and an emulated product).  One rule comes first: a pair with as many uses left as
-// segments left goes into the current segment, or its last users end up in short segments of their own (T = 64: 17 segments
-// without the rule, the last four of one term; 13 with it).  Pairs are numbered again, by first use in this order.
-template <int TT, int NCH_ = 1>
-struct FoldPlan {
-    static constexpr int SEG = 5, NCH = NCH_;
-    static constexpr i64 TERM = PairPlan<TT>::TERM;
-    // the chain bound with every segment full, however many segments: fold_ub(A) <= A/16 + R + 2^32, so 16/15 of the rest holds
-    static constexpr i64 STEADY = (SEG * TERM + (i64)MONT_ONE + ((i64)1 << 32)) / 15 * 16 + 16;
-    static_assert(NCH >= 1 && STEADY < INT64_MAX && fold_ub(STEADY) + SEG * TERM <= STEADY, "cons_sum: the chain bound is not invariant below 2^63");
-
-    int np = 0, ns = 0;                    // distinct pairs, segments
-    int pa[2 * TT]{}, pb[2 * TT]{};        // pair p = pool[pa[p]] * pool[pb[p]], numbered by first use
-    int seq[TT]{}, s1[TT]{}, s2[TT]{};     // slot s sums term seq[s] = pair s1[s] * pair s2[s]
-    int pbeg[TT + 1]{};                    // pairs [pbeg[s], pbeg[s+1]) are computed at slot s, their first use
-    int sbeg[TT + 1]{};                    // segment g = slots [sbeg[g], sbeg[g+1]), on chain g % NCH
-    int max_live = 0;                      // most pairs computed and still to be used at any slot
-    i64 max_chain = 0, max_total = 0;      // the largest chain value, the sum of the folded chains
-
-    constexpr FoldPlan() {
-        const PairPlan<TT>& pp = pair_plan<TT>;
-        int ta[TT]{}, tb[TT]{}, ref[2 * TT]{}, num[2 * TT]{};   // a term's two pairs in PairPlan's numbering, uses left, new number
-        for (int s = 0; s < TT; ++s) {
-            ta[pp.seq[s]] = pp.s1[s];
-            tb[pp.seq[s]] = pp.s2[s];
-            ++ref[pp.s1[s]];
-            ++ref[pp.s2[s]];
-        }
-        for (int i = 0; i < 2 * TT; ++i) num[i] = -1;
-        int live = 0, glen = 0, gp[2 * SEG]{};
-        bool placed[TT]{};
-        for (int slot = 0; slot < TT;) {
-            int best = -1, best_new = 3, best_last = -1, best_due = 0;
-            const int segs_left = (TT - slot + glen + SEG - 1) / SEG;   // this segment and the full ones the other terms would fill
-            if (glen < SEG)
-                for (int t = 0; t < TT; ++t) {
-                    if (placed[t]) continue;
-                    const int a = ta[t], b = tb[t];
-                    bool clash = false;
-                    for (int k = 0; k < 2 * glen; ++k) clash = clash || gp[k] == a || gp[k] == b;
-                    if (clash) continue;
-                    // a pair with as many uses left as segments left must be used in every one of them, or segments get added at the end
-                    const int most = ref[a] > ref[b] ? ref[a] : ref[b], due = most >= segs_left ? most : 0;
-                    const int fresh = (num[a] < 0) + (num[b] < 0 && b != a);
-                    const int last = a == b ? (ref[a] == 2) : (ref[a] == 1) + (ref[b] == 1);
-                    if (due > best_due || (due == best_due && (fresh < best_new || (fresh == best_new && last > best_last))))
-                        best = t, best_new = fresh, best_last = last, best_due = due;
-                }
-            if (best < 0) {                // the segment is full, or every term left shares a pair with it
-                sbeg[++ns] = slot;
-                glen = 0;
-                continue;
-            }
-            const int a = ta[best], b = tb[best];
-            for (int k = 0; k < 2; ++k) {
-                const int id = k ? b : a;
-                if (num[id] < 0) {
-                    num[id] = np;
-                    pa[np] = pp.pa[id];
-                    pb[np] = pp.pb[id];
-                    ++np;
-                    ++live;
-                }
-            }
-            if (live > max_live) max_live = live;
-            live -= (--ref[a] == 0);
-            live -= (--ref[b] == 0);
-            placed[best] = true;
-            seq[slot] = best;
-            s1[slot] = num[a];
-            s2[slot] = num[b];
-            gp[2 * glen] = a;
-            gp[2 * glen + 1] = b;
-            ++glen;
-            pbeg[++slot] = np;
-        }
         sbeg[++ns] = TT;
-        i64 chain[NCH]{};
-        for (int g = 0; g < ns; ++g) {     // chain g % NCH: folded (but for its first segment), then this segment's terms on top
-            i64& a = chain[g % NCH];
-            a = (g < NCH ? 0 : fold_ub(a)) + (sbeg[g + 1] - sbeg[g]) * TERM;
+        i64 a = 0;
+        for (int g = 0; g < ns; ++g) {     // the chain: folded (but for the first segment), then this segment's terms on top
+            a = (g == 0 ? 0 : fold_ub(a)) + (sbeg[g + 1] - sbeg[g]) * TERM;
             if (a > max_chain) max_chain = a;
         }
-        for (int c = 0; c < NCH && c < ns; ++c) max_total += fold_ub(chain[c]);
+        max_total = fold_ub(a);
     }
 };
-template <int TT, int NCH = 1>
-inline constexpr FoldPlan<TT, NCH> fold_plan{};
-constexpr int FOLD_CHAINS = 1;   // one chain: two compile to two instructions more per cell and measured slower, three lose a wave
 template <int TT>
-inline constexpr FoldPlan<TT, FOLD_CHAINS> cons_fold{};   // the plan cons_sum<TT, 4> executes
+inline constexpr FoldPlan<TT> fold_plan{};
 
 // r * R + c: the product inside fold_r, and a term of a G = 1 sum (the lone factor times the Montgomery one).  In a translation unit
 // that leaves its multiply-adds to the compiler (BX_PLAIN_MAD) the device build multiplies by an opaque copy of R, one per use: with the
@@ -497,32 +386,29 @@ BX_HD uint32_t cons_sum(const i32 (&pool)[Circuit::POOL], uint32_t /*T*/, uint32
 #pragma unroll
     for (unsigned i = 0; i < Circuit::POOL; ++i) BX_ASSERT_BOUND(pool[i] <= (i32)(P / 2) && pool[i] >= -(i32)(P / 2), "cons_sum: a pool entry that is not centred");
     if constexpr (GG == 4) {
-        using Plan = FoldPlan<TT, FOLD_CHAINS>;
-        constexpr int NCH = Plan::NCH < cons_fold<TT>.ns ? Plan::NCH : cons_fold<TT>.ns;
-        static_assert(cons_fold<TT>.max_chain <= Plan::STEADY, "cons_sum: a chain beyond its steady-state bound");
-        static_assert(cons_fold<TT>.max_total <= FINAL_MAX, "cons_sum: the folded chains beyond the last reduction's range");
+        static_assert(fold_plan<TT>.max_chain <= FoldPlan<TT>::STEADY, "cons_sum: the chain beyond its steady-state bound");
+        static_assert(fold_plan<TT>.max_total <= FINAL_MAX, "cons_sum: the folded chain beyond the last reduction's range");
         // every index below is a constant expression, so each pool entry and each pair product is a fixed register
-        i32 pr[cons_fold<TT>.np];
-        i64 chain[NCH];
-        static_for<0, cons_fold<TT>.ns>([&](auto gc) {
-            constexpr int g = decltype(gc)::value, c = g % Plan::NCH;
-            static_for<cons_fold<TT>.sbeg[g], cons_fold<TT>.sbeg[g + 1]>([&](auto sc) {
+        i32 pr[fold_plan<TT>.np];
+        i64 chain = 0;
+        static_for<0, fold_plan<TT>.ns>([&](auto gc) {
+            constexpr int g = decltype(gc)::value;
+            static_for<fold_plan<TT>.sbeg[g], fold_plan<TT>.sbeg[g + 1]>([&](auto sc) {
                 constexpr int s = decltype(sc)::value;
-                static_for<cons_fold<TT>.pbeg[s], cons_fold<TT>.pbeg[s + 1]>([&](auto pc) {
+                static_for<fold_plan<TT>.pbeg[s], fold_plan<TT>.pbeg[s + 1]>([&](auto pc) {
                     constexpr int p = decltype(pc)::value;
-                    pr[p] = sredc(smul(pool[cons_fold<TT>.pa[p]], pool[cons_fold<TT>.pb[p]], p), p);
+                    pr[p] = sredc(smul(pool[fold_plan<TT>.pa[p]], pool[fold_plan<TT>.pb[p]], p), p);
                     BX_ASSERT_BOUND(pr[p] <= PairPlan<TT>::PAIR && pr[p] >= -PairPlan<TT>::PAIR, "cons_sum pair");
                 });
-                // a segment's first term goes on top of the folded chain (the chain's first segment: on nothing), the others follow
-                if constexpr (s > cons_fold<TT>.sbeg[g]) chain[c] = smad_chain(pr[cons_fold<TT>.s1[s]], pr[cons_fold<TT>.s2[s]], chain[c], s);
-                else if constexpr (g >= Plan::NCH) chain[c] = smad_chain(pr[cons_fold<TT>.s1[s]], pr[cons_fold<TT>.s2[s]], fold_r(chain[c], g), s);
-                else chain[c] = smul(pr[cons_fold<TT>.s1[s]], pr[cons_fold<TT>.s2[s]], s);
+                // a segment's first term goes on top of the folded chain (the first segment: on nothing), the others follow
+                if constexpr (s > fold_plan<TT>.sbeg[g]) chain = smad_chain(pr[fold_plan<TT>.s1[s]], pr[fold_plan<TT>.s2[s]], chain, s);
+                else if constexpr (g > 0) chain = smad_chain(pr[fold_plan<TT>.s1[s]], pr[fold_plan<TT>.s2[s]], fold_r(chain, g), s);
+                else chain = smul(pr[fold_plan<TT>.s1[s]], pr[fold_plan<TT>.s2[s]], s);
             });
-            BX_ASSERT_BOUND(chain[c] <= cons_fold<TT>.max_chain && chain[c] >= -cons_fold<TT>.max_chain, "cons_sum chain");
+            BX_ASSERT_BOUND(chain <= fold_plan<TT>.max_chain && chain >= -fold_plan<TT>.max_chain, "cons_sum chain");
         });
-        i64 total = fold_r(chain[0], 0);
-        static_for<1, NCH>([&](auto cc) { total += fold_r(chain[decltype(cc)::value], decltype(cc)::value); });
-        BX_ASSERT_BOUND(total <= cons_fold<TT>.max_total && total >= -cons_fold<TT>.max_total, "cons_sum folded chains");
+        const i64 total = fold_r(chain, 0);
+        BX_ASSERT_BOUND(total <= fold_plan<TT>.max_total && total >= -fold_plan<TT>.max_total, "cons_sum folded chain");
         const i32 result = sredc(total, 0);   // takes away the terms' surplus factor R
         return (uint32_t)(result + (result < 0 ? (i32)P : 0));
     } else if constexpr (GG >= 3) {

@@ -1,10 +1,12 @@
-"""CPU: the fold form of the constraint sums of csrc/circuit_dev.hpp (a 64-bit chain per sum, folded hi * R + lo where the r·R
-reduction levels were, reduced once at the end), and what hipcc makes of the two kernels built on it.
+"""CPU: the constraint sums of csrc/circuit_dev.hpp (cons_sum<TT, GG>: a 64-bit chain per sum, folded hi * R + lo and reduced once at
+the end; pairs at G = 4, factored at G = 3 and G >= 5, term by term at G <= 2), and what hipcc makes of the two kernels built on them.
 
-  * tests/cons_fold_check.cpp, a stand-alone program: fold_r's identity and bound at the edges of 64 bits, the plans (FoldPlan: every
-    term once, no segment with a shared pair or beyond SEG terms, its bounds recomputed; ConsPlan's fold segments), cons_sum<TT, GG>
-    of every dispatched shape against the run-time term-by-term loop on all 2^16 sign patterns of +-P/2, the constant pools and 10^5
-    random ones, and the walk of 19 cells.  Built plainly, with every bound asserted (-DBX_CHECK_BOUNDS), and with the bounds under the
+  * tests/cons_sum_check.cpp, a stand-alone program: fold_r's identity and bound at the edges of 64 bits, the plans that run (FoldPlan
+    over PairPlan's splits: every term once, no segment with a shared pair or beyond SEG terms, its bounds recomputed; ConsPlan: every
+    term under its own first factor, its fold segments), cons_sum<TT, GG> through the centred entry and the canonical-pool signature
+    against the run-time term-by-term loop on all 2^16 sign patterns of +-P/2, the constant pools, edge words and random ones, and
+    the walk of 19 cells through centred registers against canonical ones.  Built plainly, with every bound asserted
+    (-DBX_CHECK_BOUNDS: each entering pool entry within P/2, each pair, sredc operand, fold and chain), and with the bounds under the
     address and undefined-behaviour sanitizers, where a chain that left 64 bits is a signed overflow.
   * csrc/circuit.hip compiled to gfx950 assembly (no GPU needed; skipped without hipcc), read with tools/isa_mix.py: the walk loops of
     witness_derive_kernel<64,4> and eval_check_kernel<64,4> against the counts of the commit before the fold form (312 VALU
@@ -29,16 +31,22 @@ MULTIPLIES = ("v_mad_i64", "v_mad_u64", "v_mul_lo", "v_mul_hi")
 
 @pytest.mark.parametrize("flags", [[], ["-DBX_CHECK_BOUNDS"], ["-DBX_CHECK_BOUNDS", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"]],
                          ids=["plain", "bounds", "bounds-asan-ubsan"])
-def test_fold_plans_and_fold_form_equal_the_term_by_term_sum(tmp_path, flags):
-    exe = str(tmp_path / "cons_fold_check")
+def test_plans_are_sound_and_every_form_equals_the_term_by_term_sum(tmp_path, flags):
+    exe = str(tmp_path / "cons_sum_check")
     csrc = os.path.join(ROOT, "boundless_amd", "csrc")
     r = subprocess.run(["g++", "-std=c++17", "-O2", *flags, f"-I{csrc}", f"-I{os.path.join(ROOT, 'include')}",
-                        os.path.join(ROOT, "tests", "cons_fold_check.cpp"), "-o", exe], capture_output=True, text=True)
+                        os.path.join(ROOT, "tests", "cons_sum_check.cpp"), "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert "cons_fold_check ok" in r.stdout
+    assert "cons_sum_check ok" in r.stdout
     print(r.stdout)
+    # the bound every static_assert downstream rests on is live: an entry one step outside [-P/2, P/2] is refused where bounds are asserted
+    r = subprocess.run([exe, "uncentred"], capture_output=True, text=True, timeout=60)
+    if "-DBX_CHECK_BOUNDS" in flags:
+        assert r.returncode != 0 and "a pool entry that is not centred" in r.stderr, (r.returncode, r.stdout, r.stderr)
+    else:
+        assert r.returncode == 0, r.stderr
 
 
 _BLOCK = re.compile(r"^(?:\.L(BB\d+_\d+):|; %bb\.\d+:)\s*(;.*)?$")
@@ -55,8 +63,8 @@ def _resources(asm_text, symbol):
 def _walk_loop(isa_mix, asm_text, symbol):
     """(issue classes, opcodes) of the walk over the derived columns: of the kernel's loops (the basic blocks hipcc annotates as a
     loop's header or as `in Loop: Header=` it) the one with the most signed multiply-adds.  The constraint sums are the only code of
-    these kernels that multiplies signed words; eval_check's accumulator loop, which holds more instructions than the walk since the
-    fold form (321), multiplies unsigned ones."""
+    these kernels that multiplies signed words; eval_check's accumulator loop, which holds more instructions than the walk (321),
+    multiplies unsigned ones."""
     at = asm_text.index("\n" + symbol + ":")
     cur, members = None, collections.defaultdict(list)
     for line in asm_text[at:asm_text.index("s_endpgm", at)].split("\n"):
