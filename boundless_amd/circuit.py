@@ -418,11 +418,14 @@ class ConsProgram:
         return CompiledConsProgram(lib, handle, self.n_globals)
 
 
-def _from_program(program, base, kernel=None):
-    """CircuitOps.from_program(program, base, kernel=None): the table whose taps, eval_check and constraints_at come from `program`
-    (a CompiledConsProgram) and everything else from `base` (a CircuitOps: from_object, lookup_circuit() or synthetic_circuit()).
+def _from_program(program, base, kernel=None, witness=None):
+    """CircuitOps.from_program(program, base, kernel=None, witness=None): the table whose taps, eval_check and constraints_at come from
+    `program` (a CompiledConsProgram) and everything else from `base` (a CircuitOps: from_object, lookup_circuit() or synthetic_circuit()).
     kernel: a code object generated from `program` (boundless_amd.consgen; a path or its bytes) that eval_check launches instead of
-    the interpreter; a prover's creation fails with attach_kernel's message if it is not this program's.  The result is used like any other table (HipProverServer(circuit=...), verify_seal(circuit=...)); it keeps program and base alive."""
+    the interpreter; a prover's creation fails with attach_kernel's message if it is not this program's.
+    witness: a CompiledWitnessProgram; `base`'s witgen then only has to place the free cells, the program derives the other data columns
+    on the device and its global cells become public words (bx_cons_circuit_set_witness).
+    The result is used like any other table (HipProverServer(circuit=...), verify_seal(circuit=...)); it keeps program, base and witness alive."""
     import weakref
 
     from .hal import HalError
@@ -439,10 +442,181 @@ def _from_program(program, base, kernel=None):
         if msg:
             lib.bx_cons_circuit_destroy(cc)
             raise HalError(msg.decode())
+    if witness is not None:
+        msg = _wit_lib().bx_cons_circuit_set_witness(cc, witness.handle)
+        if msg:
+            lib.bx_cons_circuit_destroy(cc)
+            raise HalError(msg.decode())
     ops = lib.bx_cons_circuit_ops(cc).contents
-    ops._keepalive = (program, base)
+    ops._keepalive = (program, base, witness)
     weakref.finalize(ops, lib.bx_cons_circuit_destroy, cc)
     return ops
+
+
+# ---- witness programs (include/bx_program.h, "Witness programs"): a circuit's derived data columns from one description ----
+OP_SET = 10  # BX_CONS_SET
+
+
+class WitGlobalCell(C.Structure):
+    _fields_ = [("global_", C.c_uint32), ("col", C.c_uint32), ("row", C.c_uint32)]
+
+
+class WitProgramDesc(C.Structure):
+    _fields_ = [("steps", C.POINTER(ConsStep)), ("n_steps", C.c_size_t), ("taps", C.POINTER(ConsTap)), ("n_taps", C.c_size_t),
+                ("cells", C.POINTER(WitGlobalCell)), ("n_cells", C.c_size_t)]
+
+
+class WitProgramInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("steps", "sets", "narrow", "instructions", "taps", "cells")]
+
+
+def _wit_lib():
+    lib = load_library()
+    if not getattr(lib, "_wit_bound", False):
+        u32p, vp = C.POINTER(C.c_uint32), C.c_void_p
+        lib.bx_wit_program_create.argtypes = [C.POINTER(WitProgramDesc), C.POINTER(vp)]
+        lib.bx_wit_program_destroy.argtypes = [vp]
+        lib.bx_wit_program_destroy.restype = None
+        lib.bx_wit_program_info_get.argtypes = [vp, C.POINTER(WitProgramInfo)]
+        lib.bx_wit_program_derives.argtypes = [vp, C.c_uint32]
+        lib.bx_wit_program_derives.restype = C.c_int
+        lib.bx_wit_program_run_host.argtypes = [vp, C.c_uint32, u32p, C.c_uint32, u32p, C.c_uint32]
+        lib.bx_wit_program_load.argtypes = [vp, vp, C.POINTER(vp)]
+        lib.bx_wit_program_unload.argtypes = [vp]
+        lib.bx_wit_program_run.argtypes = [vp, vp, C.c_uint32, BxBuf, C.c_uint32, BxBuf, C.c_uint32]
+        lib.bx_cons_circuit_set_witness.argtypes = [vp, vp]
+        for name in ("bx_wit_program_create", "bx_wit_program_info_get", "bx_wit_program_run_host", "bx_wit_program_load", "bx_wit_program_unload",
+                     "bx_wit_program_run", "bx_cons_circuit_set_witness"):
+            getattr(lib, name).restype = C.c_char_p
+        lib._wit_bound = True
+    return lib
+
+
+class CompiledWitnessProgram:
+    """A compiled witness program (bx_wit_program): host only until `load`ed on a HipHal."""
+
+    def __init__(self, lib, handle):
+        self.lib, self.handle = lib, handle
+
+    def info(self):
+        out = WitProgramInfo()
+        msg = self.lib.bx_wit_program_info_get(self.handle, C.byref(out))
+        assert not msg, msg
+        return {n: int(getattr(out, n)) for n, _ in WitProgramInfo._fields_}
+
+    def derives(self, col):
+        return bool(self.lib.bx_wit_program_derives(self.handle, int(col)))
+
+    def run_host(self, po2, code, w_code, data, w_data):
+        """bx_wit_program_run_host: code (w_code x N) and data (w_data x N) are C-contiguous uint32 numpy arrays of Montgomery words;
+        the derived columns of `data` are written in place.  A refusal raises HalError."""
+        import numpy as np
+
+        from .hal import HalError
+
+        for a, w in ((code, w_code), (data, w_data)):
+            assert a.dtype == np.uint32 and a.flags.c_contiguous and a.size == w << po2, "a group is a C-contiguous uint32 array of width x N words"
+        assert data.flags.writeable
+        u32p = C.POINTER(C.c_uint32)
+        msg = self.lib.bx_wit_program_run_host(self.handle, po2, code.ctypes.data_as(u32p), w_code, data.ctypes.data_as(u32p), w_data)
+        if msg:
+            raise HalError(msg.decode())
+
+    def load(self, hal):
+        dev = C.c_void_p()
+        hal._check(self.lib.bx_wit_program_load(hal.ctx, self.handle, C.byref(dev)))
+        return LoadedWitnessProgram(self, hal, dev)
+
+    def close(self):
+        if self.handle:
+            self.lib.bx_wit_program_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LoadedWitnessProgram:
+    """A witness program on a ctx (bx_wit_program_dev); hal.wit_program_run runs it."""
+
+    def __init__(self, program, hal, dev):
+        self.program, self.hal, self.dev = program, hal, dev
+
+    def run(self, po2, code, w_code, data, w_data):
+        self.hal.wit_program_run(self, po2, code, w_code, data, w_data)
+
+    def unload(self):
+        if self.dev:
+            dev, self.dev = self.dev, None
+            self.hal._check(self.program.lib.bx_wit_program_unload(dev))
+
+
+class WitnessProgram:
+    """Builder of a witness program (include/bx_program.h, "Witness programs"): const / get / add / sub / mul append one step and
+    return the index of the fp var it made; set(col, var) stores a var into a data column, which makes that column derived.
+
+        w = WitnessProgram()
+        x = w.get(1, 0)
+        w.set(1, w.add(w.mul(x, x), w.get(0, 0)))
+        w.global_cell(0, 1, 0)  # public word 0 = data[1][0]
+        prog = w.compile()
+    """
+
+    def __init__(self):
+        self.steps, self.tap_list, self._tap_index, self.cells = [], [], {}, []
+        self.n_fp = 0
+
+    def _fp(self, op, a=0, b=0):
+        self.steps.append((op, a, b, 0, 0))
+        self.n_fp += 1
+        return self.n_fp - 1
+
+    def const(self, a):
+        return self._fp(OP_CONST, a)
+
+    def tap(self, group, col, back=0):
+        """index of (group, col, back) in the tap list (added on first use)"""
+        key = (int(group), int(col), int(back))
+        if key not in self._tap_index:
+            self._tap_index[key] = len(self.tap_list)
+            self.tap_list.append(key)
+        return self._tap_index[key]
+
+    def get(self, group, col, back=0):
+        return self._fp(OP_GET, self.tap(group, col, back))
+
+    def add(self, a, b):
+        return self._fp(OP_ADD, a, b)
+
+    def sub(self, a, b):
+        return self._fp(OP_SUB, a, b)
+
+    def mul(self, a, b):
+        return self._fp(OP_MUL, a, b)
+
+    def set(self, col, var):
+        self.steps.append((OP_SET, col, var, 0, 0))
+
+    def global_cell(self, index, col, row):
+        self.cells.append((int(index), int(col), int(row)))
+
+    def compile(self):
+        """-> CompiledWitnessProgram.  A refusal raises HalError."""
+        from .hal import HalError
+
+        lib = _wit_lib()
+        steps = (ConsStep * max(len(self.steps), 1))(*[ConsStep(*s) for s in self.steps])
+        taps = (ConsTap * max(len(self.tap_list), 1))(*[ConsTap(*t) for t in self.tap_list])
+        cells = (WitGlobalCell * max(len(self.cells), 1))(*[WitGlobalCell(*g) for g in self.cells])
+        desc = WitProgramDesc(steps, len(self.steps), taps, len(self.tap_list), cells, len(self.cells))
+        handle = C.c_void_p()
+        msg = lib.bx_wit_program_create(C.byref(desc), C.byref(handle))
+        if msg:
+            raise HalError(msg.decode())
+        return CompiledWitnessProgram(lib, handle)
 
 
 CircuitOps.from_program = staticmethod(_from_program)

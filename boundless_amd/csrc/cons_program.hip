@@ -1,6 +1,6 @@
 // cons_program.hip — device half of constraint programs (include/bx_program.h is the normative text; cons_program.hpp the compiled
 // form): a kernel that INTERPRETS a program's instruction stream over the 4N domain, and the bx_circuit_ops table made of a program
-// and a base table.
+// and a base table (whose witgen may be completed by a witness program: wit_program.hip).
 //   lanes     one lane per domain point, 256 per workgroup
 //   slots     the two slot files live in LDS, slot-major: narrow slot s is words [256 s, 256 s + 256) (1 KiB), wide slot s four such
 //             planes (4 KiB).  A wave's access to a slot is 64 consecutive dwords: conflict-free.  A lane only ever touches its own
@@ -277,6 +277,7 @@ struct bx_cons_circuit {
     const bx_circuit_ops* base = nullptr;
     const bx_cons_program* prog = nullptr;
     std::vector<uint8_t> kernel;  // bx_cons_circuit_set_kernel: the code object create attaches (empty = the interpreter)
+    const bx_wit_program* wit = nullptr;  // bx_cons_circuit_set_witness: witgen derives columns and global cells from it (NULL = base alone)
 };
 
 namespace bx {
@@ -284,6 +285,7 @@ namespace {
 struct ConsState {
     void* base_state = nullptr;
     bx_cons_program_dev* dev = nullptr;
+    bx_wit_program_dev* wit_dev = nullptr;
     bx_segment_params shape{};
     uint32_t n_globals = 0;
 };
@@ -303,6 +305,7 @@ void cc_destroy(void* u, void* state) {
     ConsState* st = (ConsState*)state;
     if (!st) return;
     (void)bx_cons_program_unload(st->dev);
+    (void)bx_wit_program_unload(st->wit_dev);
     if (st->base_state && b->destroy) b->destroy(b->user, st->base_state);
     delete st;
 }
@@ -320,23 +323,38 @@ const char* cc_create(void* u, bx_ctx* c, const bx_segment_params* shape, void**
         snprintf(c->err, sizeof c->err, "cons circuit: the program has %u globals, the base circuit %u", cc->prog->info.n_globals, ng);
         return c->err;
     }
+    if (const bx_wit_program* w = cc->wit) {  // the witness program against the shape, before anything is loaded
+        if (const char* e = wit_program_check_widths(w->max_col, w->max_set, "cons circuit: witness program", shape->w_code, shape->w_data)) return set_msg(c, e);
+        for (size_t k = 0; k < w->cells.size(); ++k) {
+            const bx_wit_global_cell& g = w->cells[k];
+            if (g.col >= shape->w_data)
+                snprintf(c->err, sizeof c->err, "cons circuit: witness program: global cell %zu reads data column %u, the shape has %u columns there", k, g.col, shape->w_data);
+            else if (g.row >> shape->po2)
+                snprintf(c->err, sizeof c->err, "cons circuit: witness program: global cell %zu reads row %u, the trace has %u rows", k, g.row, 1u << shape->po2);
+            else if (g.global >= ng)
+                snprintf(c->err, sizeof c->err, "cons circuit: witness program: global cell %zu names global %u, the base circuit has %u", k, g.global, ng);
+            else
+                continue;
+            return c->err;
+        }
+    }
     std::unique_ptr<ConsState> st(new (std::nothrow) ConsState());
     BX_REQUIRE(c, st != nullptr, "cons circuit: out of host memory");
     st->shape = *shape;
     st->n_globals = ng;
     BX_TRY(bx_cons_program_load(c, cc->prog, &st->dev));
+    const auto undo = [&](const char* e) {  // keeps the message, unloads what this create loaded
+        const char* kept = e == c->err ? e : set_msg(c, e);
+        (void)bx_cons_program_unload(st->dev);
+        (void)bx_wit_program_unload(st->wit_dev);
+        return kept;
+    };
     if (!cc->kernel.empty())
-        if (const char* e = bx_cons_program_attach_kernel(st->dev, cc->kernel.data(), cc->kernel.size())) {
-            const char* kept = e == c->err ? e : set_msg(c, e);
-            (void)bx_cons_program_unload(st->dev);
-            return kept;
-        }
+        if (const char* e = bx_cons_program_attach_kernel(st->dev, cc->kernel.data(), cc->kernel.size())) return undo(e);
+    if (cc->wit)
+        if (const char* e = bx_wit_program_load(c, cc->wit, &st->wit_dev)) return undo(e);
     if (b->create)
-        if (const char* e = b->create(b->user, c, shape, &st->base_state)) {
-            const char* kept = e == c->err ? e : set_msg(c, e);
-            (void)bx_cons_program_unload(st->dev);
-            return kept;
-        }
+        if (const char* e = b->create(b->user, c, shape, &st->base_state)) return undo(e);
     *state = st.release();
     return nullptr;
 }
@@ -349,7 +367,20 @@ const char* cc_witgen(void* u, void* state, bx_ctx* c, bx_buf code, bx_buf data,
                       uint32_t* globals_out) {
     const bx_circuit_ops* b = ((bx_cons_circuit*)u)->base;
     BX_REQUIRE(c, b->witgen != nullptr, "cons circuit: the base circuit has no witgen");
-    return b->witgen(b->user, ((ConsState*)state)->base_state, c, code, data, segment, segment_len, segment_dev, globals_out);
+    const ConsState* st = (const ConsState*)state;
+    if (const char* e = b->witgen(b->user, st->base_state, c, code, data, segment, segment_len, segment_dev, globals_out)) return e;
+    if (!st->wit_dev) return nullptr;
+    // the base has placed the free cells: derive the rest, then take the public words that are cells of the trace
+    BX_TRY(bx_wit_program_run(c, st->wit_dev, st->shape.po2, code, st->shape.w_code, data, st->shape.w_data));
+    const std::vector<bx_wit_global_cell>& cells = ((bx_cons_circuit*)u)->wit->cells;
+    if (cells.empty()) return nullptr;
+    const uint32_t* landed[BX_MAX_GLOBALS];
+    size_t used = 0;
+    for (size_t k = 0; k < cells.size(); ++k)  // create has checked column, row and index against the shape
+        BX_TRY(d2h_batch_add(c, &used, bx_buf{(uint32_t*)data.dptr + ((size_t)cells[k].col << st->shape.po2) + cells[k].row, 1}, 1, &landed[k]));
+    BX_TRY(d2h_batch_wait(c));
+    for (size_t k = 0; k < cells.size(); ++k) globals_out[cells[k].global] = *landed[k];
+    return nullptr;
 }
 const char* cc_accumulate(void* u, void* state, bx_ctx* c, bx_buf accum, const uint32_t mix[4]) {
     const bx_circuit_ops* b = ((bx_cons_circuit*)u)->base;
@@ -408,6 +439,11 @@ extern "C" const char* bx_cons_circuit_set_kernel(bx_cons_circuit* cc, const voi
     return nullptr;
 } catch (...) {
     return "bx_cons_circuit_set_kernel: out of host memory";
+}
+extern "C" const char* bx_cons_circuit_set_witness(bx_cons_circuit* cc, const bx_wit_program* wit) {
+    if (!cc) return "bx_cons_circuit_set_witness: null argument";
+    cc->wit = wit;
+    return nullptr;
 }
 extern "C" const bx_circuit_ops* bx_cons_circuit_ops(bx_cons_circuit* cc) { return cc ? &cc->ops : nullptr; }
 extern "C" void bx_cons_circuit_destroy(bx_cons_circuit* cc) { delete cc; }

@@ -40,6 +40,8 @@ enum ConsOpcode : uint32_t {
     CP_EQZ_E,    // wide[dst] = wide[a] + pow[imm] * wide[b]                         (AND_EQZ, ext y)
     CP_COND_B,   // wide[dst] = wide[a] + (pow[imm] * wide[c]) * narrow[b]           (AND_COND, base cond)
     CP_COND_E,   // wide[dst] = wide[a] + (pow[imm] * wide[c]) * wide[b]             (AND_COND, ext cond)
+    CP_ST,       // data column imm = narrow[a]                                      (SET; witness programs only, and last: no
+                 //                                                                   existing stream or digest changes)
     CP_OPCODES
 };
 constexpr uint32_t CP_FETCH = 4;  // instructions per fetch of the kernel (8 dwords)
@@ -58,3 +60,23 @@ struct bx_cons_program {
     uint32_t ret_slot = 0;         // the wide slot that holds mix[ret].tot at the end
     uint32_t max_col[3] = {0, 0, 0};  // 1 + the largest tap column per group (0 = the group is not named)
 };
+
+// A compiled witness program ("Witness programs" of bx_program.h): the same two-word instructions, of the narrow opcodes CP_LD_B,
+// CP_TAP, CP_ADD_BB, CP_SUB_BB, CP_MUL_BB and CP_ST only.  Its `scal` table is the constants alone (imm of CP_LD_B indexes `consts`).
+struct bx_wit_program {
+    bx_wit_program_info info{};
+    std::vector<uint32_t> code;    // 2 words per instruction, padded to CP_FETCH instructions
+    std::vector<uint32_t> consts;  // Montgomery words
+    std::vector<bx_cons_tap> taps;
+    std::vector<uint32_t> sets;    // the derived data columns, in the order of their SETs
+    std::vector<bx_wit_global_cell> cells;
+    uint32_t max_col[2] = {0, 0};  // 1 + the largest tap column per group (0 = the group is not named)
+    uint32_t max_set = 0;          // 1 + the largest SET column
+};
+
+namespace bx {
+// cons_program_host.cpp: NULL, or the refusal (in the caller's thread-local buffer, led by `who`) of a tap column (max_col, per group)
+// or a SET column (max_set) that is not below its group's width: one text for bx_wit_program_run_host, bx_wit_program_run and the
+// composite table's create
+const char* wit_program_check_widths(const uint32_t max_col[2], uint32_t max_set, const char* who, uint32_t w_code, uint32_t w_data);
+}  // namespace bx

@@ -1,5 +1,6 @@
 // cons_program_host.cpp — host half of constraint programs (include/bx_program.h is the normative text): the compiler from a step list
-// to the instruction stream of cons_program.hpp, and the host executor of that stream over Fp4 (the verifier's constraints_at).
+// to the instruction stream of cons_program.hpp, and the host executor of that stream over Fp4 (the verifier's constraints_at); and
+// the same two for witness programs, which share the slot allocation and the instruction format (compile_wit, bx_wit_program_run_host).
 // No HIP: this translation unit compiles with plain g++ (tests/cons_program_check.cpp runs it under sanitizers).
 #include <stdarg.h>
 #include <stdio.h>
@@ -271,7 +272,167 @@ const char* compile(const bx_cons_program_desc* d, bx_cons_program* p) {
     return nullptr;
 }
 
+
+// ---- witness programs ("Witness programs" of bx_program.h): the same slot allocation and instruction format, one list of vars ----
+// An fp var is a value in a narrow slot, or — a GET of a derived column after its SET — another name of the var that was stored.
+struct WitVar {
+    uint32_t root = 0;  // the var that holds the value (itself unless forwarded)
+    uint32_t slot = 0, last_use = 0;
+};
+
+const char* compile_wit(const bx_wit_program_desc* d, bx_wit_program* p) {
+    if (d->n_steps > BX_CONS_MAX_STEPS) return refuse("wit_program: %zu steps, more than BX_CONS_MAX_STEPS = %d", d->n_steps, BX_CONS_MAX_STEPS);
+    if (d->n_taps > BX_CONS_MAX_TAPS) return refuse("wit_program: %zu taps, more than BX_CONS_MAX_TAPS = %d", d->n_taps, BX_CONS_MAX_TAPS);
+    if (d->n_cells > BX_MAX_GLOBALS) return refuse("wit_program: %zu global cells, more than BX_MAX_GLOBALS = %d", d->n_cells, BX_MAX_GLOBALS);
+    if ((d->n_steps && !d->steps) || (d->n_taps && !d->taps) || (d->n_cells && !d->cells)) return refuse("wit_program: null step, tap or cell list");
+
+    for (size_t t = 0; t < d->n_taps; ++t) {
+        const bx_cons_tap& tp = d->taps[t];
+        if (tp.group == 2) return refuse("wit_program: tap %zu: tap group 2 (accum) does not exist when the witness is generated", t);
+        if (tp.group > 2) return refuse("wit_program: tap %zu: tap group %u out of range (0 code, 1 data)", t, tp.group);
+        if (tp.col > BX_CONS_MAX_COL) return refuse("wit_program: tap %zu: tap column %u out of range (at most %d)", t, tp.col, BX_CONS_MAX_COL);
+        if (tp.back > BX_CONS_MAX_BACK) return refuse("wit_program: tap %zu: tap back %u out of range (at most %d)", t, tp.back, BX_CONS_MAX_BACK);
+        p->max_col[tp.group] = std::max(p->max_col[tp.group], tp.col + 1);
+    }
+    p->taps.assign(d->taps, d->taps + d->n_taps);
+    std::set<uint32_t> named;
+    for (size_t k = 0; k < d->n_cells; ++k) {
+        const bx_wit_global_cell& g = d->cells[k];
+        if (g.global >= BX_MAX_GLOBALS) return refuse("wit_program: cell %zu: global index %u is not below BX_MAX_GLOBALS = %d", k, g.global, BX_MAX_GLOBALS);
+        if (g.col > BX_CONS_MAX_COL) return refuse("wit_program: cell %zu: data column %u out of range (at most %d)", k, g.col, BX_CONS_MAX_COL);
+        if (!named.insert(g.global).second) return refuse("wit_program: cell %zu: global index %u is named twice", k, g.global);
+    }
+    p->cells.assign(d->cells, d->cells + d->n_cells);
+
+    // ---- pass 0: which data columns are derived, and where ----
+    std::map<uint32_t, size_t> set_at;  // data column -> the step that SETs it
+    for (size_t i = 0; i < d->n_steps; ++i) {
+        const bx_cons_step& s = d->steps[i];
+        if (s.op != BX_CONS_SET) continue;
+        if (s.a > BX_CONS_MAX_COL) return refuse("wit_program: step %zu: SET column %u out of range (at most %d)", i, s.a, BX_CONS_MAX_COL);
+        const auto ins = set_at.emplace(s.a, i);
+        if (!ins.second) return refuse("wit_program: step %zu: data column %u is SET a second time (first at step %zu)", i, s.a, ins.first->second);
+        p->sets.push_back(s.a);
+        p->max_set = std::max(p->max_set, s.a + 1);
+    }
+
+    // ---- pass 1: validation, forwarding, last uses ----
+    std::vector<WitVar> fp;
+    const auto use_fp = [&](size_t i, const char* what, uint32_t v) -> const char* {
+        if (v >= fp.size()) return refuse("wit_program: step %zu: operand %s = %u refers to a later or missing fp var (%zu so far)", i, what, v, fp.size());
+        fp[fp[v].root].last_use = (uint32_t)i;
+        return nullptr;
+    };
+    static const char* const kForbidden[] = {nullptr, "CONST_EXT", nullptr, "GET_GLOBAL", nullptr, nullptr, nullptr, "TRUE", "AND_EQZ", "AND_COND"};
+    for (size_t i = 0; i < d->n_steps; ++i) {
+        const bx_cons_step& s = d->steps[i];
+        WitVar f;
+        f.root = (uint32_t)fp.size();
+        f.last_use = (uint32_t)i;
+        switch (s.op) {
+        case BX_CONS_CONST:
+            if (s.a >= P) return refuse("wit_program: step %zu: constant %u is not below P", i, s.a);
+            break;
+        case BX_CONS_GET: {
+            if (s.a >= d->n_taps) return refuse("wit_program: step %zu: tap index %u out of range (%zu taps)", i, s.a, d->n_taps);
+            const bx_cons_tap& tp = d->taps[s.a];
+            const auto it = tp.group == 1 ? set_at.find(tp.col) : set_at.end();
+            if (it == set_at.end()) break;  // a free cell: a memory read
+            if (tp.back > 0)
+                return refuse("wit_program: step %zu: GET of derived data column %u with back %u: another row's value may not have been written yet", i, tp.col, tp.back);
+            if (it->second > i) return refuse("wit_program: step %zu: GET of derived data column %u before its SET at step %zu", i, tp.col, it->second);
+            f.root = fp[d->steps[it->second].b].root;  // forwarded: the var that was stored (its SET has been validated: it is earlier)
+            fp[f.root].last_use = (uint32_t)i;
+            break;
+        }
+        case BX_CONS_ADD:
+        case BX_CONS_SUB:
+        case BX_CONS_MUL:
+            if (const char* m = use_fp(i, "a", s.a)) return m;
+            if (const char* m = use_fp(i, "b", s.b)) return m;
+            break;
+        case BX_CONS_SET:
+            if (const char* m = use_fp(i, "b", s.b)) return m;
+            continue;  // appends nothing
+        default:
+            if (s.op < sizeof kForbidden / sizeof kForbidden[0] && kForbidden[s.op])
+                return refuse("wit_program: step %zu: %s does not belong in a witness program (CONST, GET, ADD, SUB, MUL, SET)", i, kForbidden[s.op]);
+            return refuse("wit_program: step %zu: unknown op %u", i, s.op);
+        }
+        fp.push_back(f);
+    }
+
+    // ---- pass 2: slots by last use, and the stream ----
+    SlotFile narrow;
+    const auto emit = [&](uint32_t op, uint32_t dst, uint32_t a, uint32_t b, uint32_t imm) {
+        p->code.push_back(cp_w0(op, dst, a, b));
+        p->code.push_back(cp_w1(0, imm));
+    };
+    uint32_t fi = 0;
+    for (size_t i = 0; i < d->n_steps; ++i) {
+        const bx_cons_step& s = d->steps[i];
+        const uint32_t step = (uint32_t)i;
+        // an operand that dies here gives its slot back BEFORE the result takes one (dst may alias a source: executors read first)
+        const auto drop = [&](uint32_t v) {
+            WitVar& r = fp[fp[v].root];
+            if (r.last_use == step) {
+                narrow.give(r.slot);
+                r.last_use = NEVER - 1;  // an operand named twice is dropped once
+            }
+        };
+        if (s.op == BX_CONS_SET) {
+            emit(CP_ST, 0, fp[fp[s.b].root].slot, 0, s.a);
+            drop(s.b);
+            continue;
+        }
+        WitVar& f = fp[fi];
+        if (f.root != fi) {  // a forwarded GET compiles to nothing
+            drop(fi);  // ... and one that nothing reads afterwards ends the stored value's life
+            ++fi;
+            continue;
+        }
+        const bool unused = f.last_use == step;
+        uint32_t sa = 0, sb = 0;
+        if (s.op >= BX_CONS_ADD) {
+            sa = fp[fp[s.a].root].slot, sb = fp[fp[s.b].root].slot;
+            drop(s.a);
+            drop(s.b);
+        }
+        const uint32_t dst = f.slot = narrow.take();
+        switch (s.op) {
+        case BX_CONS_CONST:
+            emit(CP_LD_B, dst, 0, 0, (uint32_t)p->consts.size());
+            p->consts.push_back(fp_encode(s.a));
+            break;
+        case BX_CONS_GET: emit(CP_TAP, dst, 0, 0, s.a); break;
+        case BX_CONS_ADD: emit(CP_ADD_BB, dst, sa, sb, 0); break;
+        case BX_CONS_SUB: emit(CP_SUB_BB, dst, sa, sb, 0); break;
+        default: emit(CP_MUL_BB, dst, sa, sb, 0); break;
+        }
+        if (unused) narrow.give(dst);
+        ++fi;
+        if (narrow.peak > BX_CONS_MAX_NARROW)
+            return refuse("wit_program: step %zu: the program needs %u live values, the limit is %d (BX_CONS_MAX_NARROW)", i, narrow.peak, BX_CONS_MAX_NARROW);
+    }
+    p->info.steps = (uint32_t)d->n_steps;
+    p->info.sets = (uint32_t)p->sets.size();
+    p->info.narrow = narrow.top;
+    p->info.instructions = (uint32_t)(p->code.size() / 2);
+    p->info.taps = (uint32_t)d->n_taps;
+    p->info.cells = (uint32_t)d->n_cells;
+    while ((p->code.size() / 2) % CP_FETCH) emit(CP_NOP, 0, 0, 0, 0);
+    return nullptr;
+}
+
 }  // namespace
+
+const char* wit_program_check_widths(const uint32_t max_col[2], uint32_t max_set, const char* who, uint32_t w_code, uint32_t w_data) {
+    const uint32_t widths[2] = {w_code, w_data};
+    for (int g = 0; g < 2; ++g)
+        if (max_col[g] > widths[g]) return refuse("%s: the program taps column %u of group %d, which has %u columns", who, max_col[g] - 1, g, widths[g]);
+    if (max_set > w_data) return refuse("%s: the program sets data column %u, the data group has %u columns", who, max_set - 1, w_data);
+    return nullptr;
+}
 }  // namespace bx
 
 extern "C" const char* bx_cons_program_create(const bx_cons_program_desc* desc, bx_cons_program** out) try {
@@ -372,4 +533,64 @@ extern "C" const char* bx_cons_program_constraints_at(const bx_cons_program* pro
     return err;
 } catch (...) {
     return "bx_cons_program_constraints_at: out of host memory";
+}
+
+// ---- witness programs ----
+extern "C" const char* bx_wit_program_create(const bx_wit_program_desc* desc, bx_wit_program** out) try {
+    if (!desc || !out) return "bx_wit_program_create: null argument";
+    *out = nullptr;
+    bx_wit_program* p = new bx_wit_program();
+    if (const char* e = bx::compile_wit(desc, p)) {
+        delete p;
+        return e;
+    }
+    *out = p;
+    return nullptr;
+} catch (...) {
+    return "bx_wit_program_create: out of host memory";
+}
+
+extern "C" void bx_wit_program_destroy(bx_wit_program* prog) { delete prog; }
+
+extern "C" const char* bx_wit_program_info_get(const bx_wit_program* prog, bx_wit_program_info* out) {
+    if (!prog || !out) return "bx_wit_program_info_get: null argument";
+    *out = prog->info;
+    return nullptr;
+}
+
+extern "C" int bx_wit_program_derives(const bx_wit_program* prog, uint32_t col) {
+    return prog && std::find(prog->sets.begin(), prog->sets.end(), col) != prog->sets.end() ? 1 : 0;
+}
+
+extern "C" const char* bx_wit_program_run_host(const bx_wit_program* prog, uint32_t po2, const uint32_t* code, uint32_t w_code, uint32_t* data, uint32_t w_data) {
+    using namespace bx;
+    if (!prog || (w_code && !code) || (w_data && !data)) return "bx_wit_program_run_host: null argument";
+    if (po2 < 1 || po2 > 24) return "bx_wit_program_run_host: po2 must be in [1, 24]";
+    if (const char* e = wit_program_check_widths(prog->max_col, prog->max_set, "bx_wit_program_run_host", w_code, w_data)) return e;
+    const size_t n = (size_t)1 << po2;
+    // rows in any order: no row reads a word this run writes (derived cells are forwarded, never loaded)
+    for (size_t r = 0; r < n; ++r) {
+        uint32_t nar[BX_CONS_MAX_NARROW] = {};
+        for (size_t pc = 0; pc < prog->code.size(); pc += 2) {
+            const uint32_t w0 = prog->code[pc], w1 = prog->code[pc + 1];
+            const uint32_t op = w0 & 0xFFu, dst = (w0 >> 8) & 0xFFu, a = (w0 >> 16) & 0xFFu, b = w0 >> 24, imm = w1 >> 8;
+            if (dst >= BX_CONS_MAX_NARROW || a >= BX_CONS_MAX_NARROW || b >= BX_CONS_MAX_NARROW) return "bx_wit_program_run_host: corrupt instruction stream";
+            switch (op) {
+            case CP_NOP: break;
+            case CP_LD_B: nar[dst] = prog->consts[imm]; break;
+            case CP_TAP: {
+                const bx_cons_tap& t = prog->taps[imm];
+                const uint32_t* col = (t.group == 0 ? code : data) + (size_t)t.col * n;
+                nar[dst] = col[((uint32_t)r - t.back) & (uint32_t)(n - 1)];  // N divides 2^32: the wrapped difference reduces properly
+                break;
+            }
+            case CP_ADD_BB: nar[dst] = fp_add(nar[a], nar[b]); break;
+            case CP_SUB_BB: nar[dst] = fp_sub(nar[a], nar[b]); break;
+            case CP_MUL_BB: nar[dst] = fp_mul(nar[a], nar[b]); break;
+            case CP_ST: data[(size_t)imm * n + r] = nar[a]; break;
+            default: return "bx_wit_program_run_host: corrupt instruction stream";
+            }
+        }
+    }
+    return nullptr;
 }

@@ -1,0 +1,173 @@
+// wit_program.hip — device half of witness programs ("Witness programs" of include/bx_program.h is the normative text; cons_program.hpp
+// the compiled form): a kernel that INTERPRETS a program's instruction stream over the N trace rows and stores the derived data
+// columns.  It follows the choices of the constraint interpreter (cons_program.hip), for the same reasons:
+//   lanes     one lane per row, 256 per workgroup; lanes past N return at once
+//   slots     the narrow slot file is dynamic LDS, slot-major: slot s is words [256 s, 256 s + 256) (1 KiB).  A wave's access to a slot
+//             is 64 consecutive dwords: conflict-free.  Sized per program, at most 32 KiB, so several workgroups share a CU.
+//   barriers  none: a lane only ever touches its own column of the slot file, and no lane reads a word of `data` that this launch
+//             writes (a derived cell is forwarded by the compiler, never loaded), so the result does not depend on scheduling
+//   state     nothing per lane is held in an array indexed at run time (that would be scratch): a value is in LDS or in flight
+//   stream    wave-uniform: fetched through a const __restrict__ pointer indexed by the loop counter, CP_FETCH instructions per
+//             fetch, so that it comes through the scalar cache; decode and dispatch are scalar (readfirstlane makes it explicit)
+//   values    canonical throughout (fp_add / fp_sub / fp_mul): the host executor gives identical words
+//   memory    a tap is col[(r - back) & (N - 1)]; a store is data[col * N + r]: one coalesced 256-byte line per wave
+#include <map>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <set>
+#include <vector>
+
+#include "cons_program.hpp"
+#include "ctx.hpp"
+
+namespace bx {
+
+constexpr uint32_t WP_LANES = 256;
+
+// one instruction for one lane; everything decoded from w0 / w1 is wave-uniform.  `data` is read (free columns) and written (derived
+// ones) through the one pointer: never the same word, but the same buffer.
+__device__ __forceinline__ void wp_exec(uint32_t w0v, uint32_t w1v, uint32_t* nar, const uint32_t* __restrict__ code, uint32_t* data,
+                                        const uint2* __restrict__ taps, const uint32_t* __restrict__ consts, uint32_t n, uint32_t r) {
+    const uint32_t w0 = __builtin_amdgcn_readfirstlane(w0v), w1 = __builtin_amdgcn_readfirstlane(w1v);
+    const uint32_t op = w0 & 0xFFu, dst = (w0 >> 8) & 0xFFu, a = (w0 >> 16) & 0xFFu, b = w0 >> 24, imm = w1 >> 8;
+    switch (op) {
+    case CP_LD_B: nar[dst * WP_LANES] = consts[imm]; break;
+    case CP_TAP: {
+        const uint2 t = taps[imm];
+        const uint32_t back = t.y & 0x3FFFFFFFu;
+        const uint32_t* col = ((t.y >> 30) == 0 ? code : data) + (size_t)t.x * n;
+        nar[dst * WP_LANES] = col[(r - back) & (n - 1u)];  // N divides 2^32: the wrapped difference reduces properly
+        break;
+    }
+    case CP_ADD_BB: nar[dst * WP_LANES] = fp_add(nar[a * WP_LANES], nar[b * WP_LANES]); break;
+    case CP_SUB_BB: nar[dst * WP_LANES] = fp_sub(nar[a * WP_LANES], nar[b * WP_LANES]); break;
+    case CP_MUL_BB: nar[dst * WP_LANES] = fp_mul(nar[a * WP_LANES], nar[b * WP_LANES]); break;
+    case CP_ST: data[(size_t)imm * n + r] = nar[a * WP_LANES]; break;
+    default: break;  // CP_NOP, the padding
+    }
+}
+
+__global__ __launch_bounds__(256) void wit_program_kernel(uint32_t* data, const uint32_t* __restrict__ code, const uint4* __restrict__ stream,
+                                                          const uint2* __restrict__ taps, const uint32_t* __restrict__ consts, uint32_t n, uint32_t n_fetch) {
+    extern __shared__ uint32_t slots[];
+    const uint32_t r = blockIdx.x * WP_LANES + threadIdx.x;
+    if (r >= n) return;
+    uint32_t* const nar = slots + threadIdx.x;  // slot s: nar[256 s]
+
+    static_assert(CP_FETCH == 4, "the fetch below reads two uint4 = four instructions");
+    for (uint32_t f = 0; f < n_fetch; ++f) {
+        const uint4 lo = stream[2 * (size_t)f], hi = stream[2 * (size_t)f + 1];
+        wp_exec(lo.x, lo.y, nar, code, data, taps, consts, n, r);
+        wp_exec(lo.z, lo.w, nar, code, data, taps, consts, n, r);
+        wp_exec(hi.x, hi.y, nar, code, data, taps, consts, n, r);
+        wp_exec(hi.z, hi.w, nar, code, data, taps, consts, n, r);
+    }
+}
+
+}  // namespace bx
+
+// a witness program loaded on a ctx
+struct bx_wit_program_dev {
+    bx_ctx* ctx = nullptr;
+    bx_wit_program_info info{};
+    uint32_t n_fetch = 0, max_col[2] = {0, 0}, max_set = 0;
+    size_t lds = 0;
+    bx::DevBuf code, taps, consts;
+};
+
+namespace bx {
+namespace {
+std::mutex g_loaded_mu;
+std::map<bx_ctx*, std::set<bx_wit_program_dev*>> g_loaded;  // what bx_free still has to release
+}  // namespace
+
+void wit_programs_release(bx_ctx* c) {
+    std::set<bx_wit_program_dev*> ds;
+    {
+        std::lock_guard<std::mutex> g(g_loaded_mu);
+        auto it = g_loaded.find(c);
+        if (it == g_loaded.end()) return;
+        ds.swap(it->second);
+        g_loaded.erase(it);
+    }
+    for (bx_wit_program_dev* d : ds) delete d;  // the caller has drained the stream
+}
+}  // namespace bx
+
+extern "C" const char* bx_wit_program_load(bx_ctx* c, const bx_wit_program* prog, bx_wit_program_dev** out) try {
+    using namespace bx;
+    if (!c) return "bx_wit_program_load: null ctx";
+    BX_REQUIRE(c, prog && out, "bx_wit_program_load: null argument");
+    BX_ENTER(c);
+    *out = nullptr;
+    std::unique_ptr<bx_wit_program_dev> d(new bx_wit_program_dev());
+    d->ctx = c;
+    d->info = prog->info;
+    d->n_fetch = (uint32_t)(prog->code.size() / (2 * CP_FETCH));
+    for (int g = 0; g < 2; ++g) d->max_col[g] = prog->max_col[g];
+    d->max_set = prog->max_set;
+    // the compiler refuses what does not fit; a stream from anywhere else must not reach the kernel
+    BX_REQUIRE(c, prog->info.narrow <= BX_CONS_MAX_NARROW && prog->code.size() % (2 * CP_FETCH) == 0,
+               "bx_wit_program_load: the program's slot count is outside the device limit");
+    d->lds = (size_t)prog->info.narrow * WP_LANES * 4;  // at most 32 KiB: below what a kernel may use by default
+    BX_TRY(d->code.alloc(c, prog->code.size() ? prog->code.size() : 1));
+    BX_TRY(d->taps.alloc(c, prog->taps.empty() ? 2 : 2 * prog->taps.size()));
+    BX_TRY(d->consts.alloc(c, prog->consts.empty() ? 1 : prog->consts.size()));
+    std::vector<uint32_t> tapw(2 * prog->taps.size());
+    for (size_t t = 0; t < prog->taps.size(); ++t) {
+        tapw[2 * t] = prog->taps[t].col;
+        tapw[2 * t + 1] = prog->taps[t].back | prog->taps[t].group << 30;
+    }
+    if (!prog->code.empty()) BX_HIP(c, hipMemcpyAsync(d->code.b.dptr, prog->code.data(), prog->code.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (!tapw.empty()) BX_HIP(c, hipMemcpyAsync(d->taps.b.dptr, tapw.data(), tapw.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (!prog->consts.empty()) BX_HIP(c, hipMemcpyAsync(d->consts.b.dptr, prog->consts.data(), prog->consts.size() * 4, hipMemcpyHostToDevice, c->stream));
+    BX_HIP(c, stream_wait(c));  // the host vectors go away
+    {
+        std::lock_guard<std::mutex> g(g_loaded_mu);
+        g_loaded[c].insert(d.get());
+    }
+    *out = d.release();
+    return nullptr;
+} BX_ABI_CATCH(c, "bx_wit_program_load")
+
+extern "C" const char* bx_wit_program_unload(bx_wit_program_dev* dev) try {
+    using namespace bx;
+    if (!dev) return nullptr;
+    bx_ctx* c = nullptr;
+    {
+        // found by address, without reading *dev: a handle unloaded twice, or one whose ctx was freed, names freed memory
+        std::lock_guard<std::mutex> g(g_loaded_mu);
+        for (auto it = g_loaded.begin(); it != g_loaded.end() && !c; ++it)
+            if (it->second.erase(dev)) {
+                c = it->first;
+                if (it->second.empty()) g_loaded.erase(it);
+                break;
+            }
+    }
+    if (!c) return "bx_wit_program_unload: not a loaded program (unloaded twice, or its ctx was freed)";
+    (void)hipSetDevice(c->device);
+    (void)stream_wait(c);  // a launch may still read the tables
+    delete dev;
+    return nullptr;
+} BX_ABI_CATCH(nullptr, "bx_wit_program_unload")
+
+extern "C" const char* bx_wit_program_run(bx_ctx* c, bx_wit_program_dev* dev, uint32_t po2, bx_buf code, uint32_t w_code, bx_buf data, uint32_t w_data) try {
+    using namespace bx;
+    if (!c) return "bx_wit_program_run: null ctx";
+    BX_REQUIRE(c, dev != nullptr, "bx_wit_program_run: null argument");
+    BX_REQUIRE(c, dev->ctx == c, "bx_wit_program_run: the program was loaded on another ctx");
+    BX_REQUIRE(c, po2 >= 1 && po2 <= 24, "bx_wit_program_run: po2 must be in [1, 24]");
+    BX_ENTER(c);
+    const size_t n = (size_t)1 << po2;
+    BX_REQUIRE(c, code.len == n * w_code && data.len == n * w_data, "bx_wit_program_run: buffer size mismatch (groups N x width)");
+    if (const char* e = wit_program_check_widths(dev->max_col, dev->max_set, "bx_wit_program_run", w_code, w_data)) return set_msg(c, e);
+    BX_REQUIRE(c, !bufs_overlap(code, data), "bx_wit_program_run: code and data overlap");
+    // every tap is read once, every derived column written once
+    OpScope op(c, "wit_program_run", 4.0 * (double)n * ((double)dev->info.taps + (double)dev->info.sets));
+    hipLaunchKernelGGL(wit_program_kernel, dim3((unsigned)((n + WP_LANES - 1) / WP_LANES)), dim3(WP_LANES), dev->lds, c->stream, (uint32_t*)data.dptr,
+                       (const uint32_t*)code.dptr, (const uint4*)dev->code.b.dptr, (const uint2*)dev->taps.b.dptr, (const uint32_t*)dev->consts.b.dptr, (uint32_t)n,
+                       dev->n_fetch);
+    BX_LAUNCH_CHECK(c);
+    return nullptr;
+} BX_ABI_CATCH(c, "bx_wit_program_run")

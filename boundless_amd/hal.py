@@ -329,6 +329,11 @@ class HipHal:
         self._check(loaded.program.lib.bx_cons_program_eval_check(self.ctx, loaded.dev, po2, check.raw, code_eval.raw, widths[0], data_eval.raw, widths[1],
                                                                   accum_eval.raw, widths[2], pm, m, gp, len(globals_)))
 
+    def wit_program_run(self, loaded, po2, code, w_code, data, w_data):
+        """A witness program's run (include/bx_program.h: bx_wit_program_run): `loaded` = a program loaded on this hal
+        (boundless_amd.circuit.CompiledWitnessProgram.load); derives its columns of the N x w_data group `data` in place."""
+        self._check(loaded.program.lib.bx_wit_program_run(self.ctx, loaded.dev, po2, code.raw, w_code, data.raw, w_data))
+
     def batch_evaluate_any(self, coeffs, poly_count, which, xs, out):
         self._check(self.lib.bx_batch_evaluate_any(self.ctx, coeffs.raw, poly_count, which.raw, xs.raw, out.raw))
 

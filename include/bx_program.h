@@ -90,6 +90,51 @@
  *   launch       bx_cons_program_eval_check with a kernel attached: the same argument checks and the same table updates, then
  *                the attached kernel on the ctx's stream, ceil(4N / 256) workgroups of 256 lanes, no dynamic LDS, profiled as
  *                "cons_program_eval_check_gen".
+ *
+ * Witness programs (normative)
+ * ----------------------------
+ * The derived columns of a trace are the same kind of object as its constraints: "this data column equals this polynomial of other
+ * cells of the same or earlier rows".  A WITNESS PROGRAM is a step list that derives data columns from free ones.  It is evaluated
+ * once per trace row r, 0 <= r < N = 2^po2, over Fp only (the prover's K).  It has ONE list, of fp vars, and no mix vars.
+ *
+ *   step                appends  meaning
+ *   CONST a             fp       as above
+ *   GET a               fp       tap a of the program's tap list: (group 0 code / 1 data, col, back) = that column at row
+ *                                (r - back) mod N, cyclic
+ *   ADD a b, SUB a b, MUL a b    fp       as above
+ *   SET a b             nothing  data[a][r] = fp[b]                                                   (BX_CONS_SET = 10)
+ *
+ * A data column the program SETs is DERIVED; every other data column is FREE and must be filled before the program runs.
+ * Refused by name at bx_wit_program_create:
+ *   ops          CONST_EXT, GET_GLOBAL, TRUE, AND_EQZ and AND_COND do not belong in a witness program.  (Conversely BX_CONS_SET is
+ *                refused by bx_cons_program_create, as any unknown op is.)
+ *   accum        tap group 2: the accum group does not exist yet when the witness is generated.
+ *   one SET      a data column is SET at most once.
+ *   forwarding   a GET of a derived column with back == 0, placed AFTER that column's SET, is not a memory read: the compiler
+ *                forwards the fp var that was stored (it compiles to nothing).
+ *   other rows   a GET of a derived column with back > 0 is refused: lanes are rows, and the other row's value may not have been
+ *                written yet.
+ *   order        a GET of a derived column placed BEFORE its SET is refused.
+ *   limits       BX_CONS_MAX_STEPS, BX_CONS_MAX_TAPS, BX_CONS_MAX_BACK, BX_CONS_MAX_COL, constants < P, operands name earlier
+ *                vars, and BX_CONS_MAX_NARROW = 32 live values: a program over it is refused with the number it needs and the
+ *                limit.  There are no wide slots, no degree bound and no mix powers.
+ * The three rules forwarding / other rows / order mean that no lane ever reads a word another lane of the same run writes.  That
+ * is what makes the device kernel barrier-free and its result independent of how lanes, waves and workgroups are scheduled.
+ *
+ *   global cells an optional list of (global index, data column, row): after the program has run, public word `index` is
+ *                data[column][row] as it stands in the buffer, a Montgomery word.  Index < BX_MAX_GLOBALS, each index at most once
+ *                (refused at create).  `row` is checked against N when a prover is created: the list is the one shape-dependent
+ *                part of a description.
+ *   compiled     the instruction stream of a constraint program restricted to the narrow opcodes, plus one: a store of a
+ *                narrow slot to a data column.  bx_wit_program_run_host and the device kernel read the same stream and use the
+ *                same canonical arithmetic, so they give identical words.
+ *   device       bx_wit_program_run: one lane per row, 256 per workgroup, the slot file in LDS (1 KiB per slot, at most 32 KiB),
+ *                profiled as "wit_program_run".  A tap is col[(r - back) & (N - 1)]; a store is data[col * N + r].
+ *   composite    bx_cons_circuit_set_witness: the table's witgen calls base->witgen (which fills the free cells; whatever it
+ *                leaves in derived columns is overwritten), runs the program on `code` and `data`, and then reads the global
+ *                cells back with one blocking gather into globals_out, overriding the base's words at those indices.
+ * Out of scope: a generated kernel per witness program; free-cell generators, code groups and `accumulate` from data;
+ * recurrences (a column that depends on its own earlier rows is an accumulator: prefix_products / logup_accumulate).
  */
 #ifndef BX_PROGRAM_H
 #define BX_PROGRAM_H
@@ -119,7 +164,8 @@ enum bx_cons_op {
     BX_CONS_MUL = 6,
     BX_CONS_TRUE = 7,
     BX_CONS_AND_EQZ = 8,
-    BX_CONS_AND_COND = 9
+    BX_CONS_AND_COND = 9,
+    BX_CONS_SET = 10 /* witness programs only ("Witness programs" above) */
 };
 
 /* one step: `op` and its operands in the order of the table above (unused operands are ignored) */
@@ -210,6 +256,56 @@ const char* bx_cons_circuit_create(const bx_circuit_ops* base, const bx_cons_pro
 const char* bx_cons_circuit_set_kernel(bx_cons_circuit* cc, const void* image, size_t len);
 const bx_circuit_ops* bx_cons_circuit_ops(bx_cons_circuit* cc);
 void bx_cons_circuit_destroy(bx_cons_circuit* cc);
+
+/* ---- witness programs (the section of that name above) ---- */
+typedef struct bx_wit_global_cell {
+    uint32_t global, col, row; /* public word `global` = data[col][row] after the program has run */
+} bx_wit_global_cell;
+
+typedef struct bx_wit_program_desc {
+    const bx_cons_step* steps;
+    size_t n_steps;
+    const bx_cons_tap* taps;
+    size_t n_taps;
+    const bx_wit_global_cell* cells;
+    size_t n_cells;
+} bx_wit_program_desc;
+
+typedef struct bx_wit_program_info {
+    uint32_t steps;
+    uint32_t sets;         /* derived columns */
+    uint32_t narrow;       /* slots used */
+    uint32_t instructions; /* of the compiled stream: a forwarded GET has none */
+    uint32_t taps;
+    uint32_t cells;
+} bx_wit_program_info;
+
+typedef struct bx_wit_program bx_wit_program;         /* a compiled witness program (host) */
+typedef struct bx_wit_program_dev bx_wit_program_dev; /* ... loaded on a ctx */
+
+/* Validates and compiles `desc` (nothing of it is referenced afterwards); host only.  NULL = ok; a refusal's message lives in a
+ * thread-local buffer until the calling thread's next refusal. */
+const char* bx_wit_program_create(const bx_wit_program_desc* desc, bx_wit_program** out);
+void bx_wit_program_destroy(bx_wit_program* prog);
+const char* bx_wit_program_info_get(const bx_wit_program* prog, bx_wit_program_info* out);
+/* 1 if the program sets data column `col`, else 0 */
+int bx_wit_program_derives(const bx_wit_program* prog, uint32_t col);
+/* Host executor, the reference for the device kernel: the compiled stream over the N = 2^po2 rows of host arrays, column-major
+ * (code: w_code x N, data: w_data x N Montgomery words), `data` in place.  po2 in [1, 24].  Refused: a tap or SET column that is
+ * not below its group's width.  No mutable global state. */
+const char* bx_wit_program_run_host(const bx_wit_program* prog, uint32_t po2, const uint32_t* code, uint32_t w_code, uint32_t* data, uint32_t w_data);
+/* Uploads the stream, the constants and the tap descriptors once.  bx_free releases what is still loaded on its ctx. */
+const char* bx_wit_program_load(bx_ctx* ctx, const bx_wit_program* prog, bx_wit_program_dev** out);
+const char* bx_wit_program_unload(bx_wit_program_dev* dev);
+/* Derives the program's columns of `data` on the ctx's stream; does not block.  po2 in [1, 24], code.len == w_code * N,
+ * data.len == w_data * N.  Refused: lengths that do not match, a tap or SET column that is not below its group's width, `code`
+ * and `data` sharing a byte ("Operand overlap", bx_hal.h). */
+const char* bx_wit_program_run(bx_ctx* ctx, bx_wit_program_dev* dev, uint32_t po2, bx_buf code, uint32_t w_code, bx_buf data, uint32_t w_data);
+/* The table's witgen then runs `wit` after base->witgen and takes the global cells from the trace ("composite" above); its create
+ * loads the program on the ctx and refuses by name a SET or tap column beyond the shape's widths, a cell row >= N and a cell index
+ * >= the base's n_globals.  NULL goes back to forwarding witgen to `base` alone.  `wit` must outlive the table.  Set before a
+ * prover is created. */
+const char* bx_cons_circuit_set_witness(bx_cons_circuit* cc, const bx_wit_program* wit);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
