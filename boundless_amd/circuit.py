@@ -418,13 +418,16 @@ class ConsProgram:
         return CompiledConsProgram(lib, handle, self.n_globals)
 
 
-def _from_program(program, base, kernel=None, witness=None):
-    """CircuitOps.from_program(program, base, kernel=None, witness=None): the table whose taps, eval_check and constraints_at come from
+def _from_program(program, base, kernel=None, witness=None, witness_kernel=None):
+    """CircuitOps.from_program(program, base, kernel=None, witness=None, witness_kernel=None): the table whose taps, eval_check and constraints_at come from
     `program` (a CompiledConsProgram) and everything else from `base` (a CircuitOps: from_object, lookup_circuit() or synthetic_circuit()).
     kernel: a code object generated from `program` (boundless_amd.consgen; a path or its bytes) that eval_check launches instead of
     the interpreter; a prover's creation fails with attach_kernel's message if it is not this program's.
     witness: a CompiledWitnessProgram; `base`'s witgen then only has to place the free cells, the program derives the other data columns
     on the device and its global cells become public words (bx_cons_circuit_set_witness).
+    witness_kernel: a code object generated from `witness` (boundless_amd.consgen --witness; a path or its bytes) that witgen launches
+    instead of the interpreter; a prover's creation fails with attach_kernel's message if it is not that program's, and by name if
+    there is no `witness`.
     The result is used like any other table (HipProverServer(circuit=...), verify_seal(circuit=...)); it keeps program, base and witness alive."""
     import weakref
 
@@ -444,6 +447,12 @@ def _from_program(program, base, kernel=None, witness=None):
             raise HalError(msg.decode())
     if witness is not None:
         msg = _wit_lib().bx_cons_circuit_set_witness(cc, witness.handle)
+        if msg:
+            lib.bx_cons_circuit_destroy(cc)
+            raise HalError(msg.decode())
+    if witness_kernel is not None:
+        image = _kernel_image(witness_kernel)
+        msg = _wit_lib().bx_cons_circuit_set_witness_kernel(cc, image, len(image))
         if msg:
             lib.bx_cons_circuit_destroy(cc)
             raise HalError(msg.decode())
@@ -485,8 +494,16 @@ def _wit_lib():
         lib.bx_wit_program_unload.argtypes = [vp]
         lib.bx_wit_program_run.argtypes = [vp, vp, C.c_uint32, BxBuf, C.c_uint32, BxBuf, C.c_uint32]
         lib.bx_cons_circuit_set_witness.argtypes = [vp, vp]
+        lib.bx_wit_program_digest.argtypes = [vp, u32p]
+        lib.bx_wit_program_emit_hip.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        lib.bx_wit_program_attach_kernel.argtypes = [vp, C.c_char_p, C.c_size_t]
+        lib.bx_wit_program_detach_kernel.argtypes = [vp]
+        lib.bx_wit_program_kernel_attached.argtypes = [vp]
+        lib.bx_wit_program_kernel_attached.restype = C.c_int
+        lib.bx_cons_circuit_set_witness_kernel.argtypes = [vp, C.c_char_p, C.c_size_t]
         for name in ("bx_wit_program_create", "bx_wit_program_info_get", "bx_wit_program_run_host", "bx_wit_program_load", "bx_wit_program_unload",
-                     "bx_wit_program_run", "bx_cons_circuit_set_witness"):
+                     "bx_wit_program_run", "bx_cons_circuit_set_witness", "bx_wit_program_digest", "bx_wit_program_emit_hip",
+                     "bx_wit_program_attach_kernel", "bx_wit_program_detach_kernel", "bx_cons_circuit_set_witness_kernel"):
             getattr(lib, name).restype = C.c_char_p
         lib._wit_bound = True
     return lib
@@ -522,6 +539,30 @@ class CompiledWitnessProgram:
         if msg:
             raise HalError(msg.decode())
 
+    def digest(self):
+        """bx_wit_program_digest as 64 hex digits (the 32 bytes in order): what a generated kernel carries and attach compares"""
+        from .hal import HalError
+
+        out = (C.c_uint32 * 8)()
+        msg = self.lib.bx_wit_program_digest(self.handle, out)
+        if msg:
+            raise HalError(msg.decode())
+        return b"".join(int(w).to_bytes(4, "little") for w in out).hex()
+
+    def emit_hip(self):
+        """bx_wit_program_emit_hip: the generated translation unit as text (boundless_amd.consgen --witness compiles it)"""
+        from .hal import HalError
+
+        need = C.c_size_t(0)
+        msg = self.lib.bx_wit_program_emit_hip(self.handle, None, 0, C.byref(need))
+        if msg:
+            raise HalError(msg.decode())
+        buf = C.create_string_buffer(need.value)
+        msg = self.lib.bx_wit_program_emit_hip(self.handle, buf, need.value, C.byref(need))
+        if msg:
+            raise HalError(msg.decode())
+        return buf.value.decode()
+
     def load(self, hal):
         dev = C.c_void_p()
         hal._check(self.lib.bx_wit_program_load(hal.ctx, self.handle, C.byref(dev)))
@@ -552,6 +593,19 @@ class LoadedWitnessProgram:
         if self.dev:
             dev, self.dev = self.dev, None
             self.hal._check(self.program.lib.bx_wit_program_unload(dev))
+
+    def attach_kernel(self, path_or_bytes):
+        """bx_wit_program_attach_kernel: a code object built by boundless_amd.consgen --witness for THIS program (a path, or its
+        bytes); run then launches it instead of the interpreter.  A refusal raises HalError."""
+        image = _kernel_image(path_or_bytes)
+        self.hal._check(self.program.lib.bx_wit_program_attach_kernel(self.dev, image, len(image)))
+
+    def detach_kernel(self):
+        self.hal._check(self.program.lib.bx_wit_program_detach_kernel(self.dev))
+
+    @property
+    def kernel_attached(self):
+        return bool(self.dev) and bool(self.program.lib.bx_wit_program_kernel_attached(self.dev))
 
 
 class WitnessProgram:

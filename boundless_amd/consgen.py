@@ -1,6 +1,7 @@
 """Off-line compile step of generated constraint-program kernels (include/bx_program.h, "Generated kernels").
 
     python -m boundless_amd.consgen DESC.json -o OUT.hsaco [--emit-only]
+    python -m boundless_amd.consgen --witness DESC.json -o OUT.hsaco [--emit-only]
 
 A description is JSON: {"n_globals": g, "ret": r, "taps": [[group, col, back], ...], "steps": [[op, a, b, c, d], ...]} with the op
 numbers of enum bx_cons_op.  It is compiled by bx_cons_program_create, written as text by bx_cons_program_emit_hip and built with
@@ -8,6 +9,10 @@ hipcc, device code only, with the flags the library's own kernels are built with
 -ffp-contract=off, -I csrc).  Beside OUT.hsaco goes OUT.meta.json: the program's digest, the compiler's resource report for
 bx_cp_eval (-Rpass-analysis=kernel-resource-usage: VGPRs, SGPRs, scratch, occupancy), the program's steps and instructions, and the
 seconds hipcc took.  --emit-only writes the text to OUT instead and runs no compiler.
+
+--witness takes a WITNESS program ("Generated witness kernels"): {"taps": [[group, col, back], ...], "steps": [[op, a, b, c, d], ...],
+"cells": [[global, col, row], ...]}, compiled by bx_wit_program_create, written by bx_wit_program_emit_hip and built with the same
+flags; its meta holds the digest, the resource report for bx_wp_run, steps, sets, instructions, narrow slots, text bytes and seconds.
 
 This runs where hipcc is, before the code object is needed: the library loads what was built (bx_cons_program_attach_kernel) and
 compiles nothing at run time.
@@ -22,7 +27,7 @@ import tempfile
 import time
 
 from . import build as b
-from .circuit import ConsProgram
+from .circuit import ConsProgram, WitnessProgram
 
 
 def program_of(desc):
@@ -33,6 +38,16 @@ def program_of(desc):
     p.n_fp = sum(1 for s in p.steps if s[0] < 7)
     p.n_mix = len(p.steps) - p.n_fp
     return p.compile(ret=int(desc["ret"]))
+
+
+def witness_program_of(desc):
+    """-> CompiledWitnessProgram of a witness description (a dict as in the JSON above)"""
+    w = WitnessProgram()
+    w.steps = [tuple(int(v) for v in s) for s in desc["steps"]]
+    w.tap_list = [tuple(int(v) for v in t) for t in desc["taps"]]
+    w.cells = [tuple(int(v) for v in g) for g in desc.get("cells", [])]
+    w.n_fp = sum(1 for s in w.steps if s[0] != 10)  # every step but BX_CONS_SET appends an fp var
+    return w.compile()
 
 
 def _resource_usage(stderr, kernel="bx_cp_eval"):
@@ -49,8 +64,8 @@ def _resource_usage(stderr, kernel="bx_cp_eval"):
     return out
 
 
-def compile_text(text, out_path, extra_flags=()):
-    """hipcc over one generated translation unit -> (resource report of bx_cp_eval, seconds)"""
+def compile_text(text, out_path, extra_flags=(), kernel="bx_cp_eval"):
+    """hipcc over one generated translation unit -> (resource report of `kernel`, seconds)"""
     with tempfile.TemporaryDirectory() as tmp:
         src = os.path.join(tmp, "bx_cp_generated.hip")
         with open(src, "w") as f:
@@ -62,7 +77,7 @@ def compile_text(text, out_path, extra_flags=()):
         secs = time.time() - t0
     if r.returncode != 0:
         raise RuntimeError("hipcc failed for the generated kernel:\n" + r.stdout + r.stderr[-4000:])
-    return _resource_usage(r.stderr), secs
+    return _resource_usage(r.stderr, kernel), secs
 
 
 def compile_program(desc, out_path, emit_only=False):
@@ -92,6 +107,32 @@ def compile_program(desc, out_path, emit_only=False):
         prog.close()
 
 
+def compile_witness_program(desc, out_path, emit_only=False):
+    """compile_program for a WITNESS description: the code object of bx_wp_run and its meta; -> the meta dict"""
+    if not isinstance(desc, dict):
+        with open(desc) as f:
+            desc = json.load(f)
+    prog = witness_program_of(desc)
+    try:
+        text = prog.emit_hip()
+        if emit_only:
+            with open(out_path, "w") as f:
+                f.write(text)
+            return {"digest": prog.digest()}
+        usage, secs = compile_text(text, out_path, kernel="bx_wp_run")
+        info = prog.info()
+        meta = {"digest": prog.digest(), "vgprs": usage.get("VGPRs"), "agprs": usage.get("AGPRs"), "sgprs": usage.get("TotalSGPRs"),
+                "scratch_bytes": usage.get("ScratchSize [bytes/lane]"), "occupancy_waves_per_simd": usage.get("Occupancy [waves/SIMD]"),
+                "lds_bytes": usage.get("LDS Size [bytes/block]"), "steps": info["steps"], "sets": info["sets"], "instructions": info["instructions"],
+                "narrow": info["narrow"], "text_bytes": len(text), "hipcc_seconds": round(secs, 2)}
+        with open(meta_path(out_path), "w") as f:
+            json.dump(meta, f, indent=1)
+            f.write("\n")
+        return meta
+    finally:
+        prog.close()
+
+
 def meta_path(out_path):
     return (out_path[:-6] if out_path.endswith(".hsaco") else out_path) + ".meta.json"
 
@@ -101,8 +142,9 @@ def main(argv=None):
     ap.add_argument("desc")
     ap.add_argument("-o", "--out", required=True)
     ap.add_argument("--emit-only", action="store_true")
+    ap.add_argument("--witness", action="store_true", help="DESC is a witness program: build bx_wp_run")
     a = ap.parse_args(argv)
-    print(json.dumps(compile_program(a.desc, a.out, a.emit_only)))
+    print(json.dumps((compile_witness_program if a.witness else compile_program)(a.desc, a.out, a.emit_only)))
 
 
 if __name__ == "__main__":

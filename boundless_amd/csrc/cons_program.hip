@@ -278,6 +278,7 @@ struct bx_cons_circuit {
     const bx_cons_program* prog = nullptr;
     std::vector<uint8_t> kernel;  // bx_cons_circuit_set_kernel: the code object create attaches (empty = the interpreter)
     const bx_wit_program* wit = nullptr;  // bx_cons_circuit_set_witness: witgen derives columns and global cells from it (NULL = base alone)
+    std::vector<uint8_t> wit_kernel;  // bx_cons_circuit_set_witness_kernel: the code object create attaches to `wit` (empty = the interpreter)
 };
 
 namespace bx {
@@ -323,6 +324,7 @@ const char* cc_create(void* u, bx_ctx* c, const bx_segment_params* shape, void**
         snprintf(c->err, sizeof c->err, "cons circuit: the program has %u globals, the base circuit %u", cc->prog->info.n_globals, ng);
         return c->err;
     }
+    BX_REQUIRE(c, cc->wit || cc->wit_kernel.empty(), "cons circuit: a witness kernel is set but no witness program (bx_cons_circuit_set_witness)");
     if (const bx_wit_program* w = cc->wit) {  // the witness program against the shape, before anything is loaded
         if (const char* e = wit_program_check_widths(w->max_col, w->max_set, "cons circuit: witness program", shape->w_code, shape->w_data)) return set_msg(c, e);
         for (size_t k = 0; k < w->cells.size(); ++k) {
@@ -353,6 +355,8 @@ const char* cc_create(void* u, bx_ctx* c, const bx_segment_params* shape, void**
         if (const char* e = bx_cons_program_attach_kernel(st->dev, cc->kernel.data(), cc->kernel.size())) return undo(e);
     if (cc->wit)
         if (const char* e = bx_wit_program_load(c, cc->wit, &st->wit_dev)) return undo(e);
+    if (!cc->wit_kernel.empty())
+        if (const char* e = bx_wit_program_attach_kernel(st->wit_dev, cc->wit_kernel.data(), cc->wit_kernel.size())) return undo(e);
     if (b->create)
         if (const char* e = b->create(b->user, c, shape, &st->base_state)) return undo(e);
     *state = st.release();
@@ -444,6 +448,13 @@ extern "C" const char* bx_cons_circuit_set_witness(bx_cons_circuit* cc, const bx
     if (!cc) return "bx_cons_circuit_set_witness: null argument";
     cc->wit = wit;
     return nullptr;
+}
+extern "C" const char* bx_cons_circuit_set_witness_kernel(bx_cons_circuit* cc, const void* image, size_t len) try {
+    if (!cc || (len && !image)) return "bx_cons_circuit_set_witness_kernel: null argument";
+    cc->wit_kernel.assign((const uint8_t*)image, (const uint8_t*)image + len);
+    return nullptr;
+} catch (...) {
+    return "bx_cons_circuit_set_witness_kernel: out of host memory";
 }
 extern "C" const bx_circuit_ops* bx_cons_circuit_ops(bx_cons_circuit* cc) { return cc ? &cc->ops : nullptr; }
 extern "C" void bx_cons_circuit_destroy(bx_cons_circuit* cc) { delete cc; }

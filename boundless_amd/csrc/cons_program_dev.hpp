@@ -17,6 +17,10 @@ struct bx_cons_program_dev {
 };
 
 namespace bx {
+// cons_program_gen.cpp, shared with wit_program_gen.cpp: does `image` start with the ELF magic or "__CLANG_OFFLOAD_BUNDLE__"; and a
+// device symbol of `m` copied back (false = the module has no such symbol of that size)
+bool has_code_object_magic(const void* image, size_t len);
+bool read_symbol(bx_ctx* c, hipModule_t m, const char* name, uint32_t* out, size_t words);
 // cons_program_gen.cpp: unload what is attached (no-op when nothing is; the caller has drained the stream)
 void cons_gen_release(bx_cons_program_dev* dev);
 // ... and launch it: the caller (bx_cons_program_eval_check) has checked the arguments and written `scal` and `mixpows`

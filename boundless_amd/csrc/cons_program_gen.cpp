@@ -9,7 +9,6 @@
 #include "cons_program_gen.hpp"
 
 namespace bx {
-namespace {
 
 bool has_code_object_magic(const void* image, size_t len) {
     static const char elf[4] = {0x7f, 'E', 'L', 'F'};
@@ -31,8 +30,6 @@ bool read_symbol(bx_ctx* c, hipModule_t m, const char* name, uint32_t* out, size
     }
     return true;
 }
-
-}  // namespace
 
 void cons_gen_release(bx_cons_program_dev* dev) {
     if (dev->gen_module) (void)hipModuleUnload(dev->gen_module);

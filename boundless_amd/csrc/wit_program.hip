@@ -18,8 +18,7 @@
 #include <set>
 #include <vector>
 
-#include "cons_program.hpp"
-#include "ctx.hpp"
+#include "wit_program_dev.hpp"
 
 namespace bx {
 
@@ -67,14 +66,7 @@ __global__ __launch_bounds__(256) void wit_program_kernel(uint32_t* data, const 
 
 }  // namespace bx
 
-// a witness program loaded on a ctx
-struct bx_wit_program_dev {
-    bx_ctx* ctx = nullptr;
-    bx_wit_program_info info{};
-    uint32_t n_fetch = 0, max_col[2] = {0, 0}, max_set = 0;
-    size_t lds = 0;
-    bx::DevBuf code, taps, consts;
-};
+// a witness program loaded on a ctx: bx_wit_program_dev (wit_program_dev.hpp)
 
 namespace bx {
 namespace {
@@ -91,7 +83,10 @@ void wit_programs_release(bx_ctx* c) {
         ds.swap(it->second);
         g_loaded.erase(it);
     }
-    for (bx_wit_program_dev* d : ds) delete d;  // the caller has drained the stream
+    for (bx_wit_program_dev* d : ds) {  // the caller has drained the stream
+        wit_gen_release(d);
+        delete d;
+    }
 }
 }  // namespace bx
 
@@ -107,6 +102,7 @@ extern "C" const char* bx_wit_program_load(bx_ctx* c, const bx_wit_program* prog
     d->n_fetch = (uint32_t)(prog->code.size() / (2 * CP_FETCH));
     for (int g = 0; g < 2; ++g) d->max_col[g] = prog->max_col[g];
     d->max_set = prog->max_set;
+    BX_TRY(bx_wit_program_digest(prog, d->digest));  // what a generated kernel must have been built from (attach_kernel)
     // the compiler refuses what does not fit; a stream from anywhere else must not reach the kernel
     BX_REQUIRE(c, prog->info.narrow <= BX_CONS_MAX_NARROW && prog->code.size() % (2 * CP_FETCH) == 0,
                "bx_wit_program_load: the program's slot count is outside the device limit");
@@ -148,6 +144,7 @@ extern "C" const char* bx_wit_program_unload(bx_wit_program_dev* dev) try {
     if (!c) return "bx_wit_program_unload: not a loaded program (unloaded twice, or its ctx was freed)";
     (void)hipSetDevice(c->device);
     (void)stream_wait(c);  // a launch may still read the tables
+    wit_gen_release(dev);
     delete dev;
     return nullptr;
 } BX_ABI_CATCH(nullptr, "bx_wit_program_unload")
@@ -163,6 +160,7 @@ extern "C" const char* bx_wit_program_run(bx_ctx* c, bx_wit_program_dev* dev, ui
     BX_REQUIRE(c, code.len == n * w_code && data.len == n * w_data, "bx_wit_program_run: buffer size mismatch (groups N x width)");
     if (const char* e = wit_program_check_widths(dev->max_col, dev->max_set, "bx_wit_program_run", w_code, w_data)) return set_msg(c, e);
     BX_REQUIRE(c, !bufs_overlap(code, data), "bx_wit_program_run: code and data overlap");
+    if (dev->gen_fn) return wit_gen_launch(c, dev, po2, code, data);  // the generated kernel, when one is attached
     // every tap is read once, every derived column written once
     OpScope op(c, "wit_program_run", 4.0 * (double)n * ((double)dev->info.taps + (double)dev->info.sets));
     hipLaunchKernelGGL(wit_program_kernel, dim3((unsigned)((n + WP_LANES - 1) / WP_LANES)), dim3(WP_LANES), dev->lds, c->stream, (uint32_t*)data.dptr,

@@ -1,0 +1,24 @@
+// wit_program_dev.hpp — a witness program loaded on a ctx: what wit_program.hip (load, unload, the interpreting kernel's launch) and
+// wit_program_gen.cpp (a generated kernel attached to it) share.  Host only.
+#pragma once
+#include "cons_program.hpp"
+#include "ctx.hpp"
+
+struct bx_wit_program_dev {
+    bx_ctx* ctx = nullptr;
+    bx_wit_program_info info{};
+    uint32_t n_fetch = 0, max_col[2] = {0, 0}, max_set = 0;
+    size_t lds = 0;
+    bx::DevBuf code, taps, consts;
+    // the generated kernel (bx_wit_program_attach_kernel): none unless gen_fn is set
+    uint32_t digest[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // bx_wit_program_digest of the program this was loaded from
+    hipModule_t gen_module = nullptr;
+    hipFunction_t gen_fn = nullptr;
+};
+
+namespace bx {
+// wit_program_gen.cpp: unload what is attached (no-op when nothing is; the caller has drained the stream)
+void wit_gen_release(bx_wit_program_dev* dev);
+// ... and launch it: the caller (bx_wit_program_run) has checked the arguments
+const char* wit_gen_launch(bx_ctx* c, bx_wit_program_dev* dev, uint32_t po2, bx_buf code, bx_buf data);
+}  // namespace bx

@@ -133,8 +133,59 @@
  *   composite    bx_cons_circuit_set_witness: the table's witgen calls base->witgen (which fills the free cells; whatever it
  *                leaves in derived columns is overwritten), runs the program on `code` and `data`, and then reads the global
  *                cells back with one blocking gather into globals_out, overriding the base's words at those indices.
- * Out of scope: a generated kernel per witness program; free-cell generators, code groups and `accumulate` from data;
- * recurrences (a column that depends on its own earlier rows is an accumulator: prefix_products / logup_accumulate).
+ * Out of scope: free-cell generators, code groups and `accumulate` from data; recurrences (a column that depends on its own
+ * earlier rows is an accumulator: prefix_products / logup_accumulate).
+ *
+ * Generated witness kernels (normative)
+ * -------------------------------------
+ * As a constraint program, a witness program may be given a kernel GENERATED from its compiled stream, built off line and attached
+ * to the loaded program; without one the interpreter runs, exactly as before.  Nothing is compiled at run time.
+ *
+ *   digest       bx_wit_program_digest: SHA-256 over the bytes "bx-wit-program" and then, each as a little-endian 32-bit word, the
+ *                ABI number BX_WP_ABI (1), the length of the stream in words and the stream, the number of constants and the
+ *                constants (Montgomery words), the number of taps and (group, col, back) of every tap, the number of SETs and the
+ *                SET columns in the order of their SETs.  Eight little-endian words.  The global cells are NOT hashed: the kernel
+ *                does not depend on them (they are read back by the composite table after the run), so one code object serves a
+ *                program under any cell list.
+ *   text         bx_wit_program_emit_hip, with the contract of bx_cons_program_emit_hip: a NULL buffer asks for the size, a cap
+ *                below it is refused and nothing is written.  One translation unit, a pure function of the compiled program.
+ *                Straight-line code, one statement per instruction of the stream, in stream order; a narrow slot is a uint32_t
+ *                local, so the allocator's 32 slots bound the kernel's registers.
+ *                    CP_LD_B      a Montgomery-word literal: a witness program's `scal` table is its constants alone, so nothing is
+ *                                 read per call
+ *                    CP_TAP       at.code(col, r<back>) or at.data(col, r<back>), with r<back> = (r - back) & (N - 1) computed once
+ *                                 per distinct back of a function
+ *                    CP_ADD_BB, CP_SUB_BB, CP_MUL_BB   fp_add, fp_sub, fp_mul in the interpreter's operand order: canonical words,
+ *                                 so the kernel, the interpreter and bx_wit_program_run_host agree word for word
+ *                    CP_ST        at.store(col, n<a>)
+ *                Any other opcode (the padding CP_NOP is no statement), a slot >= info.narrow, a tap or constant index outside
+ *                the program's tables, a tap group other than 0 or 1, or a store to a column above the program's largest SET
+ *                column is refused as "corrupt instruction stream".  A program of more than 1024 statements is
+ *                written as segment functions that are not inlined, the narrow slots going through a struct in memory between
+ *                two segments, exactly as for a constraint program.  The text includes csrc/wit_program_gen.hpp, the frame (a
+ *                file of its own, so that no generated constraint text's include changes):
+ *                    struct bx_wp_gen_args { uint32_t* data; const uint32_t* code; uint32_t n, po2; }  and BX_WP_ABI
+ *                a device and a host accessor, and two wrappers.  Under hipcc:
+ *                    extern "C" __global__ __launch_bounds__(256) void bx_wp_run(bx_wp_gen_args)
+ *                one lane per row, lanes with r >= n return, no LDS, no barrier, with the device symbols bx_wp_abi (one word) and
+ *                bx_wp_digest (eight).  Under a host compiler: bx_wp_run_host(args) over all rows.  Column offsets are
+ *                (size_t)col << po2, wave-uniform.  No inline assembly, no per-lane array indexed at run time.
+ *   aliasing     the three rules forwarding / other rows / order guarantee that no word a launch writes is read by any lane of it.
+ *                The device accessor therefore reads taps through a const __restrict__ pointer and stores through a second
+ *                __restrict__ pointer to the same buffer: every modified word is accessed through the store pointer only
+ *                (the argument is written out in the frame).
+ *   build        python -m boundless_amd.consgen --witness DESC.json -o OUT.hsaco: hipcc, device only, the library's own flags.
+ *   attach       bx_wit_program_attach_kernel, in the order of bx_cons_program_attach_kernel.  Refused by name before anything
+ *                reaches HIP: an image that starts with neither the ELF magic nor "__CLANG_OFFLOAD_BUNDLE__".  Refused by name with
+ *                the module unloaded again: a code object without the kernel bx_wp_run, without bx_wp_abi or bx_wp_digest; another
+ *                ABI number; a digest that is not the loaded program's ("digest mismatch"); a second attach without a detach
+ *                ("already attached").  bx_wit_program_unload and bx_free unload what is still attached.
+ *   launch       bx_wit_program_run with a kernel attached: the same argument checks in the same order with the same messages,
+ *                then the attached kernel on the ctx's stream, ceil(N / 256) workgroups of 256 lanes, no dynamic LDS, not
+ *                blocking, profiled as "wit_program_run_gen".
+ *   composite    bx_cons_circuit_set_witness_kernel: the table copies the image; its create attaches it right after it has loaded
+ *                the witness program and fails with attach's message if it is refused.  A kernel without a witness program is
+ *                refused by name at create.
  */
 #ifndef BX_PROGRAM_H
 #define BX_PROGRAM_H
@@ -306,6 +357,21 @@ const char* bx_wit_program_run(bx_ctx* ctx, bx_wit_program_dev* dev, uint32_t po
  * >= the base's n_globals.  NULL goes back to forwarding witgen to `base` alone.  `wit` must outlive the table.  Set before a
  * prover is created. */
 const char* bx_cons_circuit_set_witness(bx_cons_circuit* cc, const bx_wit_program* wit);
+
+/* Generated witness kernels (see the section of that name above).  The digest of the compiled form, eight words. */
+const char* bx_wit_program_digest(const bx_wit_program* prog, uint32_t out[8]);
+/* The generated translation unit as NUL-terminated text, with the contract of bx_cons_program_emit_hip: *need receives its size
+ * with the NUL, buf == NULL only asks for that size, a cap below *need is refused and nothing is written. */
+const char* bx_wit_program_emit_hip(const bx_wit_program* prog, char* buf, size_t cap, size_t* need);
+/* Attaches the code object `image` (len bytes; not referenced afterwards) to a loaded witness program, whose run then launches it;
+ * detach drains the stream and unloads it, and is refused when nothing is attached.  kernel_attached: 1 or 0. */
+const char* bx_wit_program_attach_kernel(bx_wit_program_dev* dev, const void* image, size_t len);
+const char* bx_wit_program_detach_kernel(bx_wit_program_dev* dev);
+int bx_wit_program_kernel_attached(const bx_wit_program_dev* dev);
+/* Copies a generated witness kernel's code object into the table: its create attaches it right after loading the witness program,
+ * and fails with attach_kernel's message if it is refused, or by name if no witness program is set.  len == 0 goes back to the
+ * interpreter.  Set before a prover is created. */
+const char* bx_cons_circuit_set_witness_kernel(bx_cons_circuit* cc, const void* image, size_t len);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
