@@ -418,8 +418,8 @@ class ConsProgram:
         return CompiledConsProgram(lib, handle, self.n_globals)
 
 
-def _from_program(program, base, kernel=None, witness=None, witness_kernel=None):
-    """CircuitOps.from_program(program, base, kernel=None, witness=None, witness_kernel=None): the table whose taps, eval_check and constraints_at come from
+def _from_program(program, base, kernel=None, witness=None, witness_kernel=None, accumulate=None):
+    """CircuitOps.from_program(program, base, kernel=None, witness=None, witness_kernel=None, accumulate=None): the table whose taps, eval_check and constraints_at come from
     `program` (a CompiledConsProgram) and everything else from `base` (a CircuitOps: from_object, lookup_circuit() or synthetic_circuit()).
     kernel: a code object generated from `program` (boundless_amd.consgen; a path or its bytes) that eval_check launches instead of
     the interpreter; a prover's creation fails with attach_kernel's message if it is not this program's.
@@ -428,6 +428,9 @@ def _from_program(program, base, kernel=None, witness=None, witness_kernel=None)
     witness_kernel: a code object generated from `witness` (boundless_amd.consgen --witness; a path or its bytes) that witgen launches
     instead of the interpreter; a prover's creation fails with attach_kernel's message if it is not that program's, and by name if
     there is no `witness`.
+    accumulate: a CompiledAccumulateProgram; the table's accumulate then calls `base`'s (if it has one: it owns filler and the accum
+    columns at or above 4 S) and writes the program's running sums and products into accum columns [0, 4 S) on the device
+    (bx_cons_circuit_set_accumulate).  A prover's creation refuses by name a program that does not fit the shape.
     The result is used like any other table (HipProverServer(circuit=...), verify_seal(circuit=...)); it keeps program, base and witness alive."""
     import weakref
 
@@ -456,8 +459,13 @@ def _from_program(program, base, kernel=None, witness=None, witness_kernel=None)
         if msg:
             lib.bx_cons_circuit_destroy(cc)
             raise HalError(msg.decode())
+    if accumulate is not None:
+        msg = _acc_lib().bx_cons_circuit_set_accumulate(cc, accumulate.handle)
+        if msg:
+            lib.bx_cons_circuit_destroy(cc)
+            raise HalError(msg.decode())
     ops = lib.bx_cons_circuit_ops(cc).contents
-    ops._keepalive = (program, base, witness)
+    ops._keepalive = (program, base, witness, accumulate)
     weakref.finalize(ops, lib.bx_cons_circuit_destroy, cc)
     return ops
 
@@ -671,6 +679,149 @@ class WitnessProgram:
         if msg:
             raise HalError(msg.decode())
         return CompiledWitnessProgram(lib, handle)
+
+
+# ---- accumulate programs (include/bx_program.h, "Accumulate programs"): a circuit's running sums and products from one description ----
+OP_SUM, OP_PROD = 11, 12  # BX_CONS_SUM, BX_CONS_PROD
+ACC_MAX_SEQS = 1024  # BX_ACC_MAX_SEQS
+
+
+class AccProgramDesc(C.Structure):
+    _fields_ = [("steps", C.POINTER(ConsStep)), ("n_steps", C.c_size_t), ("taps", C.POINTER(ConsTap)), ("n_taps", C.c_size_t), ("n_globals", C.c_uint32)]
+
+
+class AccProgramInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("steps", "sequences", "sums", "instructions", "narrow", "wide", "taps", "kept", "n_globals")]
+
+
+def _acc_lib():
+    lib = load_library()
+    if not getattr(lib, "_acc_bound", False):
+        u32p, vp = C.POINTER(C.c_uint32), C.c_void_p
+        lib.bx_acc_program_create.argtypes = [C.POINTER(AccProgramDesc), C.POINTER(vp)]
+        lib.bx_acc_program_destroy.argtypes = [vp]
+        lib.bx_acc_program_destroy.restype = None
+        lib.bx_acc_program_info_get.argtypes = [vp, C.POINTER(AccProgramInfo)]
+        lib.bx_acc_program_kept.argtypes = [vp, C.c_uint32, u32p, u32p]
+        lib.bx_acc_program_run_host.argtypes = [vp, C.c_uint32, u32p, C.c_uint32, u32p, C.c_uint32, u32p, u32p, u32p, C.c_uint32]
+        lib.bx_acc_program_load.argtypes = [vp, vp, C.POINTER(vp)]
+        lib.bx_acc_program_unload.argtypes = [vp]
+        lib.bx_acc_program_keep.argtypes = [vp, vp, C.c_uint32, BxBuf, C.c_uint32, BxBuf, C.c_uint32, BxBuf]
+        lib.bx_acc_program_run.argtypes = [vp, vp, C.c_uint32, BxBuf, u32p, u32p, BxBuf, BxBuf, BxBuf, C.c_uint32]
+        lib.bx_cons_circuit_set_accumulate.argtypes = [vp, vp]
+        for name in ("bx_acc_program_create", "bx_acc_program_info_get", "bx_acc_program_kept", "bx_acc_program_run_host", "bx_acc_program_load",
+                     "bx_acc_program_unload", "bx_acc_program_keep", "bx_acc_program_run", "bx_cons_circuit_set_accumulate"):
+            getattr(lib, name).restype = C.c_char_p
+        lib._acc_bound = True
+    return lib
+
+
+class CompiledAccumulateProgram:
+    """A compiled accumulate program (bx_acc_program): host only until `load`ed on a HipHal."""
+
+    def __init__(self, lib, handle, n_globals):
+        self.lib, self.handle, self.n_globals = lib, handle, n_globals
+
+    def info(self):
+        out = AccProgramInfo()
+        msg = self.lib.bx_acc_program_info_get(self.handle, C.byref(out))
+        assert not msg, msg
+        return {n: int(getattr(out, n)) for n, _ in AccProgramInfo._fields_}
+
+    def kept(self):
+        """the kept columns as (group, col), in kept order: what `keep` copies and the taps read"""
+        out = []
+        g, c = C.c_uint32(), C.c_uint32()
+        for i in range(self.info()["kept"]):
+            msg = self.lib.bx_acc_program_kept(self.handle, i, C.byref(g), C.byref(c))
+            assert not msg, msg
+            out.append((int(g.value), int(c.value)))
+        return out
+
+    def run_host(self, po2, code, w_code, data, w_data, globals_, mix, accum, w_accum):
+        """bx_acc_program_run_host: code (w_code x N), data (w_data x N) and accum (w_accum x N) are C-contiguous uint32 numpy arrays of
+        Montgomery words; globals_ the program's public words, mix four words.  Columns [0, 4 S) of `accum` are written in place.  A
+        refusal raises HalError."""
+        import numpy as np
+
+        from .hal import HalError
+
+        for a, w in ((code, w_code), (data, w_data), (accum, w_accum)):
+            assert a.dtype == np.uint32 and a.flags.c_contiguous and a.size == w << po2, "a group is a C-contiguous uint32 array of width x N words"
+        assert accum.flags.writeable
+        g = list(globals_)
+        assert len(g) >= self.n_globals, "fewer globals than the program names"
+        u32p = C.POINTER(C.c_uint32)
+        msg = self.lib.bx_acc_program_run_host(self.handle, po2, code.ctypes.data_as(u32p), w_code, data.ctypes.data_as(u32p), w_data, _u32x(g), _u32x(mix, 4),
+                                               accum.ctypes.data_as(u32p), w_accum)
+        if msg:
+            raise HalError(msg.decode())
+
+    def load(self, hal):
+        dev = C.c_void_p()
+        hal._check(self.lib.bx_acc_program_load(hal.ctx, self.handle, C.byref(dev)))
+        return LoadedAccumulateProgram(self, hal, dev)
+
+    def close(self):
+        if self.handle:
+            self.lib.bx_acc_program_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LoadedAccumulateProgram:
+    """An accumulate program on a ctx (bx_acc_program_dev); hal.acc_program_keep / hal.acc_program_run run it."""
+
+    def __init__(self, program, hal, dev):
+        self.program, self.hal, self.dev = program, hal, dev
+
+    def keep(self, po2, code, w_code, data, w_data, kept):
+        self.hal.acc_program_keep(self, po2, code, w_code, data, w_data, kept)
+
+    def run(self, po2, kept, globals_, mix, run_ext, mults, accum, w_accum):
+        self.hal.acc_program_run(self, po2, kept, globals_, mix, run_ext, mults, accum, w_accum)
+
+    def unload(self):
+        if self.dev:
+            dev, self.dev = self.dev, None
+            self.hal._check(self.program.lib.bx_acc_program_unload(dev))
+
+
+class AccumulateProgram(ConsProgram):
+    """Builder of an accumulate program (include/bx_program.h, "Accumulate programs"): const / const_ext / get / global_ / mix / add / sub /
+    mul append one step and return the index of the fp var it made; sum_(s, m, d) makes sequence s the running sum of m / d, prod(s, a)
+    the running product of a.  Sums are numbered before products; sequence s is accum columns 4 s .. 4 s + 3.
+
+        p = AccumulateProgram()
+        alpha = p.add(p.const_ext(0, 1, 0, 0), p.mix(0))   # an ext value built from a mix component
+        p.sum_(0, p.const(1), p.sub(alpha, p.get(1, 0)))
+        prog = p.compile()
+    """
+
+    def sum_(self, s, m, d):
+        self.steps.append((OP_SUM, s, m, d, 0))
+
+    def prod(self, s, a):
+        self.steps.append((OP_PROD, s, a, 0, 0))
+
+    def compile(self):
+        """-> CompiledAccumulateProgram.  A refusal raises HalError."""
+        from .hal import HalError
+
+        lib = _acc_lib()
+        steps = (ConsStep * max(len(self.steps), 1))(*[ConsStep(*s) for s in self.steps])
+        taps = (ConsTap * max(len(self.tap_list), 1))(*[ConsTap(*t) for t in self.tap_list])
+        desc = AccProgramDesc(steps, len(self.steps), taps, len(self.tap_list), self.n_globals)
+        handle = C.c_void_p()
+        msg = lib.bx_acc_program_create(C.byref(desc), C.byref(handle))
+        if msg:
+            raise HalError(msg.decode())
+        return CompiledAccumulateProgram(lib, handle, self.n_globals)
 
 
 CircuitOps.from_program = staticmethod(_from_program)

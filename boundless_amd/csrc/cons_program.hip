@@ -1,6 +1,7 @@
 // cons_program.hip — device half of constraint programs (include/bx_program.h is the normative text; cons_program.hpp the compiled
 // form): a kernel that INTERPRETS a program's instruction stream over the 4N domain, and the bx_circuit_ops table made of a program
-// and a base table (whose witgen may be completed by a witness program: wit_program.hip).
+// and a base table (whose witgen may be completed by a witness program, wit_program.hip, and whose accumulate by an accumulate program,
+// acc_program.hip).  One instruction's opcode bodies are in cons_program_exec.hpp, shared with acc_program.hip.
 //   lanes     one lane per domain point, 256 per workgroup
 //   slots     the two slot files live in LDS, slot-major: narrow slot s is words [256 s, 256 s + 256) (1 KiB), wide slot s four such
 //             planes (4 KiB).  A wave's access to a slot is 64 consecutive dwords: conflict-free.  A lane only ever touches its own
@@ -13,6 +14,7 @@
 //             accumulators do not outlive one product, lazy_ext.hpp).  Nothing lazy is kept across instructions, so there is no bound
 //             to carry.  Mix powers come from the canonical half of mix_power_table.
 #define BX_PLAIN_MAD 1
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -22,90 +24,35 @@
 
 #include "circuit_common.hpp"
 #include "cons_program.hpp"
+#include "acc_program_dev.hpp"
 #include "cons_program_dev.hpp"
+#include "cons_program_exec.hpp"
 
 namespace bx {
-
-constexpr uint32_t CP_LANES = 256;
 
 struct ConsLaunch {
     uint32_t zinv[4];  // 1 / (3^N w_4^m - 1), m = row mod 4
     uint32_t dom, n_fetch, n_narrow, ret_slot;
 };
 
-__device__ __forceinline__ Fp4 cp_ldw(const uint32_t* wid, uint32_t s) {
-    const uint32_t* p = wid + 4 * s * CP_LANES;
-    return Fp4{{p[0], p[CP_LANES], p[2 * CP_LANES], p[3 * CP_LANES]}};
-}
-__device__ __forceinline__ void cp_stw(uint32_t* wid, uint32_t s, const Fp4& v) {
-    uint32_t* p = wid + 4 * s * CP_LANES;
-    p[0] = v.c[0];
-    p[CP_LANES] = v.c[1];
-    p[2 * CP_LANES] = v.c[2];
-    p[3 * CP_LANES] = v.c[3];
-}
-
-// one instruction for one lane; everything decoded from w0 / w1 is wave-uniform
-__device__ __forceinline__ void cp_exec(uint32_t w0v, uint32_t w1v, uint32_t* nar, uint32_t* wid, const uint32_t* __restrict__ ecode,
-                                        const uint32_t* __restrict__ edata, const uint32_t* __restrict__ eacc, const uint2* __restrict__ taps,
-                                        const uint32_t* __restrict__ scal, const uint32_t* __restrict__ mixpows, uint32_t dom, uint32_t i) {
-    const uint32_t w0 = __builtin_amdgcn_readfirstlane(w0v), w1 = __builtin_amdgcn_readfirstlane(w1v);
-    const uint32_t op = w0 & 0xFFu, dst = (w0 >> 8) & 0xFFu, a = (w0 >> 16) & 0xFFu, b = w0 >> 24, c = w1 & 0xFFu, imm = w1 >> 8;
-    switch (op) {
-    case CP_NOP: break;
-    case CP_LD_B: nar[dst * CP_LANES] = scal[imm]; break;
-    case CP_LD_E: {
-        const uint32_t* s = scal + imm;
-        cp_stw(wid, dst, Fp4{{s[0], s[1], s[2], s[3]}});
-        break;
-    }
-    case CP_TAP: {
+// what cp_exec (cons_program_exec.hpp) asks of this kernel: a tap is a column of the 4N evaluations at row i - 4 back
+struct ConsEnv {
+    static constexpr bool MIX = true;
+    const uint32_t* __restrict__ ecode;
+    const uint32_t* __restrict__ edata;
+    const uint32_t* __restrict__ eacc;
+    const uint2* __restrict__ taps;
+    const uint32_t* __restrict__ pows;
+    uint32_t dom, i;
+    __device__ __forceinline__ uint32_t tap(uint32_t imm) const {
         const uint2 t = taps[imm];
         const uint32_t g = t.y >> 30, back = t.y & 0x3FFFFFFFu;
         const uint32_t* __restrict__ col = (g == 0 ? ecode : (g == 1 ? edata : eacc)) + (size_t)t.x * dom;
-        nar[dst * CP_LANES] = col[(i - 4u * back) & (dom - 1u)];  // dom divides 2^32: the wrapped difference reduces properly
-        break;
+        return col[(i - 4u * back) & (dom - 1u)];  // dom divides 2^32: the wrapped difference reduces properly
     }
-    case CP_ADD_BB: nar[dst * CP_LANES] = fp_add(nar[a * CP_LANES], nar[b * CP_LANES]); break;
-    case CP_SUB_BB: nar[dst * CP_LANES] = fp_sub(nar[a * CP_LANES], nar[b * CP_LANES]); break;
-    case CP_MUL_BB: nar[dst * CP_LANES] = fp_mul(nar[a * CP_LANES], nar[b * CP_LANES]); break;
-    case CP_ADD_EB: {
-        Fp4 x = cp_ldw(wid, a);
-        x.c[0] = fp_add(x.c[0], nar[b * CP_LANES]);
-        cp_stw(wid, dst, x);
-        break;
-    }
-    case CP_SUB_EB: {
-        Fp4 x = cp_ldw(wid, a);
-        x.c[0] = fp_sub(x.c[0], nar[b * CP_LANES]);
-        cp_stw(wid, dst, x);
-        break;
-    }
-    case CP_SUB_BE: {
-        const Fp4 y = cp_ldw(wid, b);
-        cp_stw(wid, dst, Fp4{{fp_sub(nar[a * CP_LANES], y.c[0]), fp_neg(y.c[1]), fp_neg(y.c[2]), fp_neg(y.c[3])}});
-        break;
-    }
-    case CP_MUL_EB: cp_stw(wid, dst, f4_scale(cp_ldw(wid, a), nar[b * CP_LANES])); break;
-    case CP_ADD_EE: cp_stw(wid, dst, f4_add(cp_ldw(wid, a), cp_ldw(wid, b))); break;
-    case CP_SUB_EE: cp_stw(wid, dst, f4_sub(cp_ldw(wid, a), cp_ldw(wid, b))); break;
-    case CP_MUL_EE: cp_stw(wid, dst, f4_mul_lz(cp_ldw(wid, a), cp_ldw(wid, b))); break;
-    case CP_ZERO: cp_stw(wid, dst, f4_zero()); break;
-    case CP_EQZ_B: cp_stw(wid, dst, f4_add(cp_ldw(wid, a), f4_scale(mix_power(mixpows, imm), nar[b * CP_LANES]))); break;
-    case CP_EQZ_E: cp_stw(wid, dst, f4_add(cp_ldw(wid, a), f4_mul_lz(mix_power(mixpows, imm), cp_ldw(wid, b)))); break;
-    case CP_COND_B: {
-        const Fp4 w = f4_mul_lz(mix_power(mixpows, imm), cp_ldw(wid, c));
-        cp_stw(wid, dst, f4_add(cp_ldw(wid, a), f4_scale(w, nar[b * CP_LANES])));
-        break;
-    }
-    case CP_COND_E: {
-        const Fp4 w = f4_mul_lz(mix_power(mixpows, imm), cp_ldw(wid, c));
-        cp_stw(wid, dst, f4_add(cp_ldw(wid, a), f4_mul_lz(w, cp_ldw(wid, b))));
-        break;
-    }
-    default: break;
-    }
-}
+    __device__ __forceinline__ const uint32_t* mixpows() const { return pows; }
+    __device__ __forceinline__ void other(uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t*) const {}
+};
 
 __global__ __launch_bounds__(256) void cons_program_kernel(uint32_t* __restrict__ check, const uint32_t* __restrict__ ecode,
                                                            const uint32_t* __restrict__ edata, const uint32_t* __restrict__ eacc,
@@ -118,13 +65,15 @@ __global__ __launch_bounds__(256) void cons_program_kernel(uint32_t* __restrict_
     uint32_t* const nar = slots + threadIdx.x;                          // narrow slot s: nar[256 s]
     uint32_t* const wid = slots + L.n_narrow * CP_LANES + threadIdx.x;  // wide slot s, plane k: wid[256 (4 s + k)]
 
+    const ConsEnv env{ecode, edata, eacc, taps, mixpows, dom, i};
+
     static_assert(CP_FETCH == 4, "the fetch below reads two uint4 = four instructions");
     for (uint32_t f = 0; f < L.n_fetch; ++f) {
         const uint4 lo = code[2 * (size_t)f], hi = code[2 * (size_t)f + 1];
-        cp_exec(lo.x, lo.y, nar, wid, ecode, edata, eacc, taps, scal, mixpows, dom, i);
-        cp_exec(lo.z, lo.w, nar, wid, ecode, edata, eacc, taps, scal, mixpows, dom, i);
-        cp_exec(hi.x, hi.y, nar, wid, ecode, edata, eacc, taps, scal, mixpows, dom, i);
-        cp_exec(hi.z, hi.w, nar, wid, ecode, edata, eacc, taps, scal, mixpows, dom, i);
+        cp_exec(lo.x, lo.y, nar, wid, scal, env);
+        cp_exec(lo.z, lo.w, nar, wid, scal, env);
+        cp_exec(hi.x, hi.y, nar, wid, scal, env);
+        cp_exec(hi.z, hi.w, nar, wid, scal, env);
     }
     const Fp4 q = f4_scale(cp_ldw(wid, L.ret_slot), L.zinv[i & 3u]);
 #pragma unroll
@@ -279,6 +228,7 @@ struct bx_cons_circuit {
     std::vector<uint8_t> kernel;  // bx_cons_circuit_set_kernel: the code object create attaches (empty = the interpreter)
     const bx_wit_program* wit = nullptr;  // bx_cons_circuit_set_witness: witgen derives columns and global cells from it (NULL = base alone)
     std::vector<uint8_t> wit_kernel;  // bx_cons_circuit_set_witness_kernel: the code object create attaches to `wit` (empty = the interpreter)
+    const bx_acc_program* acc = nullptr;  // bx_cons_circuit_set_accumulate: accumulate's columns [0, 4 S) come from it (NULL = base alone)
 };
 
 namespace bx {
@@ -287,8 +237,12 @@ struct ConsState {
     void* base_state = nullptr;
     bx_cons_program_dev* dev = nullptr;
     bx_wit_program_dev* wit_dev = nullptr;
+    bx_acc_program_dev* acc_dev = nullptr;
     bx_segment_params shape{};
     uint32_t n_globals = 0;
+    // the accumulate program's: the tapped columns as witgen left them, the scans' work space, and witgen's public words
+    DevBuf kept, run_ext, mults;
+    uint32_t globals[BX_MAX_GLOBALS] = {};
 };
 const char* cc_normalize(void* u, bx_segment_params* shape) {
     const bx_circuit_ops* b = ((bx_cons_circuit*)u)->base;
@@ -307,6 +261,7 @@ void cc_destroy(void* u, void* state) {
     if (!st) return;
     (void)bx_cons_program_unload(st->dev);
     (void)bx_wit_program_unload(st->wit_dev);
+    (void)bx_acc_program_unload(st->acc_dev);
     if (st->base_state && b->destroy) b->destroy(b->user, st->base_state);
     delete st;
 }
@@ -340,6 +295,24 @@ const char* cc_create(void* u, bx_ctx* c, const bx_segment_params* shape, void**
             return c->err;
         }
     }
+    if (const bx_acc_program* a = cc->acc) {  // the accumulate program against the shape, before anything is loaded
+        if (const char* e = acc_program_check_widths(a, "cons circuit: accumulate program", shape->w_code, shape->w_data)) return set_msg(c, e);
+        const uint32_t cols = 4 * a->info.sequences;
+        if (cols > shape->w_accum) {
+            snprintf(c->err, sizeof c->err, "cons circuit: accumulate program: %u sequences need %u accum columns, the shape has %u", a->info.sequences, cols,
+                     shape->w_accum);
+            return c->err;
+        }
+        if (a->info.n_globals != ng) {
+            snprintf(c->err, sizeof c->err, "cons circuit: accumulate program: the program has %u globals, the base circuit %u", a->info.n_globals, ng);
+            return c->err;
+        }
+        if (!b->accumulate && shape->w_accum > cols) {
+            snprintf(c->err, sizeof c->err, "cons circuit: accumulate program: accum columns %u .. %u are not the program's and the base circuit has no accumulate", cols,
+                     shape->w_accum - 1);
+            return c->err;
+        }
+    }
     std::unique_ptr<ConsState> st(new (std::nothrow) ConsState());
     BX_REQUIRE(c, st != nullptr, "cons circuit: out of host memory");
     st->shape = *shape;
@@ -349,6 +322,7 @@ const char* cc_create(void* u, bx_ctx* c, const bx_segment_params* shape, void**
         const char* kept = e == c->err ? e : set_msg(c, e);
         (void)bx_cons_program_unload(st->dev);
         (void)bx_wit_program_unload(st->wit_dev);
+        (void)bx_acc_program_unload(st->acc_dev);
         return kept;
     };
     if (!cc->kernel.empty())
@@ -357,6 +331,13 @@ const char* cc_create(void* u, bx_ctx* c, const bx_segment_params* shape, void**
         if (const char* e = bx_wit_program_load(c, cc->wit, &st->wit_dev)) return undo(e);
     if (!cc->wit_kernel.empty())
         if (const char* e = bx_wit_program_attach_kernel(st->wit_dev, cc->wit_kernel.data(), cc->wit_kernel.size())) return undo(e);
+    if (const bx_acc_program* a = cc->acc) {
+        if (const char* e = bx_acc_program_load(c, a, &st->acc_dev)) return undo(e);
+        const size_t n = (size_t)1 << shape->po2;
+        for (const char* e : {st->kept.alloc(c, std::max<size_t>(n * a->info.kept, 1)), st->run_ext.alloc(c, 4 * n * a->info.sequences),
+                              st->mults.alloc(c, std::max<size_t>(n * a->info.sums, 1))})
+            if (e) return undo(e);
+    }
     if (b->create)
         if (const char* e = b->create(b->user, c, shape, &st->base_state)) return undo(e);
     *state = st.release();
@@ -367,16 +348,11 @@ const char* cc_code_group(void* u, void* state, bx_ctx* c, bx_buf code) {
     BX_REQUIRE(c, b->code_group != nullptr, "cons circuit: the base circuit has no code_group");
     return b->code_group(b->user, ((ConsState*)state)->base_state, c, code);
 }
-const char* cc_witgen(void* u, void* state, bx_ctx* c, bx_buf code, bx_buf data, const uint8_t* segment, size_t segment_len, bx_buf segment_dev,
-                      uint32_t* globals_out) {
-    const bx_circuit_ops* b = ((bx_cons_circuit*)u)->base;
-    BX_REQUIRE(c, b->witgen != nullptr, "cons circuit: the base circuit has no witgen");
-    const ConsState* st = (const ConsState*)state;
-    if (const char* e = b->witgen(b->user, st->base_state, c, code, data, segment, segment_len, segment_dev, globals_out)) return e;
+const char* cc_witness(bx_cons_circuit* cc, const ConsState* st, bx_ctx* c, bx_buf code, bx_buf data, uint32_t* globals_out) {
     if (!st->wit_dev) return nullptr;
     // the base has placed the free cells: derive the rest, then take the public words that are cells of the trace
     BX_TRY(bx_wit_program_run(c, st->wit_dev, st->shape.po2, code, st->shape.w_code, data, st->shape.w_data));
-    const std::vector<bx_wit_global_cell>& cells = ((bx_cons_circuit*)u)->wit->cells;
+    const std::vector<bx_wit_global_cell>& cells = cc->wit->cells;
     if (cells.empty()) return nullptr;
     const uint32_t* landed[BX_MAX_GLOBALS];
     size_t used = 0;
@@ -386,10 +362,34 @@ const char* cc_witgen(void* u, void* state, bx_ctx* c, bx_buf code, bx_buf data,
     for (size_t k = 0; k < cells.size(); ++k) globals_out[cells[k].global] = *landed[k];
     return nullptr;
 }
+const char* cc_witgen(void* u, void* state, bx_ctx* c, bx_buf code, bx_buf data, const uint8_t* segment, size_t segment_len, bx_buf segment_dev,
+                      uint32_t* globals_out) {
+    const bx_circuit_ops* b = ((bx_cons_circuit*)u)->base;
+    BX_REQUIRE(c, b->witgen != nullptr, "cons circuit: the base circuit has no witgen");
+    ConsState* st = (ConsState*)state;
+    if (const char* e = b->witgen(b->user, st->base_state, c, code, data, segment, segment_len, segment_dev, globals_out)) return e;
+    BX_TRY(cc_witness((bx_cons_circuit*)u, st, c, code, data, globals_out));
+    if (!st->acc_dev) return nullptr;
+    // the prover interpolates `code` and `data` in place after this: what accumulate's program taps is copied now, and the public
+    // words are final
+    for (uint32_t k = 0; k < st->n_globals; ++k) st->globals[k] = globals_out[k];
+    return bx_acc_program_keep(c, st->acc_dev, st->shape.po2, code, st->shape.w_code, data, st->shape.w_data,
+                               st->kept.slice(0, ((size_t)st->acc_dev->info.kept) << st->shape.po2));
+}
 const char* cc_accumulate(void* u, void* state, bx_ctx* c, bx_buf accum, const uint32_t mix[4]) {
     const bx_circuit_ops* b = ((bx_cons_circuit*)u)->base;
-    BX_REQUIRE(c, b->accumulate != nullptr, "cons circuit: the base circuit has no accumulate");
-    return b->accumulate(b->user, ((ConsState*)state)->base_state, c, accum, mix);
+    ConsState* st = (ConsState*)state;
+    if (!st->acc_dev) {
+        BX_REQUIRE(c, b->accumulate != nullptr, "cons circuit: the base circuit has no accumulate");
+        return b->accumulate(b->user, st->base_state, c, accum, mix);
+    }
+    // the base owns filler and every column at or above 4 S; whatever it leaves below is overwritten
+    if (b->accumulate)
+        if (const char* e = b->accumulate(b->user, st->base_state, c, accum, mix)) return e;
+    const size_t n = (size_t)1 << st->shape.po2;
+    const bx_acc_program_info& in = st->acc_dev->info;
+    return bx_acc_program_run(c, st->acc_dev, st->shape.po2, st->kept.slice(0, n * in.kept), st->globals, mix, st->run_ext.b, st->mults.slice(0, n * in.sums), accum,
+                              st->shape.w_accum);
 }
 const char* cc_eval_check(void*, void* state, bx_ctx* c, bx_buf check, bx_buf ecode, bx_buf edata, bx_buf eacc, const uint32_t poly_mix[4], const uint32_t mix[4],
                           const uint32_t* globals) {
@@ -447,6 +447,11 @@ extern "C" const char* bx_cons_circuit_set_kernel(bx_cons_circuit* cc, const voi
 extern "C" const char* bx_cons_circuit_set_witness(bx_cons_circuit* cc, const bx_wit_program* wit) {
     if (!cc) return "bx_cons_circuit_set_witness: null argument";
     cc->wit = wit;
+    return nullptr;
+}
+extern "C" const char* bx_cons_circuit_set_accumulate(bx_cons_circuit* cc, const bx_acc_program* acc) {
+    if (!cc) return "bx_cons_circuit_set_accumulate: null argument";
+    cc->acc = acc;
     return nullptr;
 }
 extern "C" const char* bx_cons_circuit_set_witness_kernel(bx_cons_circuit* cc, const void* image, size_t len) try {

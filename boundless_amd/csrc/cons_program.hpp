@@ -42,6 +42,11 @@ enum ConsOpcode : uint32_t {
     CP_COND_E,   // wide[dst] = wide[a] + (pow[imm] * wide[c]) * wide[b]             (AND_COND, ext cond)
     CP_ST,       // data column imm = narrow[a]                                      (SET; witness programs only, and last: no
                  //                                                                   existing stream or digest changes)
+    // accumulate programs only ("Accumulate programs" of bx_program.h), appended for the same reason: a row's term of sequence imm
+    CP_TSUM_B,   // run_ext[imm][r] = (narrow[b], 0, 0, 0), mults[imm][r] = narrow[a]  (SUM, base denominator)
+    CP_TSUM_E,   // run_ext[imm][r] = wide[b],              mults[imm][r] = narrow[a]  (SUM, ext denominator)
+    CP_TPROD_B,  // run_ext[imm][r] = (narrow[a], 0, 0, 0)                             (PROD, base factor)
+    CP_TPROD_E,  // run_ext[imm][r] = wide[a]                                          (PROD, ext factor)
     CP_OPCODES
 };
 constexpr uint32_t CP_FETCH = 4;  // instructions per fetch of the kernel (8 dwords)
@@ -74,7 +79,21 @@ struct bx_wit_program {
     uint32_t max_set = 0;          // 1 + the largest SET column
 };
 
+// A compiled accumulate program ("Accumulate programs" of bx_program.h): the instructions of a constraint program without the mix
+// opcodes, plus the four term stores.  `scal` = [globals | mix (4) | consts], as for a constraint program.  CP_TAP's imm indexes `taps`;
+// tap t reads kept column tap_kept[t], which is (group, col) = kept[tap_kept[t]].
+struct bx_acc_program {
+    bx_acc_program_info info{};
+    std::vector<uint32_t> code;    // 2 words per instruction, padded to CP_FETCH instructions
+    std::vector<uint32_t> consts;  // Montgomery words: the tail of `scal`
+    std::vector<bx_cons_tap> taps;
+    std::vector<uint32_t> tap_kept;  // per tap: its kept index
+    std::vector<bx_cons_tap> kept;   // the distinct (group, col) of the tap list in order of first appearance (back unused, 0)
+};
+
 namespace bx {
+// cons_program_host.cpp: NULL, or the refusal (thread-local buffer, led by `who`) of a kept column that is not below its group's width
+const char* acc_program_check_widths(const bx_acc_program* prog, const char* who, uint32_t w_code, uint32_t w_data);
 // cons_program_host.cpp: NULL, or the refusal (in the caller's thread-local buffer, led by `who`) of a tap column (max_col, per group)
 // or a SET column (max_set) that is not below its group's width: one text for bx_wit_program_run_host, bx_wit_program_run and the
 // composite table's create

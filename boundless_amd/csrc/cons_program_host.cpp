@@ -1,6 +1,7 @@
 // cons_program_host.cpp — host half of constraint programs (include/bx_program.h is the normative text): the compiler from a step list
 // to the instruction stream of cons_program.hpp, and the host executor of that stream over Fp4 (the verifier's constraints_at); and
-// the same two for witness programs, which share the slot allocation and the instruction format (compile_wit, bx_wit_program_run_host).
+// the same two for witness programs, which share the slot allocation and the instruction format (compile_wit, bx_wit_program_run_host),
+// and for accumulate programs (compile_acc, bx_acc_program_run_host).
 // No HIP: this translation unit compiles with plain g++ (tests/cons_program_check.cpp runs it under sanitizers).
 #include <stdarg.h>
 #include <stdio.h>
@@ -424,7 +425,199 @@ const char* compile_wit(const bx_wit_program_desc* d, bx_wit_program* p) {
     return nullptr;
 }
 
+// ---- accumulate programs ("Accumulate programs" of bx_program.h): the constraint compiler's types, slot files and instructions, one
+// list of vars, and term stores in place of mix steps ----
+const char* compile_acc(const bx_acc_program_desc* d, bx_acc_program* p) {
+    if (d->n_steps > BX_CONS_MAX_STEPS) return refuse("acc_program: %zu steps, more than BX_CONS_MAX_STEPS = %d", d->n_steps, BX_CONS_MAX_STEPS);
+    if (d->n_taps > BX_CONS_MAX_TAPS) return refuse("acc_program: %zu taps, more than BX_CONS_MAX_TAPS = %d", d->n_taps, BX_CONS_MAX_TAPS);
+    if (d->n_globals > BX_MAX_GLOBALS) return refuse("acc_program: n_globals %u is above BX_MAX_GLOBALS = %d", d->n_globals, BX_MAX_GLOBALS);
+    if ((d->n_steps && !d->steps) || (d->n_taps && !d->taps)) return refuse("acc_program: null step or tap list");
+
+    // ---- the tap list: ranges, and the kept columns in order of first appearance ----
+    std::map<std::pair<uint32_t, uint32_t>, uint32_t> kept_of;
+    for (size_t t = 0; t < d->n_taps; ++t) {
+        const bx_cons_tap& tp = d->taps[t];
+        if (tp.group == 2) return refuse("acc_program: tap %zu: tap group 2 (accum): the program produces the accum group, it does not read it", t);
+        if (tp.group > 2) return refuse("acc_program: tap %zu: tap group %u out of range (0 code, 1 data)", t, tp.group);
+        if (tp.col > BX_CONS_MAX_COL) return refuse("acc_program: tap %zu: tap column %u out of range (at most %d)", t, tp.col, BX_CONS_MAX_COL);
+        if (tp.back > BX_CONS_MAX_BACK) return refuse("acc_program: tap %zu: tap back %u out of range (at most %d)", t, tp.back, BX_CONS_MAX_BACK);
+        const auto ins = kept_of.emplace(std::make_pair(tp.group, tp.col), (uint32_t)p->kept.size());
+        if (ins.second) p->kept.push_back(bx_cons_tap{tp.group, tp.col, 0u});
+        p->tap_kept.push_back(ins.first->second);
+    }
+    p->taps.assign(d->taps, d->taps + d->n_taps);
+
+    // ---- pass 1: validation, types, sequences, last uses ----
+    struct Var {
+        bool ext = false;
+        uint32_t slot = 0, last_use = 0;
+    };
+    std::vector<Var> fp;
+    std::map<uint32_t, std::pair<size_t, bool>> seqs;  // sequence -> (the step that defines it, is it a sum)
+    const auto use_fp = [&](size_t i, const char* what, uint32_t v) -> const char* {
+        if (v >= fp.size()) return refuse("acc_program: step %zu: operand %s = %u refers to a later or missing fp var (%zu so far)", i, what, v, fp.size());
+        fp[v].last_use = (uint32_t)i;
+        return nullptr;
+    };
+    const auto define = [&](size_t i, uint32_t s, bool sum) -> const char* {
+        if (s >= BX_ACC_MAX_SEQS) return refuse("acc_program: step %zu: sequence %u is not below BX_ACC_MAX_SEQS = %d", i, s, BX_ACC_MAX_SEQS);
+        const auto ins = seqs.emplace(s, std::make_pair(i, sum));
+        if (!ins.second) return refuse("acc_program: step %zu: sequence %u is defined a second time (first at step %zu)", i, s, ins.first->second.first);
+        return nullptr;
+    };
+    static const char* const kForbidden[] = {"TRUE", "AND_EQZ", "AND_COND", "SET"};
+    for (size_t i = 0; i < d->n_steps; ++i) {
+        const bx_cons_step& s = d->steps[i];
+        Var f;
+        f.last_use = (uint32_t)i;
+        switch (s.op) {
+        case BX_CONS_CONST:
+            if (s.a >= P) return refuse("acc_program: step %zu: constant %u is not below P", i, s.a);
+            break;
+        case BX_CONS_CONST_EXT:
+            if (s.a >= P || s.b >= P || s.c >= P || s.d >= P)
+                return refuse("acc_program: step %zu: ext constant (%u, %u, %u, %u) has a component not below P", i, s.a, s.b, s.c, s.d);
+            f.ext = true;
+            break;
+        case BX_CONS_GET:
+            if (s.a >= d->n_taps) return refuse("acc_program: step %zu: tap index %u out of range (%zu taps)", i, s.a, d->n_taps);
+            break;
+        case BX_CONS_GET_GLOBAL:
+            if (s.a > 1) return refuse("acc_program: step %zu: GET_GLOBAL table %u out of range (0 globals, 1 mix)", i, s.a);
+            if (s.a == 0 && s.b >= d->n_globals) return refuse("acc_program: step %zu: global index %u out of range (%u globals)", i, s.b, d->n_globals);
+            if (s.a == 1 && s.b >= 4) return refuse("acc_program: step %zu: mix component %u out of range (an ext element has 4)", i, s.b);
+            break;
+        case BX_CONS_ADD:
+        case BX_CONS_SUB:
+        case BX_CONS_MUL:
+            if (const char* m = use_fp(i, "a", s.a)) return m;
+            if (const char* m = use_fp(i, "b", s.b)) return m;
+            f.ext = fp[s.a].ext || fp[s.b].ext;
+            break;
+        case BX_CONS_SUM:
+            if (const char* m = define(i, s.a, true)) return m;
+            if (const char* m = use_fp(i, "m", s.b)) return m;
+            if (const char* m = use_fp(i, "d", s.c)) return m;
+            if (fp[s.b].ext) return refuse("acc_program: step %zu: SUM's m = %u is ext-typed; a multiplicity must be a base value", i, s.b);
+            continue;  // appends nothing
+        case BX_CONS_PROD:
+            if (const char* m = define(i, s.a, false)) return m;
+            if (const char* m = use_fp(i, "a", s.b)) return m;
+            continue;
+        default:
+            if (s.op >= BX_CONS_TRUE && s.op <= BX_CONS_SET)
+                return refuse("acc_program: step %zu: %s does not belong in an accumulate program (CONST, CONST_EXT, GET, GET_GLOBAL, ADD, SUB, MUL, SUM, PROD)", i,
+                              kForbidden[s.op - BX_CONS_TRUE]);
+            return refuse("acc_program: step %zu: unknown op %u", i, s.op);
+        }
+        fp.push_back(f);
+    }
+    if (seqs.empty()) return refuse("acc_program: the program defines no sequence (S = 0)");
+    uint32_t expect = 0, sums = 0;
+    bool prod_seen = false;
+    for (const auto& kv : seqs) {  // in sequence order
+        if (kv.first != expect) return refuse("acc_program: sequence %u is not defined: the sequences must be exactly 0 .. S-1 (sequence %u is defined)", expect, kv.first);
+        ++expect;
+        if (kv.second.second) {
+            if (prod_seen)
+                return refuse("acc_program: step %zu: SUM sequence %u is numbered above a PROD sequence: all sums come first, then all products", kv.second.first, kv.first);
+            ++sums;
+        } else {
+            prod_seen = true;
+        }
+    }
+
+    // ---- pass 2: slots by last use, and the stream ----
+    SlotFile narrow, wide;
+    const uint32_t scal_consts = d->n_globals + 4;  // where the constants start in `scal`
+    const auto emit = [&](uint32_t op, uint32_t dst, uint32_t a, uint32_t b, uint32_t imm) {
+        p->code.push_back(cp_w0(op, dst, a, b));
+        p->code.push_back(cp_w1(0, imm));
+    };
+    uint32_t fi = 0;
+    for (size_t i = 0; i < d->n_steps; ++i) {
+        const bx_cons_step& s = d->steps[i];
+        const uint32_t step = (uint32_t)i;
+        // operands that die here give their slots back BEFORE the result takes one (dst may alias a source: executors read first)
+        const auto drop = [&](uint32_t v) {
+            if (fp[v].last_use == step) {
+                (fp[v].ext ? wide : narrow).give(fp[v].slot);
+                fp[v].last_use = NEVER - 1;  // an operand named twice is dropped once
+            }
+        };
+        if (s.op == BX_CONS_SUM) {
+            emit(fp[s.c].ext ? CP_TSUM_E : CP_TSUM_B, 0, fp[s.b].slot, fp[s.c].slot, s.a);
+            drop(s.b);
+            drop(s.c);
+            continue;
+        }
+        if (s.op == BX_CONS_PROD) {
+            emit(fp[s.b].ext ? CP_TPROD_E : CP_TPROD_B, 0, fp[s.b].slot, 0, s.a);
+            drop(s.b);
+            continue;
+        }
+        Var& f = fp[fi];
+        const bool unused = f.last_use == step;
+        uint32_t sa = 0, sb = 0;
+        bool ea = false, eb = false;
+        if (s.op >= BX_CONS_ADD) {
+            sa = fp[s.a].slot, sb = fp[s.b].slot, ea = fp[s.a].ext, eb = fp[s.b].ext;
+            drop(s.a);
+            drop(s.b);
+        }
+        const uint32_t dst = f.slot = (f.ext ? wide : narrow).take();
+        switch (s.op) {
+        case BX_CONS_CONST:
+            emit(CP_LD_B, dst, 0, 0, scal_consts + (uint32_t)p->consts.size());
+            p->consts.push_back(fp_encode(s.a));
+            break;
+        case BX_CONS_CONST_EXT:
+            emit(CP_LD_E, dst, 0, 0, scal_consts + (uint32_t)p->consts.size());
+            for (uint32_t v : {s.a, s.b, s.c, s.d}) p->consts.push_back(fp_encode(v));
+            break;
+        case BX_CONS_GET: emit(CP_TAP, dst, 0, 0, s.a); break;
+        case BX_CONS_GET_GLOBAL: emit(CP_LD_B, dst, 0, 0, s.a == 0 ? s.b : d->n_globals + s.b); break;
+        case BX_CONS_ADD:
+        case BX_CONS_MUL:
+            if (!ea && !eb) emit(s.op == BX_CONS_ADD ? CP_ADD_BB : CP_MUL_BB, dst, sa, sb, 0);
+            else if (ea && eb) emit(s.op == BX_CONS_ADD ? CP_ADD_EE : CP_MUL_EE, dst, sa, sb, 0);
+            else emit(s.op == BX_CONS_ADD ? CP_ADD_EB : CP_MUL_EB, dst, ea ? sa : sb, ea ? sb : sa, 0);  // commutative: ext first
+            break;
+        default:  // BX_CONS_SUB
+            emit(!ea && !eb ? CP_SUB_BB : (ea && eb ? CP_SUB_EE : (ea ? CP_SUB_EB : CP_SUB_BE)), dst, sa, sb, 0);
+            break;
+        }
+        if (unused) (f.ext ? wide : narrow).give(dst);
+        ++fi;
+        if (narrow.peak > BX_CONS_MAX_NARROW || wide.peak > BX_CONS_MAX_WIDE) {
+            const bool nw = narrow.peak > BX_CONS_MAX_NARROW;
+            return refuse("acc_program: step %zu: the program needs %u live %s values, the limit is %d (BX_CONS_MAX_%s)", i, nw ? narrow.peak : wide.peak,
+                          nw ? "narrow (base)" : "wide (ext)", nw ? BX_CONS_MAX_NARROW : BX_CONS_MAX_WIDE, nw ? "NARROW" : "WIDE");
+        }
+    }
+    p->info.steps = (uint32_t)d->n_steps;
+    p->info.sequences = (uint32_t)seqs.size();
+    p->info.sums = sums;
+    p->info.instructions = (uint32_t)(p->code.size() / 2);
+    p->info.narrow = narrow.top;
+    p->info.wide = wide.top;
+    p->info.taps = (uint32_t)d->n_taps;
+    p->info.kept = (uint32_t)p->kept.size();
+    p->info.n_globals = d->n_globals;
+    while ((p->code.size() / 2) % CP_FETCH) emit(CP_NOP, 0, 0, 0, 0);
+    return nullptr;
+}
+
 }  // namespace
+
+const char* acc_program_check_widths(const bx_acc_program* prog, const char* who, uint32_t w_code, uint32_t w_data) {
+    for (size_t k = 0; k < prog->kept.size(); ++k) {
+        const bx_cons_tap& t = prog->kept[k];
+        const uint32_t w = t.group == 0 ? w_code : w_data;
+        if (t.col >= w) return refuse("%s: the program taps column %u of group %u (kept column %zu), which has %u columns", who, t.col, t.group, k, w);
+    }
+    return nullptr;
+}
 
 const char* wit_program_check_widths(const uint32_t max_col[2], uint32_t max_set, const char* who, uint32_t w_code, uint32_t w_data) {
     const uint32_t widths[2] = {w_code, w_data};
@@ -593,4 +786,120 @@ extern "C" const char* bx_wit_program_run_host(const bx_wit_program* prog, uint3
         }
     }
     return nullptr;
+}
+
+// ---- accumulate programs ----
+extern "C" const char* bx_acc_program_create(const bx_acc_program_desc* desc, bx_acc_program** out) try {
+    if (!desc || !out) return "bx_acc_program_create: null argument";
+    *out = nullptr;
+    bx_acc_program* p = new bx_acc_program();
+    if (const char* e = bx::compile_acc(desc, p)) {
+        delete p;
+        return e;
+    }
+    *out = p;
+    return nullptr;
+} catch (...) {
+    return "bx_acc_program_create: out of host memory";
+}
+
+extern "C" void bx_acc_program_destroy(bx_acc_program* prog) { delete prog; }
+
+extern "C" const char* bx_acc_program_info_get(const bx_acc_program* prog, bx_acc_program_info* out) {
+    if (!prog || !out) return "bx_acc_program_info_get: null argument";
+    *out = prog->info;
+    return nullptr;
+}
+
+extern "C" const char* bx_acc_program_kept(const bx_acc_program* prog, uint32_t i, uint32_t* group, uint32_t* col) {
+    if (!prog || !group || !col) return "bx_acc_program_kept: null argument";
+    if (i >= prog->kept.size()) return "bx_acc_program_kept: index is not below the number of kept columns";
+    *group = prog->kept[i].group;
+    *col = prog->kept[i].col;
+    return nullptr;
+}
+
+extern "C" const char* bx_acc_program_run_host(const bx_acc_program* prog, uint32_t po2, const uint32_t* code, uint32_t w_code, const uint32_t* data,
+                                               uint32_t w_data, const uint32_t* globals, const uint32_t mix[4], uint32_t* accum, uint32_t w_accum) try {
+    using namespace bx;
+    if (!prog || !mix || !accum || (w_code && !code) || (w_data && !data)) return "bx_acc_program_run_host: null argument";
+    if (prog->info.n_globals && !globals) return "bx_acc_program_run_host: the program names globals and none were given";
+    if (po2 < 1 || po2 > 24) return "bx_acc_program_run_host: po2 must be in [1, 24]";
+    if (const char* e = acc_program_check_widths(prog, "bx_acc_program_run_host", w_code, w_data)) return e;
+    const uint32_t S = prog->info.sequences, sums = prog->info.sums, ng = prog->info.n_globals;
+    if (w_accum < 4 * S) return refuse("bx_acc_program_run_host: the program writes %u accum columns, the accum group has %u", 4 * S, w_accum);
+    const size_t n = (size_t)1 << po2;
+    std::vector<uint32_t> scal(ng + 4 + prog->consts.size());
+    for (uint32_t i = 0; i < ng; ++i) scal[i] = globals[i];
+    for (uint32_t i = 0; i < 4; ++i) scal[ng + i] = mix[i];
+    std::copy(prog->consts.begin(), prog->consts.end(), scal.begin() + ng + 4);
+    std::vector<Fp4> run((size_t)S * n, f4_zero());  // the device's run_ext: sequence-major AoS
+    std::vector<uint32_t> mults((size_t)sums * n, 0u);
+    // (1) the terms of every row
+    for (size_t r = 0; r < n; ++r) {
+        // a slot number is eight bits: files of 256 cannot be indexed out of bounds by any stream
+        uint32_t nar[256] = {};
+        Fp4 wid[256];
+        for (Fp4& v : wid) v = f4_zero();
+        for (size_t pc = 0; pc < prog->code.size(); pc += 2) {
+            const uint32_t w0 = prog->code[pc], w1 = prog->code[pc + 1];
+            const uint32_t op = w0 & 0xFFu, dst = (w0 >> 8) & 0xFFu, a = (w0 >> 16) & 0xFFu, b = w0 >> 24, imm = w1 >> 8;
+            switch (op) {
+            case CP_NOP: break;
+            case CP_LD_B: nar[dst] = scal.at(imm); break;
+            case CP_LD_E: wid[dst] = Fp4{{scal.at(imm), scal.at(imm + 1), scal.at(imm + 2), scal.at(imm + 3)}}; break;
+            case CP_TAP: {
+                const bx_cons_tap& t = prog->taps.at(imm);
+                const uint32_t* col = (t.group == 0 ? code : data) + (size_t)t.col * n;
+                nar[dst] = col[((uint32_t)r - t.back) & (uint32_t)(n - 1)];  // N divides 2^32: the wrapped difference reduces properly
+                break;
+            }
+            case CP_ADD_BB: nar[dst] = fp_add(nar[a], nar[b]); break;
+            case CP_SUB_BB: nar[dst] = fp_sub(nar[a], nar[b]); break;
+            case CP_MUL_BB: nar[dst] = fp_mul(nar[a], nar[b]); break;
+            case CP_ADD_EB: {
+                Fp4 x = wid[a];
+                x.c[0] = fp_add(x.c[0], nar[b]);
+                wid[dst] = x;
+                break;
+            }
+            case CP_SUB_EB: {
+                Fp4 x = wid[a];
+                x.c[0] = fp_sub(x.c[0], nar[b]);
+                wid[dst] = x;
+                break;
+            }
+            case CP_SUB_BE: wid[dst] = Fp4{{fp_sub(nar[a], wid[b].c[0]), fp_neg(wid[b].c[1]), fp_neg(wid[b].c[2]), fp_neg(wid[b].c[3])}}; break;
+            case CP_MUL_EB: wid[dst] = f4_scale(wid[a], nar[b]); break;
+            case CP_ADD_EE: wid[dst] = f4_add(wid[a], wid[b]); break;
+            case CP_SUB_EE: wid[dst] = f4_sub(wid[a], wid[b]); break;
+            case CP_MUL_EE: wid[dst] = f4_mul(wid[a], wid[b]); break;
+            case CP_TSUM_B:
+            case CP_TSUM_E:
+                if (imm >= sums) return "bx_acc_program_run_host: corrupt instruction stream";
+                run[(size_t)imm * n + r] = op == CP_TSUM_B ? Fp4{{nar[b], 0u, 0u, 0u}} : wid[b];
+                mults[(size_t)imm * n + r] = nar[a];
+                break;
+            case CP_TPROD_B:
+            case CP_TPROD_E:
+                if (imm < sums || imm >= S) return "bx_acc_program_run_host: corrupt instruction stream";
+                run[(size_t)imm * n + r] = op == CP_TPROD_B ? Fp4{{nar[a], 0u, 0u, 0u}} : wid[a];
+                break;
+            default: return "bx_acc_program_run_host: corrupt instruction stream";
+            }
+        }
+    }
+    // (2) m / d with 0 -> 0 and the running sums; (3) the running products; (4) sequence s, component k -> column 4 s + k
+    for (uint32_t s = 0; s < S; ++s) {
+        Fp4 acc = s < sums ? f4_zero() : f4_one();
+        for (size_t r = 0; r < n; ++r) {
+            const Fp4& v = run[(size_t)s * n + r];
+            if (s < sums) acc = f4_add(acc, f4_is_zero(v) ? f4_zero() : f4_scale(f4_inv(v), mults[(size_t)s * n + r]));
+            else acc = f4_mul(acc, v);
+            for (uint32_t k = 0; k < 4; ++k) accum[(size_t)(4 * s + k) * n + r] = acc.c[k];
+        }
+    }
+    return nullptr;
+} catch (...) {
+    return "bx_acc_program_run_host: out of host memory or a corrupt instruction stream";
 }

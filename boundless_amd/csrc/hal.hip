@@ -327,6 +327,7 @@ extern "C" const char* bx_free(bx_ctx* c) try {
     groth16_release_keys(c);  // Groth16 keys still loaded on this ctx (bx_groth16.h)
     cons_programs_release(c);  // constraint programs still loaded on this ctx (bx_program.h)
     wit_programs_release(c);   // ... and witness programs
+    acc_programs_release(c);   // ... and accumulate programs
     drain_profile(c);
     ntt_free_tables(c);
     if (c->d_p2) (void)hipFree(c->d_p2);

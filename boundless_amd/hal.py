@@ -334,6 +334,18 @@ class HipHal:
         (boundless_amd.circuit.CompiledWitnessProgram.load); derives its columns of the N x w_data group `data` in place."""
         self._check(loaded.program.lib.bx_wit_program_run(self.ctx, loaded.dev, po2, code.raw, w_code, data.raw, w_data))
 
+    def acc_program_keep(self, loaded, po2, code, w_code, data, w_data, kept):
+        """An accumulate program's keep (include/bx_program.h: bx_acc_program_keep): `loaded` = a program loaded on this hal
+        (boundless_amd.circuit.CompiledAccumulateProgram.load); copies the columns it taps into `kept` (N x its kept columns)."""
+        self._check(loaded.program.lib.bx_acc_program_keep(self.ctx, loaded.dev, po2, code.raw, w_code, data.raw, w_data, kept.raw))
+
+    def acc_program_run(self, loaded, po2, kept, globals_, mix, run_ext, mults, accum, w_accum):
+        """An accumulate program's run (bx_acc_program_run): terms from `kept`, the scans over run_ext (4 N S words) and mults (N sums
+        words), then accum columns [0, 4 S) of the N x w_accum group `accum`; globals_ = the program's public words (host)."""
+        _, m = _words(mix)
+        _, gp = _words(list(globals_) or [0])
+        self._check(loaded.program.lib.bx_acc_program_run(self.ctx, loaded.dev, po2, kept.raw, gp, m, run_ext.raw, mults.raw, accum.raw, w_accum))
+
     def batch_evaluate_any(self, coeffs, poly_count, which, xs, out):
         self._check(self.lib.bx_batch_evaluate_any(self.ctx, coeffs.raw, poly_count, which.raw, xs.raw, out.raw))
 

@@ -133,8 +133,63 @@
  *   composite    bx_cons_circuit_set_witness: the table's witgen calls base->witgen (which fills the free cells; whatever it
  *                leaves in derived columns is overwritten), runs the program on `code` and `data`, and then reads the global
  *                cells back with one blocking gather into globals_out, overriding the base's words at those indices.
- * Out of scope: free-cell generators, code groups and `accumulate` from data; recurrences (a column that depends on its own
- * earlier rows is an accumulator: prefix_products / logup_accumulate).
+ * Out of scope: free-cell generators and code groups from data.  A column that depends on its own earlier rows is an accumulator and
+ * belongs to an accumulate program ("Accumulate programs" below): prefix_products / logup_accumulate.
+ *
+ * Accumulate programs (normative)
+ * -------------------------------
+ * The third circuit-specific stage, bx_circuit_ops::accumulate, fills the accum group with running sums (LogUp) and running products
+ * (grand products) of per-row terms.  The scans are the HAL's (bx_logup_accumulate, bx_batch_prefix_products); what differs per circuit
+ * is the terms in front of them.  An ACCUMULATE PROGRAM is a step list that gives those terms.  It is evaluated once per trace row r,
+ * 0 <= r < N = 2^po2, on the prover only, after the data commit, with accumulate's `mix` known.  It has ONE list, of fp vars, and no mix
+ * vars.  Types are those of a constraint program on the prover: a var is BASE unless a CONST_EXT flows into it.
+ *
+ *   step                appends  meaning
+ *   CONST a, CONST_EXT a b c d, ADD a b, SUB a b, MUL a b    fp    as in constraint programs (base x base, ext x base, ext x ext
+ *                                resolved by the compiler)
+ *   GET a               fp       tap a of the program's tap list: (group 0 code / 1 data, col, back) = that column at row
+ *                                (r - back) mod N, cyclic, as in witness programs
+ *   GET_GLOBAL 0 b / GET_GLOBAL 1 b    fp    public word b / base-field component b of `mix`, as in constraint programs
+ *   SUM s m d           nothing  sequence s is a running sum: acc_s[r] = sum_{j <= r} fp[m](j) / fp[d](j).  m must be BASE (it becomes a
+ *                                `mults` word of bx_logup_accumulate); d is base or ext.  A zero denominator contributes zero (the
+ *                                HAL's rule).                                                              (BX_CONS_SUM = 11)
+ *   PROD s a            nothing  sequence s is a running product: acc_s[r] = prod_{j <= r} fp[a](j); a is base or ext.
+ *                                                                                                          (BX_CONS_PROD = 12)
+ * Operands in bx_cons_step: SUM has a = s, b = m, c = d; PROD has a = s, b = a.
+ * Sequence s, component k is accum column 4 s + k.  With S sequences the program does not touch accum columns at or above 4 S.
+ * Refused by name at bx_acc_program_create:
+ *   ops          TRUE, AND_EQZ, AND_COND and SET do not belong in an accumulate program.  (BX_CONS_SUM and BX_CONS_PROD stay unknown
+ *                ops to bx_cons_program_create and bx_wit_program_create.)
+ *   accum        tap group 2: the program produces the accum group, it does not read it.
+ *   m            an ext-typed m of a SUM.
+ *   sequences    a sequence defined twice; a gap (the sequences must be exactly 0 .. S-1); S = 0; a sequence number at or above
+ *                BX_ACC_MAX_SEQS = 1024; a PROD sequence numbered below a SUM sequence (all sums come first, so that each scan is
+ *                ONE batched call over a contiguous range).
+ *   limits       BX_CONS_MAX_STEPS, BX_CONS_MAX_TAPS, BX_CONS_MAX_BACK, BX_CONS_MAX_COL, n_globals <= BX_MAX_GLOBALS, constants < P,
+ *                operands name earlier vars, and BX_CONS_MAX_NARROW / BX_CONS_MAX_WIDE live values: a program over one is refused
+ *                with the number it needs and the limit.  There is no degree bound and there are no mix powers.
+ *
+ *   kept columns the prover interpolates `code` and `data` in place right after witgen (bx_circuit.h), so the columns a program taps
+ *                are copied before that.  The compiler numbers the distinct (group, col) pairs of the tap list 0 .. K-1 in order of
+ *                first appearance in that list; bx_acc_program_kept lists them; the compiled tap table names the kept index.
+ *   compiled     the instruction stream of a constraint program without the mix opcodes, plus four appended after CP_ST (so that no
+ *                existing stream, digest or generated text changes): a term store for a sum with a base or an ext denominator and for a
+ *                product of base or ext factors, the sequence in `imm`.  `scal` = [globals | mix (4) | constants].  A generated kernel
+ *                per program is not part of this; the stream is what it would be generated from, as for the other two kinds.
+ *   host         bx_acc_program_run_host, the definition-level twin: the terms of every row, then the Fp4 inverse with 0 -> 0 times m,
+ *                the running sums and products, then columns 4 s + k.  Canonical arithmetic in the kernel's operand order, and canonical
+ *                words are unique, so host and device agree word for word.
+ *   device       bx_acc_program_keep: ONE launch that gathers the K kept columns into the caller's `kept` (K x N), profiled as
+ *                "acc_program_keep".  bx_acc_program_run: (1) the interpreting kernel, one lane per row, 256 per workgroup, slot
+ *                files in LDS, writes every term as ONE 16-byte store at run_ext[4 (s N + r)] (a base value is promoted to
+ *                (v, 0, 0, 0)) and for a sum one word at mults[s N + r], profiled as "acc_program_run"; (2) ONE bx_logup_accumulate
+ *                over sequences [0, sums), in place; (3) ONE bx_batch_prefix_products over [sums, S); (4) the transposition of the
+ *                S ext runs into accum columns [0, 4 S), profiled as "acc_program_store".  Columns at or above 4 S are not written.
+ *                A tap is kept[k N + ((r - back) & (N - 1))].  Nothing blocks.
+ *   composite    bx_cons_circuit_set_accumulate: the table's witgen ends with bx_acc_program_keep (after the witness program, if
+ *                any) and remembers the public words; its accumulate calls base->accumulate when the base has one (that call owns
+ *                filler and every column at or above 4 S; whatever it leaves below 4 S is overwritten) and then bx_acc_program_run.
+ * Out of scope: a generated kernel per accumulate program; fusing the terms into the scan's tile load; ratios inside a PROD.
  *
  * Generated witness kernels (normative)
  * -------------------------------------
@@ -204,6 +259,7 @@ extern "C" {
 #define BX_CONS_MAX_DEGREE 5    /* see "degree" above */
 #define BX_CONS_MAX_NARROW 32   /* live base values */
 #define BX_CONS_MAX_WIDE 24     /* live ext values and mix tots */
+#define BX_ACC_MAX_SEQS 1024    /* sequences of one accumulate program */
 
 enum bx_cons_op {
     BX_CONS_CONST = 0,
@@ -216,7 +272,9 @@ enum bx_cons_op {
     BX_CONS_TRUE = 7,
     BX_CONS_AND_EQZ = 8,
     BX_CONS_AND_COND = 9,
-    BX_CONS_SET = 10 /* witness programs only ("Witness programs" above) */
+    BX_CONS_SET = 10, /* witness programs only ("Witness programs" above) */
+    BX_CONS_SUM = 11, /* accumulate programs only ("Accumulate programs" above) */
+    BX_CONS_PROD = 12 /* likewise */
 };
 
 /* one step: `op` and its operands in the order of the table above (unused operands are ignored) */
@@ -372,6 +430,62 @@ int bx_wit_program_kernel_attached(const bx_wit_program_dev* dev);
  * and fails with attach_kernel's message if it is refused, or by name if no witness program is set.  len == 0 goes back to the
  * interpreter.  Set before a prover is created. */
 const char* bx_cons_circuit_set_witness_kernel(bx_cons_circuit* cc, const void* image, size_t len);
+
+/* ---- accumulate programs (the section of that name above) ---- */
+typedef struct bx_acc_program_desc {
+    const bx_cons_step* steps;
+    size_t n_steps;
+    const bx_cons_tap* taps;
+    size_t n_taps;
+    uint32_t n_globals; /* public words the program may name: GET_GLOBAL 0 b needs b < n_globals <= BX_MAX_GLOBALS */
+} bx_acc_program_desc;
+
+typedef struct bx_acc_program_info {
+    uint32_t steps;
+    uint32_t sequences;    /* S */
+    uint32_t sums;         /* sequences [0, sums) are running sums, [sums, S) running products */
+    uint32_t instructions; /* of the compiled stream */
+    uint32_t narrow;       /* slots used */
+    uint32_t wide;
+    uint32_t taps;
+    uint32_t kept; /* K: distinct tapped (group, col) pairs */
+    uint32_t n_globals;
+} bx_acc_program_info;
+
+typedef struct bx_acc_program bx_acc_program;         /* a compiled accumulate program (host) */
+typedef struct bx_acc_program_dev bx_acc_program_dev; /* ... loaded on a ctx */
+
+/* Validates and compiles `desc` (nothing of it is referenced afterwards); host only.  NULL = ok; a refusal's message lives in a
+ * thread-local buffer until the calling thread's next refusal. */
+const char* bx_acc_program_create(const bx_acc_program_desc* desc, bx_acc_program** out);
+void bx_acc_program_destroy(bx_acc_program* prog);
+const char* bx_acc_program_info_get(const bx_acc_program* prog, bx_acc_program_info* out);
+/* kept column i < info.kept: its group (0 code, 1 data) and column */
+const char* bx_acc_program_kept(const bx_acc_program* prog, uint32_t i, uint32_t* group, uint32_t* col);
+/* Host executor, the reference for the device path: host arrays, column-major (code: w_code x N, data: w_data x N, accum: w_accum x N
+ * Montgomery words); `globals` holds the program's n_globals words (may be NULL when that is 0), `mix` four.  Writes accum columns
+ * [0, 4 S) and nothing else.  po2 in [1, 24].  Refused: a kept column that is not below its group's width, w_accum < 4 S. */
+const char* bx_acc_program_run_host(const bx_acc_program* prog, uint32_t po2, const uint32_t* code, uint32_t w_code, const uint32_t* data, uint32_t w_data,
+                                    const uint32_t* globals, const uint32_t mix[4], uint32_t* accum, uint32_t w_accum);
+/* Uploads the stream, the constants, the tap and kept tables once.  bx_free releases what is still loaded on its ctx. */
+const char* bx_acc_program_load(bx_ctx* ctx, const bx_acc_program* prog, bx_acc_program_dev** out);
+const char* bx_acc_program_unload(bx_acc_program_dev* dev);
+/* Gathers the K kept columns of `code` (w_code x N) and `data` (w_data x N) into `kept` (K x N, kept column i at words [i N, i N + N));
+ * one launch, does not block.  Refused with nothing enqueued: another ctx's program, po2 outside [1, 24], lengths that do not match,
+ * a kept column that is not below its group's width, `kept` sharing a byte with `code` or `data`. */
+const char* bx_acc_program_keep(bx_ctx* ctx, bx_acc_program_dev* dev, uint32_t po2, bx_buf code, uint32_t w_code, bx_buf data, uint32_t w_data, bx_buf kept);
+/* The whole stage from `kept`: terms, scans, columns [0, 4 S) of `accum` (w_accum x N); does not block.  `globals` is a HOST array of the
+ * program's n_globals words (may be NULL when that is 0).  run_ext (4 N S words, 16-byte aligned) and mults (N sums words) are the
+ * caller's work space.  Refused with nothing enqueued: another ctx's program, po2 outside [1, 24], kept.len != K N, run_ext.len != 4 N S,
+ * mults.len != N sums, accum.len != N w_accum, w_accum < 4 S, a misaligned run_ext, any two of run_ext, mults, accum and kept sharing a
+ * byte ("Operand overlap", bx_hal.h).  Each call writes `globals` and `mix` into a table that belongs to `dev`, on the ctx's stream: a
+ * loaded program serves one stream, its calls in order. */
+const char* bx_acc_program_run(bx_ctx* ctx, bx_acc_program_dev* dev, uint32_t po2, bx_buf kept, const uint32_t* globals, const uint32_t mix[4], bx_buf run_ext,
+                               bx_buf mults, bx_buf accum, uint32_t w_accum);
+/* The table's accumulate then comes from `acc` ("composite" above); its create loads the program on the ctx and refuses by name a kept
+ * column beyond the shape's widths, 4 S > w_accum, a global count other than the base's, and a base without accumulate when
+ * w_accum > 4 S.  NULL goes back to forwarding accumulate to `base` alone.  `acc` must outlive the table.  Set before a prover is created. */
+const char* bx_cons_circuit_set_accumulate(bx_cons_circuit* cc, const bx_acc_program* acc);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
