@@ -483,6 +483,10 @@ class WitProgramDesc(C.Structure):
                 ("cells", C.POINTER(WitGlobalCell)), ("n_cells", C.c_size_t)]
 
 
+class WitCount(C.Structure):
+    _fields_ = [("col", C.c_uint32), ("bins", C.c_uint32), ("rows", C.c_uint32), ("n_sources", C.c_uint32), ("sources", C.POINTER(C.c_uint32))]
+
+
 class WitProgramInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("steps", "sets", "narrow", "instructions", "taps", "cells")]
 
@@ -492,6 +496,10 @@ def _wit_lib():
     if not getattr(lib, "_wit_bound", False):
         u32p, vp = C.POINTER(C.c_uint32), C.c_void_p
         lib.bx_wit_program_create.argtypes = [C.POINTER(WitProgramDesc), C.POINTER(vp)]
+        lib.bx_wit_program_create_counted.argtypes = [C.POINTER(WitProgramDesc), C.POINTER(WitCount), C.c_size_t, C.POINTER(vp)]
+        lib.bx_wit_program_counts.argtypes = [vp]
+        lib.bx_wit_program_counts.restype = C.c_uint32
+        lib.bx_wit_program_count_get.argtypes = [vp, C.c_uint32, u32p, u32p, u32p, u32p, C.c_uint32, u32p]
         lib.bx_wit_program_destroy.argtypes = [vp]
         lib.bx_wit_program_destroy.restype = None
         lib.bx_wit_program_info_get.argtypes = [vp, C.POINTER(WitProgramInfo)]
@@ -509,7 +517,7 @@ def _wit_lib():
         lib.bx_wit_program_kernel_attached.argtypes = [vp]
         lib.bx_wit_program_kernel_attached.restype = C.c_int
         lib.bx_cons_circuit_set_witness_kernel.argtypes = [vp, C.c_char_p, C.c_size_t]
-        for name in ("bx_wit_program_create", "bx_wit_program_info_get", "bx_wit_program_run_host", "bx_wit_program_load", "bx_wit_program_unload",
+        for name in ("bx_wit_program_create", "bx_wit_program_create_counted", "bx_wit_program_count_get", "bx_wit_program_info_get", "bx_wit_program_run_host", "bx_wit_program_load", "bx_wit_program_unload",
                      "bx_wit_program_run", "bx_cons_circuit_set_witness", "bx_wit_program_digest", "bx_wit_program_emit_hip",
                      "bx_wit_program_attach_kernel", "bx_wit_program_detach_kernel", "bx_cons_circuit_set_witness_kernel"):
             getattr(lib, name).restype = C.c_char_p
@@ -531,6 +539,20 @@ class CompiledWitnessProgram:
 
     def derives(self, col):
         return bool(self.lib.bx_wit_program_derives(self.handle, int(col)))
+
+    def counts(self):
+        """the multiplicity columns as dicts {"col", "bins", "rows", "sources"}, in list order (bx_wit_program_count_get)"""
+        from .hal import HalError
+
+        out = []
+        col, bins, rows, n_src = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        src = (C.c_uint32 * 64)()  # BX_WIT_MAX_COUNT_SOURCES
+        for i in range(self.lib.bx_wit_program_counts(self.handle)):
+            msg = self.lib.bx_wit_program_count_get(self.handle, i, C.byref(col), C.byref(bins), C.byref(rows), src, 64, C.byref(n_src))
+            if msg:
+                raise HalError(msg.decode())
+            out.append({"col": int(col.value), "bins": int(bins.value), "rows": int(rows.value), "sources": [int(v) for v in src[:n_src.value]]})
+        return out
 
     def run_host(self, po2, code, w_code, data, w_data):
         """bx_wit_program_run_host: code (w_code x N) and data (w_data x N) are C-contiguous uint32 numpy arrays of Montgomery words;
@@ -618,7 +640,9 @@ class LoadedWitnessProgram:
 
 class WitnessProgram:
     """Builder of a witness program (include/bx_program.h, "Witness programs"): const / get / add / sub / mul append one step and
-    return the index of the fp var it made; set(col, var) stores a var into a data column, which makes that column derived.
+    return the index of the fp var it made; set(col, var) stores a var into a data column, which makes that column derived;
+    count(col, sources, bins, rows=0) makes `col` a multiplicity column ("multiplicity columns"): after every row has run,
+    data[col][r] = how many cells of the `sources` columns, rows [0, rows), hold the integer r, for r < bins (rows = 0: all rows).
 
         w = WitnessProgram()
         x = w.get(1, 0)
@@ -629,6 +653,7 @@ class WitnessProgram:
 
     def __init__(self):
         self.steps, self.tap_list, self._tap_index, self.cells = [], [], {}, []
+        self.count_list = []
         self.n_fp = 0
 
     def _fp(self, op, a=0, b=0):
@@ -665,6 +690,13 @@ class WitnessProgram:
     def global_cell(self, index, col, row):
         self.cells.append((int(index), int(col), int(row)))
 
+    def count(self, col, sources, bins, rows=0):
+        entry = (int(col), [int(s) for s in sources], int(bins), int(rows))
+        for v in (entry[0], entry[2], entry[3], *entry[1]):
+            if not 0 <= v < 1 << 32:  # the library takes 32-bit words: a value that would wrap into a valid one is an error here
+                raise ValueError(f"WitnessProgram.count: {v} is not a 32-bit unsigned value")
+        self.count_list.append(entry)
+
     def compile(self):
         """-> CompiledWitnessProgram.  A refusal raises HalError."""
         from .hal import HalError
@@ -675,7 +707,13 @@ class WitnessProgram:
         cells = (WitGlobalCell * max(len(self.cells), 1))(*[WitGlobalCell(*g) for g in self.cells])
         desc = WitProgramDesc(steps, len(self.steps), taps, len(self.tap_list), cells, len(self.cells))
         handle = C.c_void_p()
-        msg = lib.bx_wit_program_create(C.byref(desc), C.byref(handle))
+        if not self.count_list:
+            msg = lib.bx_wit_program_create(C.byref(desc), C.byref(handle))
+        else:
+            srcs = [(C.c_uint32 * max(len(s), 1))(*s) for _, s, _, _ in self.count_list]
+            counts = (WitCount * len(self.count_list))(*[WitCount(col, bins, rows, len(s), C.cast(a, C.POINTER(C.c_uint32)))
+                                                         for (col, s, bins, rows), a in zip(self.count_list, srcs)])
+            msg = lib.bx_wit_program_create_counted(C.byref(desc), counts, len(self.count_list), C.byref(handle))
         if msg:
             raise HalError(msg.decode())
         return CompiledWitnessProgram(lib, handle)

@@ -66,6 +66,14 @@ struct bx_cons_program {
     uint32_t max_col[3] = {0, 0, 0};  // 1 + the largest tap column per group (0 = the group is not named)
 };
 
+namespace bx {
+// one multiplicity column of a witness program ("multiplicity columns" of bx_program.h), as create validated it
+struct WitCount {
+    uint32_t col = 0, bins = 0, rows = 0;
+    std::vector<uint32_t> sources;
+};
+}  // namespace bx
+
 // A compiled witness program ("Witness programs" of bx_program.h): the same two-word instructions, of the narrow opcodes CP_LD_B,
 // CP_TAP, CP_ADD_BB, CP_SUB_BB, CP_MUL_BB and CP_ST only.  Its `scal` table is the constants alone (imm of CP_LD_B indexes `consts`).
 struct bx_wit_program {
@@ -77,6 +85,7 @@ struct bx_wit_program {
     std::vector<bx_wit_global_cell> cells;
     uint32_t max_col[2] = {0, 0};  // 1 + the largest tap column per group (0 = the group is not named)
     uint32_t max_set = 0;          // 1 + the largest SET column
+    std::vector<bx::WitCount> counts;  // run after the stream, in list order; not hashed, not emitted
 };
 
 // A compiled accumulate program ("Accumulate programs" of bx_program.h): the instructions of a constraint program without the mix
@@ -98,4 +107,8 @@ const char* acc_program_check_widths(const bx_acc_program* prog, const char* who
 // or a SET column (max_set) that is not below its group's width: one text for bx_wit_program_run_host, bx_wit_program_run and the
 // composite table's create
 const char* wit_program_check_widths(const uint32_t max_col[2], uint32_t max_set, const char* who, uint32_t w_code, uint32_t w_data);
+// cons_program_host.cpp: NULL, or the refusal (same buffer, led by `who`) of a count whose column or source is not below w_data, whose
+// rows are above N = 2^po2, or whose bins are above N when rows == 0: the shape-dependent part of a count list, one text for the same
+// three callers
+const char* wit_program_check_counts(const std::vector<WitCount>& counts, const char* who, uint32_t po2, uint32_t w_data);
 }  // namespace bx

@@ -281,7 +281,7 @@ struct WitVar {
     uint32_t slot = 0, last_use = 0;
 };
 
-const char* compile_wit(const bx_wit_program_desc* d, bx_wit_program* p) {
+const char* compile_wit(const bx_wit_program_desc* d, const bx_wit_count* counts, size_t n_counts, bx_wit_program* p) {
     if (d->n_steps > BX_CONS_MAX_STEPS) return refuse("wit_program: %zu steps, more than BX_CONS_MAX_STEPS = %d", d->n_steps, BX_CONS_MAX_STEPS);
     if (d->n_taps > BX_CONS_MAX_TAPS) return refuse("wit_program: %zu taps, more than BX_CONS_MAX_TAPS = %d", d->n_taps, BX_CONS_MAX_TAPS);
     if (d->n_cells > BX_MAX_GLOBALS) return refuse("wit_program: %zu global cells, more than BX_MAX_GLOBALS = %d", d->n_cells, BX_MAX_GLOBALS);
@@ -362,6 +362,52 @@ const char* compile_wit(const bx_wit_program_desc* d, bx_wit_program* p) {
         }
         fp.push_back(f);
     }
+
+    // ---- the count list ("multiplicity columns"): every rule but the shape-dependent ones (wit_program_check_counts); after the step list,
+    // so that a description with a bad step is refused for that step as before ----
+    if (n_counts > BX_WIT_MAX_COUNTS) return refuse("wit_program: %zu counts, more than BX_WIT_MAX_COUNTS = %d", n_counts, BX_WIT_MAX_COUNTS);
+    if (n_counts && !counts) return refuse("wit_program: null count list");
+    std::map<uint32_t, size_t> count_of, source_of;  // data column -> the first count that fills it / reads it
+    for (size_t k = 0; k < n_counts; ++k) {
+        const bx_wit_count& ct = counts[k];
+        if (ct.col > BX_CONS_MAX_COL) return refuse("wit_program: count %zu: data column %u out of range (at most %d)", k, ct.col, BX_CONS_MAX_COL);
+        if (ct.n_sources == 0) return refuse("wit_program: count %zu: no sources", k);
+        if (ct.n_sources > BX_WIT_MAX_COUNT_SOURCES)
+            return refuse("wit_program: count %zu: %u sources, more than BX_WIT_MAX_COUNT_SOURCES = %d", k, ct.n_sources, BX_WIT_MAX_COUNT_SOURCES);
+        if (!ct.sources) return refuse("wit_program: count %zu: null source list", k);
+        if (ct.bins == 0) return refuse("wit_program: count %zu: bins is 0", k);
+        if (ct.bins > BX_WIT_MAX_COUNT_BINS) return refuse("wit_program: count %zu: bins %u is above BX_WIT_MAX_COUNT_BINS = %u", k, ct.bins, BX_WIT_MAX_COUNT_BINS);
+        if (ct.rows > (1u << 24)) return refuse("wit_program: count %zu: rows %u is above 2^24, the largest trace", k, ct.rows);
+        if (ct.rows != 0 && ct.bins > ct.rows) return refuse("wit_program: count %zu: bins %u is above rows %u", k, ct.bins, ct.rows);
+        WitCount wc;
+        wc.col = ct.col, wc.bins = ct.bins, wc.rows = ct.rows;
+        for (uint32_t q = 0; q < ct.n_sources; ++q) {
+            const uint32_t src = ct.sources[q];
+            if (src > BX_CONS_MAX_COL) return refuse("wit_program: count %zu: source %u: data column %u out of range (at most %d)", k, q, src, BX_CONS_MAX_COL);
+            if (std::find(wc.sources.begin(), wc.sources.end(), src) != wc.sources.end())
+                return refuse("wit_program: count %zu: source column %u is named twice", k, src);
+            wc.sources.push_back(src);
+            source_of.emplace(src, k);
+        }
+        const auto ins = count_of.emplace(ct.col, k);
+        if (!ins.second) return refuse("wit_program: count %zu: data column %u is already the column of count %zu", k, ct.col, ins.first->second);
+        const auto st = set_at.find(ct.col);
+        if (st != set_at.end()) return refuse("wit_program: count %zu: data column %u is also SET (step %zu)", k, ct.col, st->second);
+        p->counts.push_back(std::move(wc));
+    }
+    for (size_t k = 0; k < p->counts.size(); ++k) {  // in list order: the first count whose column is a source is the one named
+        const auto src = source_of.find(p->counts[k].col);
+        if (src != source_of.end()) return refuse("wit_program: count %zu: data column %u is a source of count %zu", k, p->counts[k].col, src->second);
+    }
+    if (!count_of.empty())
+        for (size_t i = 0; i < d->n_steps; ++i) {
+            const bx_cons_step& s = d->steps[i];
+            if (s.op != BX_CONS_GET || s.a >= d->n_taps || d->taps[s.a].group != 1) continue;
+            const auto it = count_of.find(d->taps[s.a].col);
+            if (it != count_of.end())
+                return refuse("wit_program: count %zu: data column %u is read by the GET of step %zu: a multiplicity does not exist while the program runs", it->second,
+                              it->first, i);
+        }
 
     // ---- pass 2: slots by last use, and the stream ----
     SlotFile narrow;
@@ -626,6 +672,19 @@ const char* wit_program_check_widths(const uint32_t max_col[2], uint32_t max_set
     if (max_set > w_data) return refuse("%s: the program sets data column %u, the data group has %u columns", who, max_set - 1, w_data);
     return nullptr;
 }
+
+const char* wit_program_check_counts(const std::vector<WitCount>& counts, const char* who, uint32_t po2, uint32_t w_data) {
+    const uint32_t n = 1u << po2;
+    for (size_t k = 0; k < counts.size(); ++k) {
+        const WitCount& ct = counts[k];
+        if (ct.rows > n) return refuse("%s: count %zu: rows %u is above the trace's %u rows", who, k, ct.rows, n);
+        if (ct.rows == 0 && ct.bins > n) return refuse("%s: count %zu: bins %u is above the trace's %u rows (rows == 0 counts all of them)", who, k, ct.bins, n);
+        if (ct.col >= w_data) return refuse("%s: count %zu fills data column %u, the data group has %u columns", who, k, ct.col, w_data);
+        for (size_t q = 0; q < ct.sources.size(); ++q)
+            if (ct.sources[q] >= w_data) return refuse("%s: count %zu: source %zu is data column %u, the data group has %u columns", who, k, q, ct.sources[q], w_data);
+    }
+    return nullptr;
+}
 }  // namespace bx
 
 extern "C" const char* bx_cons_program_create(const bx_cons_program_desc* desc, bx_cons_program** out) try {
@@ -729,11 +788,11 @@ extern "C" const char* bx_cons_program_constraints_at(const bx_cons_program* pro
 }
 
 // ---- witness programs ----
-extern "C" const char* bx_wit_program_create(const bx_wit_program_desc* desc, bx_wit_program** out) try {
+extern "C" const char* bx_wit_program_create_counted(const bx_wit_program_desc* desc, const bx_wit_count* counts, size_t n_counts, bx_wit_program** out) try {
     if (!desc || !out) return "bx_wit_program_create: null argument";
     *out = nullptr;
     bx_wit_program* p = new bx_wit_program();
-    if (const char* e = bx::compile_wit(desc, p)) {
+    if (const char* e = bx::compile_wit(desc, counts, n_counts, p)) {
         delete p;
         return e;
     }
@@ -741,6 +800,21 @@ extern "C" const char* bx_wit_program_create(const bx_wit_program_desc* desc, bx
     return nullptr;
 } catch (...) {
     return "bx_wit_program_create: out of host memory";
+}
+
+extern "C" const char* bx_wit_program_create(const bx_wit_program_desc* desc, bx_wit_program** out) { return bx_wit_program_create_counted(desc, nullptr, 0, out); }
+
+extern "C" uint32_t bx_wit_program_counts(const bx_wit_program* prog) { return prog ? (uint32_t)prog->counts.size() : 0u; }
+
+extern "C" const char* bx_wit_program_count_get(const bx_wit_program* prog, uint32_t i, uint32_t* col, uint32_t* bins, uint32_t* rows, uint32_t* sources_out,
+                                                uint32_t cap, uint32_t* n_sources) {
+    if (!prog || !col || !bins || !rows || !n_sources || (cap && !sources_out)) return "bx_wit_program_count_get: null argument";
+    if (i >= prog->counts.size()) return "bx_wit_program_count_get: index is not below the number of counts";
+    const bx::WitCount& ct = prog->counts[i];
+    *col = ct.col, *bins = ct.bins, *rows = ct.rows;
+    *n_sources = (uint32_t)ct.sources.size();
+    for (uint32_t q = 0; q < cap && q < ct.sources.size(); ++q) sources_out[q] = ct.sources[q];
+    return nullptr;
 }
 
 extern "C" void bx_wit_program_destroy(bx_wit_program* prog) { delete prog; }
@@ -752,14 +826,19 @@ extern "C" const char* bx_wit_program_info_get(const bx_wit_program* prog, bx_wi
 }
 
 extern "C" int bx_wit_program_derives(const bx_wit_program* prog, uint32_t col) {
-    return prog && std::find(prog->sets.begin(), prog->sets.end(), col) != prog->sets.end() ? 1 : 0;
+    if (!prog) return 0;
+    if (std::find(prog->sets.begin(), prog->sets.end(), col) != prog->sets.end()) return 1;
+    for (const bx::WitCount& ct : prog->counts)
+        if (ct.col == col) return 1;
+    return 0;
 }
 
-extern "C" const char* bx_wit_program_run_host(const bx_wit_program* prog, uint32_t po2, const uint32_t* code, uint32_t w_code, uint32_t* data, uint32_t w_data) {
+extern "C" const char* bx_wit_program_run_host(const bx_wit_program* prog, uint32_t po2, const uint32_t* code, uint32_t w_code, uint32_t* data, uint32_t w_data) try {
     using namespace bx;
     if (!prog || (w_code && !code) || (w_data && !data)) return "bx_wit_program_run_host: null argument";
     if (po2 < 1 || po2 > 24) return "bx_wit_program_run_host: po2 must be in [1, 24]";
     if (const char* e = wit_program_check_widths(prog->max_col, prog->max_set, "bx_wit_program_run_host", w_code, w_data)) return e;
+    if (const char* e = wit_program_check_counts(prog->counts, "bx_wit_program_run_host", po2, w_data)) return e;
     const size_t n = (size_t)1 << po2;
     // rows in any order: no row reads a word this run writes (derived cells are forwarded, never loaded)
     for (size_t r = 0; r < n; ++r) {
@@ -785,7 +864,20 @@ extern "C" const char* bx_wit_program_run_host(const bx_wit_program* prog, uint3
             }
         }
     }
+    // the counts, in list order, after every row: the device path's twin (clear, histogram over rows [0, rows), store)
+    for (const WitCount& ct : prog->counts) {
+        const size_t rows = ct.rows ? ct.rows : n;
+        std::vector<uint32_t> bins(ct.bins, 0u);
+        for (uint32_t src : ct.sources)
+            for (size_t j = 0; j < rows; ++j) {
+                const uint32_t v = fp_decode(data[(size_t)src * n + j]);
+                if (v < ct.bins) ++bins[v];  // at most 64 * 2^24 = 2^30 < P: no wrap, no reduction
+            }
+        for (size_t r = 0; r < rows; ++r) data[(size_t)ct.col * n + r] = r < ct.bins ? fp_mul(R2, bins[r]) : 0u;
+    }
     return nullptr;
+} catch (...) {
+    return "bx_wit_program_run_host: out of host memory";
 }
 
 // ---- accumulate programs ----

@@ -118,6 +118,7 @@ extern "C" const char* bx_wit_program_load(bx_ctx* c, const bx_wit_program* prog
     if (!prog->code.empty()) BX_HIP(c, hipMemcpyAsync(d->code.b.dptr, prog->code.data(), prog->code.size() * 4, hipMemcpyHostToDevice, c->stream));
     if (!tapw.empty()) BX_HIP(c, hipMemcpyAsync(d->taps.b.dptr, tapw.data(), tapw.size() * 4, hipMemcpyHostToDevice, c->stream));
     if (!prog->consts.empty()) BX_HIP(c, hipMemcpyAsync(d->consts.b.dptr, prog->consts.data(), prog->consts.size() * 4, hipMemcpyHostToDevice, c->stream));
+    BX_TRY(wit_counts_load(c, d.get(), prog));  // the multiplicity columns' source table and counters (wit_count.hip)
     BX_HIP(c, stream_wait(c));  // the host vectors go away
     {
         std::lock_guard<std::mutex> g(g_loaded_mu);
@@ -160,12 +161,18 @@ extern "C" const char* bx_wit_program_run(bx_ctx* c, bx_wit_program_dev* dev, ui
     BX_REQUIRE(c, code.len == n * w_code && data.len == n * w_data, "bx_wit_program_run: buffer size mismatch (groups N x width)");
     if (const char* e = wit_program_check_widths(dev->max_col, dev->max_set, "bx_wit_program_run", w_code, w_data)) return set_msg(c, e);
     BX_REQUIRE(c, !bufs_overlap(code, data), "bx_wit_program_run: code and data overlap");
-    if (dev->gen_fn) return wit_gen_launch(c, dev, po2, code, data);  // the generated kernel, when one is attached
-    // every tap is read once, every derived column written once
-    OpScope op(c, "wit_program_run", 4.0 * (double)n * ((double)dev->info.taps + (double)dev->info.sets));
-    hipLaunchKernelGGL(wit_program_kernel, dim3((unsigned)((n + WP_LANES - 1) / WP_LANES)), dim3(WP_LANES), dev->lds, c->stream, (uint32_t*)data.dptr,
-                       (const uint32_t*)code.dptr, (const uint4*)dev->code.b.dptr, (const uint2*)dev->taps.b.dptr, (const uint32_t*)dev->consts.b.dptr, (uint32_t)n,
-                       dev->n_fetch);
-    BX_LAUNCH_CHECK(c);
-    return nullptr;
+    if (const char* e = wit_program_check_counts(dev->counts, "bx_wit_program_run", po2, w_data)) return set_msg(c, e);
+    if (dev->gen_fn) {  // the generated kernel, when one is attached
+        BX_TRY(wit_gen_launch(c, dev, po2, code, data));
+        return wit_counts_run(c, dev, po2, data);
+    }
+    {
+        // every tap is read once, every derived column written once
+        OpScope op(c, "wit_program_run", 4.0 * (double)n * ((double)dev->info.taps + (double)dev->info.sets));
+        hipLaunchKernelGGL(wit_program_kernel, dim3((unsigned)((n + WP_LANES - 1) / WP_LANES)), dim3(WP_LANES), dev->lds, c->stream, (uint32_t*)data.dptr,
+                           (const uint32_t*)code.dptr, (const uint4*)dev->code.b.dptr, (const uint2*)dev->taps.b.dptr, (const uint32_t*)dev->consts.b.dptr,
+                           (uint32_t)n, dev->n_fetch);
+        BX_LAUNCH_CHECK(c);
+    }
+    return wit_counts_run(c, dev, po2, data);  // the multiplicity columns, after every row (wit_count.hip)
 } BX_ABI_CATCH(c, "bx_wit_program_run")

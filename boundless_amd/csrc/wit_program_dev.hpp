@@ -14,6 +14,12 @@ struct bx_wit_program_dev {
     uint32_t digest[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // bx_wit_program_digest of the program this was loaded from
     hipModule_t gen_module = nullptr;
     hipFunction_t gen_fn = nullptr;
+    // the multiplicity columns (wit_count.hip): the program's counts, where each one's sources start in the flat table and its bins
+    // in the counters (sum of bins words), and the two on the device
+    std::vector<bx::WitCount> counts;
+    std::vector<size_t> count_src_off, count_bin_off;
+    std::vector<uint32_t> count_flat;
+    bx::DevBuf count_sources, count_bins;
 };
 
 namespace bx {
@@ -21,4 +27,8 @@ namespace bx {
 void wit_gen_release(bx_wit_program_dev* dev);
 // ... and launch it: the caller (bx_wit_program_run) has checked the arguments
 const char* wit_gen_launch(bx_ctx* c, bx_wit_program_dev* dev, uint32_t po2, bx_buf code, bx_buf data);
+// wit_count.hip: upload the flat source table and allocate the counters (no-op without counts; the caller waits for the stream) ...
+const char* wit_counts_load(bx_ctx* c, bx_wit_program_dev* dev, const bx_wit_program* prog);
+// ... and per count clear, histogram, store on the ctx's stream: the caller (bx_wit_program_run) has checked the counts against the shape
+const char* wit_counts_run(bx_ctx* c, bx_wit_program_dev* dev, uint32_t po2, bx_buf data);
 }  // namespace bx

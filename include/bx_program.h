@@ -125,6 +125,45 @@
  *                data[column][row] as it stands in the buffer, a Montgomery word.  Index < BX_MAX_GLOBALS, each index at most once
  *                (refused at create).  `row` is checked against N when a prover is created: the list is the one shape-dependent
  *                part of a description.
+ *   multiplicity columns (normative; bx_wit_program_create_counted)
+ *                m(r) = "how many looked-up cells hold table entry r" is a histogram over whole columns: no step list can give it,
+ *                because a lane may not read what other lanes write.  A witness program therefore has an optional list of at most
+ *                BX_WIT_MAX_COUNTS = 16 COUNTS (col, bins, rows, sources[]):
+ *                  col      the data column that receives the multiplicities
+ *                  sources  1 .. BX_WIT_MAX_COUNT_SOURCES = 64 data columns.  With rows <= 2^24 a count is at most 2^30 < P: a
+ *                           uint32_t bin never wraps and no reduction is needed
+ *                  rows     only rows r < rows are counted and written; rows == 0 means all N.  Rows at or above `rows` are neither
+ *                           read nor written: they keep what the base's witgen left (the lookup circuit's noise rows)
+ *                  bins     B, 1 <= B <= rows, not necessarily a power of two, at most BX_WIT_MAX_COUNT_BINS = 2^24
+ *                Meaning: let c(v) be the number of pairs (source column s, row j < rows) whose cell, decoded from Montgomery
+ *                form, is the integer v.  After the run data[col][r] holds the value c(r) as a Montgomery word for r < B and the
+ *                value 0 for B <= r < rows.  A source cell that decodes to a value >= B is not counted (bx_lookup.h's rule: the
+ *                prover does not judge the witness).
+ *                Order: all counts run after the per-row program, in list order, on the same stream; a source may therefore be a
+ *                free column or a SET column.
+ *                Refused by name at create: a count column that is also SET; a count column named by any GET (its value does not
+ *                exist while the program runs); a count column that is a source of any count, or the column of two counts; `col` or
+ *                a source above BX_CONS_MAX_COL; no sources, or more than 64; a source named twice within one count; bins == 0,
+ *                bins > 2^24, rows > 2^24, or rows != 0 && bins > rows; more than 16 counts.
+ *                A global cell may name a count column (cells are read after the counts), and an accumulate program may tap one
+ *                (`keep` runs after the counts).  A program may consist of counts alone.
+ *                `rows` and `bins` against N are shape-dependent, like a cell's row: rows > N, or bins > N with rows == 0, is
+ *                refused by name when the program runs and when a prover is created, as is a count column or a source that is not
+ *                below the data group's width.
+ *                The counts are NOT hashed by bx_wit_program_digest and play no part in bx_wit_program_emit_hip, for the reason the
+ *                global cells are not: the per-row kernel does not depend on them, so one code object serves a program under any
+ *                count list.  With a kernel attached, bx_wit_program_run launches it and then runs the counts exactly as it does
+ *                after the interpreter.
+ *                Host: bx_wit_program_run_host runs the counts after the stream with plain loops; counts are integers, so there is
+ *                no ordering question and host and device agree word for word.
+ *                Device (csrc/wit_count.hip), per count and without blocking: (1) the count's bins are cleared; (2) a histogram
+ *                directly over the source columns of `data`, rows [0, rows), with no gathered copy, profiled as
+ *                "wit_program_count"; (3) a store to rows [0, rows) of `col`, profiled as "wit_program_count_store".  The histogram
+ *                has two forms: for B <= 32 768 (4 B <= 128 KiB) per-workgroup bins in dynamic LDS, 1024 lanes, every non-zero bin
+ *                flushed with one global atomic; above that, or with the ctx tunable lookup_hist_lds = 0, global atomics.  In both
+ *                the lanes of a wave that hit the first live lane's bin are counted with one ballot and added by one lane.
+ *                Out of scope: tables whose entries are not indexed by row (a tuple lookup supplies the index as a source column),
+ *                weighted counts, counting code columns.
  *   compiled     the instruction stream of a constraint program restricted to the narrow opcodes, plus one: a store of a
  *                narrow slot to a data column.  bx_wit_program_run_host and the device kernel read the same stream and use the
  *                same canonical arithmetic, so they give identical words.
@@ -260,6 +299,9 @@ extern "C" {
 #define BX_CONS_MAX_NARROW 32   /* live base values */
 #define BX_CONS_MAX_WIDE 24     /* live ext values and mix tots */
 #define BX_ACC_MAX_SEQS 1024    /* sequences of one accumulate program */
+#define BX_WIT_MAX_COUNTS 16    /* multiplicity columns of one witness program */
+#define BX_WIT_MAX_COUNT_SOURCES 64       /* source columns of one count */
+#define BX_WIT_MAX_COUNT_BINS (1u << 24) /* bins of one count */
 
 enum bx_cons_op {
     BX_CONS_CONST = 0,
@@ -397,22 +439,41 @@ typedef struct bx_wit_program_dev bx_wit_program_dev; /* ... loaded on a ctx */
 const char* bx_wit_program_create(const bx_wit_program_desc* desc, bx_wit_program** out);
 void bx_wit_program_destroy(bx_wit_program* prog);
 const char* bx_wit_program_info_get(const bx_wit_program* prog, bx_wit_program_info* out);
-/* 1 if the program sets data column `col`, else 0 */
+/* 1 if the program sets data column `col` or fills it as a multiplicity column, else 0 */
 int bx_wit_program_derives(const bx_wit_program* prog, uint32_t col);
+/* Multiplicity columns ("multiplicity columns" above).  One count: data[col][r] = the number of cells of the `sources` columns, rows
+ * [0, rows), that hold the integer r, for r < bins; 0 for bins <= r < rows; rows == 0 means all N rows. */
+typedef struct bx_wit_count {
+    uint32_t col, bins, rows, n_sources;
+    const uint32_t* sources;
+} bx_wit_count;
+/* bx_wit_program_create with a count list (nothing of it is referenced afterwards); with n_counts == 0 it is exactly
+ * bx_wit_program_create. */
+const char* bx_wit_program_create_counted(const bx_wit_program_desc* desc, const bx_wit_count* counts, size_t n_counts, bx_wit_program** out);
+/* the number of counts */
+uint32_t bx_wit_program_counts(const bx_wit_program* prog);
+/* count i: its column, bins and rows, the number of its sources in *n_sources and the first min(cap, *n_sources) of them in
+ * sources_out (which may be NULL when cap is 0) */
+const char* bx_wit_program_count_get(const bx_wit_program* prog, uint32_t i, uint32_t* col, uint32_t* bins, uint32_t* rows, uint32_t* sources_out, uint32_t cap,
+                                     uint32_t* n_sources);
 /* Host executor, the reference for the device kernel: the compiled stream over the N = 2^po2 rows of host arrays, column-major
- * (code: w_code x N, data: w_data x N Montgomery words), `data` in place.  po2 in [1, 24].  Refused: a tap or SET column that is
- * not below its group's width.  No mutable global state. */
+ * (code: w_code x N, data: w_data x N Montgomery words), `data` in place; the counts after the stream.  po2 in [1, 24].  Refused
+ * with nothing written: a tap or SET column that is not below its group's width, a count column or source that is not below w_data,
+ * a count's rows > N, or bins > N with rows == 0.  No mutable global state. */
 const char* bx_wit_program_run_host(const bx_wit_program* prog, uint32_t po2, const uint32_t* code, uint32_t w_code, uint32_t* data, uint32_t w_data);
-/* Uploads the stream, the constants and the tap descriptors once.  bx_free releases what is still loaded on its ctx. */
+/* Uploads the stream, the constants, the tap descriptors and the counts' source table once, and allocates the counts' bins.
+ * bx_free releases what is still loaded on its ctx. */
 const char* bx_wit_program_load(bx_ctx* ctx, const bx_wit_program* prog, bx_wit_program_dev** out);
 const char* bx_wit_program_unload(bx_wit_program_dev* dev);
-/* Derives the program's columns of `data` on the ctx's stream; does not block.  po2 in [1, 24], code.len == w_code * N,
- * data.len == w_data * N.  Refused: lengths that do not match, a tap or SET column that is not below its group's width, `code`
- * and `data` sharing a byte ("Operand overlap", bx_hal.h). */
+/* Derives the program's columns of `data` on the ctx's stream, then fills its multiplicity columns; does not block.  po2 in
+ * [1, 24], code.len == w_code * N, data.len == w_data * N.  Refused with nothing enqueued: lengths that do not match, a tap or SET
+ * column that is not below its group's width, `code` and `data` sharing a byte ("Operand overlap", bx_hal.h), and then a count
+ * column or source that is not below w_data, a count's rows > N, or bins > N with rows == 0.  The bins belong to `dev`: a loaded
+ * program serves one stream, its calls in order. */
 const char* bx_wit_program_run(bx_ctx* ctx, bx_wit_program_dev* dev, uint32_t po2, bx_buf code, uint32_t w_code, bx_buf data, uint32_t w_data);
 /* The table's witgen then runs `wit` after base->witgen and takes the global cells from the trace ("composite" above); its create
- * loads the program on the ctx and refuses by name a SET or tap column beyond the shape's widths, a cell row >= N and a cell index
- * >= the base's n_globals.  NULL goes back to forwarding witgen to `base` alone.  `wit` must outlive the table.  Set before a
+ * loads the program on the ctx and refuses by name a SET or tap column beyond the shape's widths, a cell row >= N, a cell index
+ * >= the base's n_globals, a count column or source beyond w_data and a count's rows or bins above N.  NULL goes back to forwarding witgen to `base` alone.  `wit` must outlive the table.  Set before a
  * prover is created. */
 const char* bx_cons_circuit_set_witness(bx_cons_circuit* cc, const bx_wit_program* wit);
 
