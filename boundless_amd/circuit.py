@@ -216,18 +216,115 @@ def _u32x(words, n=None):
     return (C.c_uint32 * max(len(words), 1))(*words)
 
 
-class CompiledConsProgram:
+class _CompiledProgram:
+    """What the compiled handles of the three program kinds share (bx_<kind>_program): host only until `load`ed on a HipHal.  A
+    subclass names its kind, its info structure and its loaded class."""
+
+    _KIND = _INFO = _LOADED = None
+
+    def _fn(self, name):
+        return getattr(self.lib, f"bx_{self._KIND}_program_{name}")
+
+    def info(self):
+        out = self._INFO()
+        msg = self._fn("info_get")(self.handle, C.byref(out))
+        assert not msg, msg
+        return {n: int(getattr(out, n)) for n, _ in self._INFO._fields_}
+
+    def load(self, hal):
+        dev = C.c_void_p()
+        hal._check(self._fn("load")(hal.ctx, self.handle, C.byref(dev)))
+        return self._LOADED(self, hal, dev)
+
+    def close(self):
+        if self.handle:
+            self._fn("destroy")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _EmitsKernel:
+    """... of the kinds a kernel can be generated for: the digest a generated kernel carries, and its text"""
+
+    def digest(self):
+        """bx_<kind>_program_digest as 64 hex digits (the 32 bytes in order): what a generated kernel carries and attach compares"""
+        from .hal import HalError
+
+        out = (C.c_uint32 * 8)()
+        msg = self._fn("digest")(self.handle, out)
+        if msg:
+            raise HalError(msg.decode())
+        return b"".join(int(w).to_bytes(4, "little") for w in out).hex()
+
+    def emit_hip(self):
+        """bx_<kind>_program_emit_hip: the generated translation unit as text (boundless_amd.consgen compiles it)"""
+        from .hal import HalError
+
+        need = C.c_size_t(0)
+        msg = self._fn("emit_hip")(self.handle, None, 0, C.byref(need))
+        if msg:
+            raise HalError(msg.decode())
+        buf = C.create_string_buffer(need.value)
+        msg = self._fn("emit_hip")(self.handle, buf, need.value, C.byref(need))
+        if msg:
+            raise HalError(msg.decode())
+        return buf.value.decode()
+
+
+class _LoadedProgram:
+    """What the loaded handles share (bx_<kind>_program_dev)."""
+
+    def __init__(self, program, hal, dev):
+        self.program, self.hal, self.dev = program, hal, dev
+
+    def unload(self):
+        if self.dev:
+            dev, self.dev = self.dev, None
+            self.hal._check(self.program._fn("unload")(dev))
+
+
+class _AttachesKernel:
+    """... of the kinds a kernel can be generated for"""
+
+    def attach_kernel(self, path_or_bytes):
+        """bx_<kind>_program_attach_kernel: a code object built by boundless_amd.consgen for THIS program (a path, or its bytes); the
+        program's launches then run it instead of the interpreter.  A refusal raises HalError."""
+        image = _kernel_image(path_or_bytes)
+        self.hal._check(self.program._fn("attach_kernel")(self.dev, image, len(image)))
+
+    def detach_kernel(self):
+        self.hal._check(self.program._fn("detach_kernel")(self.dev))
+
+    @property
+    def kernel_attached(self):
+        return bool(self.dev) and bool(self.program._fn("kernel_attached")(self.dev))
+
+
+def _kernel_image(path_or_bytes):
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        return bytes(path_or_bytes)
+    with open(path_or_bytes, "rb") as f:
+        return f.read()
+
+
+class LoadedConsProgram(_LoadedProgram, _AttachesKernel):
+    """A constraint program on a ctx (bx_cons_program_dev); hal.cons_program_eval_check runs it."""
+
+
+class CompiledConsProgram(_CompiledProgram, _EmitsKernel):
     """A compiled constraint program (bx_cons_program): host only until `load`ed on a HipHal."""
+
+    _KIND, _INFO, _LOADED = "cons", ConsProgramInfo, LoadedConsProgram
 
     def __init__(self, lib, handle, n_globals):
         self.lib, self.handle, self.n_globals = lib, handle, n_globals
 
-    @property
-    def info(self):
-        out = ConsProgramInfo()
-        msg = self.lib.bx_cons_program_info_get(self.handle, C.byref(out))
-        assert not msg, msg
-        return {n: int(getattr(out, n)) for n, _ in ConsProgramInfo._fields_}
+    info = property(_CompiledProgram.info)
 
     def taps(self, group, col):
         out = (C.c_uint32 * MAX_TAPS)()
@@ -259,78 +356,6 @@ class CompiledConsProgram:
         if msg:
             raise HalError(msg.decode())
         return list(out)
-
-    def digest(self):
-        """bx_cons_program_digest as 64 hex digits (the 32 bytes in order): what a generated kernel carries and attach compares"""
-        from .hal import HalError
-
-        out = (C.c_uint32 * 8)()
-        msg = self.lib.bx_cons_program_digest(self.handle, out)
-        if msg:
-            raise HalError(msg.decode())
-        return b"".join(int(w).to_bytes(4, "little") for w in out).hex()
-
-    def emit_hip(self):
-        """bx_cons_program_emit_hip: the generated translation unit as text (boundless_amd.consgen compiles it)"""
-        from .hal import HalError
-
-        need = C.c_size_t(0)
-        msg = self.lib.bx_cons_program_emit_hip(self.handle, None, 0, C.byref(need))
-        if msg:
-            raise HalError(msg.decode())
-        buf = C.create_string_buffer(need.value)
-        msg = self.lib.bx_cons_program_emit_hip(self.handle, buf, need.value, C.byref(need))
-        if msg:
-            raise HalError(msg.decode())
-        return buf.value.decode()
-
-    def load(self, hal):
-        dev = C.c_void_p()
-        hal._check(self.lib.bx_cons_program_load(hal.ctx, self.handle, C.byref(dev)))
-        return LoadedConsProgram(self, hal, dev)
-
-    def close(self):
-        if self.handle:
-            self.lib.bx_cons_program_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class LoadedConsProgram:
-    """A constraint program on a ctx (bx_cons_program_dev); hal.cons_program_eval_check runs it."""
-
-    def __init__(self, program, hal, dev):
-        self.program, self.hal, self.dev = program, hal, dev
-
-    def unload(self):
-        if self.dev:
-            dev, self.dev = self.dev, None
-            self.hal._check(self.program.lib.bx_cons_program_unload(dev))
-
-    def attach_kernel(self, path_or_bytes):
-        """bx_cons_program_attach_kernel: a code object built by boundless_amd.consgen for THIS program (a path, or its bytes);
-        hal.cons_program_eval_check then launches it instead of the interpreter.  A refusal raises HalError."""
-        image = _kernel_image(path_or_bytes)
-        self.hal._check(self.program.lib.bx_cons_program_attach_kernel(self.dev, image, len(image)))
-
-    def detach_kernel(self):
-        self.hal._check(self.program.lib.bx_cons_program_detach_kernel(self.dev))
-
-    @property
-    def kernel_attached(self):
-        return bool(self.dev) and bool(self.program.lib.bx_cons_program_kernel_attached(self.dev))
-
-
-def _kernel_image(path_or_bytes):
-    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
-        return bytes(path_or_bytes)
-    with open(path_or_bytes, "rb") as f:
-        return f.read()
 
 
 class ConsProgram:
@@ -525,17 +550,20 @@ def _wit_lib():
     return lib
 
 
-class CompiledWitnessProgram:
+class LoadedWitnessProgram(_LoadedProgram, _AttachesKernel):
+    """A witness program on a ctx (bx_wit_program_dev); hal.wit_program_run runs it."""
+
+    def run(self, po2, code, w_code, data, w_data):
+        self.hal.wit_program_run(self, po2, code, w_code, data, w_data)
+
+
+class CompiledWitnessProgram(_CompiledProgram, _EmitsKernel):
     """A compiled witness program (bx_wit_program): host only until `load`ed on a HipHal."""
+
+    _KIND, _INFO, _LOADED = "wit", WitProgramInfo, LoadedWitnessProgram
 
     def __init__(self, lib, handle):
         self.lib, self.handle = lib, handle
-
-    def info(self):
-        out = WitProgramInfo()
-        msg = self.lib.bx_wit_program_info_get(self.handle, C.byref(out))
-        assert not msg, msg
-        return {n: int(getattr(out, n)) for n, _ in WitProgramInfo._fields_}
 
     def derives(self, col):
         return bool(self.lib.bx_wit_program_derives(self.handle, int(col)))
@@ -568,74 +596,6 @@ class CompiledWitnessProgram:
         msg = self.lib.bx_wit_program_run_host(self.handle, po2, code.ctypes.data_as(u32p), w_code, data.ctypes.data_as(u32p), w_data)
         if msg:
             raise HalError(msg.decode())
-
-    def digest(self):
-        """bx_wit_program_digest as 64 hex digits (the 32 bytes in order): what a generated kernel carries and attach compares"""
-        from .hal import HalError
-
-        out = (C.c_uint32 * 8)()
-        msg = self.lib.bx_wit_program_digest(self.handle, out)
-        if msg:
-            raise HalError(msg.decode())
-        return b"".join(int(w).to_bytes(4, "little") for w in out).hex()
-
-    def emit_hip(self):
-        """bx_wit_program_emit_hip: the generated translation unit as text (boundless_amd.consgen --witness compiles it)"""
-        from .hal import HalError
-
-        need = C.c_size_t(0)
-        msg = self.lib.bx_wit_program_emit_hip(self.handle, None, 0, C.byref(need))
-        if msg:
-            raise HalError(msg.decode())
-        buf = C.create_string_buffer(need.value)
-        msg = self.lib.bx_wit_program_emit_hip(self.handle, buf, need.value, C.byref(need))
-        if msg:
-            raise HalError(msg.decode())
-        return buf.value.decode()
-
-    def load(self, hal):
-        dev = C.c_void_p()
-        hal._check(self.lib.bx_wit_program_load(hal.ctx, self.handle, C.byref(dev)))
-        return LoadedWitnessProgram(self, hal, dev)
-
-    def close(self):
-        if self.handle:
-            self.lib.bx_wit_program_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class LoadedWitnessProgram:
-    """A witness program on a ctx (bx_wit_program_dev); hal.wit_program_run runs it."""
-
-    def __init__(self, program, hal, dev):
-        self.program, self.hal, self.dev = program, hal, dev
-
-    def run(self, po2, code, w_code, data, w_data):
-        self.hal.wit_program_run(self, po2, code, w_code, data, w_data)
-
-    def unload(self):
-        if self.dev:
-            dev, self.dev = self.dev, None
-            self.hal._check(self.program.lib.bx_wit_program_unload(dev))
-
-    def attach_kernel(self, path_or_bytes):
-        """bx_wit_program_attach_kernel: a code object built by boundless_amd.consgen --witness for THIS program (a path, or its
-        bytes); run then launches it instead of the interpreter.  A refusal raises HalError."""
-        image = _kernel_image(path_or_bytes)
-        self.hal._check(self.program.lib.bx_wit_program_attach_kernel(self.dev, image, len(image)))
-
-    def detach_kernel(self):
-        self.hal._check(self.program.lib.bx_wit_program_detach_kernel(self.dev))
-
-    @property
-    def kernel_attached(self):
-        return bool(self.dev) and bool(self.program.lib.bx_wit_program_kernel_attached(self.dev))
 
 
 class WitnessProgram:
@@ -754,17 +714,23 @@ def _acc_lib():
     return lib
 
 
-class CompiledAccumulateProgram:
+class LoadedAccumulateProgram(_LoadedProgram):
+    """An accumulate program on a ctx (bx_acc_program_dev); hal.acc_program_keep / hal.acc_program_run run it."""
+
+    def keep(self, po2, code, w_code, data, w_data, kept):
+        self.hal.acc_program_keep(self, po2, code, w_code, data, w_data, kept)
+
+    def run(self, po2, kept, globals_, mix, run_ext, mults, accum, w_accum):
+        self.hal.acc_program_run(self, po2, kept, globals_, mix, run_ext, mults, accum, w_accum)
+
+
+class CompiledAccumulateProgram(_CompiledProgram):
     """A compiled accumulate program (bx_acc_program): host only until `load`ed on a HipHal."""
+
+    _KIND, _INFO, _LOADED = "acc", AccProgramInfo, LoadedAccumulateProgram
 
     def __init__(self, lib, handle, n_globals):
         self.lib, self.handle, self.n_globals = lib, handle, n_globals
-
-    def info(self):
-        out = AccProgramInfo()
-        msg = self.lib.bx_acc_program_info_get(self.handle, C.byref(out))
-        assert not msg, msg
-        return {n: int(getattr(out, n)) for n, _ in AccProgramInfo._fields_}
 
     def kept(self):
         """the kept columns as (group, col), in kept order: what `keep` copies and the taps read"""
@@ -794,40 +760,6 @@ class CompiledAccumulateProgram:
                                                accum.ctypes.data_as(u32p), w_accum)
         if msg:
             raise HalError(msg.decode())
-
-    def load(self, hal):
-        dev = C.c_void_p()
-        hal._check(self.lib.bx_acc_program_load(hal.ctx, self.handle, C.byref(dev)))
-        return LoadedAccumulateProgram(self, hal, dev)
-
-    def close(self):
-        if self.handle:
-            self.lib.bx_acc_program_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class LoadedAccumulateProgram:
-    """An accumulate program on a ctx (bx_acc_program_dev); hal.acc_program_keep / hal.acc_program_run run it."""
-
-    def __init__(self, program, hal, dev):
-        self.program, self.hal, self.dev = program, hal, dev
-
-    def keep(self, po2, code, w_code, data, w_data, kept):
-        self.hal.acc_program_keep(self, po2, code, w_code, data, w_data, kept)
-
-    def run(self, po2, kept, globals_, mix, run_ext, mults, accum, w_accum):
-        self.hal.acc_program_run(self, po2, kept, globals_, mix, run_ext, mults, accum, w_accum)
-
-    def unload(self):
-        if self.dev:
-            dev, self.dev = self.dev, None
-            self.hal._check(self.program.lib.bx_acc_program_unload(dev))
 
 
 class AccumulateProgram(ConsProgram):

@@ -12,11 +12,8 @@
 //   memory    a tap is kept[k N + ((r - back) & (N - 1))].  A term is ONE 16-byte store at run_ext[4 (s N + r)] — a base value is
 //             promoted to (v, 0, 0, 0) — so a wave writes 1 KiB contiguous; a sum also writes one word at mults[s N + r]
 #define BX_PLAIN_MAD 1
-#include <map>
 #include <memory>
-#include <mutex>
 #include <new>
-#include <set>
 #include <vector>
 
 #include "acc_program_dev.hpp"
@@ -90,8 +87,7 @@ __global__ __launch_bounds__(256) void acc_program_kernel(uint32_t* __restrict__
 }
 
 namespace {
-std::mutex g_loaded_mu;
-std::map<bx_ctx*, std::set<bx_acc_program_dev*>> g_loaded;  // what bx_free still has to release
+LoadedPrograms<bx_acc_program_dev> g_loaded;  // what bx_free still has to release
 
 // the compiler refuses what does not fit; a stream from anywhere else must not reach the kernel: every slot, table index and
 // sequence number of the stream against the program's own counts
@@ -139,15 +135,7 @@ bool stream_fits(const bx_acc_program* p) {
 }  // namespace
 
 void acc_programs_release(bx_ctx* c) {
-    std::set<bx_acc_program_dev*> ds;
-    {
-        std::lock_guard<std::mutex> g(g_loaded_mu);
-        auto it = g_loaded.find(c);
-        if (it == g_loaded.end()) return;
-        ds.swap(it->second);
-        g_loaded.erase(it);
-    }
-    for (bx_acc_program_dev* d : ds) delete d;  // the caller has drained the stream
+    for (bx_acc_program_dev* d : g_loaded.take_all(c)) delete d;  // the caller has drained the stream
 }
 }  // namespace bx
 
@@ -164,34 +152,22 @@ extern "C" const char* bx_acc_program_load(bx_ctx* c, const bx_acc_program* prog
     d->n_fetch = (uint32_t)(prog->code.size() / (2 * CP_FETCH));
     d->kept_cols = prog->kept;
     d->lds = (size_t)(prog->info.narrow + 4 * prog->info.wide) * CP_LANES * 4;
-    const size_t n_scal = prog->info.n_globals + 4 + prog->consts.size();
-    BX_TRY(d->code.alloc(c, prog->code.size() ? prog->code.size() : 1));
-    BX_TRY(d->taps.alloc(c, prog->taps.empty() ? 2 : 2 * prog->taps.size()));
+    BX_TRY(upload_program(
+        c, d->code, d->taps, d->scal, prog->code, prog->taps,
+        [&](uint32_t* w, size_t t, const bx_cons_tap& tp) { w[0] = prog->tap_kept[t], w[1] = tp.back; }, prog->consts, prog->info.n_globals + 4));
+    // the kept table, after everything above is allocated and has landed: no copy is ever in flight when an allocation fails
     BX_TRY(d->kept.alloc(c, prog->kept.empty() ? 2 : 2 * prog->kept.size()));
-    BX_TRY(d->scal.alloc(c, n_scal));
-    std::vector<uint32_t> tapw(2 * prog->taps.size()), keptw(2 * prog->kept.size()), scal(n_scal, 0u);
-    for (size_t t = 0; t < prog->taps.size(); ++t) {
-        tapw[2 * t] = prog->tap_kept[t];
-        tapw[2 * t + 1] = prog->taps[t].back;
-    }
+    std::vector<uint32_t> keptw(2 * prog->kept.size());
     for (size_t k = 0; k < prog->kept.size(); ++k) {
         keptw[2 * k] = prog->kept[k].group;
         keptw[2 * k + 1] = prog->kept[k].col;
     }
-    std::copy(prog->consts.begin(), prog->consts.end(), scal.begin() + prog->info.n_globals + 4);
-    if (!prog->code.empty()) BX_HIP(c, hipMemcpyAsync(d->code.b.dptr, prog->code.data(), prog->code.size() * 4, hipMemcpyHostToDevice, c->stream));
-    if (!tapw.empty()) BX_HIP(c, hipMemcpyAsync(d->taps.b.dptr, tapw.data(), tapw.size() * 4, hipMemcpyHostToDevice, c->stream));
-    if (!keptw.empty()) BX_HIP(c, hipMemcpyAsync(d->kept.b.dptr, keptw.data(), keptw.size() * 4, hipMemcpyHostToDevice, c->stream));
-    BX_HIP(c, hipMemcpyAsync(d->scal.b.dptr, scal.data(), scal.size() * 4, hipMemcpyHostToDevice, c->stream));
-    BX_HIP(c, stream_wait(c));  // the host vectors go away
-    // more dynamic LDS than a kernel may use by default (set once per process and kernel; cheap to repeat)
-    BX_REQUIRE(c, d->lds <= 64 * 1024 ||
-                      hipFuncSetAttribute((const void*)acc_program_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BX_CONS_MAX_NARROW * 1024 + BX_CONS_MAX_WIDE * 4096) == hipSuccess,
-               "bx_acc_program_load: the slot files' LDS could not be reserved");
-    {
-        std::lock_guard<std::mutex> g(g_loaded_mu);
-        g_loaded[c].insert(d.get());
+    if (!keptw.empty()) {
+        BX_HIP(c, hipMemcpyAsync(d->kept.b.dptr, keptw.data(), keptw.size() * 4, hipMemcpyHostToDevice, c->stream));
+        BX_HIP(c, stream_wait(c));  // keptw goes away
     }
+    BX_REQUIRE(c, reserve_slot_lds((const void*)acc_program_kernel, d->lds), "bx_acc_program_load: the slot files' LDS could not be reserved");
+    g_loaded.insert(c, d.get());
     *out = d.release();
     return nullptr;
 } BX_ABI_CATCH(c, "bx_acc_program_load")
@@ -199,17 +175,7 @@ extern "C" const char* bx_acc_program_load(bx_ctx* c, const bx_acc_program* prog
 extern "C" const char* bx_acc_program_unload(bx_acc_program_dev* dev) try {
     using namespace bx;
     if (!dev) return nullptr;
-    bx_ctx* c = nullptr;
-    {
-        // found by address, without reading *dev: a handle unloaded twice, or one whose ctx was freed, names freed memory
-        std::lock_guard<std::mutex> g(g_loaded_mu);
-        for (auto it = g_loaded.begin(); it != g_loaded.end() && !c; ++it)
-            if (it->second.erase(dev)) {
-                c = it->first;
-                if (it->second.empty()) g_loaded.erase(it);
-                break;
-            }
-    }
+    bx_ctx* c = g_loaded.take(dev);
     if (!c) return "bx_acc_program_unload: not a loaded program (unloaded twice, or its ctx was freed)";
     (void)hipSetDevice(c->device);
     (void)stream_wait(c);  // a launch may still read the tables
@@ -228,14 +194,7 @@ extern "C" const char* bx_acc_program_keep(bx_ctx* c, bx_acc_program_dev* dev, u
     const size_t n = (size_t)1 << po2, K = dev->info.kept;
     BX_REQUIRE(c, code.len == n * w_code && data.len == n * w_data && kept.len == n * K,
                "bx_acc_program_keep: buffer size mismatch (groups N x width, kept N x the program's kept columns)");
-    for (size_t k = 0; k < K; ++k) {
-        const bx_cons_tap& t = dev->kept_cols[k];
-        const uint32_t w = t.group == 0 ? w_code : w_data;
-        if (t.col >= w) {
-            snprintf(c->err, sizeof c->err, "bx_acc_program_keep: the program taps column %u of group %u (kept column %zu), which has %u columns", t.col, t.group, k, w);
-            return c->err;
-        }
-    }
+    if (const char* e = acc_program_check_widths(dev->kept_cols, "bx_acc_program_keep", w_code, w_data)) return set_msg(c, e);
     BX_REQUIRE(c, !bufs_overlap(kept, code), "bx_acc_program_keep: kept and code overlap");
     BX_REQUIRE(c, !bufs_overlap(kept, data), "bx_acc_program_keep: kept and data overlap");
     if (!K) return nullptr;

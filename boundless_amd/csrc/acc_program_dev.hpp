@@ -1,8 +1,7 @@
 // acc_program_dev.hpp — an accumulate program loaded on a ctx: what acc_program.hip (load, unload, keep, run) owns and what a
 // generated kernel attached to it would share, as cons_program_dev.hpp and wit_program_dev.hpp are.  Host only.
 #pragma once
-#include "cons_program.hpp"
-#include "ctx.hpp"
+#include "program_loaded.hpp"
 
 struct bx_acc_program_dev {
     bx_ctx* ctx = nullptr;

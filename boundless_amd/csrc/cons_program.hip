@@ -15,11 +15,8 @@
 //             to carry.  Mix powers come from the canonical half of mix_power_table.
 #define BX_PLAIN_MAD 1
 #include <algorithm>
-#include <map>
 #include <memory>
-#include <mutex>
 #include <new>
-#include <set>
 #include <vector>
 
 #include "circuit_common.hpp"
@@ -86,21 +83,12 @@ __global__ __launch_bounds__(256) void cons_program_kernel(uint32_t* __restrict_
 
 namespace bx {
 namespace {
-std::mutex g_loaded_mu;
-std::map<bx_ctx*, std::set<bx_cons_program_dev*>> g_loaded;  // what bx_free still has to release
+LoadedPrograms<bx_cons_program_dev> g_loaded;  // what bx_free still has to release
 }  // namespace
 
 void cons_programs_release(bx_ctx* c) {
-    std::set<bx_cons_program_dev*> ds;
-    {
-        std::lock_guard<std::mutex> g(g_loaded_mu);
-        auto it = g_loaded.find(c);
-        if (it == g_loaded.end()) return;
-        ds.swap(it->second);
-        g_loaded.erase(it);
-    }
-    for (bx_cons_program_dev* d : ds) {  // the caller has drained the stream
-        cons_gen_release(d);
+    for (bx_cons_program_dev* d : g_loaded.take_all(c)) {  // the caller has drained the stream
+        gen_release(d->gen);
         delete d;
     }
 }
@@ -119,35 +107,18 @@ extern "C" const char* bx_cons_program_load(bx_ctx* c, const bx_cons_program* pr
     d->ret_slot = prog->ret_slot;
     d->n_fetch = (uint32_t)(prog->code.size() / (2 * CP_FETCH));
     for (int g = 0; g < 3; ++g) d->max_col[g] = prog->max_col[g];
-    BX_TRY(bx_cons_program_digest(prog, d->digest));  // what a generated kernel must have been built from (attach_kernel)
+    BX_TRY(bx_cons_program_digest(prog, d->gen.digest));  // what a generated kernel must have been built from (attach_kernel)
     // the compiler refuses what does not fit; a stream from anywhere else must not reach the kernel
     BX_REQUIRE(c, prog->info.narrow <= BX_CONS_MAX_NARROW && prog->info.wide >= 1 && prog->info.wide <= BX_CONS_MAX_WIDE && prog->ret_slot < prog->info.wide &&
                       prog->code.size() % (2 * CP_FETCH) == 0,
                "bx_cons_program_load: the program's slot counts are outside the device limits");
     d->lds = (size_t)(prog->info.narrow + 4 * prog->info.wide) * CP_LANES * 4;
-    const size_t n_scal = prog->info.n_globals + 4 + prog->consts.size();
-    BX_TRY(d->code.alloc(c, prog->code.size() ? prog->code.size() : 1));
-    BX_TRY(d->taps.alloc(c, prog->taps.empty() ? 2 : 2 * prog->taps.size()));
-    BX_TRY(d->scal.alloc(c, n_scal));
     BX_TRY(d->mixpows.alloc(c, 8 * (size_t)prog->n_pows));
-    std::vector<uint32_t> tapw(2 * prog->taps.size()), scal(n_scal, 0u);
-    for (size_t t = 0; t < prog->taps.size(); ++t) {
-        tapw[2 * t] = prog->taps[t].col;
-        tapw[2 * t + 1] = prog->taps[t].back | prog->taps[t].group << 30;
-    }
-    std::copy(prog->consts.begin(), prog->consts.end(), scal.begin() + prog->info.n_globals + 4);
-    if (!prog->code.empty()) BX_HIP(c, hipMemcpyAsync(d->code.b.dptr, prog->code.data(), prog->code.size() * 4, hipMemcpyHostToDevice, c->stream));
-    if (!tapw.empty()) BX_HIP(c, hipMemcpyAsync(d->taps.b.dptr, tapw.data(), tapw.size() * 4, hipMemcpyHostToDevice, c->stream));
-    BX_HIP(c, hipMemcpyAsync(d->scal.b.dptr, scal.data(), scal.size() * 4, hipMemcpyHostToDevice, c->stream));
-    BX_HIP(c, stream_wait(c));  // the host vectors go away
-    // more dynamic LDS than a kernel may use by default (set once per process and kernel; cheap to repeat)
-    BX_REQUIRE(c, d->lds <= 64 * 1024 ||
-                      hipFuncSetAttribute((const void*)cons_program_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BX_CONS_MAX_NARROW * 1024 + BX_CONS_MAX_WIDE * 4096) == hipSuccess,
-               "bx_cons_program_load: the slot files' LDS could not be reserved");
-    {
-        std::lock_guard<std::mutex> g(g_loaded_mu);
-        g_loaded[c].insert(d.get());
-    }
+    BX_TRY(upload_program(
+        c, d->code, d->taps, d->scal, prog->code, prog->taps,
+        [](uint32_t* w, size_t, const bx_cons_tap& t) { w[0] = t.col, w[1] = t.back | t.group << 30; }, prog->consts, prog->info.n_globals + 4));
+    BX_REQUIRE(c, reserve_slot_lds((const void*)cons_program_kernel, d->lds), "bx_cons_program_load: the slot files' LDS could not be reserved");
+    g_loaded.insert(c, d.get());
     *out = d.release();
     return nullptr;
 } BX_ABI_CATCH(c, "bx_cons_program_load")
@@ -155,21 +126,11 @@ extern "C" const char* bx_cons_program_load(bx_ctx* c, const bx_cons_program* pr
 extern "C" const char* bx_cons_program_unload(bx_cons_program_dev* dev) try {
     using namespace bx;
     if (!dev) return nullptr;
-    bx_ctx* c = nullptr;
-    {
-        // found by address, without reading *dev: a handle unloaded twice, or one whose ctx was freed, names freed memory
-        std::lock_guard<std::mutex> g(g_loaded_mu);
-        for (auto it = g_loaded.begin(); it != g_loaded.end() && !c; ++it)
-            if (it->second.erase(dev)) {
-                c = it->first;
-                if (it->second.empty()) g_loaded.erase(it);
-                break;
-            }
-    }
+    bx_ctx* c = g_loaded.take(dev);
     if (!c) return "bx_cons_program_unload: not a loaded program (unloaded twice, or its ctx was freed)";
     (void)hipSetDevice(c->device);
     (void)stream_wait(c);  // a launch may still read the tables
-    cons_gen_release(dev);
+    gen_release(dev->gen);
     delete dev;
     return nullptr;
 } BX_ABI_CATCH(nullptr, "bx_cons_program_unload")
@@ -204,7 +165,7 @@ extern "C" const char* bx_cons_program_eval_check(bx_ctx* c, bx_cons_program_dev
     BX_TRY(mix_power_table(c, dev->mixpows.b, poly_mix, dev->n_pows));
     ConsLaunch L;
     vanishing_inverses(po2, L.zinv);
-    if (dev->gen_fn) return cons_gen_launch(c, dev, po2, L.zinv, check, code_eval, data_eval, accum_eval);  // the generated kernel, when one is attached
+    if (dev->gen.fn) return cons_gen_launch(c, dev, po2, L.zinv, check, code_eval, data_eval, accum_eval);  // the generated kernel, when one is attached
     L.dom = (uint32_t)dom;
     L.n_fetch = dev->n_fetch;
     L.n_narrow = dev->info.narrow;
@@ -297,7 +258,7 @@ const char* cc_create(void* u, bx_ctx* c, const bx_segment_params* shape, void**
         }
     }
     if (const bx_acc_program* a = cc->acc) {  // the accumulate program against the shape, before anything is loaded
-        if (const char* e = acc_program_check_widths(a, "cons circuit: accumulate program", shape->w_code, shape->w_data)) return set_msg(c, e);
+        if (const char* e = acc_program_check_widths(a->kept, "cons circuit: accumulate program", shape->w_code, shape->w_data)) return set_msg(c, e);
         const uint32_t cols = 4 * a->info.sequences;
         if (cols > shape->w_accum) {
             snprintf(c->err, sizeof c->err, "cons circuit: accumulate program: %u sequences need %u accum columns, the shape has %u", a->info.sequences, cols,

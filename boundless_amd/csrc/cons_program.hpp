@@ -1,5 +1,6 @@
 // cons_program.hpp — the compiled form of a constraint program (include/bx_program.h is the normative text): ONE instruction
-// stream that the host executor (cons_program_host.cpp, the verifier's side) and the device kernel (cons_program.hip) both read.
+// stream that the host executor (cons_program_host.cpp, the verifier's side) and the device kernel (cons_program.hip) both read; the
+// compiler that writes it for all three program kinds is program_compile.cpp.
 // Plain C++: the host half compiles without HIP.
 //
 // An instruction is two words:
@@ -101,8 +102,9 @@ struct bx_acc_program {
 };
 
 namespace bx {
-// cons_program_host.cpp: NULL, or the refusal (thread-local buffer, led by `who`) of a kept column that is not below its group's width
-const char* acc_program_check_widths(const bx_acc_program* prog, const char* who, uint32_t w_code, uint32_t w_data);
+// cons_program_host.cpp: NULL, or the refusal (thread-local buffer, led by `who`) of a kept column that is not below its group's width: one
+// text for bx_acc_program_run_host, bx_acc_program_keep and the composite table's create
+const char* acc_program_check_widths(const std::vector<bx_cons_tap>& kept, const char* who, uint32_t w_code, uint32_t w_data);
 // cons_program_host.cpp: NULL, or the refusal (in the caller's thread-local buffer, led by `who`) of a tap column (max_col, per group)
 // or a SET column (max_set) that is not below its group's width: one text for bx_wit_program_run_host, bx_wit_program_run and the
 // composite table's create

@@ -11,11 +11,8 @@
 //             fetch, so that it comes through the scalar cache; decode and dispatch are scalar (readfirstlane makes it explicit)
 //   values    canonical throughout (fp_add / fp_sub / fp_mul): the host executor gives identical words
 //   memory    a tap is col[(r - back) & (N - 1)]; a store is data[col * N + r]: one coalesced 256-byte line per wave
-#include <map>
 #include <memory>
-#include <mutex>
 #include <new>
-#include <set>
 #include <vector>
 
 #include "wit_program_dev.hpp"
@@ -70,21 +67,12 @@ __global__ __launch_bounds__(256) void wit_program_kernel(uint32_t* data, const 
 
 namespace bx {
 namespace {
-std::mutex g_loaded_mu;
-std::map<bx_ctx*, std::set<bx_wit_program_dev*>> g_loaded;  // what bx_free still has to release
+LoadedPrograms<bx_wit_program_dev> g_loaded;  // what bx_free still has to release
 }  // namespace
 
 void wit_programs_release(bx_ctx* c) {
-    std::set<bx_wit_program_dev*> ds;
-    {
-        std::lock_guard<std::mutex> g(g_loaded_mu);
-        auto it = g_loaded.find(c);
-        if (it == g_loaded.end()) return;
-        ds.swap(it->second);
-        g_loaded.erase(it);
-    }
-    for (bx_wit_program_dev* d : ds) {  // the caller has drained the stream
-        wit_gen_release(d);
+    for (bx_wit_program_dev* d : g_loaded.take_all(c)) {  // the caller has drained the stream
+        gen_release(d->gen);
         delete d;
     }
 }
@@ -102,28 +90,19 @@ extern "C" const char* bx_wit_program_load(bx_ctx* c, const bx_wit_program* prog
     d->n_fetch = (uint32_t)(prog->code.size() / (2 * CP_FETCH));
     for (int g = 0; g < 2; ++g) d->max_col[g] = prog->max_col[g];
     d->max_set = prog->max_set;
-    BX_TRY(bx_wit_program_digest(prog, d->digest));  // what a generated kernel must have been built from (attach_kernel)
+    BX_TRY(bx_wit_program_digest(prog, d->gen.digest));  // what a generated kernel must have been built from (attach_kernel)
     // the compiler refuses what does not fit; a stream from anywhere else must not reach the kernel
     BX_REQUIRE(c, prog->info.narrow <= BX_CONS_MAX_NARROW && prog->code.size() % (2 * CP_FETCH) == 0,
                "bx_wit_program_load: the program's slot count is outside the device limit");
     d->lds = (size_t)prog->info.narrow * WP_LANES * 4;  // at most 32 KiB: below what a kernel may use by default
-    BX_TRY(d->code.alloc(c, prog->code.size() ? prog->code.size() : 1));
-    BX_TRY(d->taps.alloc(c, prog->taps.empty() ? 2 : 2 * prog->taps.size()));
-    BX_TRY(d->consts.alloc(c, prog->consts.empty() ? 1 : prog->consts.size()));
-    std::vector<uint32_t> tapw(2 * prog->taps.size());
-    for (size_t t = 0; t < prog->taps.size(); ++t) {
-        tapw[2 * t] = prog->taps[t].col;
-        tapw[2 * t + 1] = prog->taps[t].back | prog->taps[t].group << 30;
-    }
-    if (!prog->code.empty()) BX_HIP(c, hipMemcpyAsync(d->code.b.dptr, prog->code.data(), prog->code.size() * 4, hipMemcpyHostToDevice, c->stream));
-    if (!tapw.empty()) BX_HIP(c, hipMemcpyAsync(d->taps.b.dptr, tapw.data(), tapw.size() * 4, hipMemcpyHostToDevice, c->stream));
-    if (!prog->consts.empty()) BX_HIP(c, hipMemcpyAsync(d->consts.b.dptr, prog->consts.data(), prog->consts.size() * 4, hipMemcpyHostToDevice, c->stream));
-    BX_TRY(wit_counts_load(c, d.get(), prog));  // the multiplicity columns' source table and counters (wit_count.hip)
-    BX_HIP(c, stream_wait(c));  // the host vectors go away
-    {
-        std::lock_guard<std::mutex> g(g_loaded_mu);
-        g_loaded[c].insert(d.get());
-    }
+    BX_TRY(upload_program(
+        c, d->code, d->taps, d->consts, prog->code, prog->taps,
+        [](uint32_t* w, size_t, const bx_cons_tap& t) { w[0] = t.col, w[1] = t.back | t.group << 30; }, prog->consts, 0));  // `scal` is the constants alone
+    // the multiplicity columns' source table and counters (wit_count.hip), after everything above is allocated and has landed: its
+    // one copy is the last thing it does, so no copy is ever in flight when an allocation fails
+    BX_TRY(wit_counts_load(c, d.get(), prog));
+    BX_HIP(c, stream_wait(c));
+    g_loaded.insert(c, d.get());
     *out = d.release();
     return nullptr;
 } BX_ABI_CATCH(c, "bx_wit_program_load")
@@ -131,21 +110,11 @@ extern "C" const char* bx_wit_program_load(bx_ctx* c, const bx_wit_program* prog
 extern "C" const char* bx_wit_program_unload(bx_wit_program_dev* dev) try {
     using namespace bx;
     if (!dev) return nullptr;
-    bx_ctx* c = nullptr;
-    {
-        // found by address, without reading *dev: a handle unloaded twice, or one whose ctx was freed, names freed memory
-        std::lock_guard<std::mutex> g(g_loaded_mu);
-        for (auto it = g_loaded.begin(); it != g_loaded.end() && !c; ++it)
-            if (it->second.erase(dev)) {
-                c = it->first;
-                if (it->second.empty()) g_loaded.erase(it);
-                break;
-            }
-    }
+    bx_ctx* c = g_loaded.take(dev);
     if (!c) return "bx_wit_program_unload: not a loaded program (unloaded twice, or its ctx was freed)";
     (void)hipSetDevice(c->device);
     (void)stream_wait(c);  // a launch may still read the tables
-    wit_gen_release(dev);
+    gen_release(dev->gen);
     delete dev;
     return nullptr;
 } BX_ABI_CATCH(nullptr, "bx_wit_program_unload")
@@ -162,7 +131,7 @@ extern "C" const char* bx_wit_program_run(bx_ctx* c, bx_wit_program_dev* dev, ui
     if (const char* e = wit_program_check_widths(dev->max_col, dev->max_set, "bx_wit_program_run", w_code, w_data)) return set_msg(c, e);
     BX_REQUIRE(c, !bufs_overlap(code, data), "bx_wit_program_run: code and data overlap");
     if (const char* e = wit_program_check_counts(dev->counts, "bx_wit_program_run", po2, w_data)) return set_msg(c, e);
-    if (dev->gen_fn) {  // the generated kernel, when one is attached
+    if (dev->gen.fn) {  // the generated kernel, when one is attached
         BX_TRY(wit_gen_launch(c, dev, po2, code, data));
         return wit_counts_run(c, dev, po2, data);
     }

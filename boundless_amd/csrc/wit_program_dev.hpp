@@ -1,8 +1,7 @@
 // wit_program_dev.hpp — a witness program loaded on a ctx: what wit_program.hip (load, unload, the interpreting kernel's launch) and
-// wit_program_gen.cpp (a generated kernel attached to it) share.  Host only.
+// program_gen.cpp (a generated kernel attached to it) share.  Host only.
 #pragma once
-#include "cons_program.hpp"
-#include "ctx.hpp"
+#include "program_loaded.hpp"
 
 struct bx_wit_program_dev {
     bx_ctx* ctx = nullptr;
@@ -10,10 +9,7 @@ struct bx_wit_program_dev {
     uint32_t n_fetch = 0, max_col[2] = {0, 0}, max_set = 0;
     size_t lds = 0;
     bx::DevBuf code, taps, consts;
-    // the generated kernel (bx_wit_program_attach_kernel): none unless gen_fn is set
-    uint32_t digest[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // bx_wit_program_digest of the program this was loaded from
-    hipModule_t gen_module = nullptr;
-    hipFunction_t gen_fn = nullptr;
+    bx::GenKernel gen;  // bx_wit_program_attach_kernel; gen.digest is bx_wit_program_digest of the program this was loaded from
     // the multiplicity columns (wit_count.hip): the program's counts, where each one's sources start in the flat table and its bins
     // in the counters (sum of bins words), and the two on the device
     std::vector<bx::WitCount> counts;
@@ -23,9 +19,7 @@ struct bx_wit_program_dev {
 };
 
 namespace bx {
-// wit_program_gen.cpp: unload what is attached (no-op when nothing is; the caller has drained the stream)
-void wit_gen_release(bx_wit_program_dev* dev);
-// ... and launch it: the caller (bx_wit_program_run) has checked the arguments
+// program_gen.cpp: launch the attached kernel: the caller (bx_wit_program_run) has checked the arguments
 const char* wit_gen_launch(bx_ctx* c, bx_wit_program_dev* dev, uint32_t po2, bx_buf code, bx_buf data);
 // wit_count.hip: upload the flat source table and allocate the counters (no-op without counts; the caller waits for the stream) ...
 const char* wit_counts_load(bx_ctx* c, bx_wit_program_dev* dev, const bx_wit_program* prog);

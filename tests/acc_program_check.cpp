@@ -1,4 +1,4 @@
-// acc_program_check.cpp — stand-alone checker of the accumulate-program compiler and host executor (csrc/cons_program_host.cpp), built
+// acc_program_check.cpp — stand-alone checker of the accumulate-program compiler and host executor (csrc/program_compile.cpp, csrc/cons_program_host.cpp), built
 // with -fsanitize=address,undefined by tests/test_acc_program_cpu.py and run as a process of its own.
 //
 // Seeded descriptors, well-formed and malformed, go through bx_acc_program_create.  Every one is either refused (with a message) or

@@ -1,6 +1,6 @@
 // consgen_host_main.cpp — runs ONE generated constraint-program body on the CPU (tests/test_consgen_cpu.py): the text
 // bx_cons_program_emit_hip wrote is included below as bx_cp_generated.inc, compiled by g++ under -fsanitize=address,undefined through
-// the host wrapper of csrc/cons_program_gen.hpp, and linked with csrc/cons_program_host.cpp.
+// the host wrapper of csrc/cons_program_gen.hpp, and linked with csrc/program_compile.cpp and csrc/cons_program_host.cpp.
 //
 //     consgen_host CASE.bin PLANES.bin
 //

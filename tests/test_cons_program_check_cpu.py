@@ -1,4 +1,4 @@
-"""CPU: the constraint-program compiler and host executor (csrc/cons_program_host.cpp) as a stand-alone program under AddressSanitizer and
+"""CPU: the constraint-program compiler and host executor (csrc/program_compile.cpp, csrc/cons_program_host.cpp) as a stand-alone program under AddressSanitizer and
 UndefinedBehaviorSanitizer: seeded malformed and well-formed descriptors are refused or compiled, and every compiled stream agrees
 with a direct evaluation of its step list (tests/cons_program_check.cpp).  Nothing is loaded into Python."""
 import os
@@ -12,7 +12,7 @@ def test_compiler_and_host_executor_under_sanitizers(tmp_path):
     csrc = os.path.join(ROOT, "boundless_amd", "csrc")
     r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Wextra",
                         f"-I{csrc}", f"-I{os.path.join(ROOT, 'include')}", os.path.join(ROOT, "tests", "cons_program_check.cpp"),
-                        os.path.join(csrc, "cons_program_host.cpp"), "-o", exe], capture_output=True, text=True)
+                        os.path.join(csrc, "cons_program_host.cpp"), os.path.join(csrc, "program_compile.cpp"), "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert not r.stderr.strip(), r.stderr  # the host half compiles without a warning under -Wall -Wextra
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)

@@ -4,7 +4,7 @@
   (tests/consgen_check.cpp): sizes, no write past `cap`, byte-equal emits, digests;
 * the generated text ITSELF, run on the CPU: for every program fixture the text is compiled by g++ with the host wrapper of
   csrc/cons_program_gen.hpp into a second stand-alone program (tests/consgen_host_main.cpp, ASan + UBSan, linked with
-  csrc/cons_program_host.cpp) that computes the four check planes over the whole domain at po2 1 and 6; Python compares them word for
+  csrc/program_compile.cpp, csrc/cons_program_host.cpp) that computes the four check planes over the whole domain at po2 1 and 6; Python compares them word for
   word with tests/cons_program_ref.py, the program itself compares every point with bx_cons_program_constraints_at;
 * where hipcc is on PATH: every fixture compiles for gfx950, without scratch except possibly at the slot limits; a long program
   compiles;
@@ -34,7 +34,7 @@ P = ref.P
 
 def test_emitter_under_sanitizers(tmp_path):
     exe = str(tmp_path / "consgen_check")
-    r = subprocess.run(SAN + [os.path.join(ROOT, "tests", "consgen_check.cpp"), os.path.join(CSRC, "cons_program_host.cpp"),
+    r = subprocess.run(SAN + [os.path.join(ROOT, "tests", "consgen_check.cpp"), os.path.join(CSRC, "cons_program_host.cpp"), os.path.join(CSRC, "program_compile.cpp"),
                               os.path.join(CSRC, "cons_program_emit.cpp"), "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert not r.stderr.strip(), r.stderr  # the emitter compiles without a warning under -Wall -Wextra
@@ -70,7 +70,7 @@ def test_generated_text_run_on_the_cpu_is_the_reference(tmp_path, name):
     (tmp_path / "bx_cp_generated.inc").write_text(text)
     exe = str(tmp_path / "consgen_host")
     # -g0: a body of hundreds of statements is one function, and gcc's variable tracking gives up on it with a note
-    r = subprocess.run(SAN + ["-g0", f"-I{tmp_path}", os.path.join(ROOT, "tests", "consgen_host_main.cpp"), os.path.join(CSRC, "cons_program_host.cpp"),
+    r = subprocess.run(SAN + ["-g0", f"-I{tmp_path}", os.path.join(ROOT, "tests", "consgen_host_main.cpp"), os.path.join(CSRC, "cons_program_host.cpp"), os.path.join(CSRC, "program_compile.cpp"),
                               os.path.join(CSRC, "cons_program_emit.cpp"), "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert not r.stderr.strip(), r.stderr  # the generated text and its frame compile without a warning

@@ -1,4 +1,4 @@
-"""GPU: generated constraint-program kernels (include/bx_program.h, "Generated kernels"; csrc/cons_program_gen.hpp, cons_program_gen.cpp)
+"""GPU: generated constraint-program kernels (include/bx_program.h, "Generated kernels"; csrc/cons_program_gen.hpp, program_gen.cpp)
 — a kernel built off line from a program's description and attached to the loaded program, against the definition-level reference
 of tests/cons_program_ref.py and against the interpreter on the same loaded program, word for word over the whole 4N domain; the
 refusals of attach / detach by message; the lookup and square circuits proved through their generated kernels, seal for seal.

@@ -35,7 +35,7 @@ def test_compiler_and_host_executor_under_sanitizers(tmp_path):
     exe = str(tmp_path / "wit_program_check")
     r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Wextra",
                         f"-I{CSRC}", f"-I{os.path.join(ROOT, 'include')}", os.path.join(ROOT, "tests", "wit_program_check.cpp"),
-                        os.path.join(CSRC, "cons_program_host.cpp"), "-o", exe], capture_output=True, text=True)
+                        os.path.join(CSRC, "cons_program_host.cpp"), os.path.join(CSRC, "program_compile.cpp"), "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert not r.stderr.strip(), r.stderr  # the host half compiles without a warning under -Wall -Wextra
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)

@@ -347,4 +347,5 @@ def test_load_and_unload_return_their_memory_and_bx_free_releases_what_is_left()
     torch.cuda.synchronize()
     assert torch.cuda.mem_get_info(0)[0] >= free_before
     for k in kept:
-        k.dev = None  # released by bx_free
+        dev, k.dev = k.dev, None  # released by bx_free: an unload of the freed handle is answered by message
+        assert b"bx_wit_program_unload: not a loaded program" in compiled.lib.bx_wit_program_unload(dev)

@@ -5,7 +5,7 @@
   hand-corrupted streams, and the constraint emitter's refusal of a store;
 * the generated text ITSELF, run on the CPU: for every fixture under tests/golden/witgen/ the text is compiled by g++ with the host
   wrapper of csrc/wit_program_gen.hpp into a second stand-alone program (tests/witgen_host_main.cpp, ASan + UBSan, linked with
-  csrc/cons_program_host.cpp) that derives the data columns at po2 1, 3 and 6 from random, all-0, all-(P - 1) and alternating columns
+  csrc/program_compile.cpp, csrc/cons_program_host.cpp) that derives the data columns at po2 1, 3 and 6 from random, all-0, all-(P - 1) and alternating columns
   with the derived ones poisoned; Python compares them word for word with tests/wit_program_ref.py, the program itself compares
   them with bx_wit_program_run_host;
 * where hipcc is on PATH: every fixture compiles for gfx950, the one-function ones without scratch and without LDS, and
@@ -35,7 +35,7 @@ PATTERNS = ("random", "zero", "all_pm1", "alternating")
 
 def test_emitter_under_sanitizers(tmp_path):
     exe = str(tmp_path / "witgen_check")
-    r = subprocess.run(SAN + [os.path.join(ROOT, "tests", "witgen_check.cpp"), os.path.join(CSRC, "cons_program_host.cpp"),
+    r = subprocess.run(SAN + [os.path.join(ROOT, "tests", "witgen_check.cpp"), os.path.join(CSRC, "cons_program_host.cpp"), os.path.join(CSRC, "program_compile.cpp"),
                               os.path.join(CSRC, "cons_program_emit.cpp"), "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert not r.stderr.strip(), r.stderr  # the emitter compiles without a warning under -Wall -Wextra
@@ -79,7 +79,7 @@ def test_generated_text_run_on_the_cpu_is_the_reference_and_the_host_executor(tm
     (tmp_path / "bx_wp_generated.inc").write_text(text)
     exe = str(tmp_path / "witgen_host")
     # -g0: a body of hundreds of statements is one function, and gcc's variable tracking gives up on it with a note
-    r = subprocess.run(SAN + ["-g0", f"-I{tmp_path}", os.path.join(ROOT, "tests", "witgen_host_main.cpp"), os.path.join(CSRC, "cons_program_host.cpp"),
+    r = subprocess.run(SAN + ["-g0", f"-I{tmp_path}", os.path.join(ROOT, "tests", "witgen_host_main.cpp"), os.path.join(CSRC, "cons_program_host.cpp"), os.path.join(CSRC, "program_compile.cpp"),
                               os.path.join(CSRC, "cons_program_emit.cpp"), "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert not r.stderr.strip(), r.stderr  # the generated text and its frame compile without a warning

@@ -1,5 +1,5 @@
 """GPU: generated witness-program kernels (include/bx_program.h, "Generated witness kernels"; csrc/wit_program_gen.hpp,
-wit_program_gen.cpp) — a kernel built off line from a witness program's description and attached to the loaded program, against the
+program_gen.cpp) — a kernel built off line from a witness program's description and attached to the loaded program, against the
 definition-level reference of tests/wit_program_ref.py, the host executor and the interpreter on the same loaded program, word for
 word over the whole data group; the refusals of attach / detach by message; release with a kernel attached; the square and cube
 circuits proved with their derived columns from the attached kernel, seal for seal.

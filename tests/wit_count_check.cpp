@@ -1,5 +1,5 @@
 // wit_count_check.cpp — stand-alone checker of a witness program's multiplicity columns on the host (bx_wit_program_create_counted and
-// bx_wit_program_run_host in csrc/cons_program_host.cpp; include/bx_program.h, "multiplicity columns", is the text), built with
+// bx_wit_program_run_host in csrc/program_compile.cpp and csrc/cons_program_host.cpp; include/bx_program.h, "multiplicity columns", is the text), built with
 // -fsanitize=address,undefined by tests/test_wit_count_cpu.py and run as a process of its own.
 //
 // 3 000 seeded descriptors with count lists, well-formed and malformed, go through create: every one is either refused (with a message)

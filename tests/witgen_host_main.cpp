@@ -1,6 +1,6 @@
 // witgen_host_main.cpp — runs ONE generated witness-program body on the CPU (tests/test_witgen_cpu.py): the text
 // bx_wit_program_emit_hip wrote is included below as bx_wp_generated.inc, compiled by g++ under -fsanitize=address,undefined through
-// the host wrapper of csrc/wit_program_gen.hpp, and linked with csrc/cons_program_host.cpp.
+// the host wrapper of csrc/wit_program_gen.hpp, and linked with csrc/program_compile.cpp and csrc/cons_program_host.cpp.
 //
 //     witgen_host CASE.bin DATA.bin [CASE.bin DATA.bin ...]
 //
