@@ -9,7 +9,7 @@
 // first factor (circuit_dev.hpp, the factored form: 16 groups at (48, 3)); for G <= 2, T*(G-1) products term by term.  At G = 4 the
 // terms are instead products of two shared pair products (circuit_dev.hpp, the pair form): at T = 64, 44 reduced pair products and 64
 // multiply-adds.  In every form the sum is one 64-bit chain that is folded (hi * R + lo, one multiply-add) where it would leave 64
-// bits — 13 times at (64, 4) — and reduced once at the end (circuit_dev.hpp, fold_r).
+// bits — 13 times at (64, 4) — and reduced once at the end (lazy_ext.hpp, fold_r).
 // The loads around it are one coalesced dword per lane and column.
 // The signed multiply-adds are left to the compiler in this translation unit (poseidon2.hip pins them as single asm
 // statements because its loop-carried cells get widened): here the terms of a cell share their inner products (7 pool entries
@@ -20,11 +20,14 @@
 // 1340 (657) -> 1265 (540).  Two things the un-pinned code must be kept from.  With a constant factor in sight hipcc turns a sum of
 // r_i * R into (sum of r_i) * R, and two terms with a common factor into one product of a 64-bit sum, each with an emulated
 // 64 x 32-bit product; and it reassociates a chain's sum so that the fold comes in through a 64-bit add.  So the fold multiplies by
-// an opaque copy of R and every step of a chain hides its result from the optimiser (circuit_dev.hpp: fold_r, smad_chain, smad_r);
+// an opaque copy of R and every step of a chain hides its result from the optimiser (lazy_ext.hpp: fold_r, smad_chain, smad_r);
 // and the walk keeps its pool centred in registers (DerivedRegs<true>) instead of centring all 16 entries per cell.  The walk's loop
 // body per cell, VALU instructions (multiplies), with the levels as multiply-adds and the centred walk: witness_derive_kernel<64,4>
 // 412 (251) -> 312 (274), eval_check_kernel<64,4> 467 (275) -> 367 (298); with the chain folded instead of reduced and rescaled:
 // -> 262 (211) and 317 (235), 54 -> 46 and 78 -> 70 VGPRs (seven waves per SIMD in eval_check).  DESIGN.md §4 has the tables.
+// eval_check's constraints behind the walk (the accumulators', the pairs', the two boundary ones) run on lazy_ext.hpp: the ext-valued
+// ones are one weighted sum of unreduced values (WeightedExtAcc), the base-valued ones join the walk's in LazyExtAcc, itself one folded
+// chain per component: per accumulator 321 -> 99 instructions, per pair 183 -> 54, the walk 317 -> 277 per cell, 70 -> 61 VGPRs (eight waves).
 #define BX_PLAIN_MAD 1
 #include <memory>
 #include <new>
@@ -151,35 +154,38 @@ __global__ __launch_bounds__(256) void eval_check_kernel(uint32_t* __restrict__ 
         mix_add(mixacc, mixpows_c, j, fp_sub(d, cons_sum<TT, GG>(pool, cc.T, cc.G)));
         w.shift(Regs::enter(d), Regs::enter(edata[(size_t)((j + 3) % cc.F) * dom + i]), code_at(j + 4));
     }
-    Fp4 tot = mixacc.finish();
-    const uint32_t first = ecode[i];
+    // the boundary constraints tying the public words to the trace, first * (data[0] - g0) and last * (data[wd-1] - g1), are base-valued
+    // like the walk's: the same accumulator takes them
+    const uint32_t first = ecode[i], last = cc.pairs || cc.globals() > 1 ? ecode[(size_t)dom + i] : 0u;
+    const size_t b0 = (size_t)cc.J + cc.E + cc.pairs;
+    mix_add(mixacc, mixpows_c, b0, fp_mul(first, fp_sub(edata[i], pt.g[0])));
+    if (cc.globals() > 1) mix_add(mixacc, mixpows_c, b0 + 1, fp_mul(last, fp_sub(edata[(size_t)(cc.wd - 1) * dom + i], pt.g[1])));
+    const Fp4 base = mixacc.finish();
+    // the ext-valued constraints are ONE weighted sum: the accumulators' a - inner * fac and the pairs' last * (hi - lo) stay unreduced
+    // words (lazy_ext.hpp: accumulator_value, pair_value) and go under their mix powers into seven 64-bit chains that are reduced once
+    const TailSelectors sel = tail_selectors(first, last);
+    WeightedExtAcc extacc;
+    extacc.reset();
     for (uint32_t e = 0; e < cc.E; ++e) {
         Fp4 a, ab;
         ext_column_at(eacc, e, dom, i, ib, a, ab);
-        Fp4 inner = f4_scale(ab, fp_sub(MONT_ONE, first));
-        inner.c[0] = fp_add(inner.c[0], first);
-        const uint4 b = *reinterpret_cast<const uint4*>(betas + 4 * (size_t)e);
-        Fp4 fac{{fp_add(b.x, edata[(size_t)cc.acc_src(e) * dom + i]), b.y, b.z, b.w}};
-        tot = f4_add(tot, f4_mul(mix_power(mixpows, cc.J + e), f4_sub(a, f4_mul(inner, fac))));
+        i32 beta[4], v[4];
+        uniform_centred(betas, e, true, beta);
+        accumulator_value(a, ab, sel, beta, edata[(size_t)cc.acc_src(e) * dom + i], v);
+        mix_add(extacc, mixpows_c, cc.J + e, v);
     }
-    if (cc.pairs) {
-        const uint32_t last = ecode[(size_t)dom + i];
-        for (uint32_t p = 0; p < cc.pairs; ++p) {
-            Fp4 d;
+    for (uint32_t p = 0; p < cc.pairs; ++p) {
+        Fp4 hi, lo;
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                d.c[k] = fp_sub(eacc[(size_t)(4 * (2 * p + 1) + k) * dom + i], eacc[(size_t)(4 * (2 * p) + k) * dom + i]);
-            tot = f4_add(tot, f4_mul(mix_power(mixpows, cc.J + cc.E + p), f4_scale(d, last)));
+        for (int k = 0; k < 4; ++k) {
+            hi.c[k] = eacc[(size_t)(4 * (2 * p + 1) + k) * dom + i];
+            lo.c[k] = eacc[(size_t)(4 * (2 * p) + k) * dom + i];
         }
+        i32 v[4];
+        pair_value(hi, lo, sel, v);
+        mix_add(extacc, mixpows_c, cc.J + cc.E + p, v);
     }
-    {   // boundary constraints tying the public words to the trace: first * (data[0] - g0), last * (data[wd-1] - g1)
-        const size_t b0 = (size_t)cc.J + cc.E + cc.pairs;
-        tot = f4_add(tot, f4_scale(mix_power(mixpows, b0), fp_mul(first, fp_sub(edata[i], pt.g[0]))));
-        if (cc.globals() > 1) {
-            const uint32_t last = ecode[(size_t)dom + i];
-            tot = f4_add(tot, f4_scale(mix_power(mixpows, b0 + 1), fp_mul(last, fp_sub(edata[(size_t)(cc.wd - 1) * dom + i], pt.g[1]))));
-        }
-    }
+    const Fp4 tot = f4_add(base, extacc.finish());
     store_check(check, tot, pt, dom, i);
 }
 

@@ -2,7 +2,8 @@
 // and its bx_circuit_ops entries; what every such table needs around them lives here, once.
 //   host    launch grids and seed derivations, the segment header, the noise seed of the next witgen, the mix-power table and the
 //           vanishing-polynomial inverses of eval_check, the store of the accumulate step's ext runs into the accum group
-//   device  the ends of an eval_check kernel: a mix power from the table, an ext column at a point and one row back, the closing division
+//   device  the ends of an eval_check kernel: a mix power from the table, the mixing of a base-valued and of an ext-valued constraint, an
+//           ext column at a point and one row back, the closing division
 // The device inlines sit on lazy_ext.hpp and therefore in the same inline namespace as circuit_dev.hpp: a circuit's translation
 // unit defines BX_PLAIN_MAD before it includes either.
 #pragma once
@@ -72,6 +73,19 @@ __device__ __forceinline__ void mix_add(LazyExtAcc& acc, const uint32_t* __restr
     const Fp4 m = mix_power(mixpows_c, k);
     const i32 w[4] = {(i32)m.c[0], (i32)m.c[1], (i32)m.c[2], (i32)m.c[3]};
     acc.add(w, x);
+}
+// four centred words of a table (a mix power from the centred half, a challenge): wave-uniform, one 16-byte scalar load; the centring of
+// a canonical table is scalar work
+__device__ __forceinline__ void uniform_centred(const uint32_t* __restrict__ table, size_t k, bool canonical, i32 w[4]) {
+    const Fp4 m = mix_power(table, k);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) w[q] = canonical ? fp_centre(m.c[q]) : (i32)m.c[q];
+}
+// acc += poly_mix^k * v for an ext-valued constraint v (|v[q]| <= P: lazy_ext.hpp), the weight from the centred half of the table
+__device__ __forceinline__ void mix_add(WeightedExtAcc& acc, const uint32_t* __restrict__ mixpows_c, size_t k, const i32 v[4]) {
+    i32 w[4];
+    uniform_centred(mixpows_c, k, false, w);
+    acc.add(w, v);
 }
 // ext column s of the accum group's evaluations (planes 4s .. 4s+3) at domain point i and one row back at ib, plane by plane: the two
 // loads of a plane share their address arithmetic

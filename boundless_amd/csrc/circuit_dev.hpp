@@ -60,14 +60,11 @@
 
 #include "circuit.hpp"
 #include "fp.hpp"
+#include "lazy_ext.hpp"  // smad_r, fold_r, smad_chain, FINAL_MAX: the chain steps and the fold
 #include "poseidon2_arith.hpp"
 
 namespace bx {
 inline namespace BX_MAD_FLAVOUR {
-
-// largest sredc operand whose result is < P in magnitude: ub(FINAL_MAX) = P - 1
-constexpr i64 FINAL_MAX = ((i64)(P / 2) - 1) * ((i64)1 << 32);
-static_assert(ub(FINAL_MAX) < (i64)P && FINAL_MAX <= SREDC_MAX, "FINAL_MAX");
 
 // f(IntC<I>{}) for I = BEGIN .. END-1, unrolled at compile time: the counter reaches the body as a constant expression
 template <int V>
@@ -99,7 +96,7 @@ struct ConsPlan {
     int nq = 0;                            // inner groups
     int first[TT]{}, len[TT]{}, term[TT][ISZ]{};  // inner group q: its shared first factor, its terms
     i64 max_inner = 0;                     // the largest inner sum
-    // ONE chain over all inner groups' s * pool[a], folded (fold_r below) at the head of every segment but the first
+    // ONE chain over all inner groups' s * pool[a], folded (fold_r) at the head of every segment but the first
     int nf = 0, fbeg[TT + 1]{};            // segment f = inner groups [fbeg[f], fbeg[f+1])
     i64 max_fchain = 0, max_ftotal = 0;    // the largest chain value, the folded chain that is reduced at the end
 
@@ -337,45 +334,6 @@ struct FoldPlan {
 };
 template <int TT>
 inline constexpr FoldPlan<TT> fold_plan{};
-
-// r * R + c: the product inside fold_r, and a term of a G = 1 sum (the lone factor times the Montgomery one).  In a translation unit
-// that leaves its multiply-adds to the compiler (BX_PLAIN_MAD) the device build multiplies by an opaque copy of R, one per use: with the
-// constant in sight hipcc rewrites a sum of r_i * R as (sum of r_i) * R, sign-extends every r_i, adds them in 64 bits and emulates a
-// 64 x 32-bit product, and it takes a single r * R apart into shifts.  The copy lives in an SGPR (an s_mov per use, no VALU work), is
-// signed so that the product stays a v_mad_i64_i32 (an opaque unsigned word gets an emulated v_mad_u64_u32 product), and comes out of a
-// volatile asm (CSE merges the copies of a plain one and the rewrite is back).  Same 64-bit integer either way.
-BX_HD i64 smad_r(i32 r, i64 c, int alt = 0) {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(BX_PLAIN_MAD)
-    (void)alt;
-    i32 k = (i32)MONT_ONE;
-    asm volatile("" : "+s"(k));
-    return (i64)r * (i64)k + c;
-#else
-    return smad_k(r, MONT_ONE, c, alt);
-#endif
-}
-
-// a -> hi(a) * R + lo(a) with lo unsigned: congruent to a mod P since 2^32 == R, and |result| <= |a|/16 + 2^32 + R.  One multiply-add,
-// by smad_r's opaque signed copy of R where the multiply-adds are the compiler's: one v_mad_i64_i32 whose addend is (lo, 0).
-BX_HD i64 fold_r(i64 a, int alt = 0) {
-    BX_ASSERT_BOUND(a >= -INT64_MAX, "fold_r operand");
-    const i64 r = smad_r((i32)(a >> 32), (i64)(uint32_t)a, alt);
-    BX_ASSERT_BOUND(iabs64(r) <= iabs64(a) / 16 + ((i64)1 << 32) + (i64)MONT_ONE, "fold_r result");
-    return r;
-}
-// a * b + c, a step of a chain.  The device build of a BX_PLAIN_MAD translation unit hides the result from the optimiser (an empty asm, no
-// instruction): left in sight, hipcc reassociates fold + t1 + ... + t5 into fold + (t1 + ... + t5), sums the terms in a chain of their own
-// and pays a 64-bit add per segment to bring the fold in; hidden, every step is the one v_mad_i64_i32 whose addend is the chain.
-BX_HD i64 smad_chain(i32 a, i32 b, i64 c, int alt = 0) {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(BX_PLAIN_MAD)
-    (void)alt;
-    i64 r = (i64)a * (i64)b + c;
-    asm("" : "+v"(r));
-    return r;
-#else
-    return smad(a, b, c, alt);
-#endif
-}
 
 // The compile-time paths, on a pool that is already centred: |pool[i]| <= P/2 is what every bound of the plans rests on, and the
 // host build (BX_CHECK_BOUNDS) asserts it for every entry.  The walk of circuit.hip calls this with the pool its DerivedRegs<true>

@@ -10,7 +10,8 @@
 // hit the first live lane's bin are counted with one ballot and added by one lane, as msm_bucket_kernel (bn254.hip) does, which
 // turns a constant column into one LDS atomic per wave — and flushes every non-zero bin with one global atomic.  ctx tunable
 // lookup_hist_lds = 0 keeps the plain form for comparison (tools/lookup_bench.py); both give the same counts.
-// eval_check costs two ext x ext products per sequence and domain point (f4_mul_lz, lazy_ext.hpp) and is VALU-bound like the
+// eval_check costs one ext x ext product per sequence and domain point (f4_mul_lz, lazy_ext.hpp) and the 16 raw products that take its
+// constraint into the weighted sum (WeightedExtAcc, reduced once per point), and is VALU-bound like the
 // synthetic circuit's; everything else here streams.
 #define BX_PLAIN_MAD 1
 #include <memory>
@@ -152,17 +153,25 @@ __global__ __launch_bounds__(256) void lookup_eval_check_kernel(uint32_t* __rest
     const uint32_t ib = (i + dom - 4u) & (dom - 1u);  // one row back: x * w_N^-1 = w_4N^(row - 4)
     const uint32_t first = ecode[i], last = ecode[(size_t)dom + i], table = ecode[2 * (size_t)dom + i];
     const uint32_t not_first = fp_sub(MONT_ONE, first);
-    // (S_s(x) - (1 - first) S_s(x w_N^-1)) * (alpha - a) + add, weighted poly_mix^(V + s); returns S_s(x) for the closing sum
-    Fp4 tot = f4_zero(), closing = f4_zero();
+    // (S_s(x) - (1 - first) S_s(x w_N^-1)) * (alpha - a) + add, weighted poly_mix^(V + s); returns S_s(x) for the closing sum.  The
+    // ext-valued constraints are one weighted sum (lazy_ext.hpp, WeightedExtAcc): a canonical value goes in as it is, under the centred
+    // mix power, and the sum is reduced once
+    WeightedExtAcc extacc;
+    extacc.reset();
+    Fp4 closing = f4_zero();
+    const auto mix_ext = [&](size_t k, const Fp4& val) {
+        const i32 v[4] = {(i32)val.c[0], (i32)val.c[1], (i32)val.c[2], (i32)val.c[3]};
+        mix_add(extacc, mixpows_c, k, v);
+    };
     const auto sequence = [&](uint32_t s, uint32_t a, const Fp4& add) {
         Fp4 cur, back;
         ext_column_at(eacc, s, dom, i, ib, cur, back);
         const Fp4 step = f4_sub(cur, f4_scale(back, not_first));
         const Fp4 den{{fp_sub(pt.alpha.c[0], a), pt.alpha.c[1], pt.alpha.c[2], pt.alpha.c[3]}};
-        tot = f4_add(tot, f4_mul_lz(mix_power(mixpows, lk.V + s), f4_add(f4_mul_lz(step, den), add)));
+        mix_ext(lk.V + s, f4_add(f4_mul_lz(step, den), add));
         closing = f4_add(closing, cur);
     };
-    LazyExtAcc mixacc;  // the base-valued constraints v - lo - B hi (ext weight x base value)
+    LazyExtAcc mixacc;  // the base-valued constraints: v - lo - B hi, and the two boundary ones
     mixacc.reset();
     const Fp4 minus_one{{fp_neg(MONT_ONE), 0u, 0u, 0u}};
     for (uint32_t j = 0; j < lk.V; ++j) {
@@ -172,12 +181,12 @@ __global__ __launch_bounds__(256) void lookup_eval_check_kernel(uint32_t* __rest
         sequence(2 * j + 1, hi, minus_one);
     }
     sequence(2 * lk.V, table, Fp4{{edata[(size_t)lk.mult_col() * dom + i], 0u, 0u, 0u}});
-    tot = f4_add(tot, mixacc.finish());
     const size_t k0 = 3 * (size_t)lk.V + 1;
-    tot = f4_add(tot, f4_mul_lz(mix_power(mixpows, k0), f4_scale(closing, last)));
+    mix_ext(k0, f4_scale(closing, last));
     const uint32_t v0 = edata[i];
-    tot = f4_add(tot, f4_scale(mix_power(mixpows, k0 + 1), fp_mul(first, fp_sub(v0, pt.at.g[0]))));
-    tot = f4_add(tot, f4_scale(mix_power(mixpows, k0 + 2), fp_mul(last, fp_sub(v0, pt.at.g[1]))));
+    mix_add(mixacc, mixpows_c, k0 + 1, fp_mul(first, fp_sub(v0, pt.at.g[0])));
+    mix_add(mixacc, mixpows_c, k0 + 2, fp_mul(last, fp_sub(v0, pt.at.g[1])));
+    const Fp4 tot = f4_add(mixacc.finish(), extacc.finish());
     store_check(check, tot, pt.at, dom, i);
 }
 
