@@ -681,6 +681,7 @@ class WitnessProgram:
 
 # ---- accumulate programs (include/bx_program.h, "Accumulate programs"): a circuit's running sums and products from one description ----
 OP_SUM, OP_PROD = 11, 12  # BX_CONS_SUM, BX_CONS_PROD
+OP_RATIO = 16  # BX_CONS_RATIO (13, 14 and 15 are no ops)
 ACC_MAX_SEQS = 1024  # BX_ACC_MAX_SEQS
 
 
@@ -707,7 +708,8 @@ def _acc_lib():
         lib.bx_acc_program_keep.argtypes = [vp, vp, C.c_uint32, BxBuf, C.c_uint32, BxBuf, C.c_uint32, BxBuf]
         lib.bx_acc_program_run.argtypes = [vp, vp, C.c_uint32, BxBuf, u32p, u32p, BxBuf, BxBuf, BxBuf, C.c_uint32]
         lib.bx_cons_circuit_set_accumulate.argtypes = [vp, vp]
-        for name in ("bx_acc_program_create", "bx_acc_program_info_get", "bx_acc_program_kept", "bx_acc_program_run_host", "bx_acc_program_load",
+        lib.bx_acc_program_ratios.argtypes = [vp, u32p]
+        for name in ("bx_acc_program_create", "bx_acc_program_info_get", "bx_acc_program_kept", "bx_acc_program_ratios", "bx_acc_program_run_host", "bx_acc_program_load",
                      "bx_acc_program_unload", "bx_acc_program_keep", "bx_acc_program_run", "bx_cons_circuit_set_accumulate"):
             getattr(lib, name).restype = C.c_char_p
         lib._acc_bound = True
@@ -742,6 +744,14 @@ class CompiledAccumulateProgram(_CompiledProgram):
             out.append((int(g.value), int(c.value)))
         return out
 
+    def ratios(self):
+        """R, the number of RATIO sequences: the last R of info()["sequences"] (bx_acc_program_ratios).  run_ext of `run` holds
+        4 N (S + R) words."""
+        r = C.c_uint32()
+        msg = self.lib.bx_acc_program_ratios(self.handle, C.byref(r))
+        assert not msg, msg
+        return int(r.value)
+
     def run_host(self, po2, code, w_code, data, w_data, globals_, mix, accum, w_accum):
         """bx_acc_program_run_host: code (w_code x N), data (w_data x N) and accum (w_accum x N) are C-contiguous uint32 numpy arrays of
         Montgomery words; globals_ the program's public words, mix four words.  Columns [0, 4 S) of `accum` are written in place.  A
@@ -765,7 +775,8 @@ class CompiledAccumulateProgram(_CompiledProgram):
 class AccumulateProgram(ConsProgram):
     """Builder of an accumulate program (include/bx_program.h, "Accumulate programs"): const / const_ext / get / global_ / mix / add / sub /
     mul append one step and return the index of the fp var it made; sum_(s, m, d) makes sequence s the running sum of m / d, prod(s, a)
-    the running product of a.  Sums are numbered before products; sequence s is accum columns 4 s .. 4 s + 3.
+    the running product of a, ratio(s, a, b) the running product of a / b.  Sums are numbered before products, products before ratios;
+    sequence s is accum columns 4 s .. 4 s + 3.
 
         p = AccumulateProgram()
         alpha = p.add(p.const_ext(0, 1, 0, 0), p.mix(0))   # an ext value built from a mix component
@@ -778,6 +789,10 @@ class AccumulateProgram(ConsProgram):
 
     def prod(self, s, a):
         self.steps.append((OP_PROD, s, a, 0, 0))
+
+    def ratio(self, s, a, b):
+        """sequence s is the running product of a / b (a zero b contributes the factor 0); ratios are numbered after all products"""
+        self.steps.append((OP_RATIO, s, a, b, 0))
 
     def compile(self):
         """-> CompiledAccumulateProgram.  A refusal raises HalError."""

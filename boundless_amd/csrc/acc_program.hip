@@ -1,7 +1,7 @@
 // acc_program.hip — device half of accumulate programs ("Accumulate programs" of include/bx_program.h is the normative text;
 // cons_program.hpp the compiled form): a kernel that gathers the columns a program taps before the prover interpolates them away, and a
 // kernel that INTERPRETS the program's instruction stream over the N trace rows and writes every sequence's per-row term where the
-// HAL's scans take it (bx_logup_accumulate, bx_batch_prefix_products).  The interpreter follows the choices of cons_program.hip, for
+// HAL's scans take it (bx_logup_accumulate, bx_batch_prefix_products, bx_batch_ratio_products).  The interpreter follows the choices of cons_program.hip, for
 // the reasons written at the top of that file, and shares its opcode bodies (cons_program_exec.hpp):
 //   lanes     one lane per row, 256 per workgroup; lanes past N return at once
 //   slots     narrow and wide slot files in dynamic LDS, slot-major, sized per program (narrow + 4 wide KiB, at most 128 KiB)
@@ -10,7 +10,8 @@
 //   stream    wave-uniform, through a const __restrict__ pointer, CP_FETCH instructions per fetch, decoded through readfirstlane
 //   values    canonical throughout, the same fp_* / f4_* calls: bx_acc_program_run_host gives identical words
 //   memory    a tap is kept[k N + ((r - back) & (N - 1))].  A term is ONE 16-byte store at run_ext[4 (s N + r)] — a base value is
-//             promoted to (v, 0, 0, 0) — so a wave writes 1 KiB contiguous; a sum also writes one word at mults[s N + r]
+//             promoted to (v, 0, 0, 0) — so a wave writes 1 KiB contiguous; a sum also writes one word at mults[s N + r]; the t-th
+//             ratio's denominator is the term of sequence S + t, behind the S sequences the store reads
 #define BX_PLAIN_MAD 1
 #include <memory>
 #include <new>
@@ -61,6 +62,8 @@ struct AccEnv {
             break;
         case CP_TPROD_B: term(imm, Fp4{{nar[a * CP_LANES], 0u, 0u, 0u}}); break;
         case CP_TPROD_E: term(imm, cp_ldw(wid, a)); break;
+        case CP_TDEN_B: term(imm, Fp4{{nar[a * CP_LANES], 0u, 0u, 0u}}); break;  // a ratio's denominator: sequences [S, S + R) of run_ext
+        case CP_TDEN_E: term(imm, cp_ldw(wid, a)); break;
         default: break;
         }
     }
@@ -95,7 +98,7 @@ bool stream_fits(const bx_acc_program* p) {
     const bx_acc_program_info& in = p->info;
     const size_t n_scal = in.n_globals + 4 + p->consts.size();
     if (in.narrow > BX_CONS_MAX_NARROW || in.wide > BX_CONS_MAX_WIDE || in.sums > in.sequences || in.sequences < 1 || in.sequences > BX_ACC_MAX_SEQS ||
-        p->code.size() % (2 * CP_FETCH) || p->tap_kept.size() != p->taps.size() || in.kept != p->kept.size())
+        p->code.size() % (2 * CP_FETCH) || p->tap_kept.size() != p->taps.size() || in.kept != p->kept.size() || p->ratios > in.sequences - in.sums)
         return false;
     for (uint32_t k : p->tap_kept)
         if (k >= p->kept.size()) return false;
@@ -126,6 +129,8 @@ bool stream_fits(const bx_acc_program* p) {
         case CP_TSUM_E: ok = N(a) && W(b) && imm < in.sums; break;
         case CP_TPROD_B: ok = N(a) && imm >= in.sums && imm < in.sequences; break;
         case CP_TPROD_E: ok = W(a) && imm >= in.sums && imm < in.sequences; break;
+        case CP_TDEN_B: ok = N(a) && imm >= in.sequences && imm < in.sequences + p->ratios; break;
+        case CP_TDEN_E: ok = W(a) && imm >= in.sequences && imm < in.sequences + p->ratios; break;
         default: ok = false; break;
         }
         if (!ok) return false;
@@ -149,6 +154,7 @@ extern "C" const char* bx_acc_program_load(bx_ctx* c, const bx_acc_program* prog
     std::unique_ptr<bx_acc_program_dev> d(new bx_acc_program_dev());
     d->ctx = c;
     d->info = prog->info;
+    d->ratios = prog->ratios;
     d->n_fetch = (uint32_t)(prog->code.size() / (2 * CP_FETCH));
     d->kept_cols = prog->kept;
     d->lds = (size_t)(prog->info.narrow + 4 * prog->info.wide) * CP_LANES * 4;
@@ -213,11 +219,12 @@ extern "C" const char* bx_acc_program_run(bx_ctx* c, bx_acc_program_dev* dev, ui
     BX_REQUIRE(c, dev->ctx == c, "bx_acc_program_run: the program was loaded on another ctx");
     BX_REQUIRE(c, po2 >= 1 && po2 <= 24, "bx_acc_program_run: po2 must be in [1, 24]");
     BX_ENTER(c);
-    const size_t n = (size_t)1 << po2, K = dev->info.kept, S = dev->info.sequences, sums = dev->info.sums;
+    const size_t n = (size_t)1 << po2, K = dev->info.kept, S = dev->info.sequences, sums = dev->info.sums, R = dev->ratios;
     const uint32_t ng = dev->info.n_globals;
     BX_REQUIRE(c, !ng || globals, "bx_acc_program_run: the program names globals and none were given");
     BX_REQUIRE(c, kept.len == n * K, "bx_acc_program_run: kept size mismatch (N x the program's kept columns)");
-    BX_REQUIRE(c, run_ext.len == 4 * n * S, "bx_acc_program_run: run_ext size mismatch (4 N words per sequence)");
+    BX_REQUIRE(c, R || run_ext.len == 4 * n * S, "bx_acc_program_run: run_ext size mismatch (4 N words per sequence)");
+    BX_REQUIRE(c, run_ext.len == 4 * n * (S + R), "bx_acc_program_run: run_ext size mismatch (4 N words per sequence and 4 N more per RATIO: its denominators)");
     BX_REQUIRE(c, mults.len == n * sums, "bx_acc_program_run: mults size mismatch (N words per running sum)");
     BX_REQUIRE(c, accum.len == n * w_accum, "bx_acc_program_run: accum size mismatch (N x w_accum)");
     if (w_accum < 4 * S) {
@@ -237,7 +244,7 @@ extern "C" const char* bx_acc_program_run(bx_ctx* c, bx_acc_program_dev* dev, ui
     BX_TRY(h2d_staged(c, dev->scal.slice(0, ng + 4), dyn, ng + 4));
     {
         // every tap is read once; a term is 16 bytes, and 4 more for a sum
-        OpScope op(c, "acc_program_run", 4.0 * (double)n * ((double)dev->info.taps + 4.0 * (double)S + (double)sums));
+        OpScope op(c, "acc_program_run", 4.0 * (double)n * ((double)dev->info.taps + 4.0 * (double)(S + R) + (double)sums));
         hipLaunchKernelGGL(acc_program_kernel, dim3((unsigned)((n + CP_LANES - 1) / CP_LANES)), dim3(CP_LANES), dev->lds, c->stream, (uint32_t*)run_ext.dptr,
                            (uint32_t*)mults.dptr, (const uint32_t*)kept.dptr, (const uint4*)dev->code.b.dptr, (const uint2*)dev->taps.b.dptr,
                            (const uint32_t*)dev->scal.b.dptr, (uint32_t)n, dev->n_fetch, dev->info.narrow);
@@ -248,7 +255,11 @@ extern "C" const char* bx_acc_program_run(bx_ctx* c, bx_acc_program_dev* dev, ui
         const bx_buf part{run, 4 * n * sums};
         BX_TRY(bx_logup_accumulate(c, part, part, mults, sums));
     }
-    if (S > sums) BX_TRY(bx_batch_prefix_products(c, bx_buf{run + 4 * n * sums, 4 * n * (S - sums)}, S - sums));
+    if (S - R > sums) BX_TRY(bx_batch_prefix_products(c, bx_buf{run + 4 * n * sums, 4 * n * (S - R - sums)}, S - R - sums));
+    if (R) {  // in place: the products replace the numerators; the denominators lie right behind them
+        const bx_buf nums{run + 4 * n * (S - R), 4 * n * R};
+        BX_TRY(bx_batch_ratio_products(c, nums, nums, bx_buf{run + 4 * n * S, 4 * n * R}, R));
+    }
     OpScope op(c, "acc_program_store", 32.0 * (double)(n * S));
     return store_ext_columns(c, accum, run_ext, po2, (uint32_t)S, (uint32_t)(4 * S), 0);  // no filler: columns >= 4 S are not written
 } BX_ABI_CATCH(c, "bx_acc_program_run")

@@ -6,6 +6,7 @@
 struct bx_acc_program_dev {
     bx_ctx* ctx = nullptr;
     bx_acc_program_info info{};
+    uint32_t ratios = 0;  // R of the compiled program: run_ext holds S + R sequences
     uint32_t n_fetch = 0;
     size_t lds = 0;
     std::vector<bx_cons_tap> kept_cols;  // host copy of the kept list: the width checks of keep

@@ -296,7 +296,7 @@ const char* cc_create(void* u, bx_ctx* c, const bx_segment_params* shape, void**
     if (const bx_acc_program* a = cc->acc) {
         if (const char* e = bx_acc_program_load(c, a, &st->acc_dev)) return undo(e);
         const size_t n = (size_t)1 << shape->po2;
-        for (const char* e : {st->kept.alloc(c, std::max<size_t>(n * a->info.kept, 1)), st->run_ext.alloc(c, 4 * n * a->info.sequences),
+        for (const char* e : {st->kept.alloc(c, std::max<size_t>(n * a->info.kept, 1)), st->run_ext.alloc(c, 4 * n * (a->info.sequences + a->ratios)),  // a RATIO's denominators behind the S terms
                               st->mults.alloc(c, std::max<size_t>(n * a->info.sums, 1))})
             if (e) return undo(e);
     }

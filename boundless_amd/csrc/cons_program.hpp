@@ -48,6 +48,10 @@ enum ConsOpcode : uint32_t {
     CP_TSUM_E,   // run_ext[imm][r] = wide[b],              mults[imm][r] = narrow[a]  (SUM, ext denominator)
     CP_TPROD_B,  // run_ext[imm][r] = (narrow[a], 0, 0, 0)                             (PROD, base factor)
     CP_TPROD_E,  // run_ext[imm][r] = wide[a]                                          (PROD, ext factor)
+    // the denominator of a RATIO, appended last for the same reason; its numerator is a CP_TPROD_B/E with imm = the sequence.  imm = S + t
+    // for the t-th of the R ratios: run_ext holds S + R sequences, [S, S + R) the denominators of sequences [S - R, S)
+    CP_TDEN_B,   // run_ext[imm][r] = (narrow[a], 0, 0, 0)                             (RATIO, base denominator)
+    CP_TDEN_E,   // run_ext[imm][r] = wide[a]                                          (RATIO, ext denominator)
     CP_OPCODES
 };
 constexpr uint32_t CP_FETCH = 4;  // instructions per fetch of the kernel (8 dwords)
@@ -99,6 +103,7 @@ struct bx_acc_program {
     std::vector<bx_cons_tap> taps;
     std::vector<uint32_t> tap_kept;  // per tap: its kept index
     std::vector<bx_cons_tap> kept;   // the distinct (group, col) of the tap list in order of first appearance (back unused, 0)
+    uint32_t ratios = 0;             // R: sequences [S - R, S) are RATIOs (not in `info`, whose layout is fixed)
 };
 
 namespace bx {

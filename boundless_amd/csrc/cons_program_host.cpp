@@ -138,6 +138,11 @@ struct AccEnv {
             if (imm < sums || imm >= S) return false;
             run[(size_t)imm * n + r] = op == CP_TPROD_B ? Fp4{{nar[a], 0u, 0u, 0u}} : wid[a];
             return true;
+        case CP_TDEN_B:
+        case CP_TDEN_E:  // the denominators of the R ratios: sequences [S, S + R) of `run`
+            if (imm < S || imm >= S + prog->ratios) return false;
+            run[(size_t)imm * n + r] = op == CP_TDEN_B ? Fp4{{nar[a], 0u, 0u, 0u}} : wid[a];
+            return true;
         default: return false;
         }
     }
@@ -311,6 +316,12 @@ extern "C" const char* bx_acc_program_kept(const bx_acc_program* prog, uint32_t 
     return nullptr;
 }
 
+extern "C" const char* bx_acc_program_ratios(const bx_acc_program* prog, uint32_t* out) {
+    if (!prog || !out) return "bx_acc_program_ratios: null argument";
+    *out = prog->ratios;
+    return nullptr;
+}
+
 extern "C" const char* bx_acc_program_run_host(const bx_acc_program* prog, uint32_t po2, const uint32_t* code, uint32_t w_code, const uint32_t* data,
                                                uint32_t w_data, const uint32_t* globals, const uint32_t mix[4], uint32_t* accum, uint32_t w_accum) try {
     using namespace bx;
@@ -322,7 +333,9 @@ extern "C" const char* bx_acc_program_run_host(const bx_acc_program* prog, uint3
     if (w_accum < 4 * S) return refuse("bx_acc_program_run_host: the program writes %u accum columns, the accum group has %u", 4 * S, w_accum);
     const size_t n = (size_t)1 << po2;
     const std::vector<uint32_t> scal = scal_table(prog->info.n_globals, globals, mix, prog->consts);
-    std::vector<Fp4> run((size_t)S * n, f4_zero());
+    const uint32_t R = prog->ratios;
+    if (R > S - sums) return "bx_acc_program_run_host: corrupt instruction stream";
+    std::vector<Fp4> run((size_t)(S + R) * n, f4_zero());
     std::vector<uint32_t> mults((size_t)sums * n, 0u);
     // (1) the terms of every row
     for (size_t r = 0; r < n; ++r) {
@@ -334,12 +347,17 @@ extern "C" const char* bx_acc_program_run_host(const bx_acc_program* prog, uint3
         for (size_t pc = 0; pc < prog->code.size(); pc += 2)
             if (!host_exec(prog->code[pc], prog->code[pc + 1], nar, wid, scal, env)) return "bx_acc_program_run_host: corrupt instruction stream";
     }
-    // (2) m / d with 0 -> 0 and the running sums; (3) the running products; (4) sequence s, component k -> column 4 s + k
+    // (2) m / d with 0 -> 0 and the running sums; (3) a / b with 1 / 0 -> 0 for the ratios, and the running products; (4) sequence s,
+    // component k -> column 4 s + k
     for (uint32_t s = 0; s < S; ++s) {
         Fp4 acc = s < sums ? f4_zero() : f4_one();
         for (size_t r = 0; r < n; ++r) {
             const Fp4& v = run[(size_t)s * n + r];
             if (s < sums) acc = f4_add(acc, f4_is_zero(v) ? f4_zero() : f4_scale(f4_inv(v), mults[(size_t)s * n + r]));
+            else if (s >= S - R) {
+                const Fp4& d = run[(size_t)(s + R) * n + r];
+                acc = f4_mul(acc, f4_is_zero(d) ? f4_zero() : f4_mul(v, f4_inv(d)));
+            }
             else acc = f4_mul(acc, v);
             for (uint32_t k = 0; k < 4; ++k) accum[(size_t)(4 * s + k) * n + r] = acc.c[k];
         }

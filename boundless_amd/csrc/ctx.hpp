@@ -81,7 +81,7 @@ struct bx_ctx {
     uint32_t* d_scan[2] = {nullptr, nullptr};
     size_t scan_cap = 0, scan_used[2] = {0, 0};
     int scan_next = 0;
-    long scan_lookback = 1;  // poly_divide / prefix_products / prefix_sums / logup_accumulate: single-pass decoupled look-back kernels (0 = the three-phase kernels)
+    long scan_lookback = 1;  // poly_divide / prefix_products / prefix_sums / logup_accumulate / batch_ratio_products: single-pass decoupled look-back kernels (0 = the three-phase kernels)
 
     // Deferred Hal::gather_sample calls (poly.hip).  MerkleTreeProver::prove issues one gather per opened row and one per path digest:
     // ~5 000 launches of a few words each per proof, 3.7 us of host time apiece on an idle GPU (19 of the 70 ms of a proof driven

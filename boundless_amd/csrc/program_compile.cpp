@@ -503,39 +503,51 @@ const char* compile_acc(const bx_acc_program_desc* d, bx_acc_program* p) {
     }));
     p->taps.assign(d->taps, d->taps + d->n_taps);
 
-    std::map<uint32_t, std::pair<size_t, bool>> seqs;  // sequence -> (the step that defines it, is it a sum)
-    const auto define = [&](size_t i, uint32_t s, bool sum) -> const char* {
+    enum : int { SEQ_SUM, SEQ_PROD, SEQ_RATIO };
+    std::map<uint32_t, std::pair<size_t, int>> seqs;  // sequence -> (the step that defines it, its kind)
+    const auto define = [&](size_t i, uint32_t s, int kind) -> const char* {
         if (s >= BX_ACC_MAX_SEQS) return refuse("acc_program: step %zu: sequence %u is not below BX_ACC_MAX_SEQS = %d", i, s, BX_ACC_MAX_SEQS);
-        const auto ins = seqs.emplace(s, std::make_pair(i, sum));
+        const auto ins = seqs.emplace(s, std::make_pair(i, kind));
         if (!ins.second) return refuse("acc_program: step %zu: sequence %u is defined a second time (first at step %zu)", i, s, ins.first->second.first);
         return nullptr;
     };
     CP_TRY(c.validate([&](size_t i, const bx_cons_step& s) -> const char* {  // both append nothing
         switch (s.op) {
         case BX_CONS_SUM:
-            CP_TRY(define(i, s.a, true));
+            CP_TRY(define(i, s.a, SEQ_SUM));
             CP_TRY(c.use(i, "m", s.b));
             CP_TRY(c.use(i, "d", s.c));
             if (c.fp[s.b].ext) return refuse("acc_program: step %zu: SUM's m = %u is ext-typed; a multiplicity must be a base value", i, s.b);
             return nullptr;
         case BX_CONS_PROD:
-            CP_TRY(define(i, s.a, false));
+            CP_TRY(define(i, s.a, SEQ_PROD));
             return c.use(i, "a", s.b);
+        case BX_CONS_RATIO:
+            CP_TRY(define(i, s.a, SEQ_RATIO));
+            CP_TRY(c.use(i, "a", s.b));
+            return c.use(i, "b", s.c);
         default: return c.no_such_op(i, s.op);
         }
     }));
     if (seqs.empty()) return refuse("acc_program: the program defines no sequence (S = 0)");
-    uint32_t expect = 0, sums = 0;
+    uint32_t expect = 0, sums = 0, ratios = 0;
     bool prod_seen = false;
+    const std::pair<const uint32_t, std::pair<size_t, int>>* ratio_seen = nullptr;  // the lowest-numbered RATIO
     for (const auto& kv : seqs) {  // in sequence order
         if (kv.first != expect) return refuse("acc_program: sequence %u is not defined: the sequences must be exactly 0 .. S-1 (sequence %u is defined)", expect, kv.first);
         ++expect;
-        if (kv.second.second) {
-            if (prod_seen)
-                return refuse("acc_program: step %zu: SUM sequence %u is numbered above a PROD sequence: all sums come first, then all products", kv.second.first, kv.first);
-            ++sums;
-        } else {
-            prod_seen = true;
+        const int kind = kv.second.second;
+        if (kind == SEQ_SUM && prod_seen)
+            return refuse("acc_program: step %zu: SUM sequence %u is numbered above a PROD sequence: all sums come first, then all products", kv.second.first, kv.first);
+        if (kind != SEQ_RATIO && ratio_seen)
+            return refuse("acc_program: step %zu: %s sequence %u is numbered above a RATIO sequence (step %zu: RATIO sequence %u is numbered below a %s sequence): "
+                          "all sums come first, then all products, then all ratios",
+                          kv.second.first, kind == SEQ_SUM ? "SUM" : "PROD", kv.first, ratio_seen->second.first, ratio_seen->first, kind == SEQ_SUM ? "SUM" : "PROD");
+        if (kind == SEQ_SUM) ++sums;
+        else if (kind == SEQ_PROD) prod_seen = true;
+        else {
+            if (!ratio_seen) ratio_seen = &kv;
+            ++ratios;
         }
     }
 
@@ -544,14 +556,20 @@ const char* compile_acc(const bx_acc_program_desc* d, bx_acc_program* p) {
             c.emit(c.fp[s.c].ext ? CP_TSUM_E : CP_TSUM_B, 0, c.fp[s.b].slot, c.fp[s.c].slot, 0, s.a);
             c.drop(s.b, step);
             c.drop(s.c, step);
-        } else {
+        } else if (s.op == BX_CONS_PROD) {
             c.emit(c.fp[s.b].ext ? CP_TPROD_E : CP_TPROD_B, 0, c.fp[s.b].slot, 0, 0, s.a);
             c.drop(s.b, step);
+        } else {  // RATIO: the numerator where a product's factor goes, the denominator R sequences further on
+            c.emit(c.fp[s.b].ext ? CP_TPROD_E : CP_TPROD_B, 0, c.fp[s.b].slot, 0, 0, s.a);
+            c.emit(c.fp[s.c].ext ? CP_TDEN_E : CP_TDEN_B, 0, c.fp[s.c].slot, 0, 0, s.a + ratios);
+            c.drop(s.b, step);
+            c.drop(s.c, step);
         }
     }));
     p->info.steps = (uint32_t)d->n_steps;
     p->info.sequences = (uint32_t)seqs.size();
     p->info.sums = sums;
+    p->ratios = ratios;
     p->info.instructions = c.pad();
     p->info.narrow = c.narrow.top;
     p->info.wide = c.wide.top;

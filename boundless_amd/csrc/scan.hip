@@ -1,5 +1,5 @@
-// scan.hip — every scan over AoS ext arrays for gfx950: the DEEP quotient (poly_divide*), prefix_products, prefix_sums, and the
-// additive half of an accumulate stage (batch inversion, logup_accumulate).
+// scan.hip — every scan over AoS ext arrays for gfx950: the DEEP quotient (poly_divide*), prefix_products, prefix_sums, the
+// additive half of an accumulate stage (batch inversion, logup_accumulate), and the running product of ratios (batch_ratio_products).
 //
 // Restates risc0_zkp::core::poly::poly_divide (run once per tap point of every DEEP combination polynomial by
 // Prover::finalize) and risc0_zkp::hal::Hal::prefix_products (risc0-zkp 3.0.3, reference Cargo.lock:9155), reached from
@@ -322,15 +322,22 @@ __device__ __forceinline__ void inv_chunk(typename F::T (&x)[K]) {
 }
 
 // The scan of `count` sequences of n elements back to back, forward: out[i] <- in[0] op .. op in[i] (prefix_products with ScanMul,
-// prefix_sums with ScanSum).  LOGUP (sums only): the element that enters the sum is mults[i] * in[i]^-1, formed in the tile load — a
-// lane's 8 elements are one inversion chunk — so the fused call reads denoms and mults once and writes out once.  in == out is
-// allowed: a tile reads only itself, before it writes.
+// prefix_sums with ScanSum).  What a tile does to its elements before it scans them is the pre-step:
+//   PRE_LOGUP (sums only): the element that enters the sum is mults[i] * in[i]^-1, formed in the tile load — a lane's 8 elements are
+//   one inversion chunk — so the fused call reads denoms and mults once and writes out once.
+//   PRE_RATIO (products only): the element that enters the product is in[i] * den[i]^-1, where `mults` points at the AoS ext
+//   denominators.  The tile of denominators goes through `sh` first and is inverted like a LogUp chunk; the tile of numerators then
+//   takes the same 36 KiB (a second static tile would pass 64 KiB of static LDS), behind the barrier its write needs after the
+//   first tile's reads.  Past the end both read as one.  Both arrays are read once, out is written once.
+// in == out is allowed: a tile reads only itself, before it writes.  `mults` is never written and never overlaps out.
 __device__ __forceinline__ uint32_t sc_mslot(uint32_t u) { return u + (u >> 5); }  // 8 words per lane, 32 banks: lanes 4 apart shift by one bank
-template <typename Op, bool LOGUP>
+enum ScanPre { PRE_NONE, PRE_LOGUP, PRE_RATIO };
+template <typename Op, ScanPre PRE>
 __global__ __launch_bounds__(SC_T) void scan_lookback_kernel(const uint32_t* in, uint32_t* out, const uint32_t* __restrict__ mults, size_t n,
                                                              uint32_t* __restrict__ state, uint32_t seq_stride, uint32_t* __restrict__ clear,
                                                              size_t clear_words) {
     __shared__ uint4 sh[SC_T * 9];
+    constexpr bool LOGUP = PRE == PRE_LOGUP;
     __shared__ uint32_t shm[LOGUP ? SC_TILE + SC_TILE / 32 : 1];
     __shared__ uint32_t wtot[4 * 4], carry_sh[4], agg_sh[4], sh_tile;
     const uint32_t q = blockIdx.y, tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
@@ -341,6 +348,12 @@ __global__ __launch_bounds__(SC_T) void scan_lookback_kernel(const uint32_t* in,
     uint4* dst = reinterpret_cast<uint4*>(out) + (size_t)q * n;
     const uint32_t valid = n - lo < (size_t)SC_TILE ? (uint32_t)(n - lo) : (uint32_t)SC_TILE;
     Fp4 pre[SC_I];  // this lane's elements, then their running values; elements past the end are identities: they change no running value
+    Fp4 den[PRE == PRE_RATIO ? SC_I : 1];
+    if constexpr (PRE == PRE_RATIO) {
+        sc_tile_load(sh, reinterpret_cast<const uint4*>(mults) + (size_t)q * n, TileUp{lo}, valid, Op::pad(), den);
+        inv_chunk<InvFp4, SC_I>(den);
+        __syncthreads();  // every lane has read its denominators: the numerators may take the tile
+    }
     sc_tile_load(sh, src, TileUp{lo}, valid, Op::pad(), pre, [=](uint32_t u) {
         if (LOGUP) shm[sc_mslot(u)] = u < valid ? mults[(size_t)q * n + lo + u] : 0u;
     });
@@ -348,6 +361,10 @@ __global__ __launch_bounds__(SC_T) void scan_lookback_kernel(const uint32_t* in,
         inv_chunk<InvFp4, SC_I>(pre);
 #pragma unroll
         for (int k = 0; k < SC_I; ++k) pre[k] = f4_scale(pre[k], shm[sc_mslot(SC_I * tid + (uint32_t)k)]);
+    }
+    if constexpr (PRE == PRE_RATIO) {
+#pragma unroll
+        for (int k = 0; k < SC_I; ++k) pre[k] = f4_mul_lz(pre[k], den[k]);
     }
 #pragma unroll
     for (int k = 1; k < SC_I; ++k) pre[k] = Op::combine_lz(pre[k - 1], pre[k]);
@@ -384,20 +401,29 @@ __global__ __launch_bounds__(SC_T) void scan_lookback_kernel(const uint32_t* in,
     sc_tile_store(sh, dst, TileUp{lo}, valid);
 }
 
-// out[i] = in[i]^-1 (times mults[i] when SCALE) over n AoS ext elements; in == out is allowed.  A workgroup owns a tile of 2048
+// out[i] = in[i]^-1 (times mults[i] when BINV_SCALE) over n AoS ext elements; in == out is allowed.  A workgroup owns a tile of 2048
 // elements, loaded coalesced and transposed through LDS like the scans, so that a lane inverts 8 consecutive elements.  Elements
 // past the end are zeros: they cost a select and are never stored.
-template <bool SCALE>
+// BINV_RATIO: out[i] = in[i] * den[i]^-1, where `mults` points at the AoS ext denominators (never written, never overlapping out): the
+// tile that is loaded and inverted is theirs, and a lane reads its own 8 numerators from `in` (in == out is allowed here too: every
+// read of a tile comes before the barrier of its store).
+enum BinvMode { BINV_PLAIN, BINV_SCALE, BINV_RATIO };
+template <BinvMode MODE>
 __global__ __launch_bounds__(SC_T) void binv_ext_kernel(const uint32_t* in, uint32_t* out, const uint32_t* __restrict__ mults, size_t n) {
+    constexpr bool SCALE = MODE == BINV_SCALE;
     __shared__ uint4 sh[SC_T * 9];
     const uint32_t tid = threadIdx.x;
     const size_t lo = (size_t)blockIdx.x * SC_TILE;
     const uint32_t valid = n - lo < (size_t)SC_TILE ? (uint32_t)(n - lo) : (uint32_t)SC_TILE;
     Fp4 x[SC_I];
-    sc_tile_load(sh, reinterpret_cast<const uint4*>(in), TileUp{lo}, valid, make_uint4(0, 0, 0, 0), x);
+    sc_tile_load(sh, reinterpret_cast<const uint4*>(MODE == BINV_RATIO ? mults : in), TileUp{lo}, valid, make_uint4(0, 0, 0, 0), x);
     inv_chunk<InvFp4, SC_I>(x);
 #pragma unroll
     for (int k = 0; k < SC_I; ++k) {
+        if constexpr (MODE == BINV_RATIO) {  // 16-byte loads 128 bytes apart between lanes — the scan_lookback = 0 path only
+            const uint32_t u = SC_I * tid + (uint32_t)k;
+            if (u < valid) x[k] = f4_mul_lz(sc_ld4(in + 4 * (lo + u)), x[k]);
+        }
         if (SCALE) {  // a lane reads its own 8 multiplicities: 4-byte loads 32 bytes apart, uncoalesced — this is the scan_lookback = 0 path only
             const uint32_t u = SC_I * tid + (uint32_t)k;
             x[k] = f4_scale(x[k], u < valid ? mults[lo + u] : 0u);
@@ -664,15 +690,16 @@ static const char* poly_divide_lookback(bx_ctx* c, uint32_t* polys, size_t size,
     }
     return nullptr;
 }
-// the look-back scan of `count` sequences of n elements, `in` to `out` (the same buffer, or denoms and mults to out for LOGUP)
-template <typename Op, bool LOGUP>
+// the look-back scan of `count` sequences of n elements, `in` to `out` (the same buffer; denoms and mults to out for PRE_LOGUP; nums, with
+// the ext denominators in `mults`, to out for PRE_RATIO)
+template <typename Op, ScanPre PRE>
 static const char* scan_lookback(bx_ctx* c, const uint32_t* in, uint32_t* out, const uint32_t* mults, size_t n, size_t count) {
     const size_t tiles = (n + SC_TILE - 1) / SC_TILE;
     const uint32_t seq_stride = SC_HDR + 8 * (uint32_t)tiles;
     uint32_t *use, *clear;
     size_t clear_words;
     BX_TRY(scan_state(c, (size_t)seq_stride * count, &use, &clear, &clear_words));
-    hipLaunchKernelGGL((scan_lookback_kernel<Op, LOGUP>), dim3((unsigned)tiles, (unsigned)count), dim3(SC_T), 0, c->stream, in, out, mults, n, use,
+    hipLaunchKernelGGL((scan_lookback_kernel<Op, PRE>), dim3((unsigned)tiles, (unsigned)count), dim3(SC_T), 0, c->stream, in, out, mults, n, use,
                        seq_stride, clear, clear_words);
     BX_LAUNCH_CHECK(c);
     return nullptr;
@@ -792,7 +819,7 @@ extern "C" const char* bx_batch_prefix_products(bx_ctx* c, bx_buf io, size_t cou
     if (n < 2) return nullptr;
     OpScope op(c, "prefix_products", 8.0 * (double)io.len);
     if (c->scan_lookback && ((uintptr_t)io.dptr & 15u) == 0)
-        return scan_lookback<ScanMul, false>(c, (const uint32_t*)io.dptr, (uint32_t*)io.dptr, nullptr, n, count);
+        return scan_lookback<ScanMul, PRE_NONE>(c, (const uint32_t*)io.dptr, (uint32_t*)io.dptr, nullptr, n, count);
     return scan_three_phase<ScanMul>(c, (uint32_t*)io.dptr, n, count);
 } BX_ABI_CATCH(c, "bx_batch_prefix_products")
 extern "C" const char* bx_prefix_products(bx_ctx* c, bx_buf io) try {
@@ -805,9 +832,9 @@ extern "C" const char* bx_prefix_products(bx_ctx* c, bx_buf io) try {
 static const char* launch_invert_ext(bx_ctx* c, const uint32_t* in, uint32_t* out, const uint32_t* mults, size_t n) {
     const unsigned tiles = (unsigned)((n + SC_TILE - 1) / SC_TILE);
     if (mults)
-        hipLaunchKernelGGL(binv_ext_kernel<true>, dim3(tiles), dim3(SC_T), 0, c->stream, in, out, mults, n);
+        hipLaunchKernelGGL(binv_ext_kernel<BINV_SCALE>, dim3(tiles), dim3(SC_T), 0, c->stream, in, out, mults, n);
     else
-        hipLaunchKernelGGL(binv_ext_kernel<false>, dim3(tiles), dim3(SC_T), 0, c->stream, in, out, mults, n);
+        hipLaunchKernelGGL(binv_ext_kernel<BINV_PLAIN>, dim3(tiles), dim3(SC_T), 0, c->stream, in, out, mults, n);
     BX_LAUNCH_CHECK(c);
     return nullptr;
 }
@@ -847,7 +874,7 @@ extern "C" const char* bx_batch_prefix_sums(bx_ctx* c, bx_buf io, size_t count) 
     const size_t n = io.len / 4 / count;
     if (n < 2) return nullptr;
     OpScope op(c, "prefix_sums", 8.0 * (double)io.len);
-    if (c->scan_lookback) return scan_lookback<ScanSum, false>(c, (const uint32_t*)io.dptr, (uint32_t*)io.dptr, nullptr, n, count);
+    if (c->scan_lookback) return scan_lookback<ScanSum, PRE_NONE>(c, (const uint32_t*)io.dptr, (uint32_t*)io.dptr, nullptr, n, count);
     return scan_three_phase<ScanSum>(c, (uint32_t*)io.dptr, n, count);
 } BX_ABI_CATCH(c, "bx_batch_prefix_sums")
 extern "C" const char* bx_prefix_sums(bx_ctx* c, bx_buf io) try {
@@ -870,9 +897,34 @@ extern "C" const char* bx_logup_accumulate(bx_ctx* c, bx_buf out, bx_buf denoms,
     if (!n) return nullptr;
     OpScope op(c, "logup_accumulate", 8.0 * (double)out.len + 4.0 * (double)(count * n));
     if (c->scan_lookback)
-        return scan_lookback<ScanSum, true>(c, (const uint32_t*)denoms.dptr, (uint32_t*)out.dptr, (const uint32_t*)mults.dptr, n, count);
+        return scan_lookback<ScanSum, PRE_LOGUP>(c, (const uint32_t*)denoms.dptr, (uint32_t*)out.dptr, (const uint32_t*)mults.dptr, n, count);
     // the three-phase form: invert and scale into out, then the three-phase running sums over out
     BX_TRY(launch_invert_ext(c, (const uint32_t*)denoms.dptr, (uint32_t*)out.dptr, (const uint32_t*)mults.dptr, n * count));
     if (n < 2) return nullptr;
     return scan_three_phase<ScanSum>(c, (uint32_t*)out.dptr, n, count);
 } BX_ABI_CATCH(c, "bx_logup_accumulate")
+extern "C" const char* bx_batch_ratio_products(bx_ctx* c, bx_buf out, bx_buf nums, bx_buf denoms, size_t count) try {
+    if (!c) return "bx_batch_ratio_products: null ctx";
+    BX_REQUIRE(c, out.len % 4 == 0 && nums.len == out.len && denoms.len == out.len,
+               "bx_batch_ratio_products: out, nums and denoms must hold the same number of AoS ext elements");
+    BX_REQUIRE(c, count >= 1 && count <= 65535, "bx_batch_ratio_products: the number of sequences must be in [1, 65535]");
+    BX_REQUIRE(c, (out.len / 4) % count == 0, "bx_batch_ratio_products: the buffers do not split into `count` equal sequences");
+    const size_t n = out.len / 4 / count;
+    BX_REQUIRE(c, out.len / 4 <= SC_MAX_ELEMS, "bx_batch_ratio_products: too many elements");  // bounds n, and the one-launch inversion over all sequences
+    BX_REQUIRE(c, bufs_same(out, nums) || !bufs_overlap(out, nums), "bx_batch_ratio_products: out and nums overlap");
+    BX_REQUIRE(c, !bufs_overlap(out, denoms), "bx_batch_ratio_products: out and denoms overlap");
+    BX_REQUIRE(c, ((uintptr_t)out.dptr & 15u) == 0 && ((uintptr_t)nums.dptr & 15u) == 0 && ((uintptr_t)denoms.dptr & 15u) == 0,
+               "bx_batch_ratio_products: buffers must be 16-byte aligned");
+    BX_ENTER(c);
+    if (!n) return nullptr;
+    OpScope op(c, "ratio_products", 12.0 * (double)out.len);
+    // the ext denominators travel where the LogUp multiplicities do: read-only, and never overlapping out
+    if (c->scan_lookback)
+        return scan_lookback<ScanMul, PRE_RATIO>(c, (const uint32_t*)nums.dptr, (uint32_t*)out.dptr, (const uint32_t*)denoms.dptr, n, count);
+    // the three-phase form: nums * denoms^-1 into out, then the three-phase running products over out
+    hipLaunchKernelGGL(binv_ext_kernel<BINV_RATIO>, dim3((unsigned)((n * count + SC_TILE - 1) / SC_TILE)), dim3(SC_T), 0, c->stream, (const uint32_t*)nums.dptr,
+                       (uint32_t*)out.dptr, (const uint32_t*)denoms.dptr, n * count);
+    BX_LAUNCH_CHECK(c);
+    if (n < 2) return nullptr;
+    return scan_three_phase<ScanMul>(c, (uint32_t*)out.dptr, n, count);
+} BX_ABI_CATCH(c, "bx_batch_ratio_products")

@@ -105,6 +105,7 @@ def load_library():
         "bx_prefix_sums": [ctx, BxBuf],
         "bx_batch_prefix_sums": [ctx, BxBuf, sz],
         "bx_logup_accumulate": [ctx, BxBuf, BxBuf, BxBuf, sz],
+        "bx_batch_ratio_products": [ctx, BxBuf, BxBuf, BxBuf, sz],
         "bx_scatter": [ctx, BxBuf, BxBuf, BxBuf, BxBuf],
         "bx_timer_start": [ctx],
         "bx_timer_stop": [ctx, C.POINTER(C.c_float)],
@@ -423,6 +424,11 @@ class HipHal:
     def logup_accumulate(self, out, denoms, mults, count=1):
         """out[s][i] = sum_{j <= i} mults[s][j] / denoms[s][j] for `count` sequences back to back; `out` may be `denoms`."""
         self._check(self.lib.bx_logup_accumulate(self.ctx, out.raw, denoms.raw, mults.raw, count))
+
+    def batch_ratio_products(self, out, nums, denoms, count=1):
+        """out[s][i] = prod_{j <= i} nums[s][j] / denoms[s][j] for `count` sequences back to back; a zero denominator contributes the
+        factor 0; `out` may be `nums`."""
+        self._check(self.lib.bx_batch_ratio_products(self.ctx, out.raw, nums.raw, denoms.raw, count))
 
     def scatter(self, into, index, offsets, values):
         self._check(self.lib.bx_scatter(self.ctx, into.raw, index.raw, offsets.raw, values.raw))

@@ -34,9 +34,9 @@
  *     nothing.  AN OUTPUT MUST NOT OVERLAP ANY OTHER OPERAND OF THE SAME CALL: the kernels write through __restrict__ pointers while
  *     other lanes still read.  Such a call is refused on the host, before anything is enqueued, with "<entry point>: <a> and <b>
  *     overlap"; nothing is written and the ctx stays usable.  Operands that touch (one ends where the other starts) do not overlap.
- *     Inputs may overlap inputs freely.  Four element-wise exceptions accept an output that IS an input (same start, same length) and
- *     still refuse every partial overlap: bx_eltwise_add_elem, bx_eltwise_copy_elem / bx_d2d, bx_logup_accumulate and
- *     bx_batch_expand_into_evaluate_ntt with expand_bits = 0; each says so below.  The rule is about the operands' ADDRESSES: what an
+ *     Inputs may overlap inputs freely.  Five element-wise exceptions accept an output that IS an input (same start, same length) and
+ *     still refuse every partial overlap: bx_eltwise_add_elem, bx_eltwise_copy_elem / bx_d2d, bx_logup_accumulate (out = denoms),
+ *     bx_batch_ratio_products (out = nums) and bx_batch_expand_into_evaluate_ntt with expand_bits = 0; each says so below.  The rule is about the operands' ADDRESSES: what an
  *     index operand in device memory holds (which, combos, sel, positions, offsets, poly_ptrs) is not read by the host, and a value
  *     out of range there stays the caller's responsibility.
  */
@@ -249,6 +249,15 @@ const char* bx_batch_prefix_sums(bx_ctx* ctx, bx_buf io_ext, size_t count);
  * scale by mults and bx_batch_prefix_sums give, with one read of denoms and mults and one write of out; out may BE denoms (same start,
  * same length); any other overlap of out with denoms, and any overlap of out with mults, is refused. */
 const char* bx_logup_accumulate(bx_ctx* ctx, bx_buf out_ext, bx_buf denoms_ext, bx_buf mults, size_t count);
+/* bx_batch_ratio_products: out[s][i] = prod_{j <= i} nums[s][j] * denoms[s][j]^-1 for `count` sequences of n = out_ext.len/4/count
+ * elements laid back to back: the running product a permutation or memory-consistency argument accumulates.  The three lengths are
+ * equal, every buffer is 16-byte aligned, count is in [1, 65535].  The inverse is bx_batch_invert_ext's: A ZERO DENOMINATOR CONTRIBUTES
+ * THE FACTOR 0, so the product is 0 from that row on (the prover does not judge the witness).  Word for word what bx_batch_invert_ext
+ * on a copy of the denominators, an element-wise Fp4 product and bx_batch_prefix_products give, with one read of nums and denoms and
+ * one write of out ("scan_lookback" = 1: one launch; 0: one inverting launch and the three-phase products).  out may BE nums (same
+ * start, same length); any other overlap of out with nums, and any overlap of out with denoms, is refused; nums and denoms may
+ * overlap freely.  Profiled as "ratio_products". */
+const char* bx_batch_ratio_products(bx_ctx* ctx, bx_buf out_ext, bx_buf nums_ext, bx_buf denoms_ext, size_t count);
 /* Hal::scatter(into, index, offsets, values): for cycle c < index.len - 1, every entry e in [index[c], index[c+1])
  * writes into[offsets[e]] = values[e].  All four are device buffers.  Asynchronous: an offset outside `into` or an index
  * range outside offsets/values is detected on the device and reported by the next blocking call on the ctx (bx_d2h,

@@ -194,16 +194,23 @@
  *                                HAL's rule).                                                              (BX_CONS_SUM = 11)
  *   PROD s a            nothing  sequence s is a running product: acc_s[r] = prod_{j <= r} fp[a](j); a is base or ext.
  *                                                                                                          (BX_CONS_PROD = 12)
- * Operands in bx_cons_step: SUM has a = s, b = m, c = d; PROD has a = s, b = a.
+ *   RATIO s a b         nothing  sequence s is a running product of ratios: acc_s[r] = prod_{j <= r} fp[a](j) / fp[b](j), what a
+ *                                permutation or memory-consistency argument accumulates (z(N-1) = 1 iff the multisets agree).  a and b
+ *                                are base or ext; a base value is promoted.  A zero denominator contributes the factor 0 (the HAL's
+ *                                rule, bx_batch_ratio_products): the sequence is 0 from that row on.  The prover does not judge the
+ *                                witness.                                      (BX_CONS_RATIO = 16; 13, 14 and 15 are no ops)
+ * Operands in bx_cons_step: SUM has a = s, b = m, c = d; PROD has a = s, b = a; RATIO has a = s, b = the numerator, c = the denominator.
  * Sequence s, component k is accum column 4 s + k.  With S sequences the program does not touch accum columns at or above 4 S.
  * Refused by name at bx_acc_program_create:
- *   ops          TRUE, AND_EQZ, AND_COND and SET do not belong in an accumulate program.  (BX_CONS_SUM and BX_CONS_PROD stay unknown
- *                ops to bx_cons_program_create and bx_wit_program_create.)
+ *   ops          TRUE, AND_EQZ, AND_COND and SET do not belong in an accumulate program.  (BX_CONS_SUM, BX_CONS_PROD and BX_CONS_RATIO
+ *                stay unknown ops to bx_cons_program_create and bx_wit_program_create; 13, 14 and 15 are unknown to all three.)
  *   accum        tap group 2: the program produces the accum group, it does not read it.
  *   m            an ext-typed m of a SUM.
  *   sequences    a sequence defined twice; a gap (the sequences must be exactly 0 .. S-1); S = 0; a sequence number at or above
- *                BX_ACC_MAX_SEQS = 1024; a PROD sequence numbered below a SUM sequence (all sums come first, so that each scan is
- *                ONE batched call over a contiguous range).
+ *                BX_ACC_MAX_SEQS = 1024; a PROD sequence numbered below a SUM sequence; a RATIO sequence numbered below a SUM or a
+ *                PROD sequence, i.e. a SUM or PROD numbered above a RATIO (all sums come first, then all products, then all ratios,
+ *                so that each scan is ONE batched call over a contiguous range).  The rules for twice, gap and the bound cover all
+ *                three kinds.
  *   limits       BX_CONS_MAX_STEPS, BX_CONS_MAX_TAPS, BX_CONS_MAX_BACK, BX_CONS_MAX_COL, n_globals <= BX_MAX_GLOBALS, constants < P,
  *                operands name earlier vars, and BX_CONS_MAX_NARROW / BX_CONS_MAX_WIDE live values: a program over one is refused
  *                with the number it needs and the limit.  There is no degree bound and there are no mix powers.
@@ -215,20 +222,27 @@
  *                existing stream, digest or generated text changes): a term store for a sum with a base or an ext denominator and for a
  *                product of base or ext factors, the sequence in `imm`.  `scal` = [globals | mix (4) | constants].  A generated kernel
  *                per program is not part of this; the stream is what it would be generated from, as for the other two kinds.
- *   host         bx_acc_program_run_host, the definition-level twin: the terms of every row, then the Fp4 inverse with 0 -> 0 times m,
- *                the running sums and products, then columns 4 s + k.  Canonical arithmetic in the kernel's operand order, and canonical
+ *                Two more are appended after those four, for the same reason: the store of a RATIO's base or ext denominator.  A
+ *                RATIO compiles to a product's term store for its numerator (imm = s) and a denominator store with imm = S + t,
+ *                t the ratio's index among the R ratios.  The work space of the terms therefore holds S + R sequences: [0, S) are
+ *                the terms, [S, S + R) the denominators of sequences [S - R, S).  bx_acc_program_ratios gives R; info.sequences
+ *                counts all three kinds.  A program without RATIO compiles to exactly the stream it had.
+ *   host         bx_acc_program_run_host, the definition-level twin: the terms of every row, then the Fp4 inverse with 0 -> 0 times m
+ *                (a SUM) or times the numerator (a RATIO), the running sums and products, then columns 4 s + k.  Canonical arithmetic in the kernel's operand order, and canonical
  *                words are unique, so host and device agree word for word.
  *   device       bx_acc_program_keep: ONE launch that gathers the K kept columns into the caller's `kept` (K x N), profiled as
  *                "acc_program_keep".  bx_acc_program_run: (1) the interpreting kernel, one lane per row, 256 per workgroup, slot
  *                files in LDS, writes every term as ONE 16-byte store at run_ext[4 (s N + r)] (a base value is promoted to
  *                (v, 0, 0, 0)) and for a sum one word at mults[s N + r], profiled as "acc_program_run"; (2) ONE bx_logup_accumulate
- *                over sequences [0, sums), in place; (3) ONE bx_batch_prefix_products over [sums, S); (4) the transposition of the
- *                S ext runs into accum columns [0, 4 S), profiled as "acc_program_store".  Columns at or above 4 S are not written.
+ *                over sequences [0, sums), in place; (3) ONE bx_batch_prefix_products over [sums, S - R) and ONE
+ *                bx_batch_ratio_products over [S - R, S), in place, with the denominators [S, S + R); (4) the transposition of the
+ *                first S ext runs into accum columns [0, 4 S), profiled as "acc_program_store".  Columns at or above 4 S are not
+ *                written.  run_ext holds 4 N (S + R) words.
  *                A tap is kept[k N + ((r - back) & (N - 1))].  Nothing blocks.
  *   composite    bx_cons_circuit_set_accumulate: the table's witgen ends with bx_acc_program_keep (after the witness program, if
  *                any) and remembers the public words; its accumulate calls base->accumulate when the base has one (that call owns
  *                filler and every column at or above 4 S; whatever it leaves below 4 S is overwritten) and then bx_acc_program_run.
- * Out of scope: a generated kernel per accumulate program; fusing the terms into the scan's tile load; ratios inside a PROD.
+ * Out of scope: a generated kernel per accumulate program; fusing the terms into the scan's tile load.
  *
  * Generated witness kernels (normative)
  * -------------------------------------
@@ -316,7 +330,9 @@ enum bx_cons_op {
     BX_CONS_AND_COND = 9,
     BX_CONS_SET = 10, /* witness programs only ("Witness programs" above) */
     BX_CONS_SUM = 11, /* accumulate programs only ("Accumulate programs" above) */
-    BX_CONS_PROD = 12 /* likewise */
+    BX_CONS_PROD = 12, /* likewise */
+    /* 13, 14 and 15 are no ops: every compiler answers them "unknown op" */
+    BX_CONS_RATIO = 16 /* accumulate programs only */
 };
 
 /* one step: `op` and its operands in the order of the table above (unused operands are ignored) */
@@ -523,6 +539,9 @@ void bx_acc_program_destroy(bx_acc_program* prog);
 const char* bx_acc_program_info_get(const bx_acc_program* prog, bx_acc_program_info* out);
 /* kept column i < info.kept: its group (0 code, 1 data) and column */
 const char* bx_acc_program_kept(const bx_acc_program* prog, uint32_t i, uint32_t* group, uint32_t* col);
+/* R, the number of RATIO sequences: sequences [S - R, S) of info.sequences (which counts all three kinds).  Not a field of
+ * bx_acc_program_info, whose layout stays what it was. */
+const char* bx_acc_program_ratios(const bx_acc_program* prog, uint32_t* out);
 /* Host executor, the reference for the device path: host arrays, column-major (code: w_code x N, data: w_data x N, accum: w_accum x N
  * Montgomery words); `globals` holds the program's n_globals words (may be NULL when that is 0), `mix` four.  Writes accum columns
  * [0, 4 S) and nothing else.  po2 in [1, 24].  Refused: a kept column that is not below its group's width, w_accum < 4 S. */
@@ -536,9 +555,9 @@ const char* bx_acc_program_unload(bx_acc_program_dev* dev);
  * a kept column that is not below its group's width, `kept` sharing a byte with `code` or `data`. */
 const char* bx_acc_program_keep(bx_ctx* ctx, bx_acc_program_dev* dev, uint32_t po2, bx_buf code, uint32_t w_code, bx_buf data, uint32_t w_data, bx_buf kept);
 /* The whole stage from `kept`: terms, scans, columns [0, 4 S) of `accum` (w_accum x N); does not block.  `globals` is a HOST array of the
- * program's n_globals words (may be NULL when that is 0).  run_ext (4 N S words, 16-byte aligned) and mults (N sums words) are the
- * caller's work space.  Refused with nothing enqueued: another ctx's program, po2 outside [1, 24], kept.len != K N, run_ext.len != 4 N S,
- * mults.len != N sums, accum.len != N w_accum, w_accum < 4 S, a misaligned run_ext, any two of run_ext, mults, accum and kept sharing a
+ * program's n_globals words (may be NULL when that is 0).  run_ext (4 N (S + R) words, R = bx_acc_program_ratios, 16-byte aligned) and
+ * mults (N sums words) are the caller's work space.  Refused with nothing enqueued: another ctx's program, po2 outside [1, 24],
+ * kept.len != K N, run_ext.len != 4 N (S + R), mults.len != N sums, accum.len != N w_accum, w_accum < 4 S, a misaligned run_ext, any two of run_ext, mults, accum and kept sharing a
  * byte ("Operand overlap", bx_hal.h).  Each call writes `globals` and `mix` into a table that belongs to `dev`, on the ctx's stream: a
  * loaded program serves one stream, its calls in order. */
 const char* bx_acc_program_run(bx_ctx* ctx, bx_acc_program_dev* dev, uint32_t po2, bx_buf kept, const uint32_t* globals, const uint32_t mix[4], bx_buf run_ext,

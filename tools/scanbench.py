@@ -1,5 +1,6 @@
-"""Times the scans and inversions of an accumulate stage: bx_batch_prefix_products (grand-product argument) and the five LogUp helpers
-(bx_batch_invert_ext, bx_batch_invert_elem, bx_prefix_sums, bx_batch_prefix_sums, bx_logup_accumulate).
+"""Times the scans and inversions of an accumulate stage: bx_batch_prefix_products (grand-product argument), the five LogUp helpers
+(bx_batch_invert_ext, bx_batch_invert_elem, bx_prefix_sums, bx_batch_prefix_sums, bx_logup_accumulate) and bx_batch_ratio_products
+(the running product of ratios; 48 B per element: numerators, denominators, out).
 
     python tools/scanbench.py [--po2 20 22] [--seqs 16] [--calls 25] [--warmup 5] [--out profiles/r10_logup_scan.json]
 
@@ -59,6 +60,7 @@ def main():
         ext = hal.copy_from(rng.integers(1, P, 4 * n * s, dtype=np.uint32))
         out = hal.alloc(4 * n * s)
         mults = hal.copy_from(rng.integers(1, P, n * s, dtype=np.uint32))
+        den = hal.copy_from(rng.integers(1, P, 4 * n * s, dtype=np.uint32))  # read-only: the denominators of ratio_products
         ext_bytes, elem_bytes = 32.0 * n * s, 8.0 * n * s
         ops = {
             "batch_prefix_products": (lambda: hal.batch_prefix_products(ext, s), ext_bytes),
@@ -69,6 +71,9 @@ def main():
             "logup_accumulate": (lambda: hal.logup_accumulate(out, ext, mults, s), ext_bytes + 4.0 * n * s),
             "logup_accumulate_in_place": (lambda: hal.logup_accumulate(ext, ext, mults, s), ext_bytes + 4.0 * n * s),
             "unfused": (lambda: (hal.batch_invert_ext(ext), hal.batch_prefix_sums(ext, s)), 2 * ext_bytes),
+            # 16 B of numerators and 16 B of denominators in, 16 B out: to be read beside batch_prefix_products (32 B) and logup_accumulate (36 B)
+            "ratio_products": (lambda: hal.batch_ratio_products(out, ext, den, s), 48.0 * n * s),
+            "ratio_products_in_place": (lambda: hal.batch_ratio_products(ext, ext, den, s), 48.0 * n * s),
         }
         # The in-place ops keep working on what the calls before them left in `ext` (running sums get inverted, inverses get summed):
         # every kernel here is free of data-dependent branches, so the words do not move the timing.
@@ -91,7 +96,7 @@ def main():
                        "fused_vs_unfused": {"fused_ms": fused, "invert_plus_sums_ms": unfused, "fused_is_faster": fused < unfused,
                                             "ratio": round(fused / unfused, 3)}})
         print(json.dumps(shapes[-1]), flush=True)
-        for b in (ext, out, mults):
+        for b in (ext, out, mults, den):
             b.free()
     doc = {"device_code_sha": device_code_hash(), "device": hal.device_name(), "scan_lookback": a.lookback,
            "note": "tools/scanbench.py: median ms per call over `calls` calls (HIP events on the ctx's stream, warm-up first, two interleaved "
