@@ -512,6 +512,11 @@ class WitCount(C.Structure):
     _fields_ = [("col", C.c_uint32), ("bins", C.c_uint32), ("rows", C.c_uint32), ("n_sources", C.c_uint32), ("sources", C.POINTER(C.c_uint32))]
 
 
+class WitSort(C.Structure):
+    _fields_ = [("rows", C.c_uint32), ("n_keys", C.c_uint32), ("n_cols", C.c_uint32), ("bits", C.POINTER(C.c_uint32)), ("sources", C.POINTER(C.c_uint32)),
+                ("dests", C.POINTER(C.c_uint32))]
+
+
 class WitProgramInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("steps", "sets", "narrow", "instructions", "taps", "cells")]
 
@@ -525,6 +530,12 @@ def _wit_lib():
         lib.bx_wit_program_counts.argtypes = [vp]
         lib.bx_wit_program_counts.restype = C.c_uint32
         lib.bx_wit_program_count_get.argtypes = [vp, C.c_uint32, u32p, u32p, u32p, u32p, C.c_uint32, u32p]
+        lib.bx_wit_program_create_sorted.argtypes = [C.POINTER(WitProgramDesc), C.POINTER(WitCount), C.c_size_t, C.POINTER(WitSort), C.c_size_t, C.POINTER(vp)]
+        lib.bx_wit_program_sorts.argtypes = [vp]
+        lib.bx_wit_program_sorts.restype = C.c_uint32
+        lib.bx_wit_program_sort_get.argtypes = [vp, C.c_uint32, u32p, u32p, u32p, u32p, u32p, C.c_uint32, u32p]
+        for name in ("bx_wit_program_create_sorted", "bx_wit_program_sort_get"):
+            getattr(lib, name).restype = C.c_char_p
         lib.bx_wit_program_destroy.argtypes = [vp]
         lib.bx_wit_program_destroy.restype = None
         lib.bx_wit_program_info_get.argtypes = [vp, C.POINTER(WitProgramInfo)]
@@ -582,6 +593,22 @@ class CompiledWitnessProgram(_CompiledProgram, _EmitsKernel):
             out.append({"col": int(col.value), "bins": int(bins.value), "rows": int(rows.value), "sources": [int(v) for v in src[:n_src.value]]})
         return out
 
+    def sorts(self):
+        """the sorted columns as dicts {"rows", "keys": [(col, bits), ...], "payload", "dests"}, in list order (bx_wit_program_sort_get)"""
+        from .hal import HalError
+
+        out = []
+        rows, n_keys, n_cols = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        bits, src, dst = (C.c_uint32 * 4)(), (C.c_uint32 * 16)(), (C.c_uint32 * 16)()  # BX_WIT_MAX_SORT_KEYS, BX_WIT_MAX_SORT_COLS
+        for i in range(self.lib.bx_wit_program_sorts(self.handle)):
+            msg = self.lib.bx_wit_program_sort_get(self.handle, i, C.byref(rows), C.byref(n_keys), bits, src, dst, 16, C.byref(n_cols))
+            if msg:
+                raise HalError(msg.decode())
+            nk, nc = int(n_keys.value), int(n_cols.value)
+            out.append({"rows": int(rows.value), "keys": [(int(src[q]), int(bits[q])) for q in range(nk)], "payload": [int(v) for v in src[nk:nc]],
+                        "dests": [int(v) for v in dst[:nc]]})
+        return out
+
     def run_host(self, po2, code, w_code, data, w_data):
         """bx_wit_program_run_host: code (w_code x N) and data (w_data x N) are C-contiguous uint32 numpy arrays of Montgomery words;
         the derived columns of `data` are written in place.  A refusal raises HalError."""
@@ -602,7 +629,8 @@ class WitnessProgram:
     """Builder of a witness program (include/bx_program.h, "Witness programs"): const / get / add / sub / mul append one step and
     return the index of the fp var it made; set(col, var) stores a var into a data column, which makes that column derived;
     count(col, sources, bins, rows=0) makes `col` a multiplicity column ("multiplicity columns"): after every row has run,
-    data[col][r] = how many cells of the `sources` columns, rows [0, rows), hold the integer r, for r < bins (rows = 0: all rows).
+    data[col][r] = how many cells of the `sources` columns, rows [0, rows), hold the integer r, for r < bins (rows = 0: all rows);
+    sort(keys, payload, dests, rows=0) writes a stably sorted copy of columns ("sorted columns"), after every row and before the counts.
 
         w = WitnessProgram()
         x = w.get(1, 0)
@@ -614,6 +642,7 @@ class WitnessProgram:
     def __init__(self):
         self.steps, self.tap_list, self._tap_index, self.cells = [], [], {}, []
         self.count_list = []
+        self.sort_list = []
         self.n_fp = 0
 
     def _fp(self, op, a=0, b=0):
@@ -657,6 +686,18 @@ class WitnessProgram:
                 raise ValueError(f"WitnessProgram.count: {v} is not a 32-bit unsigned value")
         self.count_list.append(entry)
 
+    def sort(self, keys, payload=(), dests=(), rows=0):
+        """after every row has run and before the counts ("sorted columns"): rows [0, rows) of the key columns `keys` = [(col, bits), ...]
+        (most significant first) and of the `payload` columns, stably sorted by the low `bits` bits of the keys, go to `dests`, one per
+        key and payload column in that order (rows = 0: all rows)"""
+        entry = ([(int(c), int(b)) for c, b in keys], [int(c) for c in payload], [int(c) for c in dests], int(rows))
+        if len(entry[2]) != len(entry[0]) + len(entry[1]):
+            raise ValueError(f"WitnessProgram.sort: {len(entry[2])} dests for {len(entry[0]) + len(entry[1])} key and payload columns")
+        for v in (entry[3], *[v for kb in entry[0] for v in kb], *entry[1], *entry[2]):
+            if not 0 <= v < 1 << 32:
+                raise ValueError(f"WitnessProgram.sort: {v} is not a 32-bit unsigned value")
+        self.sort_list.append(entry)
+
     def compile(self):
         """-> CompiledWitnessProgram.  A refusal raises HalError."""
         from .hal import HalError
@@ -667,12 +708,20 @@ class WitnessProgram:
         cells = (WitGlobalCell * max(len(self.cells), 1))(*[WitGlobalCell(*g) for g in self.cells])
         desc = WitProgramDesc(steps, len(self.steps), taps, len(self.tap_list), cells, len(self.cells))
         handle = C.c_void_p()
-        if not self.count_list:
+        u32p = C.POINTER(C.c_uint32)
+        srcs = [(C.c_uint32 * max(len(s), 1))(*s) for _, s, _, _ in self.count_list]
+        counts = (WitCount * max(len(self.count_list), 1))(*[WitCount(col, bins, rows, len(s), C.cast(a, u32p)) for (col, s, bins, rows), a in zip(self.count_list, srcs)])
+        if self.sort_list:
+            keep, sorts = [], (WitSort * len(self.sort_list))()
+            for k, (keys, payload, dests, rows) in enumerate(self.sort_list):
+                cols = [c for c, _ in keys] + payload
+                arrays = [(C.c_uint32 * max(len(v), 1))(*v) for v in ([b for _, b in keys], cols, dests)]
+                keep.append(arrays)
+                sorts[k] = WitSort(rows, len(keys), len(cols), *[C.cast(a, u32p) for a in arrays])
+            msg = lib.bx_wit_program_create_sorted(C.byref(desc), counts if self.count_list else None, len(self.count_list), sorts, len(self.sort_list), C.byref(handle))
+        elif not self.count_list:
             msg = lib.bx_wit_program_create(C.byref(desc), C.byref(handle))
         else:
-            srcs = [(C.c_uint32 * max(len(s), 1))(*s) for _, s, _, _ in self.count_list]
-            counts = (WitCount * len(self.count_list))(*[WitCount(col, bins, rows, len(s), C.cast(a, C.POINTER(C.c_uint32)))
-                                                         for (col, s, bins, rows), a in zip(self.count_list, srcs)])
             msg = lib.bx_wit_program_create_counted(C.byref(desc), counts, len(self.count_list), C.byref(handle))
         if msg:
             raise HalError(msg.decode())

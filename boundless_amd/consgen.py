@@ -11,8 +11,9 @@ bx_cp_eval (-Rpass-analysis=kernel-resource-usage: VGPRs, SGPRs, scratch, occupa
 seconds hipcc took.  --emit-only writes the text to OUT instead and runs no compiler.
 
 --witness takes a WITNESS program ("Generated witness kernels"): {"taps": [[group, col, back], ...], "steps": [[op, a, b, c, d], ...],
-"cells": [[global, col, row], ...], "counts": [{"col": c, "sources": [...], "bins": b, "rows": r}, ...]} (cells and counts optional;
-the counts are passed to the compiler and play no part in the kernel), compiled by bx_wit_program_create_counted, written by bx_wit_program_emit_hip and built with the same
+"cells": [[global, col, row], ...], "counts": [{"col": c, "sources": [...], "bins": b, "rows": r}, ...],
+"sorts": [{"keys": [[col, bits], ...], "payload": [...], "dests": [...], "rows": r}, ...]} (cells, counts and sorts optional;
+counts and sorts are passed to the compiler and play no part in the kernel), compiled by bx_wit_program_create_sorted, written by bx_wit_program_emit_hip and built with the same
 flags; its meta holds the digest, the resource report for bx_wp_run, steps, sets, instructions, narrow slots, text bytes and seconds.
 
 This runs where hipcc is, before the code object is needed: the library loads what was built (bx_cons_program_attach_kernel) and
@@ -49,6 +50,8 @@ def witness_program_of(desc):
     w.cells = [tuple(int(v) for v in g) for g in desc.get("cells", [])]
     for ct in desc.get("counts", []):  # multiplicity columns: passed through, no part of the emitted kernel or its digest
         w.count(ct["col"], ct["sources"], ct["bins"], ct.get("rows", 0))
+    for st in desc.get("sorts", []):  # sorted columns: likewise
+        w.sort(st["keys"], st.get("payload", []), st["dests"], st.get("rows", 0))
     w.n_fp = sum(1 for s in w.steps if s[0] != 10)  # every step but BX_CONS_SET appends an fp var
     return w.compile()
 

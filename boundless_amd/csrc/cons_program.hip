@@ -243,6 +243,7 @@ const char* cc_create(void* u, bx_ctx* c, const bx_segment_params* shape, void**
     BX_REQUIRE(c, cc->wit || cc->wit_kernel.empty(), "cons circuit: a witness kernel is set but no witness program (bx_cons_circuit_set_witness)");
     if (const bx_wit_program* w = cc->wit) {  // the witness program against the shape, before anything is loaded
         if (const char* e = wit_program_check_widths(w->max_col, w->max_set, "cons circuit: witness program", shape->w_code, shape->w_data)) return set_msg(c, e);
+        if (const char* e = wit_program_check_sorts(w->sorts, "cons circuit: witness program", shape->po2, shape->w_data)) return set_msg(c, e);
         if (const char* e = wit_program_check_counts(w->counts, "cons circuit: witness program", shape->po2, shape->w_data)) return set_msg(c, e);
         for (size_t k = 0; k < w->cells.size(); ++k) {
             const bx_wit_global_cell& g = w->cells[k];

@@ -77,6 +77,11 @@ struct WitCount {
     uint32_t col = 0, bins = 0, rows = 0;
     std::vector<uint32_t> sources;
 };
+// one sort of a witness program ("sorted columns" of bx_program.h), as create validated it: bits.size() keys, the first of `sources`
+struct WitSort {
+    uint32_t rows = 0;
+    std::vector<uint32_t> bits, sources, dests;
+};
 }  // namespace bx
 
 // A compiled witness program ("Witness programs" of bx_program.h): the same two-word instructions, of the narrow opcodes CP_LD_B,
@@ -91,6 +96,7 @@ struct bx_wit_program {
     uint32_t max_col[2] = {0, 0};  // 1 + the largest tap column per group (0 = the group is not named)
     uint32_t max_set = 0;          // 1 + the largest SET column
     std::vector<bx::WitCount> counts;  // run after the stream, in list order; not hashed, not emitted
+    std::vector<bx::WitSort> sorts;    // run after the stream and before the counts, in list order; not hashed, not emitted
 };
 
 // A compiled accumulate program ("Accumulate programs" of bx_program.h): the instructions of a constraint program without the mix
@@ -118,4 +124,7 @@ const char* wit_program_check_widths(const uint32_t max_col[2], uint32_t max_set
 // rows are above N = 2^po2, or whose bins are above N when rows == 0: the shape-dependent part of a count list, one text for the same
 // three callers
 const char* wit_program_check_counts(const std::vector<WitCount>& counts, const char* who, uint32_t po2, uint32_t w_data);
+// cons_program_host.cpp: likewise for a sort whose rows are above N = 2^po2 or whose source or dest is not below w_data: the
+// shape-dependent part of a sort list, one text for the same three callers
+const char* wit_program_check_sorts(const std::vector<WitSort>& sorts, const char* who, uint32_t po2, uint32_t w_data);
 }  // namespace bx

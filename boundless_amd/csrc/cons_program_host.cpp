@@ -43,6 +43,19 @@ const char* wit_program_check_counts(const std::vector<WitCount>& counts, const 
     return nullptr;
 }
 
+const char* wit_program_check_sorts(const std::vector<WitSort>& sorts, const char* who, uint32_t po2, uint32_t w_data) {
+    const uint32_t n = 1u << po2;
+    for (size_t k = 0; k < sorts.size(); ++k) {
+        const WitSort& s = sorts[k];
+        if (s.rows > n) return refuse("%s: sort %zu: rows %u is above the trace's %u rows", who, k, s.rows, n);
+        for (size_t q = 0; q < s.sources.size(); ++q)
+            if (s.sources[q] >= w_data) return refuse("%s: sort %zu: source %zu is data column %u, the data group has %u columns", who, k, q, s.sources[q], w_data);
+        for (size_t q = 0; q < s.dests.size(); ++q)
+            if (s.dests[q] >= w_data) return refuse("%s: sort %zu: dest %zu is data column %u, the data group has %u columns", who, k, q, s.dests[q], w_data);
+    }
+    return nullptr;
+}
+
 namespace {
 
 // `scal` of a constraint or an accumulate program for one call: [globals | mix (4) | constants]
@@ -256,11 +269,28 @@ extern "C" const char* bx_wit_program_count_get(const bx_wit_program* prog, uint
     return nullptr;
 }
 
+extern "C" uint32_t bx_wit_program_sorts(const bx_wit_program* prog) { return prog ? (uint32_t)prog->sorts.size() : 0u; }
+
+extern "C" const char* bx_wit_program_sort_get(const bx_wit_program* prog, uint32_t i, uint32_t* rows, uint32_t* n_keys, uint32_t bits_out[BX_WIT_MAX_SORT_KEYS],
+                                               uint32_t* sources_out, uint32_t* dests_out, uint32_t cap, uint32_t* n_cols) {
+    if (!prog || !rows || !n_keys || !bits_out || !n_cols || (cap && (!sources_out || !dests_out))) return "bx_wit_program_sort_get: null argument";
+    if (i >= prog->sorts.size()) return "bx_wit_program_sort_get: index is not below the number of sorts";
+    const bx::WitSort& s = prog->sorts[i];
+    *rows = s.rows;
+    *n_keys = (uint32_t)s.bits.size();
+    *n_cols = (uint32_t)s.sources.size();
+    for (size_t q = 0; q < s.bits.size() && q < BX_WIT_MAX_SORT_KEYS; ++q) bits_out[q] = s.bits[q];
+    for (uint32_t q = 0; q < cap && q < s.sources.size(); ++q) sources_out[q] = s.sources[q], dests_out[q] = s.dests[q];
+    return nullptr;
+}
+
 extern "C" int bx_wit_program_derives(const bx_wit_program* prog, uint32_t col) {
     if (!prog) return 0;
     if (std::find(prog->sets.begin(), prog->sets.end(), col) != prog->sets.end()) return 1;
     for (const bx::WitCount& ct : prog->counts)
         if (ct.col == col) return 1;
+    for (const bx::WitSort& s : prog->sorts)
+        if (std::find(s.dests.begin(), s.dests.end(), col) != s.dests.end()) return 1;
     return 0;
 }
 
@@ -269,6 +299,7 @@ extern "C" const char* bx_wit_program_run_host(const bx_wit_program* prog, uint3
     if (!prog || (w_code && !code) || (w_data && !data)) return "bx_wit_program_run_host: null argument";
     if (po2 < 1 || po2 > 24) return "bx_wit_program_run_host: po2 must be in [1, 24]";
     if (const char* e = wit_program_check_widths(prog->max_col, prog->max_set, "bx_wit_program_run_host", w_code, w_data)) return e;
+    if (const char* e = wit_program_check_sorts(prog->sorts, "bx_wit_program_run_host", po2, w_data)) return e;
     if (const char* e = wit_program_check_counts(prog->counts, "bx_wit_program_run_host", po2, w_data)) return e;
     const size_t n = (size_t)1 << po2;
     // rows in any order: no row reads a word this run writes (derived cells are forwarded, never loaded)
@@ -281,7 +312,26 @@ extern "C" const char* bx_wit_program_run_host(const bx_wit_program* prog, uint3
             if (!fits || !host_exec(w0, prog->code[pc + 1], nar, nullptr, prog->consts, env)) return "bx_wit_program_run_host: corrupt instruction stream";
         }
     }
-    // the counts, in list order, after every row: the device path's twin (clear, histogram over rows [0, rows), store)
+    // the sorts, in list order, after every row and before the counts: pi = the stable sort of rows [0, rows) by the decoded, masked key
+    // tuple; every source gathered into a temporary before a dest is written
+    for (const WitSort& s : prog->sorts) {
+        const size_t rows = s.rows ? s.rows : n, nk = s.bits.size();
+        std::vector<uint32_t> keys(rows * nk), pi(rows);
+        for (size_t k = 0; k < nk; ++k) {
+            const uint32_t mask = (uint32_t)(((uint64_t)1 << s.bits[k]) - 1);
+            for (size_t r = 0; r < rows; ++r) keys[r * nk + k] = fp_decode(data[(size_t)s.sources[k] * n + r]) & mask;
+        }
+        for (size_t r = 0; r < rows; ++r) pi[r] = (uint32_t)r;
+        std::stable_sort(pi.begin(), pi.end(), [&](uint32_t a, uint32_t b) {
+            return std::lexicographical_compare(&keys[a * nk], &keys[a * nk] + nk, &keys[b * nk], &keys[b * nk] + nk);
+        });
+        std::vector<uint32_t> tmp(rows * s.sources.size());
+        for (size_t q = 0; q < s.sources.size(); ++q)
+            for (size_t r = 0; r < rows; ++r) tmp[q * rows + r] = data[(size_t)s.sources[q] * n + pi[r]];
+        for (size_t q = 0; q < s.dests.size(); ++q)
+            for (size_t r = 0; r < rows; ++r) data[(size_t)s.dests[q] * n + r] = tmp[q * rows + r];
+    }
+    // the counts, in list order, after the sorts: the device path's twin (clear, histogram over rows [0, rows), store)
     for (const WitCount& ct : prog->counts) {
         const size_t rows = ct.rows ? ct.rows : n;
         std::vector<uint32_t> bins(ct.bins, 0u);

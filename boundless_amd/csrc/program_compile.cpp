@@ -3,7 +3,7 @@
 // the value steps CONST .. MUL with their base / ext opcodes, the slot allocation by last use, the peak check and the padding.  A kind
 // is a description (Kind) plus the code for its own steps:
 //   constraint programs   the mix vars (TRUE, AND_EQZ, AND_COND), the degrees and `ret`
-//   witness programs      SET, forwarding of GETs, the global cells and the count list
+//   witness programs      SET, forwarding of GETs, the global cells, the count list and the sort list
 //   accumulate programs   SUM / PROD, the sequence rules and the kept list
 // The ORDER in which a bad description is refused is part of the behaviour (tests/golden/progstream pins it): each kind's function
 // below reads top to bottom in that order.
@@ -429,7 +429,72 @@ const char* check_counts(const bx_wit_program_desc* d, const bx_wit_count* count
     return nullptr;
 }
 
-const char* compile_wit(const bx_wit_program_desc* d, const bx_wit_count* counts, size_t n_counts, bx_wit_program* p) {
+// the sort list ("sorted columns"): every rule but the shape-dependent ones (wit_program_check_sorts).  After check_counts: p->counts
+// is what a dest and a source are held against.
+const char* check_sorts(const bx_wit_program_desc* d, const bx_wit_sort* sorts, size_t n_sorts, const std::map<uint32_t, size_t>& set_at, bx_wit_program* p) {
+    if (n_sorts > BX_WIT_MAX_SORTS) return refuse("wit_program: %zu sorts, more than BX_WIT_MAX_SORTS = %d", n_sorts, BX_WIT_MAX_SORTS);
+    if (n_sorts && !sorts) return refuse("wit_program: null sort list");
+    std::map<uint32_t, size_t> count_of, dest_of, source_of;  // data column -> the count that fills it / the first sort that writes it / reads it
+    for (size_t k = 0; k < p->counts.size(); ++k) count_of.emplace(p->counts[k].col, k);
+    for (size_t k = 0; k < n_sorts; ++k) {
+        const bx_wit_sort& s = sorts[k];
+        if (s.n_cols == 0) return refuse("wit_program: sort %zu: no sources", k);
+        if (s.n_cols > BX_WIT_MAX_SORT_COLS) return refuse("wit_program: sort %zu: %u sources, more than BX_WIT_MAX_SORT_COLS = %d", k, s.n_cols, BX_WIT_MAX_SORT_COLS);
+        if (s.n_keys == 0) return refuse("wit_program: sort %zu: n_keys is 0", k);
+        if (s.n_keys > BX_WIT_MAX_SORT_KEYS) return refuse("wit_program: sort %zu: %u keys, more than BX_WIT_MAX_SORT_KEYS = %d", k, s.n_keys, BX_WIT_MAX_SORT_KEYS);
+        if (s.n_keys > s.n_cols) return refuse("wit_program: sort %zu: %u keys, above its %u sources", k, s.n_keys, s.n_cols);
+        if (!s.bits || !s.sources || !s.dests) return refuse("wit_program: sort %zu: null bits, source or dest list", k);
+        if (s.rows > (1u << 24)) return refuse("wit_program: sort %zu: rows %u is above 2^24, the largest trace", k, s.rows);
+        WitSort ws;
+        ws.rows = s.rows;
+        uint32_t total = 0;
+        for (uint32_t q = 0; q < s.n_keys; ++q) {
+            if (s.bits[q] == 0 || s.bits[q] > 31) return refuse("wit_program: sort %zu: key %u: bits %u is outside [1, 31]", k, q, s.bits[q]);
+            total += s.bits[q];
+            ws.bits.push_back(s.bits[q]);
+        }
+        if (total > BX_WIT_MAX_SORT_BITS) return refuse("wit_program: sort %zu: the keys have %u bits, more than BX_WIT_MAX_SORT_BITS = %d", k, total, BX_WIT_MAX_SORT_BITS);
+        for (uint32_t q = 0; q < s.n_cols; ++q) {
+            const uint32_t src = s.sources[q];
+            if (src > BX_CONS_MAX_COL) return refuse("wit_program: sort %zu: source %u: data column %u out of range (at most %d)", k, q, src, BX_CONS_MAX_COL);
+            if (std::find(ws.sources.begin(), ws.sources.end(), src) != ws.sources.end()) return refuse("wit_program: sort %zu: source column %u is named twice", k, src);
+            const auto ct = count_of.find(src);
+            if (ct != count_of.end())
+                return refuse("wit_program: sort %zu: source column %u is the column of count %zu: the counts run after the sorts", k, src, ct->second);
+            ws.sources.push_back(src);
+            source_of.emplace(src, k);
+        }
+        for (uint32_t q = 0; q < s.n_cols; ++q) {
+            const uint32_t dst = s.dests[q];
+            if (dst > BX_CONS_MAX_COL) return refuse("wit_program: sort %zu: dest %u: data column %u out of range (at most %d)", k, q, dst, BX_CONS_MAX_COL);
+            const auto ins = dest_of.emplace(dst, k);
+            if (!ins.second) return refuse("wit_program: sort %zu: dest column %u is already a dest of sort %zu", k, dst, ins.first->second);
+            const auto st = set_at.find(dst);
+            if (st != set_at.end()) return refuse("wit_program: sort %zu: dest column %u is also SET (step %zu)", k, dst, st->second);
+            const auto ct = count_of.find(dst);
+            if (ct != count_of.end()) return refuse("wit_program: sort %zu: dest column %u is the column of count %zu", k, dst, ct->second);
+            ws.dests.push_back(dst);
+        }
+        p->sorts.push_back(std::move(ws));
+    }
+    for (size_t k = 0; k < p->sorts.size(); ++k)  // in list order: the first sort with such a dest is the one named
+        for (uint32_t dst : p->sorts[k].dests) {
+            const auto src = source_of.find(dst);
+            if (src != source_of.end()) return refuse("wit_program: sort %zu: dest column %u is a source of sort %zu", k, dst, src->second);
+        }
+    if (!dest_of.empty())
+        for (size_t i = 0; i < d->n_steps; ++i) {
+            const bx_cons_step& s = d->steps[i];
+            if (s.op != BX_CONS_GET || s.a >= d->n_taps || d->taps[s.a].group != 1) continue;
+            const auto it = dest_of.find(d->taps[s.a].col);
+            if (it != dest_of.end())
+                return refuse("wit_program: sort %zu: dest column %u is read by the GET of step %zu: a sorted column does not exist while the program runs", it->second,
+                              it->first, i);
+        }
+    return nullptr;
+}
+
+const char* compile_wit(const bx_wit_program_desc* d, const bx_wit_count* counts, size_t n_counts, const bx_wit_sort* sorts, size_t n_sorts, bx_wit_program* p) {
     Core c(wit_kind(), d, 0, 0, p);  // `scal` is the constants alone
     CP_TRY(c.limits(d->cells, d->n_cells));
     CP_TRY(c.check_taps([&](size_t, const bx_cons_tap& tp) -> const char* {
@@ -476,6 +541,7 @@ const char* compile_wit(const bx_wit_program_desc* d, const bx_wit_count* counts
         }));
     // after the step list, so that a description with a bad step is refused for that step
     CP_TRY(check_counts(d, counts, n_counts, set_at, p));
+    CP_TRY(check_sorts(d, sorts, n_sorts, set_at, p));
 
     CP_TRY(c.allocate([&](uint32_t step, const bx_cons_step& s) {
         c.emit(CP_ST, 0, c.at(s.b).slot, 0, 0, s.a);
@@ -599,11 +665,16 @@ extern "C" const char* bx_cons_program_create(const bx_cons_program_desc* desc, 
     return "bx_cons_program_create: out of host memory";
 }
 
-extern "C" const char* bx_wit_program_create_counted(const bx_wit_program_desc* desc, const bx_wit_count* counts, size_t n_counts, bx_wit_program** out) try {
+extern "C" const char* bx_wit_program_create_sorted(const bx_wit_program_desc* desc, const bx_wit_count* counts, size_t n_counts, const bx_wit_sort* sorts,
+                                                    size_t n_sorts, bx_wit_program** out) try {
     if (!desc || !out) return "bx_wit_program_create: null argument";
-    return bx::create(out, [&](bx_wit_program* p) { return bx::compile_wit(desc, counts, n_counts, p); });
+    return bx::create(out, [&](bx_wit_program* p) { return bx::compile_wit(desc, counts, n_counts, sorts, n_sorts, p); });
 } catch (...) {
     return "bx_wit_program_create: out of host memory";
+}
+
+extern "C" const char* bx_wit_program_create_counted(const bx_wit_program_desc* desc, const bx_wit_count* counts, size_t n_counts, bx_wit_program** out) {
+    return bx_wit_program_create_sorted(desc, counts, n_counts, nullptr, 0, out);
 }
 
 extern "C" const char* bx_wit_program_create(const bx_wit_program_desc* desc, bx_wit_program** out) { return bx_wit_program_create_counted(desc, nullptr, 0, out); }

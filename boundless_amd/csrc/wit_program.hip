@@ -102,6 +102,8 @@ extern "C" const char* bx_wit_program_load(bx_ctx* c, const bx_wit_program* prog
     // one copy is the last thing it does, so no copy is ever in flight when an allocation fails
     BX_TRY(wit_counts_load(c, d.get(), prog));
     BX_HIP(c, stream_wait(c));
+    BX_TRY(wit_sorts_load(c, d.get(), prog));  // the sorts' column table (wit_sort.hip), likewise: allocation, then its one copy
+    BX_HIP(c, stream_wait(c));
     g_loaded.insert(c, d.get());
     *out = d.release();
     return nullptr;
@@ -130,9 +132,11 @@ extern "C" const char* bx_wit_program_run(bx_ctx* c, bx_wit_program_dev* dev, ui
     BX_REQUIRE(c, code.len == n * w_code && data.len == n * w_data, "bx_wit_program_run: buffer size mismatch (groups N x width)");
     if (const char* e = wit_program_check_widths(dev->max_col, dev->max_set, "bx_wit_program_run", w_code, w_data)) return set_msg(c, e);
     BX_REQUIRE(c, !bufs_overlap(code, data), "bx_wit_program_run: code and data overlap");
+    if (const char* e = wit_program_check_sorts(dev->sorts, "bx_wit_program_run", po2, w_data)) return set_msg(c, e);
     if (const char* e = wit_program_check_counts(dev->counts, "bx_wit_program_run", po2, w_data)) return set_msg(c, e);
     if (dev->gen.fn) {  // the generated kernel, when one is attached
         BX_TRY(wit_gen_launch(c, dev, po2, code, data));
+        BX_TRY(wit_sorts_run(c, dev, po2, data));
         return wit_counts_run(c, dev, po2, data);
     }
     {
@@ -143,5 +147,6 @@ extern "C" const char* bx_wit_program_run(bx_ctx* c, bx_wit_program_dev* dev, ui
                            (uint32_t)n, dev->n_fetch);
         BX_LAUNCH_CHECK(c);
     }
-    return wit_counts_run(c, dev, po2, data);  // the multiplicity columns, after every row (wit_count.hip)
+    BX_TRY(wit_sorts_run(c, dev, po2, data));  // the sorted columns, after every row (wit_sort.hip)
+    return wit_counts_run(c, dev, po2, data);  // the multiplicity columns, after the sorts (wit_count.hip)
 } BX_ABI_CATCH(c, "bx_wit_program_run")

@@ -16,6 +16,14 @@ struct bx_wit_program_dev {
     std::vector<size_t> count_src_off, count_bin_off;
     std::vector<uint32_t> count_flat;
     bx::DevBuf count_sources, count_bins;
+    // the sorted columns (wit_sort.hip): the program's sorts, where each one's [sources | dests] start in the flat table, that table
+    // on the device, and the work space (grown by the first run that needs more rows than sort_cap): the two (key, idx) pair buffers
+    // in sort_pairs, the digit table and its chunk sums in sort_table
+    std::vector<bx::WitSort> sorts;
+    std::vector<size_t> sort_col_off;
+    std::vector<uint32_t> sort_flat;
+    bx::DevBuf sort_cols, sort_pairs, sort_table;
+    size_t sort_cap = 0;
 };
 
 namespace bx {
@@ -25,4 +33,9 @@ const char* wit_gen_launch(bx_ctx* c, bx_wit_program_dev* dev, uint32_t po2, bx_
 const char* wit_counts_load(bx_ctx* c, bx_wit_program_dev* dev, const bx_wit_program* prog);
 // ... and per count clear, histogram, store on the ctx's stream: the caller (bx_wit_program_run) has checked the counts against the shape
 const char* wit_counts_run(bx_ctx* c, bx_wit_program_dev* dev, uint32_t po2, bx_buf data);
+// wit_sort.hip: upload the flat column table (no-op without sorts; the caller waits for the stream) ...
+const char* wit_sorts_load(bx_ctx* c, bx_wit_program_dev* dev, const bx_wit_program* prog);
+// ... and per sort pack, radix passes, gather on the ctx's stream (nothing at all without sorts): the caller (bx_wit_program_run) has
+// checked the sorts against the shape
+const char* wit_sorts_run(bx_ctx* c, bx_wit_program_dev* dev, uint32_t po2, bx_buf data);
 }  // namespace bx

@@ -164,6 +164,49 @@
  *                the lanes of a wave that hit the first live lane's bin are counted with one ballot and added by one lane.
  *                Out of scope: tables whose entries are not indexed by row (a tuple lookup supplies the index as a source column),
  *                weighted counts, counting code columns.
+ *   sorted columns (normative; bx_wit_program_create_sorted)
+ *                A permutation or memory-consistency argument (RATIO, "Accumulate programs" below) needs a sorted copy of some
+ *                columns as its witness.  No step list can give it, for the reason no step list gives m(r).  A witness program
+ *                therefore has an optional list of at most BX_WIT_MAX_SORTS = 8 SORTS (rows, n_keys, bits[], sources[], dests[]):
+ *                  sources  1 .. BX_WIT_MAX_SORT_COLS = 16 data columns.  The first n_keys of them (1 .. BX_WIT_MAX_SORT_KEYS = 4) are the
+ *                           key, most significant first; the others are payload carried along
+ *                  dests    as many data columns as sources: dests[i] receives sources[i], permuted
+ *                  bits[k]  1 .. 31: the key of a cell of key column k is the low bits[k] bits of its integer decoded from Montgomery
+ *                           form; 31 is the whole value, since P < 2^31.  The prover does not judge the witness: a value at or above
+ *                           2^bits is not an error, it sorts by its low bits and the circuit's constraints catch it.  The bits of
+ *                           one sort sum to at most BX_WIT_MAX_SORT_BITS = 64
+ *                  rows     as in a count: only rows [0, rows) are read and written, rows == 0 means all N, rows at or above
+ *                           `rows` keep what they held
+ *                Meaning: let pi be the stable sort of rows [0, rows) by the key tuple, lexicographic, ties by ascending row.  After
+ *                the run data[dests[i]][r] = data[sources[i]][pi(r)] for r < rows; the source's Montgomery word is copied unchanged.
+ *                pi is unique, so host and device agree word for word.
+ *                Order, on the one stream: (1) the per-row program (interpreter or attached kernel), (2) all sorts in list order,
+ *                (3) all counts.  A source may therefore be a free or a SET column, a count's source may be a dest, a global cell
+ *                may name a dest, and an accumulate program may tap one.  A program without sorts enqueues exactly what it did.
+ *                Refused by name at create: a dest that is SET, that is named by any GET, that is a count column, that is a source
+ *                of any sort, or that is named twice (in one sort or in two); a source that is a count column; a source named
+ *                twice within one sort; any column above BX_CONS_MAX_COL; n_keys == 0, n_keys > 4 or n_keys above the number of
+ *                sources; no sources, or more than 16; a bits value of 0 or above 31; bits that sum to more than 64; rows > 2^24;
+ *                more than 8 sorts.
+ *                Shape-dependent, refused by name by bx_wit_program_run_host, by bx_wit_program_run and when a prover is created,
+ *                with nothing written: rows > N; a source or dest that is not below the data group's width.
+ *                Like counts and global cells the sorts are NOT hashed by bx_wit_program_digest and play no part in
+ *                bx_wit_program_emit_hip: one code object serves a program under any sort list.  bx_wit_program_derives answers 1
+ *                for a dest.
+ *                Host: bx_wit_program_run_host runs the sorts after the stream and before the counts, std::stable_sort on the
+ *                decoded, masked key tuples, gathered into a temporary before anything is written.
+ *                Device (csrc/wit_sort.hip), per sort and without blocking, a stable LSD radix sort: (1) PACK, the key columns
+ *                decoded once into one uint64_t composite key per row, most significant key in the high bits, with idx[r] = r,
+ *                profiled as "wit_program_sort_pack"; (2) ceil(sum of bits / 8) stable passes of 8-bit digits, least significant
+ *                first, over (key, idx) pairs, ping-pong between two buffers, profiled together as "wit_program_sort": a per-tile
+ *                digit histogram (256 LDS bins, written digit-major [digit][tile]), an exclusive scan of that table, and a stable
+ *                scatter to base[digit][tile] + rank (the rank within a wave from a ballot match on the digit's 8 bits, across waves
+ *                and trips from per-wave counters in LDS taken in tile order); (3) GATHER, dests[i][r] = sources[i][idx[r]] for every
+ *                source in one launch, profiled as "wit_program_sort_gather".  The pair buffers and the digit table belong to the
+ *                loaded program: sized at the first run that needs more than is there, released by bx_wit_program_unload and
+ *                bx_free; a second run at the same shape allocates nothing.
+ *                Out of scope: a second per-row pass after the sorts (differences of sorted cells are the constraints' business,
+ *                through `back`); descending order; keys in the code group; a built-in memory circuit.
  *   compiled     the instruction stream of a constraint program restricted to the narrow opcodes, plus one: a store of a
  *                narrow slot to a data column.  bx_wit_program_run_host and the device kernel read the same stream and use the
  *                same canonical arithmetic, so they give identical words.
@@ -316,6 +359,10 @@ extern "C" {
 #define BX_WIT_MAX_COUNTS 16    /* multiplicity columns of one witness program */
 #define BX_WIT_MAX_COUNT_SOURCES 64       /* source columns of one count */
 #define BX_WIT_MAX_COUNT_BINS (1u << 24) /* bins of one count */
+#define BX_WIT_MAX_SORTS 8      /* sorts of one witness program */
+#define BX_WIT_MAX_SORT_COLS 16 /* source columns (keys and payload) of one sort */
+#define BX_WIT_MAX_SORT_KEYS 4  /* key columns of one sort */
+#define BX_WIT_MAX_SORT_BITS 64 /* key bits of one sort, all keys together */
 
 enum bx_cons_op {
     BX_CONS_CONST = 0,
@@ -455,7 +502,7 @@ typedef struct bx_wit_program_dev bx_wit_program_dev; /* ... loaded on a ctx */
 const char* bx_wit_program_create(const bx_wit_program_desc* desc, bx_wit_program** out);
 void bx_wit_program_destroy(bx_wit_program* prog);
 const char* bx_wit_program_info_get(const bx_wit_program* prog, bx_wit_program_info* out);
-/* 1 if the program sets data column `col` or fills it as a multiplicity column, else 0 */
+/* 1 if the program sets data column `col`, fills it as a multiplicity column or writes it as the dest of a sort, else 0 */
 int bx_wit_program_derives(const bx_wit_program* prog, uint32_t col);
 /* Multiplicity columns ("multiplicity columns" above).  One count: data[col][r] = the number of cells of the `sources` columns, rows
  * [0, rows), that hold the integer r, for r < bins; 0 for bins <= r < rows; rows == 0 means all N rows. */
@@ -472,24 +519,44 @@ uint32_t bx_wit_program_counts(const bx_wit_program* prog);
  * sources_out (which may be NULL when cap is 0) */
 const char* bx_wit_program_count_get(const bx_wit_program* prog, uint32_t i, uint32_t* col, uint32_t* bins, uint32_t* rows, uint32_t* sources_out, uint32_t cap,
                                      uint32_t* n_sources);
+/* Sorted columns ("sorted columns" above).  One sort: rows [0, rows) of the n_cols `sources` columns, stably sorted by the low bits[k]
+ * bits of the first n_keys of them (most significant first), go to the `dests` columns; rows == 0 means all N rows. */
+typedef struct bx_wit_sort {
+    uint32_t rows, n_keys, n_cols;
+    const uint32_t* bits;    /* n_keys */
+    const uint32_t* sources; /* n_cols: keys first, then payload */
+    const uint32_t* dests;   /* n_cols */
+} bx_wit_sort;
+/* bx_wit_program_create_counted with a sort list (nothing of it is referenced afterwards); with n_sorts == 0 it is exactly
+ * bx_wit_program_create_counted. */
+const char* bx_wit_program_create_sorted(const bx_wit_program_desc* desc, const bx_wit_count* counts, size_t n_counts, const bx_wit_sort* sorts, size_t n_sorts,
+                                         bx_wit_program** out);
+/* the number of sorts */
+uint32_t bx_wit_program_sorts(const bx_wit_program* prog);
+/* sort i: its rows, its n_keys bits in bits_out, the number of its columns in *n_cols and the first min(cap, *n_cols) sources and
+ * dests in sources_out and dests_out (which may be NULL when cap is 0) */
+const char* bx_wit_program_sort_get(const bx_wit_program* prog, uint32_t i, uint32_t* rows, uint32_t* n_keys, uint32_t bits_out[BX_WIT_MAX_SORT_KEYS],
+                                    uint32_t* sources_out, uint32_t* dests_out, uint32_t cap, uint32_t* n_cols);
 /* Host executor, the reference for the device kernel: the compiled stream over the N = 2^po2 rows of host arrays, column-major
- * (code: w_code x N, data: w_data x N Montgomery words), `data` in place; the counts after the stream.  po2 in [1, 24].  Refused
- * with nothing written: a tap or SET column that is not below its group's width, a count column or source that is not below w_data,
- * a count's rows > N, or bins > N with rows == 0.  No mutable global state. */
+ * (code: w_code x N, data: w_data x N Montgomery words), `data` in place; the sorts after the stream, the counts after the sorts.
+ * po2 in [1, 24].  Refused with nothing written: a tap or SET column that is not below its group's width, a sort's source or dest
+ * that is not below w_data, a sort's rows > N, a count column or source that is not below w_data, a count's rows > N, or bins > N
+ * with rows == 0.  No mutable global state. */
 const char* bx_wit_program_run_host(const bx_wit_program* prog, uint32_t po2, const uint32_t* code, uint32_t w_code, uint32_t* data, uint32_t w_data);
 /* Uploads the stream, the constants, the tap descriptors and the counts' source table once, and allocates the counts' bins.
  * bx_free releases what is still loaded on its ctx. */
 const char* bx_wit_program_load(bx_ctx* ctx, const bx_wit_program* prog, bx_wit_program_dev** out);
 const char* bx_wit_program_unload(bx_wit_program_dev* dev);
-/* Derives the program's columns of `data` on the ctx's stream, then fills its multiplicity columns; does not block.  po2 in
- * [1, 24], code.len == w_code * N, data.len == w_data * N.  Refused with nothing enqueued: lengths that do not match, a tap or SET
- * column that is not below its group's width, `code` and `data` sharing a byte ("Operand overlap", bx_hal.h), and then a count
- * column or source that is not below w_data, a count's rows > N, or bins > N with rows == 0.  The bins belong to `dev`: a loaded
- * program serves one stream, its calls in order. */
+/* Derives the program's columns of `data` on the ctx's stream, then writes its sorted columns, then fills its multiplicity columns;
+ * does not block.  po2 in [1, 24], code.len == w_code * N, data.len == w_data * N.  Refused with nothing enqueued: lengths that do
+ * not match, a tap or SET column that is not below its group's width, `code` and `data` sharing a byte ("Operand overlap",
+ * bx_hal.h), and then a sort's source or dest that is not below w_data, a sort's rows > N, a count column or source that is not
+ * below w_data, a count's rows > N, or bins > N with rows == 0.  The bins and the sorts' work space belong to `dev` (the work space
+ * grows at the first run that needs more): a loaded program serves one stream, its calls in order. */
 const char* bx_wit_program_run(bx_ctx* ctx, bx_wit_program_dev* dev, uint32_t po2, bx_buf code, uint32_t w_code, bx_buf data, uint32_t w_data);
 /* The table's witgen then runs `wit` after base->witgen and takes the global cells from the trace ("composite" above); its create
  * loads the program on the ctx and refuses by name a SET or tap column beyond the shape's widths, a cell row >= N, a cell index
- * >= the base's n_globals, a count column or source beyond w_data and a count's rows or bins above N.  NULL goes back to forwarding witgen to `base` alone.  `wit` must outlive the table.  Set before a
+ * >= the base's n_globals, a count column or source beyond w_data, a count's rows or bins above N, a sort's source or dest beyond w_data and a sort's rows above N.  NULL goes back to forwarding witgen to `base` alone.  `wit` must outlive the table.  Set before a
  * prover is created. */
 const char* bx_cons_circuit_set_witness(bx_cons_circuit* cc, const bx_wit_program* wit);
 
