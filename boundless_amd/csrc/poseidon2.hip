@@ -17,8 +17,9 @@
 namespace bx {
 
 constexpr int CELLS = 24, RATE = 16, RF_HALF = 4, RP = 21;
-constexpr int DIAG_OFF = 216;  // diagonal starts 32-byte aligned in the device parameter table (it and the tables behind it are read by 32-byte scalar loads)
-constexpr int PAIR_OFF = DIAG_OFF + 24, P2_TABLE = PAIR_OFF + 2 * CELLS;  // behind it: the paired rounds' E[24], A[24] (centred)
+constexpr int DIAG_OFF = P2_DIAG_OFF;  // diagonal starts 32-byte aligned in the device parameter table (it and the tables behind it are read by 32-byte scalar loads)
+constexpr int PAIR_OFF = P2_PAIR_OFF;  // behind it: the paired rounds' E[24], A[24] (centred)
+constexpr int FOLD_OFF = P2_FOLD_OFF, P2_TABLE = P2_TABLE_WORDS;  // behind them: the folded external constants, eight blocks of 24 pairs {K, 0}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Instruction budget.  The kernel is VALU-issue-bound and on gfx950 a 32-bit multiply-class op (v_mad_[iu]64_[iu]32,
@@ -31,18 +32,24 @@ constexpr int PAIR_OFF = DIAG_OFF + 24, P2_TABLE = PAIR_OFF + 2 * CELLS;  // beh
 //     conditional subtraction at all except for the 24 words that leave it;
 //   * linear layers run UNREDUCED in 64 bits (v_mad_i64_i32 multiplies by the small matrix entries and accumulates in one
 //     instruction; external-layer outputs < 2^38, internal-layer sum < 2^37);
-//   * the return to 32 bits is one bare REDC per cell with the next round constant in its accumulator:
-//     x = REDC(y + rc') [REDC = * 2^-32 mod P].  The factor 2^-32 is not compensated: the cells of a round share a known
+//   * the return to 32 bits is one bare REDC per cell, x = REDC(y + rc') [REDC = * 2^-32 mod P], and for six of the eight external
+//     rounds (1, 2, 3, 5, 6, 7) the constant is not an instruction at all: the layer is linear, M x + rc' = M (x + c) with
+//     c = M^-1 rc', and K = c * 2^32 mod P rides as a 64-bit SCALAR addend on the last product of the S-boxes in front of the
+//     layer (it was the literal 0), so that x = REDC(y) (sredc_all: 2 instructions per cell, not 3).  Round 0's constants follow no
+//     S-box and round 4's ride in the last internal round, where every addend is taken: those two keep the 64-bit add.
+//     The factor 2^-32 is not compensated: the cells of a round share a known
 //     representation factor R^e that the (homogeneous) linear layers carry along and the S-box maps to R^(7e-6); the round
 //     constants are stored pre-scaled, and only the two layers that must hand back Montgomery form (before the internal
 //     rounds, and at the end) multiply by a correction constant (poseidon2_arith.hpp: representation tracking).
 // Results are congruent mod P at every step and the words that leave the permutation are canonical, so the output is
-// bit-identical to the reduce-everywhere form (6.1 k VALU instructions per permutation by PMC, down from ~14.5 k).
+// bit-identical to the reduce-everywhere form (5 949 VALU instructions per permutation by PMC, down from ~14.5 k).
 //
 // Magnitude bounds (rho = P / 2^32 = 0.46875; sredc(t) in [t/2^32 - P/2, t/2^32 + P/2); int32 holds 1.0667 P):
 //   redc64s output                     |x| <= 57 + P/2                           (external rounds' S-box input)
 //   sbox7s(|x| <= 0.945 P)             |x2| < 0.919 P, |x3| < 0.907 P, |x4| < 0.896 P, |x7| < 0.881 P; products <= 0.893 P^2 < 1.2 P^2
+//   ... with a folded constant          |x3 x4 + K| <= 0.907 * 0.896 P^2 + P (K canonical), the output bound grows by at most 1 (B_SBOX_K)
 //   m_ext64s(any int32 cells)          rows sum to <= 112, |y| <= 112 * 2^31 < 2^38
+//   sredc_all output                   |x| <= 57 + P/2, as redc64s
 //   red64ks<MID>/<END> output          |x| < K1 + 26 + P/2  = 0.626 P / 0.555 P    (K1 = R^2801, R^400 mod P)
 //   internal rounds                    cell i: sredc(d_i s_i + sum_r [+ rc]) with d_i < P: B -> rho B + P/2 + 2 has its fixed
 //                                      point at 0.9412 P, 0.945 P is invariant; |sum| < 22.7 P < 2^37; |sum_r| < 0.791 P thanks to
@@ -54,17 +61,38 @@ constexpr int PAIR_OFF = DIAG_OFF + 24, P2_TABLE = PAIR_OFF + 2 * CELLS;  // beh
 // Device parameter table (round constants scaled by p2_rc_scale(i) so that they can ride in a REDC accumulator of the
 // round's representation): [0,96) external rounds 0-3 | [96,117) internal rounds | [117,213) external rounds 4-7 |
 // [216,240) internal diagonal (plain Montgomery form, used as a multiplier; 32-byte aligned) | [240,288) the constants of the
-// paired internal rounds derived from it (p2_pair_consts: E[24], A[24], centred, as two's-complement words).
-// Input: cells < P (canonical).  Output: canonical.
+// paired internal rounds derived from it (p2_pair_consts: E[24], A[24], centred, as two's-complement words) | [288,672) the folded
+// external constants (p2_fold_consts): eight blocks of 24 pairs {K, 0}, one block per external round's S-boxes in execution order;
+// blocks 0, 1, 2 carry rounds 1, 2, 3, blocks 4, 5, 6 rounds 5, 6, 7, and blocks 3 and 7 are zero (the layers behind those S-boxes
+// change the representation, red64ks_all), so that each external-round loop keeps one copy of its S-boxes.  Words [0,288) are what
+// they were before the region existed: the quad kernels read [0,240) only.  poseidon2_arith.hpp: p2_build_table builds all of it.
+// Input: cells < P (canonical; the capacity of a sponge's later blocks: the signed words carried from the permutation before).
+// Output: canonical (SIGNED: the carried capacity).
 // [LO, HI) is the LIVE RANGE: the output cells the caller reads.  A sponge that absorbs again reads the capacity, <16, 24> (the rate is
 // overwritten by the next 16 columns); its last permutation and every Merkle fold read the digest, <0, 8>.  The compiler drops what plain
 // C computes for a dead cell by itself, but not the pinned multiply-adds, so the last layer is split: all 24 S-boxes and the layer's blocks
 // and column sums are computed as ever (every output needs them), and the final add, the reduction that restores the Montgomery form,
 // canon and the store run for the live cells only.  io[] keeps its input words in the dead cells.
 typedef uint32_t sgpr8 __attribute__((ext_vector_type(8)));
-static_assert(DIAG_OFF % 8 == 0 && PAIR_OFF % 8 == 0 && CELLS % 8 == 0, "the tables are read as 32-byte octets");
-template <int LO = 0, int HI = CELLS>
+typedef uint64_t sgpr4q __attribute__((ext_vector_type(4)));  // the same 32 bytes as four 64-bit addends (SGPR pairs)
+static_assert(DIAG_OFF % 8 == 0 && PAIR_OFF % 8 == 0 && FOLD_OFF % 8 == 0 && CELLS % 8 == 0, "the tables are read as 32-byte octets");
+// Half h (12 cells) of the S-boxes of external round `block` (0..7 in execution order), with the next round's folded constants on the
+// last products.  The 12 pairs {K, 0} are fetched like the other tables: the compiler's own 32-byte scalar loads from the wave-uniform
+// table pointer, pinned by an empty statement; 24 SGPRs are live, for this half only.
+__device__ __forceinline__ void sbox_half_folded(i32* s, const uint32_t* __restrict__ prm, int block, int h) {
+    const sgpr4q* fp = reinterpret_cast<const sgpr4q*>(prm + FOLD_OFF + block * P2_FOLD_BLOCK + h * CELLS);
+    sgpr4q f0 = fp[0], f1 = fp[1], f2 = fp[2];
+    asm volatile("" : "+s"(f0), "+s"(f1), "+s"(f2));
+    i64 K[CELLS / 2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) K[i] = (i64)f0[i], K[4 + i] = (i64)f1[i], K[8 + i] = (i64)f2[i];
+    sbox7s_n<CELLS / 2>(s + h * (CELLS / 2), K);
+}
+// SIGNED (a sponge's non-final permutations, live cells inside the capacity): the live cells leave as the signed words of the last
+// reduction (|v| < 0.555 P), without canon; the next permutation bit-casts them back and its first layer accepts any int32.
+template <int LO = 0, int HI = CELLS, bool SIGNED = false>
 __device__ __forceinline__ void poseidon2_mix(uint32_t* io, const uint32_t* __restrict__ prm) {
+    static_assert(!SIGNED || LO >= RATE, "only capacity cells are carried signed");
     i32 s[CELLS];
     i64 y[CELLS];
 #pragma unroll
@@ -72,15 +100,16 @@ __device__ __forceinline__ void poseidon2_mix(uint32_t* io, const uint32_t* __re
     // initial external layer; round-0 constants ride in the reduction
     m_ext64s(s, y);
     redc64s_all(y, prm, s);
-    // external rounds 0..3: S-box, layer, reduction with the NEXT round's constants (after round 3 only cell 0 has one:
-    // the first internal round's)
+    // external rounds 0..3: S-box with the NEXT round's folded constants on its last product, layer, bare reduction (after round 3
+    // the block is zero and only cell 0 has a constant: the first internal round's)
 #pragma unroll 1
     for (int r = 0; r < RF_HALF; ++r) {
-        sbox7s_n<CELLS / 2>(s);  // two halves: 12 independent chains are enough ILP and halve the live 64-bit temporaries
-        sbox7s_n<CELLS / 2>(s + CELLS / 2);
+        asm volatile("" : "+s"(r));  // the counter stays a scalar (see the second loop)
+        sbox_half_folded(s, prm, r, 0);  // two halves: 12 independent chains are enough ILP and halve the live 64-bit temporaries
+        sbox_half_folded(s, prm, r, 1);
         m_ext64s(s, y);
         if (r < RF_HALF - 1) {
-            redc64s_all(y, prm + (r + 1) * CELLS, s);
+            sredc_all(y, s);
         } else {  // back to the Montgomery representation for the internal rounds
             red64ks_all<K1_MID, K2_MID, true>(y, prm[96], s);
         }
@@ -127,18 +156,18 @@ __device__ __forceinline__ void poseidon2_mix(uint32_t* io, const uint32_t* __re
     i64 t[4];
 #pragma unroll 1
     for (int r = 0;; ++r) {
-        sbox7s_n<CELLS / 2>(s);  // two halves: 12 independent chains are enough ILP and halve the live 64-bit temporaries
-        sbox7s_n<CELLS / 2>(s + CELLS / 2);
-        m_ext64s_core(s, y, t);
         asm volatile("" : "+s"(r));  // the counter stays a scalar: left alone it becomes a 64-bit byte offset in VGPRs, compared and read back per round
+        sbox_half_folded(s, prm, RF_HALF + r, 0);  // rounds 5..7's constants; the last round's block is zero
+        sbox_half_folded(s, prm, RF_HALF + r, 1);
+        m_ext64s_core(s, y, t);
         if (r == RF_HALF - 1) break;
         m_ext64s_finish(y, t);
-        redc64s_all(y, prm + 117 + (r + 1) * CELLS, s);
+        sredc_all(y, s);
     }
     m_ext64s_finish<LO, HI>(y, t);
     red64ks_all<K1_END, K2_END, false, LO, HI>(y, 0u, s);
 #pragma unroll
-    for (int i = LO; i < HI; ++i) io[i] = canon(s[i]);  // canonical Montgomery words leave the permutation
+    for (int i = LO; i < HI; ++i) io[i] = SIGNED ? (uint32_t)s[i] : canon(s[i]);  // canonical Montgomery words leave the permutation (SIGNED: the carried capacity)
 }
 
 // Occupancy: the stage-wise order fixes the register pressure (the statements are volatile), so the stages are 12 cells wide
@@ -159,7 +188,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     for (; c + RATE < cols; c += RATE) {
 #pragma unroll
         for (int i = 0; i < RATE; ++i) s[i] = p[(size_t)(c + i) * rows];
-        poseidon2_mix<RATE, CELLS>(s, prm);
+        poseidon2_mix<RATE, CELLS, true>(s, prm);  // the capacity is carried as signed words: nothing but the next permutation reads it
     }
 #pragma unroll
     for (int i = 0; i < RATE; ++i) s[i] = (c + i < cols) ? p[(size_t)(c + i) * rows] : 0u;
@@ -513,13 +542,10 @@ __global__ __launch_bounds__(64) void transcript_step_kernel(uint32_t* __restric
 }
 
 const char* poseidon2_upload_params(bx_ctx* c) {
-    uint32_t h[P2_TABLE] = {0};
-    // round constants ride in REDC accumulators, pre-scaled to the representation of the round they are added in
-    for (int i = 0; i < 213; ++i) h[i] = (uint32_t)((uint64_t)(c->h_rc[i] % P) * p2_rc_scale(i) % P);
-    for (int i = 0; i < 24; ++i) h[DIAG_OFF + i] = fp_encode(c->h_diag[i]);
-    i32 pe[CELLS], pa[CELLS];
-    p2_pair_consts(h + DIAG_OFF, pe, pa);
-    for (int i = 0; i < CELLS; ++i) h[PAIR_OFF + i] = (uint32_t)pe[i], h[PAIR_OFF + CELLS + i] = (uint32_t)pa[i];
+    uint32_t h[P2_TABLE];
+    // poseidon2_arith.hpp: the scaled round constants, the diagonal, the paired rounds' constants and the folded external constants,
+    // which are checked against the layer (M c == rc') as they are derived
+    if (!p2_build_table(c->h_rc, c->h_diag, h)) return "poseidon2_upload_params: the folded round constants do not reproduce the stored ones";
     if (!c->d_p2) BX_HIP(c, hipMalloc(&c->d_p2, sizeof h));
     BX_HIP(c, hipMemcpyAsync(c->d_p2, h, sizeof h, hipMemcpyHostToDevice, c->stream));
     BX_HIP(c, stream_wait(c));

@@ -118,6 +118,16 @@ BX_HD i64 smul(i32 a, i32 b, int alt = 0) {  // a*b
     return (i64)a * (i64)b;
 #endif
 }
+BX_HD i64 smad_c64(i32 a, i32 b, i64 c, int alt = 0) {  // a*b + c, c a wave-uniform 64-bit constant: an SGPR pair, one constant-bus read
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(BX_PLAIN_MAD)
+    i64 r;
+    BX_MAD_ASM("v_mad_i64_i32", "%1, %2, %3", "v"(a), "v"(b), "s"(c));
+    return r;
+#else
+    (void)alt;
+    return (i64)a * (i64)b + c;
+#endif
+}
 BX_HD i64 smad_k(i32 a, uint32_t k, i64 c, int alt = 0) {  // a*k + c, k a wave-uniform constant < 2^31 (scalar operand)
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(BX_PLAIN_MAD)
     i64 r;
@@ -254,9 +264,18 @@ BX_HD i32 sbox7s(i32 x) {
     const i32 x4 = sredc(smul(x2, x2));
     return sredc(smul(x3, x4));
 }
-// the same on N cells at once, stage-wise
-template <int N>
-BX_HD void sbox7s_n(i32* x) {
+// The S-box that also adds the NEXT external round's constants.  The external layer is linear, M x + rc = M (x + c) with c = M^-1 rc,
+// and the last product of an S-box is a multiply-add whose addend is otherwise the literal 0: with K = c * 2^32 mod P (canonical) in
+// that addend, sredc(x3 x4 + K) == x^7 + c, and the reduction behind the layer is a bare sredc with no constant (sredc_all) instead of
+// a 64-bit add per cell (redc64s_all).  K is wave-uniform and comes as a 64-bit scalar operand (smad_c64); p2_fold_consts derives it.
+// |x3 x4 + K| <= 0.907 * 0.896 P^2 + P, and the output bound of the S-box grows by at most 1.
+constexpr i64 B_X2 = ub(B_INT * B_INT), B_X3 = ub(B_X2 * B_INT), B_X4 = ub(B_X2 * B_X2);
+constexpr i64 T_SBOX_K = B_X3 * B_X4 + (i64)P - 1;  // the last product plus a folded constant
+constexpr i64 B_SBOX_K = ub(T_SBOX_K);               // ... reduced: the cells entering an external layer
+static_assert(T_SBOX_K <= SREDC_MAX && B_SBOX_K <= ub(B_X3 * B_X4) + 1 && B_SBOX_K <= B_INT, "S-box with a folded constant leaves its bounds");
+// the S-box on N cells at once, stage-wise; HAS_K: K[i] rides on the last product of cell i
+template <int N, bool HAS_K>
+BX_HD void sbox7s_stages(i32* x, const i64* K) {
     i64 t[N], u[N];
     i32 x2[N], x3[N], x4[N];
 #pragma unroll
@@ -273,9 +292,25 @@ BX_HD void sbox7s_n(i32* x) {
     sredc_n<N>(t, x3);
     sredc_n<N>(u, x4);
 #pragma unroll
-    for (int i = 0; i < N; ++i) t[i] = smul(x3[i], x4[i], i & 3);
+    for (int i = 0; i < N; ++i) {
+        if constexpr (HAS_K) {
+            BX_ASSERT_BOUND(K[i] >= 0 && K[i] < (i64)P, "folded round constant");
+            t[i] = smad_c64(x3[i], x4[i], K[i], i & 3);
+            BX_ASSERT_BOUND(iabs64(t[i]) <= T_SBOX_K, "sbox last product");
+        } else {
+            t[i] = smul(x3[i], x4[i], i & 3);
+        }
+    }
     sredc_n<N>(t, x);
+    if constexpr (HAS_K) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) BX_ASSERT_BOUND(iabs64(x[i]) <= B_SBOX_K, "sbox output");
+    }
 }
+template <int N>
+BX_HD void sbox7s_n(i32* x) { sbox7s_stages<N, false>(x, nullptr); }
+template <int N>
+BX_HD void sbox7s_n(i32* x, const i64* K) { sbox7s_stages<N, true>(x, K); }
 
 // Bare REDC of an external-layer output plus a pre-scaled round constant (canonical, < P):  r == (y + rc) * 2^-32 (mod P),
 // |r| <= B_EXT.  3 instructions (64-bit add, v_mul_lo, v_mad_i64_i32).
@@ -301,6 +336,18 @@ BX_HD void redc64s_all(const i64* y, const uint32_t* rc, i32* s) {
     }
 #pragma unroll
     for (int i = 0; i < P2_CELLS; ++i) BX_ASSERT_BOUND(iabs64(s[i]) <= B_EXT, "redc64s output");
+}
+
+// the 24 bare reductions of a layer whose round constants came in with the S-boxes in front of it (sbox7s_n with K): r == y * 2^-32
+// (mod P), |r| <= B_EXT, 2 instructions per cell; the same two halves
+BX_HD void sredc_all(const i64* y, i32* s) {
+    constexpr int H = P2_CELLS / 2;
+#pragma unroll
+    for (int i = 0; i < P2_CELLS; ++i) BX_ASSERT_BOUND(iabs64(y[i]) <= B_Y, "external layer output");
+#pragma unroll
+    for (int h = 0; h < P2_CELLS; h += H) sredc_n<H>(y + h, s + h);
+#pragma unroll
+    for (int i = 0; i < P2_CELLS; ++i) BX_ASSERT_BOUND(iabs64(s[i]) <= B_EXT, "sredc_all output");
 }
 
 // REDC with a change of representation:  r == (y * K1 + add) * 2^-32 (mod P),  K2 = K1 * 2^32 mod P,  y = y_hi * 2^32 + y_lo
@@ -638,28 +685,168 @@ BX_HD uint32_t canon(i32 v) {
     return umin(u, u + P);
 }
 
+// ---- the parameter table ------------------------------------------------------------------------------------------------
+// [0,96) external rounds 0-3 | [96,117) internal rounds | [117,213) external rounds 4-7: round constants * p2_rc_scale(i), canonical
+// [216,240) the internal diagonal (Montgomery form) | [240,288) E[24], A[24] of the paired internal rounds (p2_pair_consts)
+// [288,672) the FOLDED constants of the external rounds: eight blocks of 24 pairs {K, 0} (a 64-bit addend each), one block per external
+//   round's S-boxes in execution order.  Blocks 0, 1, 2 carry rounds 1, 2, 3 and blocks 4, 5, 6 rounds 5, 6, 7; blocks 3 and 7 are zero
+//   (behind those S-boxes stand the layers with a change of representation, red64ks_all), so that each external-round loop keeps ONE
+//   copy of its S-boxes.  Round 0's constants follow no S-box and round 4's ride in the last internal round: both stay in [0,213).
+constexpr int P2_RC_WORDS = 213, P2_DIAG_OFF = 216, P2_PAIR_OFF = P2_DIAG_OFF + P2_CELLS, P2_FOLD_OFF = P2_PAIR_OFF + 2 * P2_CELLS;
+constexpr int P2_FOLD_BLOCK = 2 * P2_CELLS, P2_FOLD_BLOCKS = 8, P2_FOLD_WORDS = P2_FOLD_BLOCKS * P2_FOLD_BLOCK;
+constexpr int P2_TABLE_WORDS = P2_FOLD_OFF + P2_FOLD_WORDS;
+static_assert(P2_DIAG_OFF % 8 == 0 && P2_PAIR_OFF % 8 == 0 && P2_FOLD_OFF % 8 == 0 && (P2_FOLD_BLOCK / 2) % 8 == 0, "the tables are read as 32-byte octets");
+
+// M4 of the external layer and its inverse over F_P (Gauss-Jordan at compile time)
+struct P2M4 {
+    uint32_t a[4][4];
+};
+constexpr uint32_t cx_sub(uint32_t a, uint32_t b) { return a >= b ? a - b : a + P - b; }
+constexpr P2M4 P2_M4 = {{{5, 7, 1, 3}, {4, 6, 1, 1}, {1, 3, 5, 7}, {1, 1, 4, 6}}};
+constexpr P2M4 p2_m4_mul(const P2M4& x, const P2M4& y) {
+    P2M4 r = {};
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            uint32_t v = 0;
+            for (int k = 0; k < 4; ++k) v = (uint32_t)(((uint64_t)x.a[i][k] * y.a[k][j] + v) % P);
+            r.a[i][j] = v;
+        }
+    return r;
+}
+constexpr P2M4 p2_m4_inverse() {
+    uint32_t m[4][8] = {};
+    for (int i = 0; i < 4; ++i) {
+        for (int j = 0; j < 4; ++j) m[i][j] = P2_M4.a[i][j];
+        m[i][4 + i] = 1;
+    }
+    for (int col = 0; col < 4; ++col) {
+        int p = col;
+        while (p < 3 && m[p][col] == 0) ++p;
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t v = m[p][j];
+            m[p][j] = m[col][j];
+            m[col][j] = v;
+        }
+        const uint32_t inv = cx_pow(m[col][col], P - 2);
+        for (int j = 0; j < 8; ++j) m[col][j] = cx_mul(m[col][j], inv);
+        for (int i = 0; i < 4; ++i) {
+            if (i == col) continue;
+            const uint32_t f = m[i][col];
+            for (int j = 0; j < 8; ++j) m[i][j] = cx_sub(m[i][j], cx_mul(f, m[col][j]));
+        }
+    }
+    P2M4 r = {};
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) r.a[i][j] = m[i][4 + j];
+    return r;
+}
+constexpr bool p2_m4_is_identity(const P2M4& x) {
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j)
+            if (x.a[i][j] != (i == j ? 1u : 0u)) return false;
+    return true;
+}
+static_assert(p2_m4_is_identity(p2_m4_mul(P2_M4, p2_m4_inverse())), "M4^-1");
+
+// the stored constants of the external round that the S-boxes of block b hand their outputs to (nullptr: a zero block)
+BX_HD const uint32_t* p2_fold_source(const uint32_t* prm, int b) {
+    return (b & 3) == 3 ? nullptr : b < 3 ? prm + (b + 1) * P2_CELLS : prm + 117 + (b - 3) * P2_CELLS;
+}
+// fold[P2_FOLD_WORDS] from the scaled round constants prm[0, 213).  The stored constants rc' of round r are scaled to the representation
+// of the layer output they were added to, which is also that of the S-box outputs in front of the (homogeneous) layer, so
+// c = M^-1 rc' on the stored words:  M = circ(2 M4, M4, ..., M4) = (I6 + J6) (x) M4,  M^-1 = (I6 - J6 / 7) (x) M4^-1,  and
+// K = c * 2^32 mod P, canonical, as the pair {K, 0}.  Returns whether M c == rc' holds for every folded round (recomputed by the
+// layer's definition, not by the inverse).
+BX_HD bool p2_fold_consts(const uint32_t* prm, uint32_t* fold) {
+    constexpr P2M4 inv = p2_m4_inverse();
+    constexpr uint32_t inv7 = cx_pow(7u, P - 2);
+    bool ok = true;
+    for (int b = 0; b < P2_FOLD_BLOCKS; ++b) {
+        uint32_t* out = fold + b * P2_FOLD_BLOCK;
+        for (int i = 0; i < P2_FOLD_BLOCK; ++i) out[i] = 0u;
+        const uint32_t* rc = p2_fold_source(prm, b);
+        if (!rc) continue;
+        uint32_t c[P2_CELLS], seventh[4], t[4] = {0u, 0u, 0u, 0u};
+        for (int j = 0; j < 4; ++j) {
+            uint64_t sum = 0;
+            for (int k = 0; k < P2_CELLS; k += 4) sum += rc[k + j] % P;
+            seventh[j] = (uint32_t)(sum % P * inv7 % P);
+        }
+        for (int k = 0; k < P2_CELLS; k += 4)  // c_k = M4^-1 (rc'_k - (sum of the blocks) / 7)
+            for (int i = 0; i < 4; ++i) {
+                uint64_t v = 0;
+                for (int j = 0; j < 4; ++j) v = ((uint64_t)inv.a[i][j] * ((rc[k + j] % P + P - seventh[j]) % P) + v) % P;
+                c[k + i] = (uint32_t)v;
+            }
+        uint32_t w[P2_CELLS];
+        for (int k = 0; k < P2_CELLS; k += 4)  // the layer itself: w_k = M4 c_k, T = sum_k w_k, y_k = w_k + T
+            for (int i = 0; i < 4; ++i) {
+                uint64_t v = 0;
+                for (int j = 0; j < 4; ++j) v += (uint64_t)P2_M4.a[i][j] * c[k + j];
+                w[k + i] = (uint32_t)(v % P);
+                t[i] = (uint32_t)(((uint64_t)t[i] + w[k + i]) % P);
+            }
+        for (int i = 0; i < P2_CELLS; ++i) {
+            ok = ok && (uint32_t)(((uint64_t)w[i] + t[i & 3]) % P) == rc[i] % P;
+            out[2 * i] = (uint32_t)((uint64_t)c[i] * MONT_ONE % P);
+        }
+    }
+    return ok;
+}
+// the 12 addends of half h (0, 1) of block b as the S-boxes take them
+BX_HD void p2_fold_half(const uint32_t* fold, int b, int h, i64* K) {
+    const uint32_t* f = fold + b * P2_FOLD_BLOCK + h * P2_CELLS;
+    for (int i = 0; i < P2_CELLS / 2; ++i) K[i] = (i64)(((uint64_t)f[2 * i + 1] << 32) | f[2 * i]);
+}
+// the whole device table from canonical round constants and a canonical diagonal; false if a folded round fails M c == rc'
+BX_HD bool p2_build_table(const uint32_t* rc213, const uint32_t* diag24, uint32_t* table) {
+    for (int i = 0; i < P2_TABLE_WORDS; ++i) table[i] = 0u;
+    // round constants ride in REDC accumulators, pre-scaled to the representation of the round they are added in
+    for (int i = 0; i < P2_RC_WORDS; ++i) table[i] = (uint32_t)((uint64_t)(rc213[i] % P) * p2_rc_scale(i) % P);
+    for (int i = 0; i < P2_CELLS; ++i) table[P2_DIAG_OFF + i] = fp_encode(diag24[i]);
+    i32 pe[P2_CELLS], pa[P2_CELLS];
+    p2_pair_consts(table + P2_DIAG_OFF, pe, pa);
+    for (int i = 0; i < P2_CELLS; ++i) table[P2_PAIR_OFF + i] = (uint32_t)pe[i], table[P2_PAIR_OFF + P2_CELLS + i] = (uint32_t)pa[i];
+    return p2_fold_consts(table, table + P2_FOLD_OFF);
+}
+
 // The whole permutation in the exact order and arithmetic of the device kernel (poseidon2.hip: poseidon2_mix); the device
-// version differs only in pinning the internal-round sum to v_mad_i64_i32 and in reading the diagonal and the paired rounds'
-// constants from its parameter table (where poseidon2_upload_params put what p2_pair_consts derives) into SGPRs.
+// version differs only in pinning the internal-round sum to v_mad_i64_i32 and in reading the diagonal, the paired rounds'
+// constants and the folded external constants from its parameter table (where poseidon2_upload_params put what p2_pair_consts and
+// p2_fold_consts derive) into SGPRs.
 // prm: [0,96) | [96,117) | [117,213) round constants * p2_rc_scale(i) (canonical), [DIAG..DIAG+24) diagonal (Montgomery).
 // Input and output: canonical Montgomery words.  [LO, HI): the live cells, as in the device's poseidon2_mix<LO, HI>: the last layer is
 // finished, reduced, made canonical and stored for those cells only, and io[] keeps its input words everywhere else.
-template <int DIAG, int LO = 0, int HI = P2_CELLS>
+// SIGNED_OUT (a sponge that absorbs again, live cells inside the capacity): the live cells are left as the signed words the last
+// reduction gave (|v| <= B_CARRY), not made canonical; the next permutation takes them as they are, since the first layer accepts any
+// int32.  So the capacity cells of the INPUT are canonical or such carried words; the rate is canonical.
+constexpr i64 B_CARRY = (i64)K1_END + (i64)(P / 2) + 60;  // red64ks<K1_END> output (0.555 P)
+static_assert(B_CARRY < (i64)P, "carried capacity cells");
+template <int DIAG, int LO = 0, int HI = P2_CELLS, bool SIGNED_OUT = false>
 BX_HD void poseidon2_mix_bounded(uint32_t* io, const uint32_t* prm) {
+    static_assert(!SIGNED_OUT || LO >= 16, "only capacity cells are carried signed");
     i32 s[P2_CELLS];
-    i64 y[P2_CELLS];
+    i64 y[P2_CELLS], K[P2_CELLS / 2];
     const uint32_t* diag = prm + DIAG;
     for (int i = 0; i < P2_CELLS; ++i) {
-        BX_ASSERT_BOUND(io[i] <= B_IN, "canonical input");
+        if (i < 16) BX_ASSERT_BOUND(io[i] <= B_IN, "canonical input");
+        else BX_ASSERT_BOUND(iabs64((i32)io[i]) <= B_IN, "capacity input: canonical or carried signed");
         s[i] = (i32)io[i];
     }
+    uint32_t fold[P2_FOLD_WORDS];  // the device reads these from its parameter table behind the paired rounds' constants
+    const bool folded = p2_fold_consts(prm, fold);
+    BX_ASSERT_BOUND(folded, "M c == rc' for the folded rounds");
+    (void)folded;
     m_ext64s(s, y);
     redc64s_all(y, prm, s);
     for (int r = 0; r < 4; ++r) {
-        sbox7s_n<P2_CELLS>(s);
+        for (int h = 0; h < 2; ++h) {
+            p2_fold_half(fold, r, h, K);
+            sbox7s_n<P2_CELLS / 2>(s + h * (P2_CELLS / 2), K);
+        }
         m_ext64s(s, y);
         if (r < 3) {
-            redc64s_all(y, prm + (r + 1) * P2_CELLS, s);
+            sredc_all(y, s);
         } else {
             red64ks_all<K1_MID, K2_MID, true>(y, prm[96], s);
             for (int i = 0; i < P2_CELLS; ++i) BX_ASSERT_BOUND(iabs64(s[i]) <= B_MIDOUT, "mid transition output");
@@ -671,15 +858,25 @@ BX_HD void poseidon2_mix_bounded(uint32_t* io, const uint32_t* prm) {
     internal_round<true>(s, diag, prm + 117);
     for (int r = 0; r < 4; ++r) {
         i64 t[4];
-        sbox7s_n<P2_CELLS>(s);
+        for (int h = 0; h < 2; ++h) {
+            p2_fold_half(fold, 4 + r, h, K);
+            sbox7s_n<P2_CELLS / 2>(s + h * (P2_CELLS / 2), K);
+        }
         m_ext64s_core(s, y, t);
         if (r < 3) {
             m_ext64s_finish(y, t);
-            redc64s_all(y, prm + 117 + (r + 1) * P2_CELLS, s);
+            sredc_all(y, s);
         } else {
             m_ext64s_finish<LO, HI>(y, t);
             red64ks_all<K1_END, K2_END, false, LO, HI>(y, 0u, s);
-            for (int i = LO; i < HI; ++i) io[i] = canon(s[i]);
+            for (int i = LO; i < HI; ++i) {
+                if (SIGNED_OUT) {
+                    BX_ASSERT_BOUND(iabs64(s[i]) <= B_CARRY, "carried capacity cell");
+                    io[i] = (uint32_t)s[i];
+                } else {
+                    io[i] = canon(s[i]);
+                }
+            }
         }
     }
 }
