@@ -859,3 +859,235 @@ class AccumulateProgram(ConsProgram):
 
 
 CircuitOps.from_program = staticmethod(_from_program)
+
+
+# ---- trace layouts (include/bx_layout.h): a circuit's code group and free cells from one description — the base of from_program ----
+(LAYOUT_CONST, LAYOUT_FIRST, LAYOUT_LAST, LAYOUT_ACTIVE, LAYOUT_ROW, LAYOUT_PERIODIC, LAYOUT_WORD) = range(7)  # enum bx_layout_code_kind
+LAYOUT_MAX_STRIDE = 128  # BX_LAYOUT_MAX_STRIDE
+SEGMENT_WIRE_BYTES = 28  # BX_SEGMENT_WIRE_BYTES
+
+
+class LayoutCodeCol(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("a", C.c_uint32), ("b", C.c_uint32)]
+
+
+class LayoutField(C.Structure):
+    _fields_ = [("col", C.c_uint32), ("word", C.c_uint32), ("shift", C.c_uint32), ("bits", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class TraceLayoutDesc(C.Structure):
+    _fields_ = [("code", C.POINTER(LayoutCodeCol)), ("n_code", C.c_uint32), ("table", C.POINTER(C.c_uint32)), ("n_table", C.c_uint32),
+                ("fields", C.POINTER(LayoutField)), ("n_fields", C.c_uint32), ("stride", C.c_uint32), ("noise_rows", C.c_uint32), ("n_globals", C.c_uint32)]
+
+
+class TraceLayoutInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("n_code", "n_table", "n_fields", "stride", "noise_rows", "n_globals", "min_w_data")]
+
+
+def _layout_lib():
+    lib = load_library()
+    if not getattr(lib, "_layout_bound", False):
+        u32p, vp = C.POINTER(C.c_uint32), C.c_void_p
+        lib.bx_trace_layout_create.argtypes = [C.POINTER(TraceLayoutDesc), C.POINTER(vp)]
+        lib.bx_trace_layout_destroy.argtypes = [vp]
+        lib.bx_trace_layout_destroy.restype = None
+        lib.bx_trace_layout_info_get.argtypes = [vp, C.POINTER(TraceLayoutInfo)]
+        lib.bx_trace_layout_ops.argtypes = [vp]
+        lib.bx_trace_layout_ops.restype = C.POINTER(CircuitOps)
+        lib.bx_trace_layout_code_host.argtypes = [vp, C.c_uint32, u32p]
+        lib.bx_trace_layout_data_host.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), u32p, C.c_uint32]
+        lib.bx_trace_layout_control_id_host_hashfn.argtypes = [vp, C.c_uint32, C.c_char_p, u32p]
+        lib.bx_trace_layout_load.argtypes = [vp, vp, C.POINTER(vp)]
+        lib.bx_trace_layout_unload.argtypes = [vp]
+        lib.bx_trace_layout_code.argtypes = [vp, vp, C.c_uint32, BxBuf]
+        lib.bx_trace_layout_place.argtypes = [vp, vp, C.c_uint32, BxBuf, C.c_size_t, C.c_uint64, BxBuf, C.c_uint32]
+        for name in ("bx_trace_layout_create", "bx_trace_layout_info_get", "bx_trace_layout_code_host", "bx_trace_layout_data_host",
+                     "bx_trace_layout_control_id_host_hashfn", "bx_trace_layout_load", "bx_trace_layout_unload", "bx_trace_layout_code", "bx_trace_layout_place"):
+            getattr(lib, name).restype = C.c_char_p
+        lib._layout_bound = True
+    return lib
+
+
+def encode_records(records):
+    """The payload of a trace-layout segment (include/bx_layout.h, "data"): a 2-D array-like of R records x stride 32-bit words ->
+    the R * stride words as little-endian bytes, record after record."""
+    import numpy as np
+
+    a = np.asarray(records)
+    if a.ndim != 2:
+        raise ValueError("encode_records: a 2-D array of records x stride words is needed")
+    if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+        raise ValueError("encode_records: a word is not a 32-bit unsigned value")
+    return np.ascontiguousarray(a, dtype="<u4").tobytes()
+
+
+class LoadedTraceLayout:
+    """A trace layout on a ctx (bx_trace_layout_dev): the two kernels outside a proof."""
+
+    def __init__(self, layout, hal, dev):
+        self.layout, self.hal, self.dev = layout, hal, dev
+
+    def code(self, po2, code):
+        """bx_trace_layout_code: fills the N x n_code group `code` (a hal Buffer)"""
+        self.hal.trace_layout_code(self, po2, code)
+
+    def place(self, po2, segment_dev, segment_len, noise_seed, data, w_data):
+        """bx_trace_layout_place: the free cells of the N x w_data group `data` from the segment's bytes in `segment_dev` (header
+        included; segment_len bytes); noise_seed is the noise seed itself"""
+        self.hal.trace_layout_place(self, po2, segment_dev, segment_len, noise_seed, data, w_data)
+
+    def unload(self):
+        if self.dev:
+            dev, self.dev = self.dev, None
+            self.hal._check(self.layout.lib.bx_trace_layout_unload(dev))
+
+
+class CompiledTraceLayout:
+    """A compiled trace layout (bx_trace_layout): host only until `load`ed on a HipHal or made a circuit's base with `ops`."""
+
+    def __init__(self, lib, handle):
+        self.lib, self.handle = lib, handle
+
+    def info(self):
+        out = TraceLayoutInfo()
+        msg = self.lib.bx_trace_layout_info_get(self.handle, C.byref(out))
+        assert not msg, msg
+        return {n: int(getattr(out, n)) for n, _ in TraceLayoutInfo._fields_}
+
+    def ops(self):
+        """bx_trace_layout_ops: the layout as a CircuitOps, usable as `base` of CircuitOps.from_program (it keeps the layout alive)"""
+        ops = self.lib.bx_trace_layout_ops(self.handle).contents
+        ops._keepalive = self
+        return ops
+
+    def code_host(self, po2):
+        """bx_trace_layout_code_host -> the code group as a (n_code, N) uint32 array of Montgomery words.  A refusal raises HalError."""
+        import numpy as np
+
+        from .hal import HalError
+
+        out = np.zeros((self.info()["n_code"], 1 << po2), np.uint32)
+        msg = self.lib.bx_trace_layout_code_host(self.handle, po2, out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if msg:
+            raise HalError(msg.decode())
+        return out
+
+    def data_host(self, po2, segment_bytes, w_data, noise_seed=None, out=None):
+        """bx_trace_layout_data_host -> the data group's free cells as a (w_data, N) uint32 array; segment_bytes = header + payload
+        (prover.Segment(...).to_bytes()); noise_seed None = derived from the segment's seed.  out: a C-contiguous (w_data, N) uint32
+        array to fill instead of a new one (a refusal leaves it untouched).  A refusal raises HalError."""
+        import numpy as np
+
+        from .hal import HalError
+
+        if out is None:
+            out = np.zeros((w_data, 1 << po2), np.uint32)
+        assert out.dtype == np.uint32 and out.flags.c_contiguous and out.size == w_data << po2
+        seed = None if noise_seed is None else C.byref(C.c_uint64(int(noise_seed)))
+        msg = self.lib.bx_trace_layout_data_host(self.handle, po2, bytes(segment_bytes), len(segment_bytes), seed, out.ctypes.data_as(C.POINTER(C.c_uint32)), w_data)
+        if msg:
+            raise HalError(msg.decode())
+        return out
+
+    def control_id_host(self, po2, hashfn="poseidon2"):
+        """bx_trace_layout_control_id_host_hashfn -> the 8 words of the control ID of a circuit over this layout at po2"""
+        import numpy as np
+
+        from .hal import HalError
+
+        out = np.zeros(8, np.uint32)
+        msg = self.lib.bx_trace_layout_control_id_host_hashfn(self.handle, po2, hashfn.encode(), out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if msg:
+            raise HalError(msg.decode())
+        return out
+
+    def load(self, hal):
+        dev = C.c_void_p()
+        hal._check(self.lib.bx_trace_layout_load(hal.ctx, self.handle, C.byref(dev)))
+        return LoadedTraceLayout(self, hal, dev)
+
+    def close(self):
+        if self.handle:
+            self.lib.bx_trace_layout_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TraceLayout:
+    """Builder of a trace layout (include/bx_layout.h): the code_* methods append one code column each and return its index;
+    field(col, word, ...) names the record word a free data column comes from.
+
+        t = TraceLayout(stride=2, noise_rows=0)
+        t.code_first()
+        t.code_last()
+        t.field(0, 0, bits=8)            # data column 0 = the low 8 bits of record word 0
+        t.field(1, 1, bits=30)
+        layout = t.compile()
+        ops = CircuitOps.from_program(cons, layout.ops(), witness=wit, accumulate=acc)
+    """
+
+    def __init__(self, stride=1, noise_rows=1994, n_globals=0):
+        self.stride, self.noise_rows, self.n_globals = stride, noise_rows, n_globals
+        self.code, self.table, self.fields = [], [], []
+
+    def _code(self, kind, a=0, b=0):
+        self.code.append((int(kind), int(a), int(b)))
+        return len(self.code) - 1
+
+    def code_const(self, value):
+        return self._code(LAYOUT_CONST, value)
+
+    def code_first(self):
+        return self._code(LAYOUT_FIRST)
+
+    def code_last(self, back=0):
+        """1 at row A - 1 - back"""
+        return self._code(LAYOUT_LAST, back)
+
+    def code_active(self, back=0):
+        """1 on rows below A - back"""
+        return self._code(LAYOUT_ACTIVE, back)
+
+    def code_row(self, below=0):
+        """the value r on rows below `below` (0 = every row), else 0"""
+        return self._code(LAYOUT_ROW, below)
+
+    def code_periodic(self, values):
+        """the values repeat with period len(values), a power of two up to 4096; they are appended to the layout's table"""
+        values = [int(v) for v in values]
+        bits = len(values).bit_length() - 1
+        if not values or 1 << bits != len(values):
+            raise ValueError("TraceLayout.code_periodic: the period must be a power of two")
+        at = len(self.table)
+        self.table += values
+        return self._code(LAYOUT_PERIODIC, bits, at)
+
+    def code_word(self, seed):
+        """the pseudo-random words word(seed, c, r) of bx_prover.h"""
+        return self._code(LAYOUT_WORD, int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
+
+    def field(self, col, word, shift=0, bits=30, pad=0):
+        self.fields.append((int(col), int(word), int(shift), int(bits), int(pad)))
+
+    def compile(self):
+        """-> CompiledTraceLayout.  A refusal raises HalError."""
+        from .hal import HalError
+
+        for v in [self.stride, self.noise_rows, self.n_globals, *self.table, *[v for c in self.code for v in c], *[v for f in self.fields for v in f]]:
+            if not 0 <= int(v) < 1 << 32:  # the library takes 32-bit words: a value that would wrap into a valid one is an error here
+                raise ValueError(f"TraceLayout.compile: {v} is not a 32-bit unsigned value")
+        lib = _layout_lib()
+        code = (LayoutCodeCol * max(len(self.code), 1))(*[LayoutCodeCol(*c) for c in self.code])
+        table = (C.c_uint32 * max(len(self.table), 1))(*self.table)
+        fields = (LayoutField * max(len(self.fields), 1))(*[LayoutField(*f) for f in self.fields])
+        desc = TraceLayoutDesc(code, len(self.code), table, len(self.table), fields, len(self.fields), self.stride, self.noise_rows, self.n_globals)
+        handle = C.c_void_p()
+        msg = lib.bx_trace_layout_create(C.byref(desc), C.byref(handle))
+        if msg:
+            raise HalError(msg.decode())
+        return CompiledTraceLayout(lib, handle)

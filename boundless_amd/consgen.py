@@ -56,6 +56,28 @@ def witness_program_of(desc):
     return w.compile()
 
 
+_LAYOUT_KINDS = ("const", "first", "last", "active", "row", "periodic", "word")  # enum bx_layout_code_kind, in order
+
+
+def layout_of(desc):
+    """-> CompiledTraceLayout of a description's "layout" key (include/bx_layout.h):
+    {"layout": {"stride": s, "noise_rows": z, "n_globals": g, "table": [...],
+                "code": [["first"], ["last", a], ["const", a], ["active", a], ["row", a], ["periodic", a, b], ["word", a, b]],
+                "fields": [{"col": c, "word": w, "shift": 0, "bits": 30, "pad": 0}, ...]}}
+    A code column is its kind (a name or its number) and its operands a, b (0 when left out); PERIODIC windows index "table"."""
+    from .circuit import TraceLayout
+
+    d = desc["layout"]
+    t = TraceLayout(stride=int(d.get("stride", 1)), noise_rows=int(d.get("noise_rows", 1994)), n_globals=int(d.get("n_globals", 0)))
+    t.table = [int(v) for v in d.get("table", [])]
+    for col in d["code"]:
+        kind, ops = col[0], [int(v) for v in col[1:]] + [0, 0]
+        t.code.append((_LAYOUT_KINDS.index(kind) if isinstance(kind, str) else int(kind), ops[0], ops[1]))
+    for f in d.get("fields", []):
+        t.field(f["col"], f["word"], f.get("shift", 0), f.get("bits", 30), f.get("pad", 0))
+    return t.compile()
+
+
 def _resource_usage(stderr, kernel="bx_cp_eval"):
     out, on = {}, False
     for line in stderr.splitlines():

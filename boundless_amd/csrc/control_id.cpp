@@ -23,6 +23,7 @@
 #include "../../include/bx_circuit.h"
 #include "circuit.hpp"
 #include "lookup.hpp"
+#include "trace_layout.hpp"
 #include "fp.hpp"
 #include "poseidon2_params.hpp"
 #include "hash_suite.hpp"
@@ -152,6 +153,10 @@ std::mutex cache_mu;
 enum BuiltIn : uint32_t { BUILTIN_SYNTHETIC = 0, BUILTIN_LOOKUP = 1 };
 std::map<std::array<uint32_t, 4>, Digest> cache;  // (circuit, po2, w_code, suite) -> host-computed control ID
 
+constexpr HostIdErrors LAYOUT_ID_ERRORS = {
+    "bx_trace_layout_control_id_host: shape out of range (po2 in [9, 24])",
+    "bx_trace_layout_control_id_host: the code group is too large for the host computation (build a verifier context from bx_prover_control_id instead)"};
+
 // the cached host computation for one of the built-in circuits
 const char* cached_control_id(BuiltIn which, uint32_t po2, uint32_t wc, int suite, uint32_t out[8]) {
     const std::array<uint32_t, 4> key{(uint32_t)which, po2, wc, (uint32_t)suite};
@@ -209,6 +214,14 @@ const char* lookup_check_code_suite(const bx_segment_params* s, const uint32_t r
 }
 const char* lookup_check_code(void*, const bx_segment_params* s, const uint32_t root[8]) {
     return lookup_check_code_suite(s, root, SUITE_POSEIDON2);
+}
+// a trace layout's code group through the same definition-level path (trace_layout_host.cpp checks the shape and caches the result)
+const char* layout_host_control_id(const bx_trace_layout* l, uint32_t po2, int suite, uint32_t out[8]) {
+    const uint32_t n = 1u << (po2 & 31u), act = layout_active_rows(po2 & 31u, l->noise_rows);
+    const bx_layout_code_col* code = l->code.data();
+    const uint32_t* table = l->table.data();
+    return host_control_id(po2, (uint32_t)l->code.size(), suite, [=](uint32_t c, uint32_t r) { return layout_code_cell(code[c], table, c, r, n, act); },
+                           LAYOUT_ID_ERRORS, out);
 }
 // the built-in circuits' control IDs follow the hash suite (a table's check_code has no suite parameter): what verify.cpp asks under a
 // suite other than the default when it has no context.  Any other table (a plug-in circuit) is refused.

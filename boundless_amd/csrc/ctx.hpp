@@ -264,6 +264,7 @@ const char* gather_flush(bx_ctx* c);  // poly.hip: launch the queued gather_samp
 void cons_programs_release(bx_ctx* c);  // cons_program.hip: constraint programs still loaded on this ctx (bx_free; the stream is drained)
 void wit_programs_release(bx_ctx* c);   // wit_program.hip: witness programs, likewise
 void acc_programs_release(bx_ctx* c);   // acc_program.hip: accumulate programs, likewise
+void trace_layouts_release(bx_ctx* c);  // trace_layout.hip: trace layouts, likewise
 constexpr uint32_t FLAG_SLOT_SCATTER_RANGE = 0u;  // words of bx_ctx::h_flag
 constexpr uint32_t FLAG_SLOT_SCATTER_INDEX = 1u;
 constexpr uint32_t FLAG_SLOTS = 4u;

@@ -328,6 +328,7 @@ extern "C" const char* bx_free(bx_ctx* c) try {
     cons_programs_release(c);  // constraint programs still loaded on this ctx (bx_program.h)
     wit_programs_release(c);   // ... and witness programs
     acc_programs_release(c);   // ... and accumulate programs
+    trace_layouts_release(c);  // ... and trace layouts (bx_layout.h)
     drain_profile(c);
     ntt_free_tables(c);
     if (c->d_p2) (void)hipFree(c->d_p2);

@@ -335,6 +335,16 @@ class HipHal:
         (boundless_amd.circuit.CompiledWitnessProgram.load); derives its columns of the N x w_data group `data` in place."""
         self._check(loaded.program.lib.bx_wit_program_run(self.ctx, loaded.dev, po2, code.raw, w_code, data.raw, w_data))
 
+    def trace_layout_code(self, loaded, po2, code):
+        """A trace layout's code group (include/bx_layout.h: bx_trace_layout_code): `loaded` = a layout loaded on this hal
+        (boundless_amd.circuit.CompiledTraceLayout.load); fills the N x n_code group `code`."""
+        self._check(loaded.layout.lib.bx_trace_layout_code(self.ctx, loaded.dev, po2, code.raw))
+
+    def trace_layout_place(self, loaded, po2, segment_dev, segment_len, noise_seed, data, w_data):
+        """A trace layout's free cells (bx_trace_layout_place): the segment's bytes in `segment_dev` (header included, segment_len
+        bytes) -> the N x w_data group `data`, column-major Montgomery words; rows at or above A hold noise from `noise_seed`."""
+        self._check(loaded.layout.lib.bx_trace_layout_place(self.ctx, loaded.dev, po2, segment_dev.raw, segment_len, int(noise_seed) & (2**64 - 1), data.raw, w_data))
+
     def acc_program_keep(self, loaded, po2, code, w_code, data, w_data, kept):
         """An accumulate program's keep (include/bx_program.h: bx_acc_program_keep): `loaded` = a program loaded on this hal
         (boundless_amd.circuit.CompiledAccumulateProgram.load); copies the columns it taps into `kept` (N x its kept columns)."""
