@@ -36,7 +36,7 @@ __global__ void acc_program_keep_kernel(uint32_t* __restrict__ kept, const uint3
 
 // what cp_exec asks of this kernel: a tap is a kept column at row r - back; the opcodes cp_exec does not know are the term stores
 struct AccEnv {
-    static constexpr bool MIX = false;
+    static constexpr bool MIX = false, EXT = true;
     const uint32_t* __restrict__ kept;
     const uint2* __restrict__ taps;  // (kept index, back)
     uint32_t* __restrict__ run_ext;
@@ -91,52 +91,6 @@ __global__ __launch_bounds__(256) void acc_program_kernel(uint32_t* __restrict__
 
 namespace {
 LoadedPrograms<bx_acc_program_dev> g_loaded;  // what bx_free still has to release
-
-// the compiler refuses what does not fit; a stream from anywhere else must not reach the kernel: every slot, table index and
-// sequence number of the stream against the program's own counts
-bool stream_fits(const bx_acc_program* p) {
-    const bx_acc_program_info& in = p->info;
-    const size_t n_scal = in.n_globals + 4 + p->consts.size();
-    if (in.narrow > BX_CONS_MAX_NARROW || in.wide > BX_CONS_MAX_WIDE || in.sums > in.sequences || in.sequences < 1 || in.sequences > BX_ACC_MAX_SEQS ||
-        p->code.size() % (2 * CP_FETCH) || p->tap_kept.size() != p->taps.size() || in.kept != p->kept.size() || p->ratios > in.sequences - in.sums)
-        return false;
-    for (uint32_t k : p->tap_kept)
-        if (k >= p->kept.size()) return false;
-    for (const bx_cons_tap& t : p->kept)
-        if (t.group > 1) return false;
-    for (size_t pc = 0; pc < p->code.size(); pc += 2) {
-        const uint32_t w0 = p->code[pc], w1 = p->code[pc + 1];
-        const uint32_t op = w0 & 0xFFu, dst = (w0 >> 8) & 0xFFu, a = (w0 >> 16) & 0xFFu, b = w0 >> 24, imm = w1 >> 8;
-        const auto N = [&](uint32_t s) { return s < in.narrow; };
-        const auto W = [&](uint32_t s) { return s < in.wide; };
-        bool ok;
-        switch (op) {
-        case CP_NOP: ok = true; break;
-        case CP_LD_B: ok = N(dst) && imm < n_scal; break;
-        case CP_LD_E: ok = W(dst) && (size_t)imm + 4 <= n_scal; break;
-        case CP_TAP: ok = N(dst) && imm < p->taps.size(); break;
-        case CP_ADD_BB:
-        case CP_SUB_BB:
-        case CP_MUL_BB: ok = N(dst) && N(a) && N(b); break;
-        case CP_ADD_EB:
-        case CP_SUB_EB:
-        case CP_MUL_EB: ok = W(dst) && W(a) && N(b); break;
-        case CP_SUB_BE: ok = W(dst) && N(a) && W(b); break;
-        case CP_ADD_EE:
-        case CP_SUB_EE:
-        case CP_MUL_EE: ok = W(dst) && W(a) && W(b); break;
-        case CP_TSUM_B: ok = N(a) && N(b) && imm < in.sums; break;
-        case CP_TSUM_E: ok = N(a) && W(b) && imm < in.sums; break;
-        case CP_TPROD_B: ok = N(a) && imm >= in.sums && imm < in.sequences; break;
-        case CP_TPROD_E: ok = W(a) && imm >= in.sums && imm < in.sequences; break;
-        case CP_TDEN_B: ok = N(a) && imm >= in.sequences && imm < in.sequences + p->ratios; break;
-        case CP_TDEN_E: ok = W(a) && imm >= in.sequences && imm < in.sequences + p->ratios; break;
-        default: ok = false; break;
-        }
-        if (!ok) return false;
-    }
-    return true;
-}
 }  // namespace
 
 void acc_programs_release(bx_ctx* c) {
@@ -150,7 +104,8 @@ extern "C" const char* bx_acc_program_load(bx_ctx* c, const bx_acc_program* prog
     BX_REQUIRE(c, prog && out, "bx_acc_program_load: null argument");
     BX_ENTER(c);
     *out = nullptr;
-    BX_REQUIRE(c, stream_fits(prog), "bx_acc_program_load: the program's stream or counts are outside the device limits");
+    // the compiler refuses what does not fit; a stream from anywhere else must not reach the kernel
+    BX_REQUIRE(c, program_fits(prog), "bx_acc_program_load: the program's stream or counts are outside the device limits");
     std::unique_ptr<bx_acc_program_dev> d(new bx_acc_program_dev());
     d->ctx = c;
     d->info = prog->info;

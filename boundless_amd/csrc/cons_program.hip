@@ -34,7 +34,7 @@ struct ConsLaunch {
 
 // what cp_exec (cons_program_exec.hpp) asks of this kernel: a tap is a column of the 4N evaluations at row i - 4 back
 struct ConsEnv {
-    static constexpr bool MIX = true;
+    static constexpr bool MIX = true, EXT = true;
     const uint32_t* __restrict__ ecode;
     const uint32_t* __restrict__ edata;
     const uint32_t* __restrict__ eacc;
@@ -100,6 +100,8 @@ extern "C" const char* bx_cons_program_load(bx_ctx* c, const bx_cons_program* pr
     BX_REQUIRE(c, prog && out, "bx_cons_program_load: null argument");
     BX_ENTER(c);
     *out = nullptr;
+    // the compiler refuses what does not fit; a stream from anywhere else must not reach the kernel
+    BX_REQUIRE(c, program_fits(prog), "bx_cons_program_load: the program's slot counts are outside the device limits");
     std::unique_ptr<bx_cons_program_dev> d(new bx_cons_program_dev());
     d->ctx = c;
     d->info = prog->info;
@@ -108,10 +110,6 @@ extern "C" const char* bx_cons_program_load(bx_ctx* c, const bx_cons_program* pr
     d->n_fetch = (uint32_t)(prog->code.size() / (2 * CP_FETCH));
     for (int g = 0; g < 3; ++g) d->max_col[g] = prog->max_col[g];
     BX_TRY(bx_cons_program_digest(prog, d->gen.digest));  // what a generated kernel must have been built from (attach_kernel)
-    // the compiler refuses what does not fit; a stream from anywhere else must not reach the kernel
-    BX_REQUIRE(c, prog->info.narrow <= BX_CONS_MAX_NARROW && prog->info.wide >= 1 && prog->info.wide <= BX_CONS_MAX_WIDE && prog->ret_slot < prog->info.wide &&
-                      prog->code.size() % (2 * CP_FETCH) == 0,
-               "bx_cons_program_load: the program's slot counts are outside the device limits");
     d->lds = (size_t)(prog->info.narrow + 4 * prog->info.wide) * CP_LANES * 4;
     BX_TRY(d->mixpows.alloc(c, 8 * (size_t)prog->n_pows));
     BX_TRY(upload_program(

@@ -59,6 +59,42 @@ constexpr uint32_t CP_FETCH = 4;  // instructions per fetch of the kernel (8 dwo
 inline uint32_t cp_w0(uint32_t op, uint32_t dst, uint32_t a, uint32_t b) { return op | dst << 8 | a << 16 | b << 24; }
 inline uint32_t cp_w1(uint32_t c, uint32_t imm) { return c | imm << 8; }
 
+// The opcode comments above in machine form: what each field of an instruction is, per opcode (cons_program_host.cpp: op_rules).
+// A field the opcode does not use carries anything and is never looked at.
+enum SlotClass : uint8_t { SLOT_NONE, SLOT_NARROW, SLOT_WIDE };
+enum ImmClass : uint8_t {
+    IMM_NONE,
+    IMM_SCAL,    // one word of `scal`
+    IMM_CONST4,  // four consecutive words of `scal`, all of them constants
+    IMM_TAP,     // an entry of the tap list
+    IMM_POW,     // a mix power
+    IMM_SET,     // a data column below max_set
+    IMM_SUM,     // a sequence in [0, sums)
+    IMM_PROD,    // a sequence in [sums, S)
+    IMM_DEN,     // a ratio's denominator: a sequence in [S, S + R)
+};
+enum ProgramKind : uint8_t { KIND_CONS = 1, KIND_WIT = 2, KIND_ACC = 4 };
+struct OpRule {
+    uint8_t dst, a, b, c;  // SlotClass
+    uint8_t imm;           // ImmClass
+    uint8_t kinds;         // the ProgramKinds whose streams may hold the opcode
+};
+const OpRule* op_rules();  // CP_OPCODES entries, indexed by opcode
+
+// what a stream is held against: the program's own counts
+struct StreamLimits {
+    uint8_t kind;           // one ProgramKind
+    uint32_t narrow, wide;  // the slot files
+    size_t n_scal, consts_at;  // the size of `scal`, and where its constants begin
+    const bx_cons_tap* taps;
+    size_t n_taps;
+    uint32_t tap_groups;    // a tap's group is below this
+    uint32_t n_pows, max_set, sums, sequences, ratios;
+};
+// Does every instruction of `code` belong to the kind, and does every field its opcode uses stay inside its file or table?  Also
+// false: slot files above BX_CONS_MAX_*, a length that is no whole number of fetches, a tap of an illegal group.
+bool stream_fits(const std::vector<uint32_t>& code, const StreamLimits& lim);
+
 }  // namespace bx
 
 struct bx_cons_program {
@@ -113,6 +149,12 @@ struct bx_acc_program {
 };
 
 namespace bx {
+// cons_program_host.cpp: stream_fits against the program's own counts, and the kind's header rules (ret_slot, the coherence of an
+// accumulate program's kept / tap_kept / ratios).  The compiler's output always passes (the creates check it); every consumer of a
+// program — the loads, the host executors, the emitters — calls this once and then trusts the stream.
+bool program_fits(const bx_cons_program* p);
+bool program_fits(const bx_wit_program* p);
+bool program_fits(const bx_acc_program* p);
 // cons_program_host.cpp: NULL, or the refusal (thread-local buffer, led by `who`) of a kept column that is not below its group's width: one
 // text for bx_acc_program_run_host, bx_acc_program_keep and the composite table's create
 const char* acc_program_check_widths(const std::vector<bx_cons_tap>& kept, const char* who, uint32_t w_code, uint32_t w_data);

@@ -88,31 +88,11 @@ struct Stmt {  // one instruction that does something
 
 const char* const group_fn[3] = {"code", "data", "accum"};
 
-// every CP_TAP names an entry of the tap list, of a group below `groups`
-bool taps_in_table(const std::vector<uint32_t>& code, const std::vector<bx_cons_tap>& taps, uint32_t groups) {
-    for (size_t pc = 0; pc < code.size(); pc += 2)
-        if ((code[pc] & 0xFFu) == CP_TAP) {
-            const uint32_t imm = code[pc + 1] >> 8;
-            if (imm >= taps.size() || taps[imm].group >= groups) return false;
-        }
-    return true;
-}
-
-// the statements of the narrow opcodes both kinds of program have; false = a slot outside the narrow file
-bool tap_stmt(Text& t, uint32_t d, const bx_cons_tap& tp, uint32_t nn) {
-    if (d >= nn) return false;
-    t.f("    n%u = at.%s(%uu, r%u);\n", d, group_fn[tp.group], tp.col, tp.back);
-    return true;
-}
-bool const_stmt(Text& t, uint32_t d, uint32_t word, uint32_t nn) {
-    if (d >= nn) return false;
-    t.f("    n%u = 0x%08xu;\n", d, word);
-    return true;
-}
-bool arith_bb_stmt(Text& t, uint32_t op, uint32_t d, uint32_t a, uint32_t b, uint32_t nn) {
-    if (d >= nn || a >= nn || b >= nn) return false;
+// the statements of the narrow opcodes both kinds of program have
+void tap_stmt(Text& t, uint32_t d, const bx_cons_tap& tp) { t.f("    n%u = at.%s(%uu, r%u);\n", d, group_fn[tp.group], tp.col, tp.back); }
+void const_stmt(Text& t, uint32_t d, uint32_t word) { t.f("    n%u = 0x%08xu;\n", d, word); }
+void arith_bb_stmt(Text& t, uint32_t op, uint32_t d, uint32_t a, uint32_t b) {
     t.f("    n%u = %s(n%u, n%u);\n", d, op == CP_ADD_BB ? "fp_add" : (op == CP_SUB_BB ? "fp_sub" : "fp_mul"), a, b);
-    return true;
 }
 
 // what differs between the two texts around the statements
@@ -170,121 +150,80 @@ void write_functions(Text& t, const std::vector<Stmt>& stmts, const Frame& fr) {
     t.f("}\n\n%s_WRAPPERS\n", fr.up);
 }
 
-// a constraint program's body, one statement per instruction; false = the stream names something outside the program's own tables
+// a constraint program's body, one statement per instruction; false = the stream does not pass program_fits, and nothing is written
 bool emit_text(const bx_cons_program* p, Text& out) {
+    if (!program_fits(p)) return false;
     Text& t = out;
     const uint32_t nn = p->info.narrow, nw = p->info.wide, ng = p->info.n_globals;
-    const size_t n_scal = (size_t)ng + 4 + p->consts.size();
-    if (nn > BX_CONS_MAX_NARROW || nw < 1 || nw > BX_CONS_MAX_WIDE || p->ret_slot >= nw || p->code.size() % 2) return false;
     uint32_t dg[8];
     digest_of(p, dg);
     t.f("// generated by bx_cons_program_emit_hip: ABI %u, %u instructions, %u narrow and %u wide slots\n", BX_CP_ABI, p->info.instructions, nn, nw);
     t.f("#define BX_PLAIN_MAD 1\n#define BX_CP_DIGEST_WORDS 0x%08xu, 0x%08xu, 0x%08xu, 0x%08xu, 0x%08xu, 0x%08xu, 0x%08xu, 0x%08xu\n", dg[0], dg[1], dg[2], dg[3], dg[4],
         dg[5], dg[6], dg[7]);
     t.f("#include \"cons_program_gen.hpp\"\n\n");
-    if (!taps_in_table(p->code, p->taps, 3)) return false;
     std::vector<Stmt> stmts;  // in stream order
     for (size_t pc = 0; pc < p->code.size(); pc += 2) {
         Text t;  // this instruction's statement
         const uint32_t w0 = p->code[pc], w1 = p->code[pc + 1];
         const uint32_t op = w0 & 0xFFu, d = (w0 >> 8) & 0xFFu, a = (w0 >> 16) & 0xFFu, b = w0 >> 24, c = w1 & 0xFFu, imm = w1 >> 8;
-        const auto N = [&](uint32_t s) { return s < nn; };
-        const auto W = [&](uint32_t s) { return s < nw; };
-        bool ok = true;
         switch (op) {
-        case CP_NOP: break;
         case CP_LD_B:
-            ok = N(d) && imm < n_scal;
-            if (ok && imm < ng + 4) t.f("    n%u = at.scalar(%uu);\n", d, imm);
-            else if (ok) const_stmt(t, d, p->consts[imm - ng - 4], nn);
+            if (imm < ng + 4) t.f("    n%u = at.scalar(%uu);\n", d, imm);
+            else const_stmt(t, d, p->consts[imm - ng - 4]);
             break;
         case CP_LD_E: {
-            ok = W(d) && imm >= ng + 4 && (size_t)imm + 3 < n_scal;
-            if (!ok) break;
             const uint32_t* k = &p->consts[imm - ng - 4];
             t.f("    w%u = Fp4{{0x%08xu, 0x%08xu, 0x%08xu, 0x%08xu}};\n", d, k[0], k[1], k[2], k[3]);
             break;
         }
-        case CP_TAP: ok = tap_stmt(t, d, p->taps[imm], nn); break;  // imm and the group were checked above
+        case CP_TAP: tap_stmt(t, d, p->taps[imm]); break;
         case CP_ADD_BB:
         case CP_SUB_BB:
-        case CP_MUL_BB: ok = arith_bb_stmt(t, op, d, a, b, nn); break;
+        case CP_MUL_BB: arith_bb_stmt(t, op, d, a, b); break;
         case CP_ADD_EB:
         case CP_SUB_EB:
-        case CP_MUL_EB:
-            ok = W(d) && W(a) && N(b);
-            if (ok) t.f("    w%u = %s(w%u, n%u);\n", d, op == CP_ADD_EB ? "cp_add_eb" : (op == CP_SUB_EB ? "cp_sub_eb" : "f4_scale"), a, b);
-            break;
-        case CP_SUB_BE:
-            ok = W(d) && N(a) && W(b);
-            if (ok) t.f("    w%u = cp_sub_be(n%u, w%u);\n", d, a, b);
-            break;
+        case CP_MUL_EB: t.f("    w%u = %s(w%u, n%u);\n", d, op == CP_ADD_EB ? "cp_add_eb" : (op == CP_SUB_EB ? "cp_sub_eb" : "f4_scale"), a, b); break;
+        case CP_SUB_BE: t.f("    w%u = cp_sub_be(n%u, w%u);\n", d, a, b); break;
         case CP_ADD_EE:
         case CP_SUB_EE:
-        case CP_MUL_EE:
-            ok = W(d) && W(a) && W(b);
-            if (ok) t.f("    w%u = %s(w%u, w%u);\n", d, op == CP_ADD_EE ? "f4_add" : (op == CP_SUB_EE ? "f4_sub" : "f4_mul_lz"), a, b);
-            break;
-        case CP_ZERO:
-            ok = W(d);
-            if (ok) t.f("    w%u = f4_zero();\n", d);
-            break;
-        case CP_EQZ_B:
-            ok = W(d) && W(a) && N(b) && imm < p->n_pows;
-            if (ok) t.f("    w%u = f4_add(w%u, f4_scale(at.power(%uu), n%u));\n", d, a, imm, b);
-            break;
-        case CP_EQZ_E:
-            ok = W(d) && W(a) && W(b) && imm < p->n_pows;
-            if (ok) t.f("    w%u = f4_add(w%u, f4_mul_lz(at.power(%uu), w%u));\n", d, a, imm, b);
-            break;
-        case CP_COND_B:
-            ok = W(d) && W(a) && N(b) && W(c) && imm < p->n_pows;
-            if (ok) t.f("    w%u = f4_add(w%u, f4_scale(f4_mul_lz(at.power(%uu), w%u), n%u));\n", d, a, imm, c, b);
-            break;
-        case CP_COND_E:
-            ok = W(d) && W(a) && W(b) && W(c) && imm < p->n_pows;
-            if (ok) t.f("    w%u = f4_add(w%u, f4_mul_lz(f4_mul_lz(at.power(%uu), w%u), w%u));\n", d, a, imm, c, b);
-            break;
-        default: ok = false; break;  // CP_ST among them: a store belongs to witness programs
+        case CP_MUL_EE: t.f("    w%u = %s(w%u, w%u);\n", d, op == CP_ADD_EE ? "f4_add" : (op == CP_SUB_EE ? "f4_sub" : "f4_mul_lz"), a, b); break;
+        case CP_ZERO: t.f("    w%u = f4_zero();\n", d); break;
+        case CP_EQZ_B: t.f("    w%u = f4_add(w%u, f4_scale(at.power(%uu), n%u));\n", d, a, imm, b); break;
+        case CP_EQZ_E: t.f("    w%u = f4_add(w%u, f4_mul_lz(at.power(%uu), w%u));\n", d, a, imm, b); break;
+        case CP_COND_B: t.f("    w%u = f4_add(w%u, f4_scale(f4_mul_lz(at.power(%uu), w%u), n%u));\n", d, a, imm, c, b); break;
+        case CP_COND_E: t.f("    w%u = f4_add(w%u, f4_mul_lz(f4_mul_lz(at.power(%uu), w%u), w%u));\n", d, a, imm, c, b); break;
+        default: break;  // CP_NOP, the padding
         }
-        if (!ok) return false;
         if (!t.s.empty()) stmts.push_back(Stmt{t.s, op == CP_TAP, op == CP_TAP ? p->taps[imm].back : 0u});
     }
     write_functions(t, stmts, Frame{"bx_cp", "BX_CP", nn, nw, (int)p->ret_slot});
     return true;
 }
 
-// a witness program's body: the narrow opcodes and the store, nothing else
+// a witness program's body: the narrow opcodes and the store, nothing else; false as above
 bool emit_text(const bx_wit_program* p, Text& out) {
+    if (!program_fits(p)) return false;
     Text& t = out;
     const uint32_t nn = p->info.narrow;
-    if (nn > BX_CONS_MAX_NARROW || p->code.size() % 2) return false;
     uint32_t dg[8];
     digest_of(p, dg);
     t.f("// generated by bx_wit_program_emit_hip: ABI %u, %u instructions, %u narrow slots, %zu derived columns\n", BX_WP_ABI, p->info.instructions, nn, p->sets.size());
     t.f("#define BX_WP_DIGEST_WORDS 0x%08xu, 0x%08xu, 0x%08xu, 0x%08xu, 0x%08xu, 0x%08xu, 0x%08xu, 0x%08xu\n", dg[0], dg[1], dg[2], dg[3], dg[4], dg[5], dg[6], dg[7]);
     t.f("#include \"wit_program_gen.hpp\"\n\n");
-    if (!taps_in_table(p->code, p->taps, 2)) return false;
     std::vector<Stmt> stmts;
     for (size_t pc = 0; pc < p->code.size(); pc += 2) {
         Text t;
         const uint32_t w0 = p->code[pc], w1 = p->code[pc + 1];
         const uint32_t op = w0 & 0xFFu, d = (w0 >> 8) & 0xFFu, a = (w0 >> 16) & 0xFFu, b = w0 >> 24, imm = w1 >> 8;
-        bool ok = true;
         switch (op) {
-        case CP_NOP: break;  // the padding
-        case CP_LD_B: ok = imm < p->consts.size() && const_stmt(t, d, p->consts[imm], nn); break;  // `scal` is the constants alone
-        case CP_TAP: ok = tap_stmt(t, d, p->taps[imm], nn); break;
+        case CP_LD_B: const_stmt(t, d, p->consts[imm]); break;  // `scal` is the constants alone
+        case CP_TAP: tap_stmt(t, d, p->taps[imm]); break;
         case CP_ADD_BB:
         case CP_SUB_BB:
-        case CP_MUL_BB: ok = arith_bb_stmt(t, op, d, a, b, nn); break;
-        case CP_ST:  // a column below max_set is below the data width: bx_wit_program_run checks max_set before it launches
-            ok = a < nn && imm < p->max_set;
-            if (ok) t.f("    at.store(%uu, n%u);\n", imm, a);
-            break;
-        default: ok = false; break;
+        case CP_MUL_BB: arith_bb_stmt(t, op, d, a, b); break;
+        case CP_ST: t.f("    at.store(%uu, n%u);\n", imm, a); break;  // below max_set, which bx_wit_program_run holds against the data width
+        default: break;  // CP_NOP, the padding
         }
-        if (!ok) return false;
         if (!t.s.empty()) stmts.push_back(Stmt{t.s, op == CP_TAP, op == CP_TAP ? p->taps[imm].back : 0u});
     }
     write_functions(t, stmts, Frame{"bx_wp", "BX_WP", nn, 0, -1});

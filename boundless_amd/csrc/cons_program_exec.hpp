@@ -1,11 +1,15 @@
 // cons_program_exec.hpp — one instruction of a compiled program for one lane: the opcode bodies the interpreting kernels share
-// (cons_program.hip over the 4N domain, acc_program.hip over the N trace rows).  Device only; the including translation unit defines
-// BX_PLAIN_MAD first (circuit_common.hpp).  What differs between the two kernels comes through `Env`:
+// (cons_program.hip over the 4N domain, acc_program.hip and wit_program.hip over the N trace rows).  Device only; the including
+// translation unit defines BX_PLAIN_MAD first (circuit_common.hpp).  What differs between the kernels comes through `Env`:
+//   EXT          does the kind have ext values (CP_LD_E, CP_ADD_EB .. CP_MUL_EE); when not, their bodies are not compiled and `wid`
+//                is never touched
 //   MIX          does the stream hold the mix opcodes (CP_ZERO .. CP_COND_E); when not, their bodies are not compiled
 //   tap(imm)     the word tap imm reads for this lane
 //   mixpows()    the canonical mix-power table (MIX only)
-//   other(...)   any opcode this file does not know (the term stores of an accumulate program; nothing for a constraint program)
+//   other(...)   any opcode this file does not know (CP_ST of a witness program, the term stores of an accumulate program; nothing
+//                for a constraint program)
 // The slot files live in LDS, slot-major: narrow slot s of lane t is nar[256 s], wide slot s four such planes (cons_program.hip).
+// No index is checked here: a stream reaches a kernel only through a load, which holds it against program_fits (cons_program.hpp).
 #pragma once
 #include "circuit_common.hpp"
 #include "cons_program.hpp"
@@ -34,36 +38,48 @@ __device__ __forceinline__ void cp_exec(uint32_t w0v, uint32_t w1v, uint32_t* na
     switch (op) {
     case CP_NOP: break;
     case CP_LD_B: nar[dst * CP_LANES] = scal[imm]; break;
-    case CP_LD_E: {
-        const uint32_t* s = scal + imm;
-        cp_stw(wid, dst, Fp4{{s[0], s[1], s[2], s[3]}});
+    case CP_LD_E:
+        if constexpr (Env::EXT) {
+            const uint32_t* s = scal + imm;
+            cp_stw(wid, dst, Fp4{{s[0], s[1], s[2], s[3]}});
+        }
         break;
-    }
     case CP_TAP: nar[dst * CP_LANES] = env.tap(imm); break;
     case CP_ADD_BB: nar[dst * CP_LANES] = fp_add(nar[a * CP_LANES], nar[b * CP_LANES]); break;
     case CP_SUB_BB: nar[dst * CP_LANES] = fp_sub(nar[a * CP_LANES], nar[b * CP_LANES]); break;
     case CP_MUL_BB: nar[dst * CP_LANES] = fp_mul(nar[a * CP_LANES], nar[b * CP_LANES]); break;
-    case CP_ADD_EB: {
-        Fp4 x = cp_ldw(wid, a);
-        x.c[0] = fp_add(x.c[0], nar[b * CP_LANES]);
-        cp_stw(wid, dst, x);
+    case CP_ADD_EB:
+        if constexpr (Env::EXT) {
+            Fp4 x = cp_ldw(wid, a);
+            x.c[0] = fp_add(x.c[0], nar[b * CP_LANES]);
+            cp_stw(wid, dst, x);
+        }
         break;
-    }
-    case CP_SUB_EB: {
-        Fp4 x = cp_ldw(wid, a);
-        x.c[0] = fp_sub(x.c[0], nar[b * CP_LANES]);
-        cp_stw(wid, dst, x);
+    case CP_SUB_EB:
+        if constexpr (Env::EXT) {
+            Fp4 x = cp_ldw(wid, a);
+            x.c[0] = fp_sub(x.c[0], nar[b * CP_LANES]);
+            cp_stw(wid, dst, x);
+        }
         break;
-    }
-    case CP_SUB_BE: {
-        const Fp4 y = cp_ldw(wid, b);
-        cp_stw(wid, dst, Fp4{{fp_sub(nar[a * CP_LANES], y.c[0]), fp_neg(y.c[1]), fp_neg(y.c[2]), fp_neg(y.c[3])}});
+    case CP_SUB_BE:
+        if constexpr (Env::EXT) {
+            const Fp4 y = cp_ldw(wid, b);
+            cp_stw(wid, dst, Fp4{{fp_sub(nar[a * CP_LANES], y.c[0]), fp_neg(y.c[1]), fp_neg(y.c[2]), fp_neg(y.c[3])}});
+        }
         break;
-    }
-    case CP_MUL_EB: cp_stw(wid, dst, f4_scale(cp_ldw(wid, a), nar[b * CP_LANES])); break;
-    case CP_ADD_EE: cp_stw(wid, dst, f4_add(cp_ldw(wid, a), cp_ldw(wid, b))); break;
-    case CP_SUB_EE: cp_stw(wid, dst, f4_sub(cp_ldw(wid, a), cp_ldw(wid, b))); break;
-    case CP_MUL_EE: cp_stw(wid, dst, f4_mul_lz(cp_ldw(wid, a), cp_ldw(wid, b))); break;
+    case CP_MUL_EB:
+        if constexpr (Env::EXT) cp_stw(wid, dst, f4_scale(cp_ldw(wid, a), nar[b * CP_LANES]));
+        break;
+    case CP_ADD_EE:
+        if constexpr (Env::EXT) cp_stw(wid, dst, f4_add(cp_ldw(wid, a), cp_ldw(wid, b)));
+        break;
+    case CP_SUB_EE:
+        if constexpr (Env::EXT) cp_stw(wid, dst, f4_sub(cp_ldw(wid, a), cp_ldw(wid, b)));
+        break;
+    case CP_MUL_EE:
+        if constexpr (Env::EXT) cp_stw(wid, dst, f4_mul_lz(cp_ldw(wid, a), cp_ldw(wid, b)));
+        break;
     case CP_ZERO:
         if constexpr (Env::MIX) cp_stw(wid, dst, f4_zero());
         break;

@@ -6,12 +6,101 @@
 #include <string.h>
 
 #include <algorithm>
-#include <stdexcept>
 
 #include "fp.hpp"
 #include "program_internal.hpp"
 
 namespace bx {
+
+// a function, not an object: the library's build compiles this file as HIP, where a namespace-scope constant would be emitted for the
+// device too
+const OpRule* op_rules() {
+    constexpr uint8_t _ = SLOT_NONE, N = SLOT_NARROW, W = SLOT_WIDE, ALL = KIND_CONS | KIND_WIT | KIND_ACC, EXT = KIND_CONS | KIND_ACC;
+    static constexpr OpRule rules[] = {
+        //           dst a  b  c  imm         kinds
+        /* NOP     */ {_, _, _, _, IMM_NONE, ALL},
+        /* LD_B    */ {N, _, _, _, IMM_SCAL, ALL},
+        /* LD_E    */ {W, _, _, _, IMM_CONST4, EXT},
+        /* TAP     */ {N, _, _, _, IMM_TAP, ALL},
+        /* ADD_BB  */ {N, N, N, _, IMM_NONE, ALL},
+        /* SUB_BB  */ {N, N, N, _, IMM_NONE, ALL},
+        /* MUL_BB  */ {N, N, N, _, IMM_NONE, ALL},
+        /* ADD_EB  */ {W, W, N, _, IMM_NONE, EXT},
+        /* SUB_EB  */ {W, W, N, _, IMM_NONE, EXT},
+        /* SUB_BE  */ {W, N, W, _, IMM_NONE, EXT},
+        /* MUL_EB  */ {W, W, N, _, IMM_NONE, EXT},
+        /* ADD_EE  */ {W, W, W, _, IMM_NONE, EXT},
+        /* SUB_EE  */ {W, W, W, _, IMM_NONE, EXT},
+        /* MUL_EE  */ {W, W, W, _, IMM_NONE, EXT},
+        /* ZERO    */ {W, _, _, _, IMM_NONE, KIND_CONS},
+        /* EQZ_B   */ {W, W, N, _, IMM_POW, KIND_CONS},
+        /* EQZ_E   */ {W, W, W, _, IMM_POW, KIND_CONS},
+        /* COND_B  */ {W, W, N, W, IMM_POW, KIND_CONS},
+        /* COND_E  */ {W, W, W, W, IMM_POW, KIND_CONS},
+        /* ST      */ {_, N, _, _, IMM_SET, KIND_WIT},
+        /* TSUM_B  */ {_, N, N, _, IMM_SUM, KIND_ACC},
+        /* TSUM_E  */ {_, N, W, _, IMM_SUM, KIND_ACC},
+        /* TPROD_B */ {_, N, _, _, IMM_PROD, KIND_ACC},
+        /* TPROD_E */ {_, W, _, _, IMM_PROD, KIND_ACC},
+        /* TDEN_B  */ {_, N, _, _, IMM_DEN, KIND_ACC},
+        /* TDEN_E  */ {_, W, _, _, IMM_DEN, KIND_ACC},
+    };
+    static_assert(sizeof rules / sizeof rules[0] == CP_OPCODES, "one row per opcode, in the order of ConsOpcode");
+    return rules;
+}
+
+bool stream_fits(const std::vector<uint32_t>& code, const StreamLimits& lim) {
+    if (lim.narrow > BX_CONS_MAX_NARROW || lim.wide > BX_CONS_MAX_WIDE || code.size() % (2 * CP_FETCH)) return false;
+    for (size_t t = 0; t < lim.n_taps; ++t)
+        if (lim.taps[t].group >= lim.tap_groups) return false;
+    const OpRule* const rules = op_rules();
+    const auto slot = [&](uint8_t cls, uint32_t s) { return cls == SLOT_NONE || s < (cls == SLOT_NARROW ? lim.narrow : lim.wide); };
+    for (size_t pc = 0; pc < code.size(); pc += 2) {
+        const uint32_t w0 = code[pc], w1 = code[pc + 1], op = w0 & 0xFFu;
+        const size_t imm = w1 >> 8;
+        if (op >= CP_OPCODES || !(rules[op].kinds & lim.kind)) return false;
+        const OpRule& r = rules[op];
+        if (!slot(r.dst, (w0 >> 8) & 0xFFu) || !slot(r.a, (w0 >> 16) & 0xFFu) || !slot(r.b, w0 >> 24) || !slot(r.c, w1 & 0xFFu)) return false;
+        bool ok = true;
+        switch (r.imm) {
+        case IMM_SCAL: ok = imm < lim.n_scal; break;
+        case IMM_CONST4: ok = imm >= lim.consts_at && imm + 4 <= lim.n_scal; break;
+        case IMM_TAP: ok = imm < lim.n_taps; break;
+        case IMM_POW: ok = imm < lim.n_pows; break;
+        case IMM_SET: ok = imm < lim.max_set; break;
+        case IMM_SUM: ok = imm < lim.sums; break;
+        case IMM_PROD: ok = imm >= lim.sums && imm < lim.sequences; break;
+        case IMM_DEN: ok = imm >= lim.sequences && imm < (size_t)lim.sequences + lim.ratios; break;
+        default: break;  // IMM_NONE
+        }
+        if (!ok) return false;
+    }
+    return true;
+}
+
+bool program_fits(const bx_cons_program* p) {
+    const bx_cons_program_info& in = p->info;
+    const size_t at = (size_t)in.n_globals + 4;
+    return p->ret_slot < in.wide && p->n_pows >= 1 &&
+           stream_fits(p->code, StreamLimits{KIND_CONS, in.narrow, in.wide, at + p->consts.size(), at, p->taps.data(), p->taps.size(), 3, p->n_pows, 0, 0, 0, 0});
+}
+
+bool program_fits(const bx_wit_program* p) {  // `scal` is the constants alone
+    return stream_fits(p->code, StreamLimits{KIND_WIT, p->info.narrow, 0, p->consts.size(), 0, p->taps.data(), p->taps.size(), 2, 0, p->max_set, 0, 0, 0});
+}
+
+bool program_fits(const bx_acc_program* p) {
+    const bx_acc_program_info& in = p->info;
+    if (in.sequences < 1 || in.sequences > BX_ACC_MAX_SEQS || in.sums > in.sequences || p->ratios > in.sequences - in.sums || p->tap_kept.size() != p->taps.size() ||
+        in.kept != p->kept.size())
+        return false;
+    for (uint32_t k : p->tap_kept)
+        if (k >= p->kept.size()) return false;
+    for (const bx_cons_tap& t : p->kept)
+        if (t.group > 1) return false;
+    const size_t at = (size_t)in.n_globals + 4;
+    return stream_fits(p->code, StreamLimits{KIND_ACC, in.narrow, in.wide, at + p->consts.size(), at, p->taps.data(), p->taps.size(), 2, 0, 0, in.sums, in.sequences, p->ratios});
+}
 
 const char* acc_program_check_widths(const std::vector<bx_cons_tap>& kept, const char* who, uint32_t w_code, uint32_t w_data) {
     for (size_t k = 0; k < kept.size(); ++k) {
@@ -68,42 +157,41 @@ std::vector<uint32_t> scal_table(uint32_t ng, const uint32_t* globals, const uin
 }
 
 // One instruction for one row, on the prover's types: the host twin of cp_exec (cons_program_exec.hpp), over a narrow file of words and
-// a wide file of Fp4, canonical arithmetic in the device's operand order.  The caller sees to it that no slot number indexes past its
-// files (a slot number is eight bits).  `env` supplies tap(imm), says with Env::EXT whether the kind has ext values at all (without
+// a wide file of Fp4, canonical arithmetic in the device's operand order.  The caller has held the stream against program_fits: no
+// slot or table index is checked here.  `env` supplies tap(imm), says with Env::EXT whether the kind has ext values at all (without
 // them `wid` is never touched), and executes the opcodes this function does not know in other(): CP_ST, the term stores.
-// false = an instruction of no kind of this program: a corrupt stream.  A table index past `scal` throws std::out_of_range.
 template <class Env>
-bool host_exec(uint32_t w0, uint32_t w1, uint32_t* nar, Fp4* wid, const std::vector<uint32_t>& scal, Env& env) {
+void host_exec(uint32_t w0, uint32_t w1, uint32_t* nar, Fp4* wid, const std::vector<uint32_t>& scal, Env& env) {
     const uint32_t op = w0 & 0xFFu, dst = (w0 >> 8) & 0xFFu, a = (w0 >> 16) & 0xFFu, b = w0 >> 24, imm = w1 >> 8;
     switch (op) {
-    case CP_NOP: return true;
-    case CP_LD_B: nar[dst] = scal.at(imm); return true;
-    case CP_TAP: nar[dst] = env.tap(imm); return true;
-    case CP_ADD_BB: nar[dst] = fp_add(nar[a], nar[b]); return true;
-    case CP_SUB_BB: nar[dst] = fp_sub(nar[a], nar[b]); return true;
-    case CP_MUL_BB: nar[dst] = fp_mul(nar[a], nar[b]); return true;
+    case CP_NOP: return;
+    case CP_LD_B: nar[dst] = scal[imm]; return;
+    case CP_TAP: nar[dst] = env.tap(imm); return;
+    case CP_ADD_BB: nar[dst] = fp_add(nar[a], nar[b]); return;
+    case CP_SUB_BB: nar[dst] = fp_sub(nar[a], nar[b]); return;
+    case CP_MUL_BB: nar[dst] = fp_mul(nar[a], nar[b]); return;
     default: break;
     }
     if (!Env::EXT) return env.other(op, a, b, imm, nar, wid);
     switch (op) {
-    case CP_LD_E: wid[dst] = Fp4{{scal.at(imm), scal.at(imm + 1), scal.at(imm + 2), scal.at(imm + 3)}}; return true;
+    case CP_LD_E: wid[dst] = Fp4{{scal[imm], scal[imm + 1], scal[imm + 2], scal[imm + 3]}}; return;
     case CP_ADD_EB: {
         Fp4 x = wid[a];
         x.c[0] = fp_add(x.c[0], nar[b]);
         wid[dst] = x;
-        return true;
+        return;
     }
     case CP_SUB_EB: {
         Fp4 x = wid[a];
         x.c[0] = fp_sub(x.c[0], nar[b]);
         wid[dst] = x;
-        return true;
+        return;
     }
-    case CP_SUB_BE: wid[dst] = Fp4{{fp_sub(nar[a], wid[b].c[0]), fp_neg(wid[b].c[1]), fp_neg(wid[b].c[2]), fp_neg(wid[b].c[3])}}; return true;
-    case CP_MUL_EB: wid[dst] = f4_scale(wid[a], nar[b]); return true;
-    case CP_ADD_EE: wid[dst] = f4_add(wid[a], wid[b]); return true;
-    case CP_SUB_EE: wid[dst] = f4_sub(wid[a], wid[b]); return true;
-    case CP_MUL_EE: wid[dst] = f4_mul(wid[a], wid[b]); return true;
+    case CP_SUB_BE: wid[dst] = Fp4{{fp_sub(nar[a], wid[b].c[0]), fp_neg(wid[b].c[1]), fp_neg(wid[b].c[2]), fp_neg(wid[b].c[3])}}; return;
+    case CP_MUL_EB: wid[dst] = f4_scale(wid[a], nar[b]); return;
+    case CP_ADD_EE: wid[dst] = f4_add(wid[a], wid[b]); return;
+    case CP_SUB_EE: wid[dst] = f4_sub(wid[a], wid[b]); return;
+    case CP_MUL_EE: wid[dst] = f4_mul(wid[a], wid[b]); return;
     default: return env.other(op, a, b, imm, nar, wid);
     }
 }
@@ -120,11 +208,9 @@ struct WitEnv {
     const uint32_t* code;
     uint32_t* data;
     size_t n, r;
-    uint32_t tap(uint32_t imm) const { return row_tap(prog->taps.at(imm), code, data, n, r); }
-    bool other(uint32_t op, uint32_t a, uint32_t, uint32_t imm, const uint32_t* nar, const Fp4*) const {
-        if (op != CP_ST) return false;
-        data[(size_t)imm * n + r] = nar[a];
-        return true;
+    uint32_t tap(uint32_t imm) const { return row_tap(prog->taps[imm], code, data, n, r); }
+    void other(uint32_t op, uint32_t a, uint32_t, uint32_t imm, const uint32_t* nar, const Fp4*) const {
+        if (op == CP_ST) data[(size_t)imm * n + r] = nar[a];
     }
 };
 
@@ -136,27 +222,23 @@ struct AccEnv {
     Fp4* run;         // the device's run_ext: sequence-major AoS
     uint32_t* mults;
     size_t n, r;
-    uint32_t tap(uint32_t imm) const { return row_tap(prog->taps.at(imm), code, data, n, r); }
-    bool other(uint32_t op, uint32_t a, uint32_t b, uint32_t imm, const uint32_t* nar, const Fp4* wid) const {
-        const uint32_t S = prog->info.sequences, sums = prog->info.sums;
+    uint32_t tap(uint32_t imm) const { return row_tap(prog->taps[imm], code, data, n, r); }
+    void other(uint32_t op, uint32_t a, uint32_t b, uint32_t imm, const uint32_t* nar, const Fp4* wid) const {
         switch (op) {
         case CP_TSUM_B:
         case CP_TSUM_E:
-            if (imm >= sums) return false;
             run[(size_t)imm * n + r] = op == CP_TSUM_B ? Fp4{{nar[b], 0u, 0u, 0u}} : wid[b];
             mults[(size_t)imm * n + r] = nar[a];
-            return true;
+            return;
         case CP_TPROD_B:
+        case CP_TDEN_B:  // the denominators of the R ratios: sequences [S, S + R) of `run`
+            run[(size_t)imm * n + r] = Fp4{{nar[a], 0u, 0u, 0u}};
+            return;
         case CP_TPROD_E:
-            if (imm < sums || imm >= S) return false;
-            run[(size_t)imm * n + r] = op == CP_TPROD_B ? Fp4{{nar[a], 0u, 0u, 0u}} : wid[a];
-            return true;
-        case CP_TDEN_B:
-        case CP_TDEN_E:  // the denominators of the R ratios: sequences [S, S + R) of `run`
-            if (imm < S || imm >= S + prog->ratios) return false;
-            run[(size_t)imm * n + r] = op == CP_TDEN_B ? Fp4{{nar[a], 0u, 0u, 0u}} : wid[a];
-            return true;
-        default: return false;
+        case CP_TDEN_E:
+            run[(size_t)imm * n + r] = wid[a];
+            return;
+        default: return;
         }
     }
 };
@@ -196,6 +278,7 @@ extern "C" const char* bx_cons_program_constraints_at(const bx_cons_program* pro
     using namespace bx;
     if (!prog || !taps || !taps->at || !poly_mix || !mix || !out) return "bx_cons_program_constraints_at: null argument";
     if (prog->info.n_globals && !globals) return "bx_cons_program_constraints_at: the program names globals and none were given";
+    if (!program_fits(prog)) return "bx_cons_program_constraints_at: corrupt instruction stream";  // as long as the walk it guards
     const std::vector<uint32_t> scal = scal_table(prog->info.n_globals, globals, mix, prog->consts);
     std::vector<Fp4> pows(prog->n_pows);
     const Fp4 pm{{poly_mix[0], poly_mix[1], poly_mix[2], poly_mix[3]}};
@@ -210,7 +293,6 @@ extern "C" const char* bx_cons_program_constraints_at(const bx_cons_program* pro
         const uint32_t w0 = prog->code[pc], w1 = prog->code[pc + 1];
         const uint32_t op = w0 & 0xFFu, dst = (w0 >> 8) & 0xFFu, a = (w0 >> 16) & 0xFFu, b = w0 >> 24, c = w1 & 0xFFu, imm = w1 >> 8;
         switch (op) {
-        case CP_NOP: break;
         case CP_LD_B: nar[dst] = base(scal[imm]); break;
         case CP_LD_E: wid[dst] = Fp4{{scal[imm], scal[imm + 1], scal[imm + 2], scal[imm + 3]}}; break;
         case CP_TAP: {
@@ -238,7 +320,7 @@ extern "C" const char* bx_cons_program_constraints_at(const bx_cons_program* pro
         case CP_EQZ_E: wid[dst] = f4_add(wid[a], f4_mul(pows[imm], wid[b])); break;
         case CP_COND_B: wid[dst] = f4_add(wid[a], f4_mul(f4_mul(pows[imm], wid[c]), nar[b])); break;
         case CP_COND_E: wid[dst] = f4_add(wid[a], f4_mul(f4_mul(pows[imm], wid[c]), wid[b])); break;
-        default: return "bx_cons_program_constraints_at: corrupt instruction stream";
+        default: break;  // CP_NOP, the padding
         }
     }
     memcpy(out, wid[prog->ret_slot].c, 16);
@@ -301,16 +383,13 @@ extern "C" const char* bx_wit_program_run_host(const bx_wit_program* prog, uint3
     if (const char* e = wit_program_check_widths(prog->max_col, prog->max_set, "bx_wit_program_run_host", w_code, w_data)) return e;
     if (const char* e = wit_program_check_sorts(prog->sorts, "bx_wit_program_run_host", po2, w_data)) return e;
     if (const char* e = wit_program_check_counts(prog->counts, "bx_wit_program_run_host", po2, w_data)) return e;
+    if (!program_fits(prog)) return "bx_wit_program_run_host: corrupt instruction stream";
     const size_t n = (size_t)1 << po2;
     // rows in any order: no row reads a word this run writes (derived cells are forwarded, never loaded)
     for (size_t r = 0; r < n; ++r) {
         uint32_t nar[BX_CONS_MAX_NARROW] = {};
         WitEnv env{prog, code, data, n, r};
-        for (size_t pc = 0; pc < prog->code.size(); pc += 2) {
-            const uint32_t w0 = prog->code[pc];
-            const bool fits = ((w0 >> 8) & 0xFFu) < BX_CONS_MAX_NARROW && ((w0 >> 16) & 0xFFu) < BX_CONS_MAX_NARROW && (w0 >> 24) < BX_CONS_MAX_NARROW;
-            if (!fits || !host_exec(w0, prog->code[pc + 1], nar, nullptr, prog->consts, env)) return "bx_wit_program_run_host: corrupt instruction stream";
-        }
+        for (size_t pc = 0; pc < prog->code.size(); pc += 2) host_exec(prog->code[pc], prog->code[pc + 1], nar, nullptr, prog->consts, env);
     }
     // the sorts, in list order, after every row and before the counts: pi = the stable sort of rows [0, rows) by the decoded, masked key
     // tuple; every source gathered into a temporary before a dest is written
@@ -343,8 +422,6 @@ extern "C" const char* bx_wit_program_run_host(const bx_wit_program* prog, uint3
         for (size_t r = 0; r < rows; ++r) data[(size_t)ct.col * n + r] = r < ct.bins ? fp_mul(R2, bins[r]) : 0u;
     }
     return nullptr;
-} catch (const std::out_of_range&) {  // a constant or tap index past its table
-    return "bx_wit_program_run_host: corrupt instruction stream";
 } catch (...) {
     return "bx_wit_program_run_host: out of host memory";
 }
@@ -381,21 +458,19 @@ extern "C" const char* bx_acc_program_run_host(const bx_acc_program* prog, uint3
     if (const char* e = acc_program_check_widths(prog->kept, "bx_acc_program_run_host", w_code, w_data)) return e;
     const uint32_t S = prog->info.sequences, sums = prog->info.sums;
     if (w_accum < 4 * S) return refuse("bx_acc_program_run_host: the program writes %u accum columns, the accum group has %u", 4 * S, w_accum);
+    if (!program_fits(prog)) return "bx_acc_program_run_host: corrupt instruction stream";
     const size_t n = (size_t)1 << po2;
     const std::vector<uint32_t> scal = scal_table(prog->info.n_globals, globals, mix, prog->consts);
     const uint32_t R = prog->ratios;
-    if (R > S - sums) return "bx_acc_program_run_host: corrupt instruction stream";
     std::vector<Fp4> run((size_t)(S + R) * n, f4_zero());
     std::vector<uint32_t> mults((size_t)sums * n, 0u);
     // (1) the terms of every row
     for (size_t r = 0; r < n; ++r) {
-        // a slot number is eight bits: files of 256 cannot be indexed out of bounds by any stream
-        uint32_t nar[256] = {};
-        Fp4 wid[256];
+        uint32_t nar[BX_CONS_MAX_NARROW] = {};
+        Fp4 wid[BX_CONS_MAX_WIDE];
         for (Fp4& v : wid) v = f4_zero();
         AccEnv env{prog, code, data, run.data(), mults.data(), n, r};
-        for (size_t pc = 0; pc < prog->code.size(); pc += 2)
-            if (!host_exec(prog->code[pc], prog->code[pc + 1], nar, wid, scal, env)) return "bx_acc_program_run_host: corrupt instruction stream";
+        for (size_t pc = 0; pc < prog->code.size(); pc += 2) host_exec(prog->code[pc], prog->code[pc + 1], nar, wid, scal, env);
     }
     // (2) m / d with 0 -> 0 and the running sums; (3) a / b with 1 / 0 -> 0 for the ratios, and the running products; (4) sequence s,
     // component k -> column 4 s + k
@@ -414,5 +489,5 @@ extern "C" const char* bx_acc_program_run_host(const bx_acc_program* prog, uint3
     }
     return nullptr;
 } catch (...) {
-    return "bx_acc_program_run_host: out of host memory or a corrupt instruction stream";
+    return "bx_acc_program_run_host: out of host memory";
 }

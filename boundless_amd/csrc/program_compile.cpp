@@ -644,12 +644,14 @@ const char* compile_acc(const bx_acc_program_desc* d, bx_acc_program* p) {
     p->info.n_globals = d->n_globals;
     return nullptr;
 }
-// create: compile into a fresh program, which is the caller's only when nothing was refused
+// create: compile into a fresh program, which is the caller's only when nothing was refused.  What the compiler wrote must pass the
+// check every consumer makes (program_fits): the two are written apart, so each holds the other to the operand table
 template <class Prog, class Compile>
-const char* create(Prog** out, Compile compile_into) {
+const char* create(const Kind& k, Prog** out, Compile compile_into) {
     *out = nullptr;
     std::unique_ptr<Prog> p(new Prog());
     CP_TRY(compile_into(p.get()));
+    if (!program_fits(p.get())) return refuse("%s: internal error: the compiled stream does not pass program_fits", k.who);
     *out = p.release();
     return nullptr;
 }
@@ -660,7 +662,7 @@ const char* create(Prog** out, Compile compile_into) {
 
 extern "C" const char* bx_cons_program_create(const bx_cons_program_desc* desc, bx_cons_program** out) try {
     if (!desc || !out) return "bx_cons_program_create: null argument";
-    return bx::create(out, [&](bx_cons_program* p) { return bx::compile(desc, p); });
+    return bx::create(bx::cons_kind(), out, [&](bx_cons_program* p) { return bx::compile(desc, p); });
 } catch (...) {
     return "bx_cons_program_create: out of host memory";
 }
@@ -668,7 +670,7 @@ extern "C" const char* bx_cons_program_create(const bx_cons_program_desc* desc, 
 extern "C" const char* bx_wit_program_create_sorted(const bx_wit_program_desc* desc, const bx_wit_count* counts, size_t n_counts, const bx_wit_sort* sorts,
                                                     size_t n_sorts, bx_wit_program** out) try {
     if (!desc || !out) return "bx_wit_program_create: null argument";
-    return bx::create(out, [&](bx_wit_program* p) { return bx::compile_wit(desc, counts, n_counts, sorts, n_sorts, p); });
+    return bx::create(bx::wit_kind(), out, [&](bx_wit_program* p) { return bx::compile_wit(desc, counts, n_counts, sorts, n_sorts, p); });
 } catch (...) {
     return "bx_wit_program_create: out of host memory";
 }
@@ -681,7 +683,7 @@ extern "C" const char* bx_wit_program_create(const bx_wit_program_desc* desc, bx
 
 extern "C" const char* bx_acc_program_create(const bx_acc_program_desc* desc, bx_acc_program** out) try {
     if (!desc || !out) return "bx_acc_program_create: null argument";
-    return bx::create(out, [&](bx_acc_program* p) { return bx::compile_acc(desc, p); });
+    return bx::create(bx::acc_kind(), out, [&](bx_acc_program* p) { return bx::compile_acc(desc, p); });
 } catch (...) {
     return "bx_acc_program_create: out of host memory";
 }

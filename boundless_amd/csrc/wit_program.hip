@@ -1,63 +1,58 @@
 // wit_program.hip — device half of witness programs ("Witness programs" of include/bx_program.h is the normative text; cons_program.hpp
 // the compiled form): a kernel that INTERPRETS a program's instruction stream over the N trace rows and stores the derived data
-// columns.  It follows the choices of the constraint interpreter (cons_program.hip), for the same reasons:
+// columns.  It follows the choices of the constraint interpreter (cons_program.hip), for the reasons written at the top of that file,
+// and shares its opcode bodies (cons_program_exec.hpp).  What is its own:
 //   lanes     one lane per row, 256 per workgroup; lanes past N return at once
-//   slots     the narrow slot file is dynamic LDS, slot-major: slot s is words [256 s, 256 s + 256) (1 KiB).  A wave's access to a slot
-//             is 64 consecutive dwords: conflict-free.  Sized per program, at most 32 KiB, so several workgroups share a CU.
+//   slots     the narrow slot file alone, sized per program: at most 32 KiB of dynamic LDS, so several workgroups share a CU
 //   barriers  none: a lane only ever touches its own column of the slot file, and no lane reads a word of `data` that this launch
 //             writes (a derived cell is forwarded by the compiler, never loaded), so the result does not depend on scheduling
-//   state     nothing per lane is held in an array indexed at run time (that would be scratch): a value is in LDS or in flight
-//   stream    wave-uniform: fetched through a const __restrict__ pointer indexed by the loop counter, CP_FETCH instructions per
-//             fetch, so that it comes through the scalar cache; decode and dispatch are scalar (readfirstlane makes it explicit)
 //   values    canonical throughout (fp_add / fp_sub / fp_mul): the host executor gives identical words
 //   memory    a tap is col[(r - back) & (N - 1)]; a store is data[col * N + r]: one coalesced 256-byte line per wave
+#define BX_PLAIN_MAD 1
 #include <memory>
 #include <new>
 #include <vector>
 
+#include "circuit_common.hpp"
+#include "cons_program_exec.hpp"
 #include "wit_program_dev.hpp"
 
 namespace bx {
 
-constexpr uint32_t WP_LANES = 256;
-
-// one instruction for one lane; everything decoded from w0 / w1 is wave-uniform.  `data` is read (free columns) and written (derived
-// ones) through the one pointer: never the same word, but the same buffer.
-__device__ __forceinline__ void wp_exec(uint32_t w0v, uint32_t w1v, uint32_t* nar, const uint32_t* __restrict__ code, uint32_t* data,
-                                        const uint2* __restrict__ taps, const uint32_t* __restrict__ consts, uint32_t n, uint32_t r) {
-    const uint32_t w0 = __builtin_amdgcn_readfirstlane(w0v), w1 = __builtin_amdgcn_readfirstlane(w1v);
-    const uint32_t op = w0 & 0xFFu, dst = (w0 >> 8) & 0xFFu, a = (w0 >> 16) & 0xFFu, b = w0 >> 24, imm = w1 >> 8;
-    switch (op) {
-    case CP_LD_B: nar[dst * WP_LANES] = consts[imm]; break;
-    case CP_TAP: {
+// what cp_exec asks of this kernel: a tap is a column of the trace at row r - back; the one opcode cp_exec does not know is the store.
+// `data` is read (free columns) and written (derived ones) through the one pointer: never the same word, but the same buffer.
+struct WitEnv {
+    static constexpr bool MIX = false, EXT = false;
+    const uint32_t* __restrict__ code;
+    uint32_t* data;
+    const uint2* __restrict__ taps;
+    uint32_t n, r;
+    __device__ __forceinline__ uint32_t tap(uint32_t imm) const {
         const uint2 t = taps[imm];
         const uint32_t back = t.y & 0x3FFFFFFFu;
         const uint32_t* col = ((t.y >> 30) == 0 ? code : data) + (size_t)t.x * n;
-        nar[dst * WP_LANES] = col[(r - back) & (n - 1u)];  // N divides 2^32: the wrapped difference reduces properly
-        break;
+        return col[(r - back) & (n - 1u)];  // N divides 2^32: the wrapped difference reduces properly
     }
-    case CP_ADD_BB: nar[dst * WP_LANES] = fp_add(nar[a * WP_LANES], nar[b * WP_LANES]); break;
-    case CP_SUB_BB: nar[dst * WP_LANES] = fp_sub(nar[a * WP_LANES], nar[b * WP_LANES]); break;
-    case CP_MUL_BB: nar[dst * WP_LANES] = fp_mul(nar[a * WP_LANES], nar[b * WP_LANES]); break;
-    case CP_ST: data[(size_t)imm * n + r] = nar[a * WP_LANES]; break;
-    default: break;  // CP_NOP, the padding
+    __device__ __forceinline__ void other(uint32_t op, uint32_t a, uint32_t, uint32_t imm, uint32_t* nar, uint32_t*) const {
+        if (op == CP_ST) data[(size_t)imm * n + r] = nar[a * CP_LANES];
     }
-}
+};
 
 __global__ __launch_bounds__(256) void wit_program_kernel(uint32_t* data, const uint32_t* __restrict__ code, const uint4* __restrict__ stream,
                                                           const uint2* __restrict__ taps, const uint32_t* __restrict__ consts, uint32_t n, uint32_t n_fetch) {
     extern __shared__ uint32_t slots[];
-    const uint32_t r = blockIdx.x * WP_LANES + threadIdx.x;
+    const uint32_t r = blockIdx.x * CP_LANES + threadIdx.x;
     if (r >= n) return;
     uint32_t* const nar = slots + threadIdx.x;  // slot s: nar[256 s]
+    const WitEnv env{code, data, taps, n, r};
 
     static_assert(CP_FETCH == 4, "the fetch below reads two uint4 = four instructions");
     for (uint32_t f = 0; f < n_fetch; ++f) {
         const uint4 lo = stream[2 * (size_t)f], hi = stream[2 * (size_t)f + 1];
-        wp_exec(lo.x, lo.y, nar, code, data, taps, consts, n, r);
-        wp_exec(lo.z, lo.w, nar, code, data, taps, consts, n, r);
-        wp_exec(hi.x, hi.y, nar, code, data, taps, consts, n, r);
-        wp_exec(hi.z, hi.w, nar, code, data, taps, consts, n, r);
+        cp_exec(lo.x, lo.y, nar, nullptr, consts, env);  // `scal` is the constants alone
+        cp_exec(lo.z, lo.w, nar, nullptr, consts, env);
+        cp_exec(hi.x, hi.y, nar, nullptr, consts, env);
+        cp_exec(hi.z, hi.w, nar, nullptr, consts, env);
     }
 }
 
@@ -84,6 +79,8 @@ extern "C" const char* bx_wit_program_load(bx_ctx* c, const bx_wit_program* prog
     BX_REQUIRE(c, prog && out, "bx_wit_program_load: null argument");
     BX_ENTER(c);
     *out = nullptr;
+    // the compiler refuses what does not fit; a stream from anywhere else must not reach the kernel
+    BX_REQUIRE(c, program_fits(prog), "bx_wit_program_load: the program's slot count is outside the device limit");
     std::unique_ptr<bx_wit_program_dev> d(new bx_wit_program_dev());
     d->ctx = c;
     d->info = prog->info;
@@ -91,10 +88,7 @@ extern "C" const char* bx_wit_program_load(bx_ctx* c, const bx_wit_program* prog
     for (int g = 0; g < 2; ++g) d->max_col[g] = prog->max_col[g];
     d->max_set = prog->max_set;
     BX_TRY(bx_wit_program_digest(prog, d->gen.digest));  // what a generated kernel must have been built from (attach_kernel)
-    // the compiler refuses what does not fit; a stream from anywhere else must not reach the kernel
-    BX_REQUIRE(c, prog->info.narrow <= BX_CONS_MAX_NARROW && prog->code.size() % (2 * CP_FETCH) == 0,
-               "bx_wit_program_load: the program's slot count is outside the device limit");
-    d->lds = (size_t)prog->info.narrow * WP_LANES * 4;  // at most 32 KiB: below what a kernel may use by default
+    d->lds = (size_t)prog->info.narrow * CP_LANES * 4;  // at most 32 KiB: below what a kernel may use by default
     BX_TRY(upload_program(
         c, d->code, d->taps, d->consts, prog->code, prog->taps,
         [](uint32_t* w, size_t, const bx_cons_tap& t) { w[0] = t.col, w[1] = t.back | t.group << 30; }, prog->consts, 0));  // `scal` is the constants alone
@@ -142,7 +136,7 @@ extern "C" const char* bx_wit_program_run(bx_ctx* c, bx_wit_program_dev* dev, ui
     {
         // every tap is read once, every derived column written once
         OpScope op(c, "wit_program_run", 4.0 * (double)n * ((double)dev->info.taps + (double)dev->info.sets));
-        hipLaunchKernelGGL(wit_program_kernel, dim3((unsigned)((n + WP_LANES - 1) / WP_LANES)), dim3(WP_LANES), dev->lds, c->stream, (uint32_t*)data.dptr,
+        hipLaunchKernelGGL(wit_program_kernel, dim3((unsigned)((n + CP_LANES - 1) / CP_LANES)), dim3(CP_LANES), dev->lds, c->stream, (uint32_t*)data.dptr,
                            (const uint32_t*)code.dptr, (const uint4*)dev->code.b.dptr, (const uint2*)dev->taps.b.dptr, (const uint32_t*)dev->consts.b.dptr,
                            (uint32_t)n, dev->n_fetch);
         BX_LAUNCH_CHECK(c);

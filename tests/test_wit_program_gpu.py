@@ -6,7 +6,8 @@ second small circuit whose public word is a derived cell; and what a ctx holds.
 
 Sizes are the smallest at which each thing can break: po2 1 (two rows: a tap 1 or 3 rows back wraps), 6 and 7 (less than one
 workgroup: lanes return early), 8 (one workgroup exactly), 9 (two workgroups, and the prover's smallest); programs of one SET, about
-40 and about 700 steps, every step form with a forwarded value used three columns later, and 32 live values (the whole 32 KiB of LDS)."""
+40 and about 700 steps, every step form with a forwarded value used three columns later, and 32 live values (the whole 32 KiB of LDS);
+and, at po2 1 and 9, the shortest stream there is (a constant, a store, padding) and a destination slot that is both its sources."""
 import os
 import sys
 
@@ -88,6 +89,40 @@ def test_run_is_the_reference_on_extreme_columns(hal, programs, pattern):
         code, data = columns(prog, po2, WIDTHS, pattern)
         got, want, host = _three_ways(hal, prog, compiled, loaded, po2, code, data)
         _assert_same(prog, got, want, host, data, f"{name} on {pattern}")
+
+
+def _lone_constant_program():
+    """one constant, one store, and two NOPs of padding: the shortest stream there is"""
+    p = ref.Program()
+    p.set(3, p.const(7))
+    return p
+
+
+def _aliased_destination_program():
+    """x = data[0](r-1); y = x * x with x dead afterwards, so that y takes x's slot: an instruction whose destination is both its sources"""
+    p = ref.Program()
+    x = p.get(1, 0, 1)
+    p.set(3, p.add(p.mul(x, x), p.get(0, 1, 0)))
+    return p
+
+
+@pytest.mark.parametrize("po2", [1, 9])  # two rows: most of the only wave returns at once, and row 0 wraps to the last row; two workgroups
+def test_the_shortest_stream_and_a_destination_that_is_its_own_source(hal, programs, po2):
+    assert programs["narrow_limit"][1].info()["narrow"] == ref.MAX_NARROW  # the named programs reach the whole slot file
+    for name, make, instructions, text in (("lone constant", _lone_constant_program, 2, "at.store(3u, n0)"),
+                                           ("aliased destination", _aliased_destination_program, 5, "n0 = fp_mul(n0, n0)")):
+        prog = make()
+        compiled = compile_ref(prog)
+        assert compiled.info()["instructions"] == instructions and text in compiled.emit_hip(), f"{name}: the compiled stream is not the one this test is about"
+        loaded = compiled.load(hal)
+        try:
+            code, data = columns(prog, po2, WIDTHS, "random", seed=3)
+            got, want, host = _three_ways(hal, prog, compiled, loaded, po2, code, data)
+            assert not np.any(want[prog.derived()] == P - 1), "degenerate reference: a kernel that writes nothing could pass"
+            _assert_same(prog, got, want, host, data, f"{name} at po2 {po2}: {compiled.info()}")
+        finally:
+            loaded.unload()
+            compiled.close()
 
 
 # ---- the synthetic circuit's derive stage as a program ----
